@@ -22,9 +22,16 @@ counters, profiles/) when the committed measurement belongs to the sources being
 FP64 matrix peak that actually bounds the kernel at P = 256.  `cpu_baseline` times the CPU oracle (a port of
 the reference's pass structure; FFTW/PETSc are not installed) on this box's host cores, rank 0, N = 1 only.
 `spinup` untimed matvecs run before the W warm-up steps (setup: an idle MI355X needs a few ms of load before
-its clocks settle) and are reported in the line.  After the timed region (N = 1, informational): `extras_us` (the other
-callbacks of BASELINE configs 2, 4, 5), `dist_rank_compute` (one slab rank's kernels without a wire) and `solves` (end-to-end
-solves of the callers; each is run twice and the second run is `seconds`, the first `seconds_first_run`).
+its clocks settle) and are reported in the line.
+
+A plain run does only what the headline needs: set-up, spin-up, the W warm-up steps, the K timed steps, the line.  `--full`
+adds, after the timed region (N = 1, informational): `cpu_baseline` and the full-size `parity` against the oracle, `power`,
+`extras_us` (the other callbacks of BASELINE configs 2, 4, 5), `dist_rank_compute` (one slab rank's kernels without a wire) and
+`solves` (end-to-end solves of the callers; each is run twice and the second run is `seconds`, the first `seconds_first_run`);
+`--no-cpu-baseline` / `--no-extras` drop parts of it.
+`--dump-outputs DIR` writes, after the timed steps, the result vector of the last timed step as DIR/<name>.npy (float64; a fixed
+seeded sample of its entries where it is larger than the budget, see dump_outputs()); the inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -49,8 +56,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--spinup", type=int, default=100, help="untimed setup matvecs before the W warm-up steps (reported as `spinup`)")
     ap.add_argument("--size", type=int, default=256, help="points per dimension P (BASELINE: 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary timings of the other BASELINE configs")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the line's timed steps also run the CPU baselines with the full-size parity check, package power, the "
+                         "secondary timings of the other BASELINE configs, the end-to-end solves and one slab rank's compute (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result vector of the last timed step as DIR/<name>.npy (float64, a fixed seeded sample where it is large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines (and the full-size parity check)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: keep the CPU baselines only (no power sample, secondary timings, solves, slab rank's compute)")
     ap.add_argument("--cpu-threads", type=int, default=1)
     ap.add_argument("--launch-selftest", action="store_true",
                     help="N > 1 plumbing only (tests/test_bench_launch.py): spawn, rendezvous, one all-reduce, rank 0's line; no GPU, no compute, no metric")
@@ -173,6 +185,21 @@ def csrc_hash():
     for f in sorted(glob.glob(os.path.join(d, "*.hip")) + glob.glob(os.path.join(d, "*.h")) + glob.glob(os.path.join(d, "*.cpp")) + [os.path.join(d, "Makefile")]):
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()
+
+
+DUMP_VALUES = 1 << 22      # --dump-outputs: float64 values written in all (32 MiB)
+
+
+def dump_outputs(dirname, name, V, budget=DUMP_VALUES):
+    """--dump-outputs: the result vector V of the last timed step (what the caller of the matvec receives) as DIR/<name>.npy, float64.
+    Where V holds more than `budget` values, a sample of `budget` of its entries in index order, at positions drawn from a fixed seed:
+    the same positions on every run with the same arguments (the 256^3 vector itself is 131 MB)."""
+    import numpy as np
+    v = V.detach().reshape(-1).cpu().numpy().astype(np.float64, copy=False)
+    if v.size > budget:
+        v = v[np.sort(np.random.default_rng(SEED + 17).choice(v.size, size=budget, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
 
 
 def cpu_baseline(P, threads, U, V=None, warm=2, reps=5):
@@ -667,6 +694,8 @@ def local_threads_main(args):
                 walls[r] = time.perf_counter() - t0
                 devms[r] = e0.elapsed_time(e1)
                 assert torch.isfinite(V).all()
+                if args.dump_outputs:                       # each rank's slab of the result, its share of the budget
+                    dump_outputs(args.dump_outputs, "poisson_matvec_out_rank%d" % r, V, DUMP_VALUES // G)
                 op.destroy()
         except BaseException as e:                          # noqa: a failing rank must not leave the others at a barrier
             errs[r] = e
@@ -873,6 +902,12 @@ def main():
     wall = t.item()
     wd.leave()
     assert torch.isfinite(V).all()
+    if args.dump_outputs:
+        if world == 1:
+            dump_outputs(args.dump_outputs, "poisson_matvec_out", V)
+        else:                                               # each rank's slab of the result, its share of the budget
+            dump_outputs(args.dump_outputs, "poisson_matvec_out_rank%d" % rank, V, DUMP_VALUES // world)
+    full = world == 1 and args.full                         # everything below the headline: N = 1 and --full only
     if rank == 0:
         ms_per_step = wall * 1e3 / args.steps
         value = args.steps / wall
@@ -909,7 +944,7 @@ def main():
                 out["config"]["c_host_fallback"] = dist_fallback
             if ipc_note:
                 out["config"]["ipc_fallback"] = ipc_note[:300]
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             try:
                 Uh, Vh = U.cpu().numpy(), V.cpu().numpy()
                 # the faithful one (the reference is serial); bounded to ~30 s of CPU work: 1 warm-up + 3 timed applies at one
@@ -925,25 +960,25 @@ def main():
                 out["cpu_baseline"] = {"value": None, "unit": "matvecs/s", "cores": args.cpu_threads, "kind": "port", "sample": "failed: " + repr(e)[:160]}
             if out.get("parity") and out["parity"]["rel_l2_vs_oracle"] > out["parity"]["tolerance"]:
                 raise SystemExit("parity failure: GPU matvec differs from the oracle by %.3e" % out["parity"]["rel_l2_vs_oracle"])
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             try:
                 pw = package_power(step, torch)
                 if pw:
                     out["power"] = pw
             except Exception as e:
                 out["power_error"] = repr(e)[:200]
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             try:                                            # informational: never at the expense of the metric line
                 out["extras_us"] = extras(sp, torch)        # (before solves(): the callbacks' handles are made in a fresh allocator state)
                 out["extras_frac"] = extras_frac(out["extras_us"])
             except Exception as e:
                 out["extras_us"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             try:
                 out["solves"] = solves(sp, torch)
             except Exception as e:
                 out["solves_error"] = repr(e)[:300]
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             try:                                            # compute side of one rank at G = 2, 4, 8 (no wire)
                 out["dist_rank_compute"] = dist_rank_compute(sp, ge.load_dist(), torch, dev_ms / args.steps * 1e3)
             except Exception as e:

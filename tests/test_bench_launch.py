@@ -149,3 +149,26 @@ def test_bench_gpus_2_as_typed_prints_one_parsed_line():
     assert rec["parity"]["rel_l2_vs_oracle"] <= 1e-10 and rec["parity"]["ranks"] == 2
     assert rec["config"]["parallelism"].startswith("slab2+all2all(C host") and "c_host_fallback" not in rec["config"]
     assert rec["roofline"]["priced_per"] == "step of one GPU" and rec["roofline"]["avg_launch_us"] is None
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `--gpus 1` run is the headline alone (no CPU baseline, extras or solves: those are `--full`), and `--dump-outputs DIR`
+    writes the result of the last timed step; at 34^3 the whole vector fits the budget, so it is checked against the oracle on the
+    bench's own seeded input."""
+    import numpy as np
+    import torch
+    import oracle_lib as orc
+    r = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--spinup", "2", "--size", "34", "--dump-outputs", str(tmp_path)], {}, 600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    rec = lines[0]
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64" and rec["unit"] == "matvecs/s"
+    assert not any(k in rec for k in ("cpu_baseline", "parity", "power", "extras_us", "solves", "dist_rank_compute")), sorted(rec)
+    V = np.load(str(tmp_path / "poisson_matvec_out.npy"))
+    assert V.dtype == np.float64 and V.shape == (32 ** 3,)
+    g = torch.Generator(device="cuda").manual_seed(20240229)                  # bench.SEED: the input of the timed steps
+    U = torch.randn(32 ** 3, dtype=torch.float64, device="cuda", generator=g).cpu().numpy()
+    ref = orc.elliptic_mult((34, 34, 34), U, mode=orc.FAST)
+    assert np.linalg.norm(V - ref) <= 1e-10 * np.linalg.norm(ref)

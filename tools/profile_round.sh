@@ -31,5 +31,5 @@ rec = {"P": 256, "kernel": "cheb_sweep_vec4_kernel", "launches_per_matvec": 3, "
 json.dump(rec, open("$R/$out/${tag}_traffic.json", "w"), indent=1)
 print(rec)
 PY
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cat $out/${tag}_bench.json
