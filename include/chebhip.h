@@ -97,6 +97,34 @@ int cheb_slab_unpack_add(long m0, long M1, long R, int G, const long *c1_host, c
                          const double *acc_dev, double alpha, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Resampling: moves a field between two Chebyshev-Gauss-Lobatto grids (no    */
+/* counterpart in the reference; the interpolation PETSc's                    */
+/* -snes_grid_sequence needs between levels).  Tensors are row-major with     */
+/* ncomp components innermost (node-major, as the Stokes velocity).  Per      */
+/* direction a grid of n points has two node sets:                            */
+/*   CHEB_NODES_ALL       x_j = cos(pi j/(n-1)), j = 0 .. n-1 (n values)      */
+/*   CHEB_NODES_INTERIOR  the points j = 1 .. n-2 of that grid (n-2 values):  */
+/*                        the global-vector layout of the MatShells and the   */
+/*                        node set of the Stokes pressure                     */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_resample cheb_resample;
+enum { CHEB_NODES_ALL = 0, CHEB_NODES_INTERIOR = 1 };
+
+/* y = (R_0 (x) ... (x) R_{d-1}) x, R_k the Lagrange interpolation matrix from the input to the output node set of direction k.
+ * 1 <= d <= 10; 2 <= dims[k] <= 1024 (3 for INTERIOR); 1 <= ncomp <= 4; fewer than 2^31 values on either side.  dims are copied;
+ * the matrices are built in long double at create (barycentric form; an output node that is an input node gets an exact unit
+ * row, so equal grids copy their input and coarse values are injected unchanged into a finer grid containing their nodes).
+ * The handle owns its matrices and two work buffers: apply allocates nothing and does not synchronise the host. */
+int  cheb_resample_create(int d, const int *dims_in, int nodes_in, const int *dims_out, int nodes_out,
+                          int ncomp, cheb_resample **out);
+/* x: cheb_resample_size(r, 0) values, y: cheb_resample_size(r, 1) values; x and y must not overlap.  Asynchronous on `stream`. */
+int  cheb_resample_apply(cheb_resample *r, const double *x_dev, double *y_dev, void *stream);
+int  cheb_resample_destroy(cheb_resample *r);
+long cheb_resample_size(const cheb_resample *r, int which);           /* 0: input values, 1: output values; -1 on a bad argument */
+/* The (stored n_out) x (stored n_in) matrix of one direction, row-major, into a HOST buffer; needs no device. */
+int  cheb_resample_matrix_host(int n_in, int nodes_in, int n_out, int nodes_out, double *R);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

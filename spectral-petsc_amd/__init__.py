@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "chebhip_dist_ell_create", "chebhip_dist_ell_destroy", "chebhip_dist_ell_op", "chebhip_dist_ell_ranges",
     "stokes_pc_create_slab", "ell_pc_create_slab", "chebhip_fdpc_pencil_transform", "chebhip_dist_stokes_pc", "chebhip_dist_ell_pc",
     "stokes_saddle_create_slab",
+    "cheb_resample_create", "cheb_resample_apply", "cheb_resample_destroy", "cheb_resample_size", "cheb_resample_matrix_host",
 ]
 
 
@@ -212,6 +213,12 @@ def lib():
             getattr(L, "%s_pc_create_slab" % nm).argtypes = [vp, C.c_long, vp, vp, C.POINTER(vp)]
         L.chebhip_fdpc_pencil_transform.argtypes = [vp, C.c_int, C.c_int, C.c_long, vp, vp, vp]
         L.stokes_saddle_create_slab.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
+        L.cheb_resample_create.argtypes = [C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
+        L.cheb_resample_apply.argtypes = [vp, vp, vp, vp]
+        L.cheb_resample_destroy.argtypes = [vp]
+        L.cheb_resample_size.argtypes = [vp, C.c_int]
+        L.cheb_resample_size.restype = C.c_long
+        L.cheb_resample_matrix_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp]
         _lib = L
     return _lib
 
@@ -327,6 +334,62 @@ class ChebPlan:
     def destroy(self):
         if self._h:
             lib().cheb_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+NODES = {"all": 0, "interior": 1}
+
+
+def _nodes(v):
+    if v in NODES.values():
+        return int(v)
+    if v not in NODES:
+        raise ValueError("node set %r: expected one of %s" % (v, sorted(NODES)))
+    return NODES[v]
+
+
+def resample_matrix(n_in, n_out, nodes_in="all", nodes_out="all"):
+    """The interpolation matrix of one direction (cheb_resample_matrix_host) as a numpy array of shape
+    (stored output nodes, stored input nodes); needs no device."""
+    import numpy as np
+    ni, no = _nodes(nodes_in), _nodes(nodes_out)
+    R = np.empty((max(int(n_out) - 2 * no, 0), max(int(n_in) - 2 * ni, 0)))
+    _chk(lib().cheb_resample_matrix_host(int(n_in), ni, int(n_out), no, R.ctypes.data_as(C.POINTER(C.c_double)) if R.size else None))
+    return R
+
+
+class Resample:
+    """y = (R_0 x ... x R_{d-1}) x: a field on the CGL grid dims_in (node set nodes_in: "all" or "interior") interpolated to the
+    grid dims_out (cheb_resample_*); ncomp components innermost.  Sizes: size(0) input values, size(1) output values."""
+
+    def __init__(self, dims_in, dims_out, nodes_in="all", nodes_out="all", ncomp=1):
+        self.dims_in = tuple(int(d) for d in dims_in)
+        self.dims_out = tuple(int(d) for d in dims_out)
+        if len(self.dims_in) != len(self.dims_out):
+            raise ValueError("dims_in and dims_out have different lengths")
+        h = C.c_void_p()
+        _chk(lib().cheb_resample_create(len(self.dims_in), _ints(self.dims_in), _nodes(nodes_in), _ints(self.dims_out),
+                                        _nodes(nodes_out), int(ncomp), C.byref(h)))
+        self._h = h
+        self.ncomp = int(ncomp)
+
+    def size(self, which):
+        return lib().cheb_resample_size(self._h, int(which))
+
+    def apply(self, x, y):
+        """Asynchronous on torch's current stream."""
+        _chk(lib().cheb_resample_apply(self._h, _dev_ptr(x, self.size(0)), _dev_ptr(y, self.size(1)), _stream()))
+        return y
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_resample_destroy(self._h)
             self._h = None
 
     def __del__(self):

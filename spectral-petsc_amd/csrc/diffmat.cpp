@@ -390,6 +390,48 @@ void centro_part(int M, const std::vector<long double> &A, int part, std::vector
     }
 }
 
+// Lagrange interpolation matrix between two node sets of Chebyshev-Gauss-Lobatto grids (cheb_resample_*, resample.hip):
+// R[t][s] (n_out stored rows x n_in stored columns, row-major) maps the values at the stored input nodes to the stored output
+// nodes.  Stored node s of a grid of n points is grid index j = s (all nodes) or j = s + 1 (interior: j = 1 .. n-2), angle
+// pi j / (n-1).  Generic barycentric weights w_j = 1 / prod_{k != j} (x_j - x_k) over the stored set, second barycentric form;
+// every difference of two nodes is formed from the angles (cos a - cos b = -2 sin((a+b)/2) sin((a-b)/2), the half-angles as
+// exact integer ratios), so the nodes never lose digits to cancellation.  A row whose output node IS an input node (angle
+// indices i (n_in-1) == j (n_out-1), decided in integers) is an exact unit row: equal grids give I, and coarse values are
+// injected unchanged into a finer grid that contains their nodes.
+void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior, double *R) {
+  const int a_in = in_interior ? 1 : 0, a_out = out_interior ? 1 : 0;
+  const int K = n_in - 2 * a_in, M = n_out - 2 * a_out;
+  const long ni = n_in - 1, no = n_out - 1;
+  // x_{i on grid of (m+1) points} - x_{j on grid of (n+1) points}, m, n = intervals
+  auto diff = [](long i, long m, long j, long n) -> long double {
+    const long double den = 2.0L * (long double)m * (long double)n;
+    const long sum = i * n + j * m, dif = i * n - j * m;
+    return -2.0L * sinl(PI_L * (long double)sum / den) * sinl(PI_L * (long double)dif / den);
+  };
+  std::vector<long double> w(K);
+  for (int s = 0; s < K; s++) {
+    long double prod = 1.0L;
+    for (int k = 0; k < K; k++)
+      if (k != s) prod *= diff(s + a_in, ni, k + a_in, ni);
+    w[s] = 1.0L / prod;
+  }
+  std::vector<long double> c(K);
+  for (int t = 0; t < M; t++) {
+    const long i = t + a_out;
+    double *row = R + (size_t)t * K;
+    int hit = -1;
+    for (int s = 0; s < K && hit < 0; s++)
+      if (i * ni == (long)(s + a_in) * no) hit = s;
+    if (hit >= 0) {
+      for (int s = 0; s < K; s++) row[s] = s == hit ? 1.0 : 0.0;
+      continue;
+    }
+    long double sum = 0.0L;
+    for (int s = 0; s < K; s++) { c[s] = w[s] / diff(i, no, s + a_in, ni); sum += c[s]; }
+    for (int s = 0; s < K; s++) row[s] = (double)(c[s] / sum);
+  }
+}
+
 void diffmat_destroy(DiffMat *m) {
   if (m->fragE) (void)hipFree(m->fragE);
   if (m->fragO) (void)hipFree(m->fragO);

@@ -112,6 +112,9 @@ hipError_t diffmat_from_dense(int M, const long double *A, int sym, DiffMat *out
 hipError_t diffmat_from_blocks(int M, const long double *ME, const long double *MO, int sym, DiffMat *out);
 // Host-side dense differentiation matrix (row-major P x P), for tests and the adapter.
 void diffmat_dense_host(int P, double *D);
+// Host-side Lagrange interpolation matrix between the stored nodes of two CGL grids (resample.hip; arguments checked there):
+// (n_out - 2 out_interior) x (n_in - 2 in_interior), row-major
+void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior, double *R);
 
 // Launches one sweep.  jfast selects the line-contiguous tiling.
 hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream);

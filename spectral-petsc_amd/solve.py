@@ -83,7 +83,6 @@ def stokes_solve(sp, op, x, rheology=(0, 1.0, 1.0, 1.0, 1.0), cont0=0, cont=1, s
     Returns a list of (exponent, regularization, newton_its, ksp_its, |F|) per stage."""
     kind, hardness, exponent, regularization, gamma0 = rheology
     n = op.global_size
-    F = torch.empty_like(x); dx = torch.empty_like(x)
     own_ks, own_pc = ks is None, pc is None
     if own_ks:
         ks = sp.Fgmres(n, restart=ksp_restart, rtol=ksp_rtol, max_it=ksp_max_it)
@@ -98,38 +97,201 @@ def stokes_solve(sp, op, x, rheology=(0, 1.0, 1.0, 1.0, 1.0), cont0=0, cont=1, s
             pc = sp.StokesSaddlePc(op, saddle_type, vel, schur, svel, pc_sweeps, schur_jacobi)
         gnorm = lambda t: float(t.norm())
     stages = continuation_schedule(exponent, regularization, cont0, cont) if kind == 1 else [(exponent, regularization)]
-    out = []
-    fails = 0
+    fails = [0]
     try:
-        for (e_i, r_i) in stages:
-            op.set_rheology(kind, hardness, e_i, r_i, gamma0)                  # stokes.C:219-220
-            op.function(x, F)
-            f0 = fn = gnorm(F); it = 0; total = 0
-            while it < snes_max_it and fn > max(snes_rtol * f0, snes_atol):
-                pc.setup()                                                      # StokesPCSetUp0 after the new viscosity
-                F.neg_()
-                ks.solve(op, F, dx, M=pc)
-                total += ks.iterations
-                if ks.reason < 0:
-                    fails += 1
-                    if fails >= max_linear_fail or ks.reason != -3:
-                        raise RuntimeError("stage (%g, %g) Newton step %d: linear solve diverged (reason %d, %d its, residual %.3e)"
-                                           % (e_i, r_i, it + 1, ks.reason, ks.iterations, ks.residual))
-                lam, fold = 1.0, fn
-                x.add_(dx)
-                op.function(x, F); fn = gnorm(F)
-                while line_search and not (fn <= (1.0 - 1e-4 * lam) * fold) and lam > 1e-6:
-                    x.add_(dx, alpha=-0.5 * lam); lam *= 0.5
-                    op.function(x, F); fn = gnorm(F)
-                it += 1
-                if monitor:
-                    monitor(e_i, r_i, it, fn, ks.iterations, lam)
-            out.append((e_i, r_i, it, total, fn))
+        out = _stokes_stages(op, x, stages, kind, hardness, gamma0, ks, pc, gnorm, fails, snes_rtol, snes_atol, snes_max_it,
+                             line_search, monitor, max_linear_fail)
     finally:
         if own_ks:
             ks.destroy()
         if own_pc:
             pc.destroy()
         if stats is not None:
-            stats["linear_fails"] = fails
+            stats["linear_fails"] = fails[0]
+    return out
+
+
+def _stokes_stages(op, x, stages, kind, hardness, gamma0, ks, pc, gnorm, fails, snes_rtol, snes_atol, snes_max_it, line_search,
+                   monitor, max_linear_fail):
+    """The continuation stages `stages` ((exponent, regularization) pairs) of stokes_solve on one grid, x in place; fails[0] counts
+    the linear solves that ended on their iteration limit (over all calls that share the list)."""
+    F = torch.empty_like(x); dx = torch.empty_like(x)
+    out = []
+    for (e_i, r_i) in stages:
+        op.set_rheology(kind, hardness, e_i, r_i, gamma0)                  # stokes.C:219-220
+        op.function(x, F)
+        f0 = fn = gnorm(F); it = 0; total = 0
+        while it < snes_max_it and fn > max(snes_rtol * f0, snes_atol):
+            pc.setup()                                                      # StokesPCSetUp0 after the new viscosity
+            F.neg_()
+            ks.solve(op, F, dx, M=pc)
+            total += ks.iterations
+            if ks.reason < 0:
+                fails[0] += 1
+                if fails[0] >= max_linear_fail or ks.reason != -3:
+                    raise RuntimeError("stage (%g, %g) Newton step %d: linear solve diverged (reason %d, %d its, residual %.3e)"
+                                       % (e_i, r_i, it + 1, ks.reason, ks.iterations, ks.residual))
+            lam, fold = 1.0, fn
+            x.add_(dx)
+            op.function(x, F); fn = gnorm(F)
+            while line_search and not (fn <= (1.0 - 1e-4 * lam) * fold) and lam > 1e-6:
+                x.add_(dx, alpha=-0.5 * lam); lam *= 0.5
+                op.function(x, F); fn = gnorm(F)
+            it += 1
+            if monitor:
+                monitor(e_i, r_i, it, fn, ks.iterations, lam)
+        out.append((e_i, r_i, it, total, fn))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Grid sequencing (PETSc's -snes_grid_sequence): solve on a coarse Chebyshev grid, interpolate the solution to the next grid
+# (cheb_resample_*) and use it there as the Newton starting point.  One GPU, no slab distribution.
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+_prolong_cache = {}
+
+
+def _node_split(dims, device):
+    """Row-major (BlockIt) indices of the interior and of the boundary nodes of the full grid `dims`, as device index tensors."""
+    inside = torch.zeros(tuple(dims), dtype=torch.bool)
+    inside[tuple(slice(1, n - 1) for n in dims)] = True
+    inside = inside.ravel()
+    return torch.nonzero(inside).ravel().to(device), torch.nonzero(~inside).ravel().to(device)
+
+
+def _prolongation(sp, kind, dims_c, dims_f, device):
+    """Index tensors and resamplers of one level pair, built once: (interior, boundary, velocity / scalar resampler, pressure resampler)."""
+    dims_c, dims_f = tuple(int(n) for n in dims_c), tuple(int(n) for n in dims_f)
+    key = (kind, dims_c, dims_f, str(device))
+    if key not in _prolong_cache:
+        inner, bnd = _node_split(dims_c, device)
+        ncomp = len(dims_c) if kind == "stokes" else 1
+        rv = sp.Resample(dims_c, dims_f, "all", "interior", ncomp=ncomp)
+        rp = sp.Resample(dims_c, dims_f, "interior", "interior") if kind == "stokes" else None
+        _prolong_cache[key] = (inner, bnd, rv, rp)
+    return _prolong_cache[key]
+
+
+def _dev_values(v, like):
+    return torch.as_tensor(v, dtype=torch.float64).to(like.device)
+
+
+def prolong_elliptic(sp, dims_c, x_c, dirichlet_c, dims_f):
+    """The global vector of the grid dims_f interpolated from the coarse global vector x_c (interior nodes, row-major) and the
+    coarse compact Dirichlet values (ell_op_set_dirichlet order): the full coarse field, resampled ALL -> INTERIOR.  Device tensors
+    throughout (dirichlet_c may be a host array)."""
+    inner, bnd, r, _ = _prolongation(sp, "elliptic", dims_c, dims_f, x_c.device)
+    full = torch.empty(r.size(0), dtype=torch.float64, device=x_c.device)
+    full[inner] = x_c
+    full[bnd] = _dev_values(dirichlet_c, x_c)
+    return r.apply(full, torch.empty(r.size(1), dtype=torch.float64, device=x_c.device))
+
+
+def prolong_stokes(sp, dims_c, x_c, dirichlet_c, dims_f):
+    """The same for a Stokes state [v_0 .. v_{d-1}, p] per interior node: the velocity as the full coarse field with its Dirichlet
+    values (node-major, d components) resampled ALL -> INTERIOR, the pressure INTERIOR -> INTERIOR, interleaved again."""
+    d = len(dims_c)
+    inner, bnd, rv, rp = _prolongation(sp, "stokes", dims_c, dims_f, x_c.device)
+    xc = x_c.view(-1, d + 1)
+    full = torch.empty((rv.size(0) // d, d), dtype=torch.float64, device=x_c.device)
+    full[inner] = xc[:, :d]
+    full[bnd] = _dev_values(dirichlet_c, x_c).view(-1, d)
+    v = rv.apply(full.view(-1), torch.empty(rv.size(1), dtype=torch.float64, device=x_c.device))
+    p = rp.apply(xc[:, d].contiguous(), torch.empty(rp.size(1), dtype=torch.float64, device=x_c.device))
+    out = torch.empty((rp.size(1), d + 1), dtype=torch.float64, device=x_c.device)
+    out[:, :d] = v.view(-1, d)
+    out[:, d] = p
+    return out.view(-1)
+
+
+def newton_krylov_sequenced(sp, levels, gamma=0.0, exponent=2.0, x=None, x0=None, ks=None, monitor=None, dist=None, **newton_kw):
+    """Grid-sequenced newton_krylov: levels = [(op, b, dirichlet, M), ...] coarsest first (op an EllipticOp whose Dirichlet values
+    are `dirichlet`, b its right-hand side, M its preconditioner or None).  Every level is solved to the tolerances of newton_kw,
+    the finer ones from the prolongation of the previous level's solution (PETSc's semantics).
+    x: a device tensor of the finest level's global size that receives the solution; x0: the coarsest level's starting point
+    (None: zero).  ks: one Fgmres per level to use and keep, or None.  monitor(level, it, |F|, ksp_its) after every
+    Newton step.  Returns the per-level (newton_its, ksp_its, |F|)."""
+    if dist is not None:
+        raise ValueError("grid sequencing runs on one GPU: no slab-distributed levels")
+    if x is None or x.numel() != levels[-1][0].global_size:
+        raise ValueError("x: a device tensor of the finest level's global size receives the solution")
+    out = []
+    prev = None
+    for lev, (op, b, dirichlet, M) in enumerate(levels):
+        n = op.global_size
+        last = lev == len(levels) - 1
+        if prev is None:
+            xl = torch.zeros(n, dtype=torch.float64, device=x.device) if x0 is None else x0.clone()
+        else:
+            xl = prolong_elliptic(sp, prev[0].dims, prev[1], prev[2], op.dims)
+        if last:
+            x.copy_(xl); xl = x
+        mon = None if monitor is None else (lambda it, fn, k, lev=lev: monitor(lev, it, fn, k))
+        out.append(newton_krylov(sp, op, b, xl, gamma, exponent, M=M, monitor=mon, ks=None if ks is None else ks[lev], **newton_kw))
+        prev = (op, xl, dirichlet)
+    return out
+
+
+def default_stage_level(nstages, nlevels):
+    """Every continuation stage but the last on the coarsest level, the last one on the finest."""
+    return [0] * (nstages - 1) + [nlevels - 1]
+
+
+def stokes_solve_sequenced(sp, levels, stage_level=None, rheology=(0, 1.0, 1.0, 1.0, 1.0), cont0=0, cont=1, x=None, ks=None, pc=None,
+                           saddle_type=0, snes_rtol=1e-8, snes_atol=1e-50, snes_max_it=50, ksp_rtol=1e-5, ksp_restart=30, ksp_max_it=10000,
+                           vel=(4, 1e-5), schur=(3, 1e-5), svel=(0, 1e-5), pc_sweeps=0, line_search=True, monitor=None, max_linear_fail=1,
+                           schur_jacobi=True, stats=None, dist=None):
+    """Grid-sequenced stokes_solve: levels = [(op, dirichlet), ...] coarsest first, StokesOps with Dirichlet values `dirichlet` and
+    their force set.  stage_level[i] (non-decreasing) is the level of continuation stage i (default: default_stage_level).  Stage i
+    is solved on every level above the previous stage's level up to its own (stage 0: from the coarsest), and the state is
+    prolonged (prolong_stokes) whenever the level changes; with one stage (linear rheology) that is PETSc's grid sequencing.
+    x: a device tensor of the finest level's global size that receives the state (the last stage runs on the finest level).
+    ks, pc: one Fgmres / StokesSaddlePc per level to use and keep, or None (made and destroyed here).  Other arguments as stokes_solve.
+    Returns stokes_solve's log with a level column: (exponent, regularization, newton_its, ksp_its, |F|, level) per solve."""
+    if dist is not None:
+        raise ValueError("grid sequencing runs on one GPU: no slab-distributed levels")
+    kind, hardness, exponent, regularization, gamma0 = rheology
+    stages = continuation_schedule(exponent, regularization, cont0, cont) if kind == 1 else [(exponent, regularization)]
+    nl = len(levels)
+    stage_level = default_stage_level(len(stages), nl) if stage_level is None else [int(v) for v in stage_level]
+    if len(stage_level) != len(stages) or any(b < a for a, b in zip(stage_level, stage_level[1:])) or stage_level[0] < 0 or stage_level[-1] != nl - 1:
+        raise ValueError("stage_level %r: one non-decreasing level index per stage (%d stages), the last one %d" % (stage_level, len(stages), nl - 1))
+    if x is None or x.numel() != levels[-1][0].global_size:
+        raise ValueError("x: a device tensor of the finest level's global size receives the state")
+    kss = list(ks) if ks is not None else [None] * nl
+    pcs = list(pc) if pc is not None else [None] * nl
+    own = [(kss[l] is None, pcs[l] is None) for l in range(nl)]
+    gnorm = lambda t: float(t.norm())
+    fails = [0]
+    out = []
+    cur, xl = -1, None
+    try:
+        for i, st in enumerate(stages):
+            first = stage_level[i - 1] + 1 if i else 0
+            for lev in (range(first, stage_level[i] + 1) if stage_level[i] >= first else [stage_level[i]]):
+                op, dv = levels[lev]
+                if lev != cur:
+                    if cur < 0:
+                        xl = torch.zeros(op.global_size, dtype=torch.float64, device=x.device)
+                    else:
+                        xl = prolong_stokes(sp, levels[cur][0].dims, xl, levels[cur][1], op.dims)
+                    cur = lev
+                    if lev == nl - 1:
+                        x.copy_(xl); xl = x
+                    if kss[lev] is None:
+                        kss[lev] = sp.Fgmres(op.global_size, restart=ksp_restart, rtol=ksp_rtol, max_it=ksp_max_it)
+                    if pcs[lev] is None:
+                        pcs[lev] = sp.StokesSaddlePc(op, saddle_type, vel, schur, svel, pc_sweeps, schur_jacobi)
+                log = _stokes_stages(op, xl, [st], kind, hardness, gamma0, kss[lev], pcs[lev], gnorm, fails, snes_rtol, snes_atol,
+                                     snes_max_it, line_search, monitor, max_linear_fail)
+                out.extend(row + (lev,) for row in log)
+    finally:
+        for l in range(nl):
+            if own[l][0] and kss[l] is not None:
+                kss[l].destroy()
+            if own[l][1] and pcs[l] is not None:
+                pcs[l].destroy()
+        if stats is not None:
+            stats["linear_fails"] = fails[0]
     return out
