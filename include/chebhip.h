@@ -449,6 +449,35 @@ int chebhip_fdpc_apply(void *pc, const double *r_dev, double *z_dev, void *strea
 /* The same for a Stokes velocity preconditioner (stokes_pc_create*) on component-major vectors (stokes_op_mult_vv_cm): the fast
  * diagonalisation z = P_1^-1 (r / eta) (sweeps = 0) only. */
 int chebhip_fdpc_apply_cm(void *pc, const double *r_cm_dev, double *z_cm_dev, void *stream);
+/* The spectral kind of the same handle: z = (sigma I + A)^-1 (r / eta), exact in the constant-coefficient part (A as for
+ * cheb_helmholtz).  chebhip_fdpc_update refreshes eta only; sweeps must stay 0 and chebhip_fdpc_mult is refused (no stencil).
+ * A slab-mode operator is refused. */
+int ell_pc_create_spectral(ell_op *op, double sigma, chebhip_fdpc **out);           /* z = (sigma I + A)^-1 (r / eta) */
+
+/* ------------------------------------------------------------------------- */
+/* Direct Chebyshev Poisson / Helmholtz solves by fast diagonalisation         */
+/* (Haidvogel-Zang; no counterpart in the reference, which solves by Krylov).  */
+/* A is the operator ell_op_mult applies at eta == 1: per direction the line   */
+/* operator A_1 = -(D D)[1..n-1, 1..n-1] on the interior nodes, zero Dirichlet */
+/* values.  A_1 = S diag(lam) S^-1 is computed once per extent in long double  */
+/* (nonsymmetric eigensolver, modes split by parity), and (sigma I + A)^-1 is  */
+/* 2d batched line transforms with the modal weights                           */
+/* 1 / (sigma + lam_i + lam_j + ...) -- the pipeline of the finite-difference  */
+/* preconditioner below, with the spectral line operator in place of its       */
+/* three-point one.                                                            */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_helmholtz cheb_helmholtz;      /* (sigma I + A) u = f on interior nodes, zero Dirichlet, eta == 1 */
+/* d 1..10, dims[k] 3..258 points (boundary included), sigma >= 0 and finite, nfields 1..16 stacked interior fields (component-
+ * major: several right-hand sides per call).  Errors as ell_pc_create.  The handle owns its matrices and work buffers: solve
+ * allocates nothing and does not synchronise the host. */
+int  cheb_helmholtz_create(int d, const int *dims, double sigma, int nfields, cheb_helmholtz **out);
+int  cheb_helmholtz_solve(cheb_helmholtz *h, const double *f_dev, double *u_dev, void *stream);  /* u == f allowed */
+int  cheb_helmholtz_apply(void *h, const double *x_dev, double *y_dev, void *stream);            /* chebhip_apply_fn */
+int  cheb_helmholtz_destroy(cheb_helmholtz *h);
+long cheb_helmholtz_size(const cheb_helmholtz *h);                                   /* nfields * prod(dims - 2); -1: NULL */
+/* S (nodal <- modal), S^-1 and lam of A_1 for a line of P points into HOST buffers (M = P - 2; S, Sinv M x M row-major, lam M);
+ * needs no device.  Modes by parity: position p < ceil(M/2) the p-th even mode, M-1-q the q-th odd one, each by ascending lam. */
+int  cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *lam);          /* M = P - 2, row-major */
 
 /* ------------------------------------------------------------------------- */
 /* The block preconditioners of the Stokes saddle-point system:  */

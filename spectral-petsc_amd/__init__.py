@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "stokes_pc_create_slab", "ell_pc_create_slab", "chebhip_fdpc_pencil_transform", "chebhip_dist_stokes_pc", "chebhip_dist_ell_pc",
     "stokes_saddle_create_slab",
     "cheb_resample_create", "cheb_resample_apply", "cheb_resample_destroy", "cheb_resample_size", "cheb_resample_matrix_host",
+    "cheb_helmholtz_create", "cheb_helmholtz_solve", "cheb_helmholtz_apply", "cheb_helmholtz_destroy", "cheb_helmholtz_size",
+    "cheb_helmholtz_line_host", "ell_pc_create_spectral",
 ]
 
 
@@ -219,6 +221,14 @@ def lib():
         L.cheb_resample_size.argtypes = [vp, C.c_int]
         L.cheb_resample_size.restype = C.c_long
         L.cheb_resample_matrix_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp]
+        L.cheb_helmholtz_create.argtypes = [C.c_int, ip, C.c_double, C.c_int, C.POINTER(vp)]
+        for f in (L.cheb_helmholtz_solve, L.cheb_helmholtz_apply):
+            f.argtypes = [vp, vp, vp, vp]
+        L.cheb_helmholtz_destroy.argtypes = [vp]
+        L.cheb_helmholtz_size.argtypes = [vp]
+        L.cheb_helmholtz_size.restype = C.c_long
+        L.cheb_helmholtz_line_host.argtypes = [C.c_int, dp, dp, dp]
+        L.ell_pc_create_spectral.argtypes = [vp, C.c_double, C.POINTER(vp)]
         _lib = L
     return _lib
 
@@ -390,6 +400,48 @@ class Resample:
     def destroy(self):
         if getattr(self, "_h", None):
             lib().cheb_resample_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def helmholtz_line(P):
+    """(S, Sinv, lam) of the spectral line operator A_1 = -(D D)[1..n-1, 1..n-1] of a line of P points (cheb_helmholtz_line_host):
+    A_1 = S diag(lam) S^-1, M = P - 2; modes by parity (even ones first, odd ones from the end).  Needs no device."""
+    import numpy as np
+    M = max(int(P) - 2, 0)
+    S, Si, lam = np.empty((M, M)), np.empty((M, M)), np.empty(M)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+    _chk(lib().cheb_helmholtz_line_host(int(P), ptr(S), ptr(Si), ptr(lam)))
+    return S, Si, lam
+
+
+class HelmholtzSolver:
+    """u = (sigma I + A)^-1 f with A the EllipticOp operator at eta == 1 (zero Dirichlet values) by fast diagonalisation
+    (cheb_helmholtz_*): `nfields` stacked interior fields of the grid `dims` per call; `size` values.  Usable as the M of
+    Fgmres.solve."""
+
+    def __init__(self, dims, sigma=0.0, nfields=1):
+        self.dims = tuple(int(d) for d in dims)
+        self.sigma = float(sigma)
+        self.nfields = int(nfields)
+        h = C.c_void_p()
+        _chk(lib().cheb_helmholtz_create(len(self.dims), _ints(self.dims), self.sigma, self.nfields, C.byref(h)))
+        self._h = h
+        self.size = lib().cheb_helmholtz_size(h)
+
+    def solve(self, f, u):
+        """Asynchronous on torch's current stream; u may be f."""
+        _chk(lib().cheb_helmholtz_solve(self._h, _dev_ptr(f, self.size), _dev_ptr(u, self.size), _stream()))
+        return u
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_helmholtz_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -768,6 +820,38 @@ class FdPc:
             pass
 
 
+class SpectralPc:
+    """z = (sigma I + A)^-1 (r / eta) for an EllipticOp (ell_pc_create_spectral): the direct solve of the constant-coefficient
+    operator after division by the viscosity.  `update` refreshes eta from the operator's last FormFunction; pass the object as
+    the `M` of Fgmres.solve."""
+
+    def __init__(self, op, sigma=0.0):
+        h = C.c_void_p()
+        _chk(lib().ell_pc_create_spectral(op._h, float(sigma), C.byref(h)))
+        self._h = h
+        self._op = op                     # the handle reads the operator's state: keep it alive
+        self.n = op.global_size
+        self.sigma = float(sigma)
+
+    def update(self):
+        _chk(lib().chebhip_fdpc_update(self._h, _stream()))
+
+    def apply(self, r, z):
+        _chk(lib().chebhip_fdpc_apply(self._h, _dev_ptr(r, self.n), _dev_ptr(z, self.n), _stream()))
+        return z
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().chebhip_fdpc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class StokesSaddlePc:
     """StokesPCApply0..3 (stokes.C:1714-1817) on the device: block LU / upper / diagonal / lower preconditioners of the
     saddle-point system, with the inner solves KSPVelocity, KSPSchur, KSPSchurVelocity (stokes.C:328-341).
@@ -838,8 +922,10 @@ class Fgmres:
         if op is None:
             return None, None
         kind = type(op).__name__
-        if kind == "FdPc":
+        if kind in ("FdPc", "SpectralPc"):
             return C.cast(lib().chebhip_fdpc_apply, C.c_void_p), op._h
+        if kind == "HelmholtzSolver":
+            return C.cast(lib().cheb_helmholtz_apply, C.c_void_p), op._h
         if kind == "StokesSaddlePc":
             return C.cast(lib().stokes_saddle_apply, C.c_void_p), op._h
         if kind in ("EllipticOp", "StokesOp"):

@@ -379,6 +379,331 @@ bool fdm_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fast diagonalisation of the SPECTRAL line operator (Haidvogel-Zang): A_1 = -(D D)[1..n-1, 1..n-1] on the M = P-2 interior
+// nodes, the operator MatMult_Elliptic applies along one direction at eta == 1 (elliptic.C:305-334).  A_1 is not symmetric and
+// no diagonal scaling makes it so; its eigenvalues are real, positive and simple (pi^2/4 .. ~0.05 n^4).  A_1 is centro-symmetric,
+// so, as in fdm_line, the even and the odd vectors are diagonalised separately:
+//     even half  Ae[i][j] = A[i][j] + A[i][m-j]   (odd M: the middle column j = m/2 once),   x_{m-i} = x_i
+//     odd half   Ao[i][j] = A[i][j] - A[i][m-j],                                            x_{m-i} = -x_i (middle 0)
+// Each half: balancing (exact powers of two), Householder reduction to Hessenberg form, Francis double-shift QR for the
+// eigenvalues (EISPACK hqr), eigenvectors by inverse iteration on the Hessenberg matrix, all in long double.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+typedef std::vector<long double> LVec;
+
+// A <- D^-1 A D with D = diag(scale), powers of two (EISPACK balanc without the permutations)
+void balance(int n, LVec &A, LVec &scale) {
+  scale.assign(n, 1.0L);
+  const long double RADIX = 2.0L, SQRDX = RADIX * RADIX;
+  bool done = false;
+  while (!done) {
+    done = true;
+    for (int i = 0; i < n; i++) {
+      long double r = 0.0L, c = 0.0L;
+      for (int j = 0; j < n; j++)
+        if (j != i) { c += fabsl(A[(size_t)j * n + i]); r += fabsl(A[(size_t)i * n + j]); }
+      if (c == 0.0L || r == 0.0L) continue;
+      long double g = r / RADIX, f = 1.0L;
+      const long double s = c + r;
+      while (c < g) { f *= RADIX; c *= SQRDX; }
+      g = r * RADIX;
+      while (c > g) { f /= RADIX; c /= SQRDX; }
+      if ((c + r) / f < 0.95L * s) {
+        done = false;
+        g = 1.0L / f;
+        scale[i] *= f;
+        for (int j = 0; j < n; j++) A[(size_t)i * n + j] *= g;
+        for (int j = 0; j < n; j++) A[(size_t)j * n + i] *= f;
+      }
+    }
+  }
+}
+
+// A <- Q^T A Q upper Hessenberg (Householder); Q (row-major, n x n) returned explicitly
+void hessenberg(int n, LVec &A, LVec &Q) {
+  Q.assign((size_t)n * n, 0.0L);
+  for (int i = 0; i < n; i++) Q[(size_t)i * n + i] = 1.0L;
+  LVec v(n);
+  for (int k = 0; k + 2 < n; k++) {
+    long double nx = 0.0L;
+    for (int i = k + 1; i < n; i++) nx += A[(size_t)i * n + k] * A[(size_t)i * n + k];
+    nx = sqrtl(nx);
+    if (nx == 0.0L) continue;
+    const long double x0 = A[(size_t)(k + 1) * n + k], alpha = x0 < 0 ? nx : -nx;
+    long double vv = 0.0L;
+    for (int i = k + 1; i < n; i++) { v[i] = A[(size_t)i * n + k]; }
+    v[k + 1] -= alpha;
+    for (int i = k + 1; i < n; i++) vv += v[i] * v[i];
+    if (vv == 0.0L) continue;
+    const long double beta = 2.0L / vv;
+    for (int j = 0; j < n; j++) {                       // A <- (I - beta v v^T) A
+      long double s = 0.0L;
+      for (int i = k + 1; i < n; i++) s += v[i] * A[(size_t)i * n + j];
+      s *= beta;
+      for (int i = k + 1; i < n; i++) A[(size_t)i * n + j] -= s * v[i];
+    }
+    for (int i = 0; i < n; i++) {                       // A <- A (I - beta v v^T),  Q <- Q (I - beta v v^T)
+      long double s = 0.0L, t = 0.0L;
+      for (int j = k + 1; j < n; j++) { s += A[(size_t)i * n + j] * v[j]; t += Q[(size_t)i * n + j] * v[j]; }
+      s *= beta; t *= beta;
+      for (int j = k + 1; j < n; j++) { A[(size_t)i * n + j] -= s * v[j]; Q[(size_t)i * n + j] -= t * v[j]; }
+    }
+    for (int i = k + 2; i < n; i++) A[(size_t)i * n + k] = 0.0L;
+  }
+}
+
+// Eigenvalues (wr, wi) of the upper Hessenberg matrix a (destroyed): EISPACK hqr, Francis double-shift QR
+bool hqr(int n, LVec a, LVec &wr, LVec &wi) {
+  auto A = [&](int i, int j) -> long double & { return a[(size_t)(i - 1) * n + (j - 1)]; };   // 1-based, as EISPACK
+  wr.assign(n + 1, 0.0L); wi.assign(n + 1, 0.0L);
+  long double anorm = 0.0L;
+  for (int i = 1; i <= n; i++)
+    for (int j = std::max(i - 1, 1); j <= n; j++) anorm += fabsl(A(i, j));
+  int nn = n, l = 1;
+  long double t = 0.0L, p = 0.0L, q = 0.0L, r = 0.0L, s, w, x, y, z;
+  while (nn >= 1) {
+    int its = 0;
+    do {
+      for (l = nn; l >= 2; l--) {
+        s = fabsl(A(l - 1, l - 1)) + fabsl(A(l, l));
+        if (s == 0.0L) s = anorm;
+        if (fabsl(A(l, l - 1)) + s == s) { A(l, l - 1) = 0.0L; break; }
+      }
+      x = A(nn, nn);
+      if (l == nn) { wr[nn] = x + t; wi[nn--] = 0.0L; }
+      else {
+        y = A(nn - 1, nn - 1);
+        w = A(nn, nn - 1) * A(nn - 1, nn);
+        if (l == nn - 1) {
+          p = 0.5L * (y - x);
+          q = p * p + w;
+          z = sqrtl(fabsl(q));
+          x += t;
+          if (q >= 0.0L) {
+            z = p + (p >= 0 ? z : -z);
+            wr[nn - 1] = wr[nn] = x + z;
+            if (z != 0.0L) wr[nn] = x - w / z;
+            wi[nn - 1] = wi[nn] = 0.0L;
+          } else {
+            wr[nn - 1] = wr[nn] = x + p;
+            wi[nn - 1] = -(wi[nn] = z);
+          }
+          nn -= 2;
+        } else {
+          if (its == 60) return false;
+          if (its == 10 || its == 20 || its == 40) {       // exceptional shifts
+            t += x;
+            for (int i = 1; i <= nn; i++) A(i, i) -= x;
+            s = fabsl(A(nn, nn - 1)) + fabsl(A(nn - 1, nn - 2));
+            y = x = 0.75L * s;
+            w = -0.4375L * s * s;
+          }
+          ++its;
+          int m;
+          for (m = nn - 2; m >= l; m--) {
+            z = A(m, m);
+            r = x - z;
+            s = y - z;
+            p = (r * s - w) / A(m + 1, m) + A(m, m + 1);
+            q = A(m + 1, m + 1) - z - r - s;
+            r = A(m + 2, m + 1);
+            s = fabsl(p) + fabsl(q) + fabsl(r);
+            p /= s; q /= s; r /= s;
+            if (m == l) break;
+            const long double u = fabsl(A(m, m - 1)) * (fabsl(q) + fabsl(r));
+            const long double v = fabsl(p) * (fabsl(A(m - 1, m - 1)) + fabsl(z) + fabsl(A(m + 1, m + 1)));
+            if (u + v == v) break;
+          }
+          for (int i = m + 2; i <= nn; i++) {
+            A(i, i - 2) = 0.0L;
+            if (i != m + 2) A(i, i - 3) = 0.0L;
+          }
+          for (int k = m; k <= nn - 1; k++) {
+            if (k != m) {
+              p = A(k, k - 1);
+              q = A(k + 1, k - 1);
+              r = 0.0L;
+              if (k != nn - 1) r = A(k + 2, k - 1);
+              if ((x = fabsl(p) + fabsl(q) + fabsl(r)) != 0.0L) { p /= x; q /= x; r /= x; }
+            }
+            const long double sq = sqrtl(p * p + q * q + r * r);
+            if ((s = (p >= 0 ? sq : -sq)) != 0.0L) {
+              if (k == m) { if (l != m) A(k, k - 1) = -A(k, k - 1); }
+              else A(k, k - 1) = -s * x;
+              p += s;
+              x = p / s; y = q / s; z = r / s;
+              q /= p; r /= p;
+              for (int j = k; j <= nn; j++) {
+                p = A(k, j) + q * A(k + 1, j);
+                if (k != nn - 1) { p += r * A(k + 2, j); A(k + 2, j) -= p * z; }
+                A(k + 1, j) -= p * y;
+                A(k, j) -= p * x;
+              }
+              const int mmin = nn < k + 3 ? nn : k + 3;
+              for (int i = l; i <= mmin; i++) {
+                p = x * A(i, k) + y * A(i, k + 1);
+                if (k != nn - 1) { p += z * A(i, k + 2); A(i, k + 2) -= p * r; }
+                A(i, k + 1) -= p * q;
+                A(i, k) -= p;
+              }
+            }
+          }
+        }
+      }
+    } while (l < nn - 1);
+  }
+  wr.erase(wr.begin()); wi.erase(wi.begin());
+  return true;
+}
+
+// Eigenvector y of the upper Hessenberg matrix H for its eigenvalue mu: inverse iteration, (H - mu I) = LU with partial pivoting
+// (neighbouring rows only), a zero pivot replaced by eps |H|
+void hess_inverse_iteration(int n, const LVec &H, long double mu, long double hnorm, LVec &y) {
+  LVec U((size_t)n * n);
+  for (size_t i = 0; i < U.size(); i++) U[i] = H[i];
+  for (int i = 0; i < n; i++) U[(size_t)i * n + i] -= mu;
+  std::vector<char> swp(n, 0);
+  LVec lm(n, 0.0L);
+  const long double tiny = 1e-19L * (hnorm > 0 ? hnorm : 1.0L);
+  for (int k = 0; k + 1 < n; k++) {
+    if (fabsl(U[(size_t)(k + 1) * n + k]) > fabsl(U[(size_t)k * n + k])) {
+      swp[k] = 1;
+      for (int j = k; j < n; j++) std::swap(U[(size_t)k * n + j], U[(size_t)(k + 1) * n + j]);
+    }
+    if (U[(size_t)k * n + k] == 0.0L) U[(size_t)k * n + k] = tiny;
+    const long double f = U[(size_t)(k + 1) * n + k] / U[(size_t)k * n + k];
+    lm[k] = f;
+    U[(size_t)(k + 1) * n + k] = 0.0L;
+    for (int j = k + 1; j < n; j++) U[(size_t)(k + 1) * n + j] -= f * U[(size_t)k * n + j];
+  }
+  if (U[(size_t)(n - 1) * n + n - 1] == 0.0L) U[(size_t)(n - 1) * n + n - 1] = tiny;
+  y.assign(n, 1.0L);
+  for (int it = 0; it < 3; it++) {
+    for (int k = 0; k + 1 < n; k++) {                     // L
+      if (swp[k]) std::swap(y[k], y[k + 1]);
+      y[k + 1] -= lm[k] * y[k];
+    }
+    for (int i = n - 1; i >= 0; i--) {                    // U
+      long double s = y[i];
+      for (int j = i + 1; j < n; j++) s -= U[(size_t)i * n + j] * y[j];
+      y[i] = s / U[(size_t)i * n + i];
+    }
+    long double mx = 0.0L;
+    for (int i = 0; i < n; i++) mx = std::max(mx, fabsl(y[i]));
+    if (!(mx > 0.0L) || !std::isfinite((double)mx)) return;
+    for (int i = 0; i < n; i++) y[i] /= mx;
+  }
+}
+
+// In-place inverse of a dense n x n matrix (LU with partial pivoting); false if singular
+bool invert(int n, LVec &A) {
+  LVec inv((size_t)n * n, 0.0L);
+  for (int i = 0; i < n; i++) inv[(size_t)i * n + i] = 1.0L;
+  for (int k = 0; k < n; k++) {
+    int piv = k;
+    for (int i = k + 1; i < n; i++) if (fabsl(A[(size_t)i * n + k]) > fabsl(A[(size_t)piv * n + k])) piv = i;
+    if (A[(size_t)piv * n + k] == 0.0L) return false;
+    if (piv != k)
+      for (int j = 0; j < n; j++) { std::swap(A[(size_t)k * n + j], A[(size_t)piv * n + j]); std::swap(inv[(size_t)k * n + j], inv[(size_t)piv * n + j]); }
+    const long double d = A[(size_t)k * n + k];
+    for (int i = 0; i < n; i++) {
+      if (i == k) continue;
+      const long double f = A[(size_t)i * n + k] / d;
+      if (f == 0.0L) continue;
+      for (int j = 0; j < n; j++) { A[(size_t)i * n + j] -= f * A[(size_t)k * n + j]; inv[(size_t)i * n + j] -= f * inv[(size_t)k * n + j]; }
+    }
+    for (int j = 0; j < n; j++) { A[(size_t)k * n + j] /= d; inv[(size_t)k * n + j] /= d; }
+  }
+  A.swap(inv);
+  return true;
+}
+
+// Real eigenvalues (ascending) and eigenvectors (columns of V, row-major n x n) of a dense real matrix A whose spectrum is
+// real and simple; false on complex or repeated eigenvalues or if the QR iteration does not converge
+bool eig_real_simple(int n, const LVec &A0, LVec &lam, LVec &V) {
+  LVec A = A0, scale, Q, wr, wi;
+  balance(n, A, scale);
+  hessenberg(n, A, Q);
+  long double hnorm = 0.0L;
+  for (int i = 0; i < n; i++) for (int j = std::max(i - 1, 0); j < n; j++) hnorm = std::max(hnorm, fabsl(A[(size_t)i * n + j]));
+  if (!hqr(n, A, wr, wi)) return false;
+  for (int i = 0; i < n; i++) if (wi[i] != 0.0L) return false;
+  std::sort(wr.begin(), wr.end());
+  for (int i = 0; i + 1 < n; i++)                       // (a gap of a few thousand rounding units of |H|: not distinguishable)
+    if (wr[i + 1] - wr[i] <= 1e-15L * hnorm) return false;
+  lam = wr;
+  V.assign((size_t)n * n, 0.0L);
+  LVec y;
+  for (int q = 0; q < n; q++) {
+    hess_inverse_iteration(n, A, lam[q], hnorm, y);
+    for (int i = 0; i < n; i++) {                       // x = D Q y
+      long double s = 0.0L;
+      for (int j = 0; j < n; j++) s += Q[(size_t)i * n + j] * y[j];
+      V[(size_t)i * n + q] = scale[i] * s;
+    }
+  }
+  for (size_t i = 0; i < V.size(); i++) if (!std::isfinite((double)V[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam) {
+  const int n = P - 1, M = P - 2;
+  if (M < 1) return false;
+  const int m = M - 1, He = (M + 1) / 2, Ho = M / 2;
+  const bool has_mid = (M & 1) != 0;
+  std::vector<long double> D((size_t)P * P), A((size_t)M * M);
+  for (int i = 0; i < P; i++) for (int j = 0; j < P; j++) D[(size_t)i * P + j] = dentry(i, j, n);
+  for (int i = 0; i < M; i++)
+    for (int j = 0; j < M; j++) {
+      long double s = 0.0L;
+      for (int q = 0; q < P; q++) s += D[(size_t)(i + 1) * P + q] * D[(size_t)q * P + (j + 1)];
+      A[(size_t)i * M + j] = -s;
+    }
+  S.assign((size_t)M * M, 0.0L); Sinv.assign((size_t)M * M, 0.0L);
+  lam.assign(M, 0.0L);
+  for (int parity = 0; parity < 2; parity++) {            // 0: even, 1: odd
+    const int h = parity == 0 ? He : Ho;
+    if (h == 0) continue;
+    const long double sg = parity == 0 ? 1.0L : -1.0L;
+    LVec Ah((size_t)h * h), lh, V;
+    for (int i = 0; i < h; i++)
+      for (int j = 0; j < h; j++)
+        Ah[(size_t)i * h + j] = (has_mid && parity == 0 && j == h - 1) ? A[(size_t)i * M + j] : A[(size_t)i * M + j] + sg * A[(size_t)i * M + (m - j)];
+    if (!eig_real_simple(h, Ah, lh, V)) return false;
+    // columns normalised as full-line vectors: the half coordinate i < h stands for two points (one: the middle point)
+    for (int q = 0; q < h; q++) {
+      long double nrm = 0.0L;
+      for (int i = 0; i < h; i++) nrm += ((has_mid && parity == 0 && i == h - 1) ? 1.0L : 2.0L) * V[(size_t)i * h + q] * V[(size_t)i * h + q];
+      nrm = sqrtl(nrm);
+      // sign: the largest component positive (a deterministic choice)
+      int im = 0;
+      for (int i = 1; i < h; i++) if (fabsl(V[(size_t)i * h + q]) > fabsl(V[(size_t)im * h + q])) im = i;
+      if (V[(size_t)im * h + q] < 0) nrm = -nrm;
+      for (int i = 0; i < h; i++) V[(size_t)i * h + q] /= nrm;
+    }
+    LVec Vi = V;
+    if (!invert(h, Vi)) return false;
+    for (int q = 0; q < h; q++) {
+      const int pos = parity == 0 ? q : m - q;
+      lam[pos] = lh[q];
+      for (int i = 0; i < h; i++) {
+        const long double v = V[(size_t)i * h + q];
+        const bool mid = has_mid && parity == 0 && i == h - 1;
+        // S^-1 S = I with rows of the same parity: the half-coordinate inverse, halved where a coordinate stands for two points
+        const long double r = mid ? Vi[(size_t)q * h + i] : 0.5L * Vi[(size_t)q * h + i];
+        S[(size_t)i * M + pos] = v;
+        Sinv[(size_t)pos * M + i] = r;
+        if (!mid) { S[(size_t)(m - i) * M + pos] = sg * v; Sinv[(size_t)pos * M + (m - i)] = sg * r; }
+      }
+    }
+  }
+  return true;
+}
+
 // centro-symmetric (part = 1) or centro-antisymmetric (part = 0) part of a dense M x M matrix
 void centro_part(int M, const std::vector<long double> &A, int part, std::vector<long double> &out) {
   out.resize((size_t)M * M);

@@ -17,6 +17,11 @@
 // scaling.  For eta == 1 that is the exact inverse of P; for variable coefficients the approximate solve is
 // `sweeps` iterations of GMRES on P z = r with P_1^-1 (1/eta) as its right preconditioner (sweeps = 0: that
 // preconditioner alone) -- a varying, hence flexible, preconditioner for the outer FGMRES, as ILU(2) is not.
+//
+// The same pipeline diagonalises the SPECTRAL operator (Haidvogel-Zang): with the line operator A_1 = -(D D)[interior]
+// (diffmat.cpp: spec_line) in place of T, the solve is the exact inverse of MatMult_Elliptic at eta == 1, shifted by sigma
+// (every modal weight becomes 1 / (sigma + l_i + l_j + l_k): sigma rides on a per-handle copy of dimension 0's eigenvalues).
+// Such a handle has no stencil: ell_pc_create_spectral gives z = (sigma I + A)^-1 (r / eta), cheb_helmholtz_* the bare solve.
 #include "../../include/chebhip.h"
 #include "ops.h"
 #include "sweep.h"
@@ -282,8 +287,13 @@ struct LineMats { DiffMat Fcs, Fca, Bcs, Bca, Fraw, Braw; double *lam = nullptr;
 
 }  // namespace
 
+enum LineKind { LINE_FD = 0, LINE_SPECTRAL = 1 };
+
 struct chebhip_fdpc {
   Geo geo;
+  int kind = LINE_FD;                          // LINE_SPECTRAL: lines from spec_line, no stencil (sweeps = 0 only)
+  bool bare = false;                           // no operator behind the handle (cheb_helmholtz): no eta, no update
+  double *lam0 = nullptr;                      // spectral: sigma + eigenvalues of dimension 0 (a copy: lines[] is shared by extents)
   long N = 0, G = 0;
   int nf = 1;                                  // 1: scalar operator; d: Stokes velocity (component-major inside)
   bool interleaved = false;                    // vectors at the ABI are node-major (Stokes)
@@ -315,12 +325,15 @@ static void fdpc_free(chebhip_fdpc *pc) {
     if (kv.second.lam) (void)hipFree(kv.second.lam);
   }
   for (int k = 0; k < MAXD; k++) if (pc->xs[k]) (void)hipFree(pc->xs[k]);
-  double *all[] = {pc->cf, pc->eta_g, pc->t0, pc->t1, pc->t2, pc->t3, pc->t4, pc->t5, pc->W, pc->Einv};
+  double *all[] = {pc->cf, pc->eta_g, pc->t0, pc->t1, pc->t2, pc->t3, pc->t4, pc->t5, pc->W, pc->Einv, pc->lam0};
   for (double *p : all) if (p) (void)hipFree(p);
   delete pc;
 }
 
-static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc **out, int gP0 = 0) {
+// kind: LINE_FD (the finite-difference matrix) or LINE_SPECTRAL (sigma + the collocation operator at eta == 1); bare: a spectral
+// handle without an operator (v0.ixL / eta unused): only the buffers of the plain solve are allocated
+static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc **out, int gP0 = 0, int kind = LINE_FD, double sigma = 0.0,
+                       bool bare = false) {
   *out = nullptr;
   FdView v = v0;
   std::vector<int> gdims(v0.dims, v0.dims + (v0.d >= 1 && v0.d <= MAXD ? v0.d : 0));
@@ -333,6 +346,8 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
   chebhip_fdpc *pc = new (std::nothrow) chebhip_fdpc;
   if (!pc) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   pc->geo.d = v.d; pc->N = v.N; pc->G = v.G; pc->nf = nf; pc->interleaved = interleaved;
+  pc->kind = kind; pc->bare = bare;
+  if (kind == LINE_SPECTRAL) { pc->sweeps = 0; pc->assembled = bare; }
   for (int k = 0; k < v.d; k++) pc->geo.dims[k] = v.dims[k];
   { long s = 1; for (int k = v.d - 1; k >= 0; k--) { pc->geo.gs[k] = s; s *= (v.dims[k] - 2); } }
 #define PCCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fdpc_free(pc); \
@@ -349,7 +364,10 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     if (pc->lines.count(P)) continue;
     LineMats lm;
     std::vector<long double> S, Si, lam, part;
-    if (!fdm_line(P, S, Si, lam)) { fdpc_free(pc); return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point line operator failed", P); }
+    if (!(kind == LINE_SPECTRAL ? spec_line(P, S, Si, lam) : fdm_line(P, S, Si, lam))) {
+      fdpc_free(pc);
+      return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point %s line operator failed", P, kind == LINE_SPECTRAL ? "spectral" : "finite-difference");
+    }
     centro_part(M, Si, 1, part); PCCHK(diffmat_from_dense(M, part.data(), 1, &lm.Fcs));
     centro_part(M, Si, 0, part); PCCHK(diffmat_from_dense(M, part.data(), 0, &lm.Fca));
     centro_part(M, S, 1, part);  PCCHK(diffmat_from_dense(M, part.data(), 1, &lm.Bcs));
@@ -380,19 +398,29 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     lm.ok = true;
     pc->lines[P] = lm;
   }
+  if (kind == LINE_SPECTRAL) {
+    const int M0 = v.dims[0] - 2;
+    std::vector<double> l0(M0);
+    PCCHK(hipMemcpy(l0.data(), pc->lines[v.dims[0]].lam, M0 * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < M0; i++) l0[i] += sigma;
+    PCCHK(hipMalloc((void **)&pc->lam0, M0 * sizeof(double)));
+    PCCHK(hipMemcpy(pc->lam0, l0.data(), M0 * sizeof(double), hipMemcpyHostToDevice));
+  }
   const size_t gb = (size_t)(v.G > 0 ? v.G : 1) * sizeof(double);
-  PCCHK(hipMalloc((void **)&pc->cf, (2 * v.d + 1) * gb));
-  PCCHK(hipMalloc((void **)&pc->eta_g, gb));
+  if (kind == LINE_FD) PCCHK(hipMalloc((void **)&pc->cf, (2 * v.d + 1) * gb));
+  if (!bare) PCCHK(hipMalloc((void **)&pc->eta_g, gb));
   PCCHK(hipMalloc((void **)&pc->t0, nf * gb)); PCCHK(hipMalloc((void **)&pc->t1, nf * gb));
-  PCCHK(hipMalloc((void **)&pc->t2, nf * gb)); PCCHK(hipMalloc((void **)&pc->t3, nf * gb));
-  PCCHK(hipMalloc((void **)&pc->t4, nf * gb)); PCCHK(hipMalloc((void **)&pc->t5, nf * gb));
+  if (!bare) {
+    PCCHK(hipMalloc((void **)&pc->t2, nf * gb)); PCCHK(hipMalloc((void **)&pc->t3, nf * gb));
+    PCCHK(hipMalloc((void **)&pc->t4, nf * gb)); PCCHK(hipMalloc((void **)&pc->t5, nf * gb));
+  }
   // the operand arrays of the pointwise steps that ride inside the line transforms (fdm_solve: filled on first use / by update);
   // allocated here so that no solve meets a hipMalloc.  A failed allocation only means the separate passes run.
   if (!opt(OPT_FDM_PASSES) && v.G > 0) {
     bool any_long = false;
     for (int k = 0; k < v.d; k++) any_long = any_long || v.dims[k] - 2 > 64;
     if (v.d >= 2 && v.d <= 3 && hipMalloc((void **)&pc->W, nf * gb) != hipSuccess) { pc->W = nullptr; (void)hipGetLastError(); }
-    if (any_long && hipMalloc((void **)&pc->Einv, nf * gb) != hipSuccess) { pc->Einv = nullptr; (void)hipGetLastError(); }
+    if (any_long && !bare && hipMalloc((void **)&pc->Einv, nf * gb) != hipSuccess) { pc->Einv = nullptr; (void)hipGetLastError(); }
   }
 #undef PCCHK
   *out = pc;
@@ -414,12 +442,13 @@ static int fdpc_eta_inverse(chebhip_fdpc *pc, hipStream_t st) {
 }
 
 static int fdpc_update(chebhip_fdpc *pc, hipStream_t st) {
+  if (pc->bare) return 0;
   FdView v;
   int rc = pc->eop ? ell_op_fd_view_any(pc->eop, &v, nullptr) : stokes_op_fd_view_any(pc->sop, &v, nullptr);
   if (!rc && pc->eop) rc = ell_op_sync_coeffs(pc->eop, (void *)st);
   if (rc) return rc;
   if (pc->G == 0) { pc->assembled = true; return 0; }
-  if (pc->slab) {
+  if (pc->slab || pc->kind == LINE_SPECTRAL) {            // no stencil: only eta at the interior nodes
     hipLaunchKernelGGL(k_eta_g, dim3(pgrid(pc->N)), dim3(256), 0, st, pc->N, v.ixL, v.eta, pc->eta_g);
     PHIPCHK(hipGetLastError());
     pc->assembled = true;
@@ -504,6 +533,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
     }
   }
   LamPtrs lam; for (int k = 0; k < MAXD; k++) lam.p[k] = k < d ? pc->lines[pc->geo.dims[k]].lam : nullptr;
+  if (pc->lam0) lam.p[0] = pc->lam0;                      // spectral: sigma + l_0 (every weight path reads dimension 0's array)
   const int nl = pc->geo.dims[d - 1] - 2;
   const long lines = pc->G / nl;
   if (pc->slab && d >= 2) lam.p[0] += pc->i0_off;         // the slab's first interior plane is plane i0_off of the global line
@@ -570,6 +600,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
 
 static int fdpc_mult(chebhip_fdpc *pc, const double *x, double *y, hipStream_t st) {
   if (pc->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_mult: the stencil of P is not available on slabs (no halo exchange)");
+  if (pc->kind == LINE_SPECTRAL) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_mult: a spectral preconditioner has no stencil");
   if (!pc->assembled) { int rc = fdpc_update(pc, st); if (rc) return rc; }
   if (pc->G == 0) return 0;
   const long n = pc->G * pc->nf;
@@ -679,6 +710,7 @@ extern "C" int chebhip_fdpc_update(chebhip_fdpc *pc, void *stream) { if (!pc) re
 extern "C" int chebhip_fdpc_set_sweeps(chebhip_fdpc *pc, int sweeps) {
   if (!pc || sweeps < 0 || sweeps > 64) return chebhip_fail(CHEBHIP_ERR_ARG, "sweeps must be in 0..64");
   if (pc->slab && sweeps != 0) return chebhip_fail(CHEBHIP_ERR_ARG, "slab-mode preconditioner: sweeps must be 0");
+  if (pc->kind == LINE_SPECTRAL && sweeps != 0) return chebhip_fail(CHEBHIP_ERR_ARG, "spectral preconditioner: sweeps must be 0");
   pc->sweeps = sweeps; return 0;
 }
 extern "C" int chebhip_fdpc_mult(chebhip_fdpc *pc, const double *x, double *y, void *stream) {
@@ -705,4 +737,81 @@ extern "C" int chebhip_fdpc_apply(void *ctx, const double *r, double *z, void *s
   if (r && r == z) return chebhip_fail(CHEBHIP_ERR_ARG, "r and z must be distinct");
   StageTimer tm(CHEBHIP_STAGE_FDPC_APPLY, stream);
   return fdpc_apply(pc, r, z, (hipStream_t)stream);
+}
+
+// ---- C ABI: the spectral preconditioner and the direct Helmholtz solve ------------------------------------------
+static int check_sigma(double sigma) {
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return chebhip_fail(CHEBHIP_ERR_ARG, "sigma = %g must be finite and >= 0", sigma);
+  return 0;
+}
+
+extern "C" int ell_pc_create_spectral(ell_op *op, double sigma, chebhip_fdpc **out) {
+  if (!op || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  int rc = check_sigma(sigma); if (rc) return rc;
+  FdView v; rc = ell_op_fd_view(op, &v); if (rc) return rc;             // (refuses slab-mode handles)
+  rc = fdpc_create(v, 1, false, out, 0, LINE_SPECTRAL, sigma); if (rc) return rc;
+  (*out)->eop = op;
+  return 0;
+}
+
+struct cheb_helmholtz {
+  chebhip_fdpc *pc = nullptr;
+  long n = 0;                                  // nfields * prod(dims - 2)
+};
+
+extern "C" int cheb_helmholtz_create(int d, const int *dims, double sigma, int nfields, cheb_helmholtz **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  int rc = check_sigma(sigma); if (rc) return rc;
+  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  long N = 1, G = 1;
+  for (int k = 0; k < d; k++) {
+    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
+    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
+    G *= dims[k] - 2;
+    if (G * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 unknowns");
+    N *= dims[k];                              // (<= 3^d G: no overflow)
+  }
+  FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
+  cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true);
+  if (rc) { delete h; return rc; }
+  h->n = G * nfields;
+  *out = h;
+  return 0;
+}
+
+extern "C" int cheb_helmholtz_solve(cheb_helmholtz *h, const double *f_dev, double *u_dev, void *stream) {
+  if (!h || !h->pc) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!f_dev || !u_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL vector");
+  // the first forward transform reads f into scratch and the last backward one writes u: u == f is safe
+  return fdm_solve(h->pc, f_dev, u_dev, (hipStream_t)stream);
+}
+
+extern "C" int cheb_helmholtz_apply(void *h, const double *x_dev, double *y_dev, void *stream) {
+  return cheb_helmholtz_solve((cheb_helmholtz *)h, x_dev, y_dev, stream);
+}
+
+extern "C" int cheb_helmholtz_destroy(cheb_helmholtz *h) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  fdpc_free(h->pc);
+  delete h;
+  return 0;
+}
+
+extern "C" long cheb_helmholtz_size(const cheb_helmholtz *h) { return h ? h->n : -1; }
+
+extern "C" int cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *lam) {
+  if (P < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "P = %d: a line needs interior nodes (P >= 3)", P);
+  if (P > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "P = %d: at most 258 points per line", P);
+  if (!S || !Sinv || !lam) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  std::vector<long double> s, si, l;
+  if (!spec_line(P, s, si, l)) return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point spectral line operator failed", P);
+  const int M = P - 2;
+  for (size_t i = 0; i < (size_t)M * M; i++) { S[i] = (double)s[i]; Sinv[i] = (double)si[i]; }
+  for (int i = 0; i < M; i++) lam[i] = (double)l[i];
+  return 0;
 }

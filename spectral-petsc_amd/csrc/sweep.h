@@ -215,6 +215,9 @@ int opt_find(const char *name);      // -1: no such option
 // Fast diagonalisation of the 1-D three-point operator of the finite-difference preconditioners (diffmat.cpp)
 // Modes are ordered by parity: position p < ceil(M/2) holds the p-th even mode, position M-1-q the q-th odd one
 bool fdm_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam);
+// The same layout for the spectral line operator A_1 = -(D D)[1..n-1, 1..n-1] (nonsymmetric; real, simple, positive spectrum):
+// A_1 = S diag(lam) S^-1, false on complex / repeated eigenvalues (diffmat.cpp)
+bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam);
 void centro_part(int M, const std::vector<long double> &A, int part, std::vector<long double> &out);
 
 }  // namespace chebhip

@@ -5,6 +5,7 @@ Each Newton step evaluates FormFunction (which leaves eta, eta', grad u behind, 
 solves J dx = -F with the matrix-free Jacobian MatMult_Elliptic (elliptic.C:297-339) by restarted FGMRES
 (chebhip_fgmres_*), and updates x along dx with a backtracking line search; `M` is the slot for a right preconditioner
 (the reference uses ILU(2) of a finite-difference matrix, elliptic.C:184-185, which stays PETSc's).
+poisson_solve is the direct route for the linear problem (gamma = 0): one FormFunction and one fast-diagonalisation solve.
 """
 import torch
 
@@ -52,6 +53,29 @@ def newton_krylov(sp, op, b, x, gamma=0.0, exponent=2.0, snes_rtol=1e-8, snes_at
         if own_ks:
             ks.destroy()
     return it, total, fn
+
+
+def poisson_solve(sp, op, b, x, sigma=0.0, solver=None):
+    """The linear problem sigma u + A u = b with the Dirichlet values set on `op` (A: MatMult_Elliptic at gamma = 0, eta == 1),
+    solved directly instead of by Newton-Krylov: one FormFunction at x = 0 gives F0 = A_IB g - b (the boundary values' part of the
+    operator minus the right-hand side), and x = (sigma I + A_II)^-1 (-F0) by fast diagonalisation (sp.HelmholtzSolver).
+    b, x: device tensors of op.global_size (x is overwritten; it may not be b).  solver: a caller's HelmholtzSolver(op.dims, sigma)
+    to use and keep; None: one is made and destroyed here.  Returns x."""
+    own = solver is None
+    if own:
+        solver = sp.HelmholtzSolver(op.dims, sigma)
+    elif solver.dims != tuple(op.dims) or solver.sigma != float(sigma) or solver.size != op.global_size:
+        raise ValueError("solver: a HelmholtzSolver of the operator's grid with sigma = %g and one field" % sigma)
+    try:
+        x.zero_()
+        F = torch.empty_like(x)
+        op.function(x, b, F, 0.0, 2.0)
+        F.neg_()
+        solver.solve(F, x)
+    finally:
+        if own:
+            solver.destroy()
+    return x
 
 
 def continuation_schedule(exponent, regularization, cont0=0, cont=1):
