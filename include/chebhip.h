@@ -479,6 +479,33 @@ long cheb_helmholtz_size(const cheb_helmholtz *h);                              
  * needs no device.  Modes by parity: position p < ceil(M/2) the p-th even mode, M-1-q the q-th odd one, each by ascending lam. */
 int  cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *lam);          /* M = P - 2, row-major */
 
+/* The same solve with a condition alpha u + beta du/dnu = g on every face: Dirichlet (1, 0), Neumann (0, 1),  */
+/* Robin otherwise; du/dnu is the outward normal derivative.  An end whose row eliminates it from the collocation of      */
+/* -(D D) turns each line operator into A~ = -(DD)_II - (DD)_IB Q, with u_B = Q u_I + B_BB^-1 g; equal ends keep the      */
+/* parity split, different ends one dense decomposition (two-launch transforms).  The unknowns stay the interior nodes:    */
+/* (sigma I + sum_k A~_k) u_I = f_I + sum_k L_k g (the lift), then the boundary of the full grid is rebuilt direction by   */
+/* direction (k = 0 .. d-1: every node is set once, by the highest direction in which it is an end node, from that face's  */
+/* condition).  sigma = 0 with Neumann on every face is singular: the product of the zero modes gets weight 0, so the      */
+/* solution has no component along it (w . u_I = 0, w the product of the lines' zero-mode rows of S^-1) and that part of  */
+/* the lifted right-hand side is discarded.                                                                               */
+/* bc: 4*d doubles, per direction k: alpha_first, beta_first, alpha_last, beta_last
+ * ("first" = grid index 0 = x=+1, "last" = index n = x=-1; du/dnu outward).  alpha, beta >= 0, finite, not both 0.  Other
+ * limits as cheb_helmholtz_create, and nfields * N <= 2^31 - 1.  cheb_helmholtz_solve / _apply on such a handle solve the
+ * interior problem with g = 0 (usable as Fgmres's M). */
+int  cheb_helmholtz_create_bc(int d, const int *dims, const double *bc, double sigma, int nfields, cheb_helmholtz **out);
+/* f: nfields x G interior values; g: nfields x (N-G) compact boundary values in row-major node order (the
+ * ell_op_set_dirichlet layout), NULL = zero data; u: nfields x N full-grid values.  u may not alias f or g.  Asynchronous
+ * on the stream, allocates nothing. */
+int  cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, const double *g_dev, double *u_dev, void *stream);
+long cheb_helmholtz_full_size(const cheb_helmholtz *h);       /* nfields * N       */
+long cheb_helmholtz_boundary_size(const cheb_helmholtz *h);   /* nfields * (N - G) */
+int  cheb_helmholtz_singular(const cheb_helmholtz *h);        /* 1: the zero mode is dropped */
+/* S, Sinv (M x M), lam (M) of A~, Q (2 x M), L (M x 2), B_BB^-1 (2 x 2), row-major HOST buffers, for a line of P points with
+ * bc4 = {alpha_first, beta_first, alpha_last, beta_last}.  Equal ends: the parity layout of cheb_helmholtz_line_host (all
+ * Dirichlet: its matrices, bit for bit); different ends: modes by ascending lam.  Neumann at both ends: lam = 0 exactly. */
+int  cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam,
+                                 double *Q /* 2 x M */, double *L /* M x 2 */, double *Binv /* 2 x 2 */);
+
 /* ------------------------------------------------------------------------- */
 /* The block preconditioners of the Stokes saddle-point system:  */
 /* StokesPCApply0..3 (stokes.C:1714-1817) with the inner solves KSPVelocity,    */

@@ -62,6 +62,8 @@ ABI_SYMBOLS = [
     "cheb_resample_create", "cheb_resample_apply", "cheb_resample_destroy", "cheb_resample_size", "cheb_resample_matrix_host",
     "cheb_helmholtz_create", "cheb_helmholtz_solve", "cheb_helmholtz_apply", "cheb_helmholtz_destroy", "cheb_helmholtz_size",
     "cheb_helmholtz_line_host", "ell_pc_create_spectral",
+    "cheb_helmholtz_create_bc", "cheb_helmholtz_solve_bc", "cheb_helmholtz_full_size", "cheb_helmholtz_boundary_size",
+    "cheb_helmholtz_singular", "cheb_helmholtz_line_bc_host",
 ]
 
 
@@ -229,6 +231,13 @@ def lib():
         L.cheb_helmholtz_size.restype = C.c_long
         L.cheb_helmholtz_line_host.argtypes = [C.c_int, dp, dp, dp]
         L.ell_pc_create_spectral.argtypes = [vp, C.c_double, C.POINTER(vp)]
+        L.cheb_helmholtz_create_bc.argtypes = [C.c_int, ip, dp, C.c_double, C.c_int, C.POINTER(vp)]
+        L.cheb_helmholtz_solve_bc.argtypes = [vp, vp, vp, vp, vp]
+        for f in (L.cheb_helmholtz_full_size, L.cheb_helmholtz_boundary_size):
+            f.argtypes = [vp]
+            f.restype = C.c_long
+        L.cheb_helmholtz_singular.argtypes = [vp]
+        L.cheb_helmholtz_line_bc_host.argtypes = [C.c_int, dp, dp, dp, dp, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -420,23 +429,102 @@ def helmholtz_line(P):
     return S, Si, lam
 
 
+def _bc_spec(spec):
+    """(alpha, beta) of one end: "dirichlet", "neumann" or a pair of numbers."""
+    if isinstance(spec, str):
+        if spec.lower() == "dirichlet":
+            return (1.0, 0.0)
+        if spec.lower() == "neumann":
+            return (0.0, 1.0)
+        raise ValueError("unknown boundary condition %r: 'dirichlet', 'neumann' or (alpha, beta)" % spec)
+    try:
+        a, b = spec
+        return (float(a), float(b))
+    except (TypeError, ValueError):
+        raise ValueError("a boundary condition is 'dirichlet', 'neumann' or (alpha, beta), got %r" % (spec,))
+
+
+def _bc_ends(entry):
+    """(alpha_first, beta_first, alpha_last, beta_last) of one direction: one spec for both ends or a pair (index 0, index n)."""
+    if isinstance(entry, str):
+        return _bc_spec(entry) * 2
+    entry = tuple(entry)
+    if len(entry) == 2 and all(isinstance(e, (int, float)) for e in entry):
+        return _bc_spec(entry) * 2
+    if len(entry) == 2:
+        return _bc_spec(entry[0]) + _bc_spec(entry[1])
+    raise ValueError("a direction's boundary condition is one spec or a pair of specs, got %r" % (entry,))
+
+
+def bc_array(bc, d):
+    """The 4 d doubles of cheb_helmholtz_create_bc from a length-d sequence of per-direction entries (HelmholtzSolver's `bc`)."""
+    if isinstance(bc, str) or len(bc) != d:
+        raise ValueError("bc needs one entry per direction (%d)" % d)
+    return [v for entry in bc for v in _bc_ends(entry)]
+
+
+def helmholtz_line_bc(P, bc):
+    """(S, Sinv, lam, Q, L, Binv) of the line operator with the ends eliminated by `bc` (one spec or a pair, as an entry of
+    HelmholtzSolver's bc; cheb_helmholtz_line_bc_host): A~ = -(DD)_II - (DD)_IB Q = S diag(lam) S^-1, the end values
+    u_B = Q u_I + Binv g, the lift L = (DD)_IB Binv.  Needs no device."""
+    import numpy as np
+    M = max(int(P) - 2, 0)
+    b4 = np.array(_bc_ends(bc), dtype=np.float64)
+    S, Si, lam, Q, L, Bi = np.empty((M, M)), np.empty((M, M)), np.empty(M), np.empty((2, M)), np.empty((M, 2)), np.empty((2, 2))
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+    _chk(lib().cheb_helmholtz_line_bc_host(int(P), ptr(b4), ptr(S), ptr(Si), ptr(lam), ptr(Q), ptr(L), ptr(Bi)))
+    return S, Si, lam, Q, L, Bi
+
+
 class HelmholtzSolver:
     """u = (sigma I + A)^-1 f with A the EllipticOp operator at eta == 1 (zero Dirichlet values) by fast diagonalisation
     (cheb_helmholtz_*): `nfields` stacked interior fields of the grid `dims` per call; `size` values.  Usable as the M of
-    Fgmres.solve."""
+    Fgmres.solve.
 
-    def __init__(self, dims, sigma=0.0, nfields=1):
+    bc (None: Dirichlet on every face, today's solver): one entry per direction, either one spec for both ends or a pair
+    (spec at index 0, spec at index n-1); a spec is "dirichlet", "neumann" or (alpha, beta) for alpha u + beta du/dnu = g,
+    du/dnu outward.  Such a solver also has solve_full (full-grid output from interior f and boundary data g), full_size,
+    boundary_size and singular (sigma = 0 with Neumann everywhere: the constant-like zero mode is dropped)."""
+
+    def __init__(self, dims, sigma=0.0, nfields=1, bc=None):
         self.dims = tuple(int(d) for d in dims)
         self.sigma = float(sigma)
         self.nfields = int(nfields)
+        self.bc = None
         h = C.c_void_p()
-        _chk(lib().cheb_helmholtz_create(len(self.dims), _ints(self.dims), self.sigma, self.nfields, C.byref(h)))
+        if bc is None:
+            _chk(lib().cheb_helmholtz_create(len(self.dims), _ints(self.dims), self.sigma, self.nfields, C.byref(h)))
+        else:
+            b = bc_array(bc, len(self.dims))
+            self.bc = tuple(tuple(b[4 * k:4 * k + 4]) for k in range(len(self.dims)))
+            _chk(lib().cheb_helmholtz_create_bc(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), self.sigma,
+                                                self.nfields, C.byref(h)))
+            self.full_size = lib().cheb_helmholtz_full_size(h)
+            self.boundary_size = lib().cheb_helmholtz_boundary_size(h)
+            self.singular = bool(lib().cheb_helmholtz_singular(h))
         self._h = h
         self.size = lib().cheb_helmholtz_size(h)
 
     def solve(self, f, u):
-        """Asynchronous on torch's current stream; u may be f."""
+        """Asynchronous on torch's current stream; u may be f.  With bc: the interior problem with zero boundary data."""
         _chk(lib().cheb_helmholtz_solve(self._h, _dev_ptr(f, self.size), _dev_ptr(u, self.size), _stream()))
+        return u
+
+    def solve_full(self, f, g, u):
+        """With bc: f (size interior values), g (boundary_size compact boundary values in row-major node order, or None: zero
+        data) -> u (full_size full-grid values, boundary included).  u may not alias f or g.  Asynchronous on torch's current
+        stream."""
+        import torch
+        if self.bc is None:
+            raise ValueError("solve_full needs a solver made with bc")
+        for name, t, n in (("f", f, self.size), ("g", g, self.boundary_size), ("u", u, self.full_size)):
+            if t is None and name == "g":
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 device tensor" % name)
+            if t.numel() != n:
+                raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), n))
+        _chk(lib().cheb_helmholtz_solve_bc(self._h, f.data_ptr(), None if g is None else g.data_ptr(), u.data_ptr(), _stream()))
         return u
 
     def destroy(self):

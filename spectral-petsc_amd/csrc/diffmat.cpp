@@ -648,21 +648,10 @@ bool eig_real_simple(int n, const LVec &A0, LVec &lam, LVec &V) {
   return true;
 }
 
-}  // namespace
-
-bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam) {
-  const int n = P - 1, M = P - 2;
-  if (M < 1) return false;
+// S, S^-1, lam of a centro-symmetric M x M matrix A in the parity mode layout (spec_line's; see above)
+static bool parity_eig(int M, const LVec &A, LVec &S, LVec &Sinv, LVec &lam) {
   const int m = M - 1, He = (M + 1) / 2, Ho = M / 2;
   const bool has_mid = (M & 1) != 0;
-  std::vector<long double> D((size_t)P * P), A((size_t)M * M);
-  for (int i = 0; i < P; i++) for (int j = 0; j < P; j++) D[(size_t)i * P + j] = dentry(i, j, n);
-  for (int i = 0; i < M; i++)
-    for (int j = 0; j < M; j++) {
-      long double s = 0.0L;
-      for (int q = 0; q < P; q++) s += D[(size_t)(i + 1) * P + q] * D[(size_t)q * P + (j + 1)];
-      A[(size_t)i * M + j] = -s;
-    }
   S.assign((size_t)M * M, 0.0L); Sinv.assign((size_t)M * M, 0.0L);
   lam.assign(M, 0.0L);
   for (int parity = 0; parity < 2; parity++) {            // 0: even, 1: odd
@@ -702,6 +691,98 @@ bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sin
     }
   }
   return true;
+}
+
+}  // namespace
+
+bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam) {
+  const int n = P - 1, M = P - 2;
+  if (M < 1) return false;
+  std::vector<long double> D((size_t)P * P), A((size_t)M * M);
+  for (int i = 0; i < P; i++) for (int j = 0; j < P; j++) D[(size_t)i * P + j] = dentry(i, j, n);
+  for (int i = 0; i < M; i++)
+    for (int j = 0; j < M; j++) {
+      long double s = 0.0L;
+      for (int q = 0; q < P; q++) s += D[(size_t)(i + 1) * P + q] * D[(size_t)q * P + (j + 1)];
+      A[(size_t)i * M + j] = -s;
+    }
+  return parity_eig(M, A, S, Sinv, lam);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same line operator with a Neumann or Robin condition at either end (cheb_helmholtz_create_bc).  End e of the line gets
+// alpha_e u + beta_e du/dnu = g_e with du/dnu the outward derivative (+D at index 0, -D at index n); its collocation row
+//     B_row = [alpha_0 e_0 + beta_0 D_0 ; alpha_1 e_n - beta_1 D_n]          (2 x P)
+// gives the end values from the interior ones, u_B = Q u_I + B_BB^-1 g with Q = -B_BB^-1 B_BI, and eliminating them from
+// -(D D) u at the interior nodes leaves  A~ = -(DD)_II - (DD)_IB Q  and the lift  L = (DD)_IB B_BB^-1  of the boundary data.
+// Equal ends: A~ is centro-symmetric and goes through the parity split above (the raw transforms and the one-launch z solve stay
+// usable).  Different ends: one dense eigenproblem, modes by ascending eigenvalue (parity = false).  A Neumann/Neumann line has
+// the constants as its null space: that eigenvalue is set to exactly 0, which is what the solve's singular-mode test looks for.
+// ---------------------------------------------------------------------------------------------
+int spec_line_bc(int P, const double *bc4, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam,
+                 std::vector<long double> &Q, std::vector<long double> &L, std::vector<long double> &Binv, bool &parity) {
+  if (P < 3) return SPEC_BC_SIZE;
+  for (int e = 0; e < 2; e++) {
+    const double a = bc4[2 * e], b = bc4[2 * e + 1];
+    if (!std::isfinite(a) || !std::isfinite(b) || a < 0.0 || b < 0.0 || (a == 0.0 && b == 0.0)) return SPEC_BC_COND;
+  }
+  const int n = P - 1, M = P - 2;
+  const long double a0 = bc4[0], b0 = bc4[1], a1 = bc4[2], b1 = bc4[3];
+  const bool dirichlet = bc4[0] == 1.0 && bc4[1] == 0.0 && bc4[2] == 1.0 && bc4[3] == 0.0;
+  parity = bc4[0] == bc4[2] && bc4[1] == bc4[3];
+  LVec D((size_t)P * P), DD((size_t)P * P), Br((size_t)2 * P);
+  for (int i = 0; i < P; i++) for (int j = 0; j < P; j++) D[(size_t)i * P + j] = dentry(i, j, n);
+  for (int i = 0; i < P; i++)
+    for (int j = 0; j < P; j++) {
+      long double s = 0.0L;
+      for (int q = 0; q < P; q++) s += D[(size_t)i * P + q] * D[(size_t)q * P + j];
+      DD[(size_t)i * P + j] = s;
+    }
+  for (int j = 0; j < P; j++) {
+    Br[j] = (j == 0 ? a0 : 0.0L) + b0 * D[j];
+    Br[(size_t)P + j] = (j == n ? a1 : 0.0L) - b1 * D[(size_t)n * P + j];
+  }
+  const long double b00 = Br[0], b01 = Br[n], b10 = Br[P], b11 = Br[(size_t)P + n], det = b00 * b11 - b01 * b10;
+  if (!(det != 0.0L) || !std::isfinite((double)det)) return SPEC_BC_SINGULAR;
+  Binv.assign(4, 0.0L);
+  Binv[0] = b11 / det; Binv[1] = -b01 / det; Binv[2] = -b10 / det; Binv[3] = b00 / det;
+  if (dirichlet) { Binv[0] = 1.0L; Binv[1] = 0.0L; Binv[2] = 0.0L; Binv[3] = 1.0L; }
+  Q.assign((size_t)2 * M, 0.0L); L.assign((size_t)M * 2, 0.0L);
+  for (int e = 0; e < 2; e++)
+    for (int j = 0; j < M; j++) if (!dirichlet) Q[(size_t)e * M + j] = -(Binv[2 * e] * Br[j + 1] + Binv[2 * e + 1] * Br[(size_t)P + j + 1]);
+  for (int i = 0; i < M; i++)
+    for (int e = 0; e < 2; e++) L[(size_t)i * 2 + e] = DD[(size_t)(i + 1) * P] * Binv[e] + DD[(size_t)(i + 1) * P + n] * Binv[2 + e];
+  if (dirichlet) return spec_line(P, S, Sinv, lam) ? 0 : SPEC_BC_EIG;       // Q = 0, A~ = A_1: spec_line's matrices, bit for bit
+  LVec A((size_t)M * M);
+  for (int i = 0; i < M; i++)
+    for (int j = 0; j < M; j++)
+      A[(size_t)i * M + j] = -DD[(size_t)(i + 1) * P + j + 1] - (DD[(size_t)(i + 1) * P] * Q[j] + DD[(size_t)(i + 1) * P + n] * Q[(size_t)M + j]);
+  if (parity) {
+    if (!parity_eig(M, A, S, Sinv, lam)) return SPEC_BC_EIG;
+  } else {
+    LVec V;
+    if (!eig_real_simple(M, A, lam, V)) return SPEC_BC_EIG;
+    for (int q = 0; q < M; q++) {                        // unit columns, the largest component positive (as spec_line)
+      long double nrm = 0.0L;
+      int im = 0;
+      for (int i = 0; i < M; i++) { nrm += V[(size_t)i * M + q] * V[(size_t)i * M + q]; if (fabsl(V[(size_t)i * M + q]) > fabsl(V[(size_t)im * M + q])) im = i; }
+      nrm = sqrtl(nrm);
+      if (V[(size_t)im * M + q] < 0) nrm = -nrm;
+      for (int i = 0; i < M; i++) V[(size_t)i * M + q] /= nrm;
+    }
+    Sinv = V;
+    if (!invert(M, Sinv)) return SPEC_BC_EIG;
+    S.swap(V);
+  }
+  if (bc4[0] == 0.0 && bc4[2] == 0.0) {                  // Neumann / Neumann: the constant mode, eigenvalue exactly 0
+    int iz = 0;
+    for (int i = 1; i < M; i++) if (fabsl(lam[i]) < fabsl(lam[iz])) iz = i;
+    long double lmax = 0.0L;
+    for (int i = 0; i < M; i++) lmax = std::max(lmax, fabsl(lam[i]));
+    if (fabsl(lam[iz]) > 1e-10L * (lmax > 1.0L ? lmax : 1.0L)) return SPEC_BC_EIG;
+    lam[iz] = 0.0L;
+  }
+  return 0;
 }
 
 // centro-symmetric (part = 1) or centro-antisymmetric (part = 0) part of a dense M x M matrix

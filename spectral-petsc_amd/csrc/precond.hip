@@ -27,6 +27,7 @@
 #include "sweep.h"
 #include "timers.h"
 #include <cmath>
+#include <array>
 #include <map>
 #include <new>
 #include <vector>
@@ -104,12 +105,14 @@ __global__ void k_fd_mult(Geo geo, long G, int nf, const double *__restrict__ cf
 }
 
 // modal scaling: t /= (l_0[i_0] + ... + l_{d-1}[i_{d-1}])
+// A sum that is exactly 0 is the dropped mode of a singular solve (sigma = 0, Neumann on every face: each direction's zero
+// eigenvalue is set to exactly 0 when its line is built, and every other sum is > 0); every weight path gives it weight 0.
 struct LamPtrs { const double *p[MAXD]; };
 __global__ void k_modal_scale(Geo geo, long G, int nf, LamPtrs lam, double *__restrict__ t) {
   GS_LOOP(q, G * nf) {
     long g = q % G; double s = 0.0;
     for (int j = 0; j < geo.d; j++) { const long i = g / geo.gs[j]; g -= i * geo.gs[j]; s += lam.p[j][i]; }
-    t[q] = t[q] / s;
+    t[q] = s != 0.0 ? t[q] / s : 0.0;
   }
 }
 // The same for d <= 3 without an integer-division chain per element (four 64-bit divisions cost more than the pass moves):
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256) void k_modal_scale3(int d, int n1, int nl, lon
   else if (d == 2) s = l0[line];
   const double *ll = d == 3 ? l2 : (d == 2 ? l1 : l0);
   double *row = t + (long)blockIdx.z * G + (long)line * nl;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) row[i] = row[i] / (s + ll[i]);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) { const double w = s + ll[i]; row[i] = w != 0.0 ? row[i] / w : 0.0; }
 }
 
 // w = 1 / (l_0[i_0] + ... + l_{d-1}[i_{d-1}]) on nf stacked copies of the interior grid (d <= 3): the operand of the last forward
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(256) void k_modal_weights3(int d, int n1, int nl, l
   else if (d == 2) s = l0[line];
   const double *ll = d == 3 ? l2 : (d == 2 ? l1 : l0);
   double *row = w + (long)blockIdx.z * G + (long)line * nl;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) row[i] = 1.0 / (s + ll[i]);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) { const double w = s + ll[i]; row[i] = w != 0.0 ? 1.0 / w : 0.0; }
 }
 
 // out = (a - (y ? y : 0)) / eta_g  on nf stacked fields
@@ -249,7 +252,8 @@ __global__ __launch_bounds__(256, 3) void k_fdm_zsolve16(const FzParams p) {
             if (p.d == 3) { const unsigned i0 = lf / (unsigned)p.n1, i1 = lf - i0 * (unsigned)p.n1; sxy = p.l0[i0] + p.l1[i1]; }
             else sxy = p.l0[lf];
           }
-          we[sub][r] = ok ? 1.0 / (sxy + lze) : 0.0; wo[sub][r] = ok ? 1.0 / (sxy + lzo) : 0.0;
+          const double se = sxy + lze, so = sxy + lzo;                 // (0: the dropped mode of a singular solve)
+          we[sub][r] = ok && se != 0.0 ? 1.0 / se : 0.0; wo[sub][r] = ok && so != 0.0 ? 1.0 / so : 0.0;
         }
       fz_v4 ce[2], co[2];
       chains(p.FE, p.FO, ce, co);
@@ -283,7 +287,12 @@ __global__ __launch_bounds__(256, 3) void k_fdm_zsolve16(const FzParams p) {
   }
 }
 
-struct LineMats { DiffMat Fcs, Fca, Bcs, Bca, Fraw, Braw; double *lam = nullptr; bool ok = false; };
+// parity: the modes use the parity layout (raw transforms, OUT_MUL and k_fdm_zsolve16 usable); a line whose two ends differ has
+// ascending modes and runs the two-launch transforms only.  bcm (boundary-condition lines): Q (2 x M), L^T (2 x M), B_BB^-1 (2 x 2)
+struct LineMats { DiffMat Fcs, Fca, Bcs, Bca, Fraw, Braw; double *lam = nullptr; double *bcm = nullptr; bool ok = false, parity = true; };
+// lines are shared by the directions of equal extent AND equal end conditions (alpha_first, beta_first, alpha_last, beta_last)
+typedef std::pair<int, std::array<double, 4>> LineKey;
+static const std::array<double, 4> BC_DIRICHLET = {1.0, 0.0, 1.0, 0.0};
 
 }  // namespace
 
@@ -293,11 +302,12 @@ struct chebhip_fdpc {
   Geo geo;
   int kind = LINE_FD;                          // LINE_SPECTRAL: lines from spec_line, no stencil (sweeps = 0 only)
   bool bare = false;                           // no operator behind the handle (cheb_helmholtz): no eta, no update
-  double *lam0 = nullptr;                      // spectral: sigma + eigenvalues of dimension 0 (a copy: lines[] is shared by extents)
+  double *lam0 = nullptr;                      // spectral: sigma + eigenvalues of dimension 0 (a copy: lines[] is shared by directions)
   long N = 0, G = 0;
   int nf = 1;                                  // 1: scalar operator; d: Stokes velocity (component-major inside)
   bool interleaved = false;                    // vectors at the ABI are node-major (Stokes)
-  std::map<int, LineMats> lines;               // per distinct extent
+  std::map<LineKey, LineMats> lines;           // per distinct (extent, end conditions)
+  LineMats *ln[MAXD] = {nullptr};              // direction k's entry of lines
   std::vector<unsigned> inner_g, ncols_g;
   double *xs[MAXD] = {nullptr};
   double *cf = nullptr, *eta_g = nullptr;
@@ -323,6 +333,7 @@ static void fdpc_free(chebhip_fdpc *pc) {
     diffmat_destroy(&kv.second.Fcs); diffmat_destroy(&kv.second.Fca); diffmat_destroy(&kv.second.Bcs); diffmat_destroy(&kv.second.Bca);
     diffmat_destroy(&kv.second.Fraw); diffmat_destroy(&kv.second.Braw);
     if (kv.second.lam) (void)hipFree(kv.second.lam);
+    if (kv.second.bcm) (void)hipFree(kv.second.bcm);
   }
   for (int k = 0; k < MAXD; k++) if (pc->xs[k]) (void)hipFree(pc->xs[k]);
   double *all[] = {pc->cf, pc->eta_g, pc->t0, pc->t1, pc->t2, pc->t3, pc->t4, pc->t5, pc->W, pc->Einv, pc->lam0};
@@ -332,8 +343,9 @@ static void fdpc_free(chebhip_fdpc *pc) {
 
 // kind: LINE_FD (the finite-difference matrix) or LINE_SPECTRAL (sigma + the collocation operator at eta == 1); bare: a spectral
 // handle without an operator (v0.ixL / eta unused): only the buffers of the plain solve are allocated
+// bc (spectral only; may be null = Dirichlet everywhere): 4 d end conditions, spec_line_bc
 static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc **out, int gP0 = 0, int kind = LINE_FD, double sigma = 0.0,
-                       bool bare = false) {
+                       bool bare = false, const double *bc = nullptr) {
   *out = nullptr;
   FdView v = v0;
   std::vector<int> gdims(v0.dims, v0.dims + (v0.d >= 1 && v0.d <= MAXD ? v0.d : 0));
@@ -361,10 +373,31 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     for (int i = 0; i < P; i++) x[i] = cos(i * 3.14159265358979323846 / (P - 1));          // elliptic.C:279, stokes.C:296
     PCCHK(hipMalloc((void **)&pc->xs[k], P * sizeof(double)));
     PCCHK(hipMemcpy(pc->xs[k], x.data(), P * sizeof(double), hipMemcpyHostToDevice));
-    if (pc->lines.count(P)) continue;
+    std::array<double, 4> bk = BC_DIRICHLET;
+    if (bc) for (int e = 0; e < 4; e++) bk[e] = bc[4 * k + e];
+    const LineKey key(P, bk);
+    if (pc->lines.count(key)) { pc->ln[k] = &pc->lines[key]; continue; }
     LineMats lm;
-    std::vector<long double> S, Si, lam, part;
-    if (!(kind == LINE_SPECTRAL ? spec_line(P, S, Si, lam) : fdm_line(P, S, Si, lam))) {
+    std::vector<long double> S, Si, lam, part, Qb, Lb, Bi;
+    if (bc) {
+      bool par = true;
+      const int rc = spec_line_bc(P, bk.data(), S, Si, lam, Qb, Lb, Bi, par);
+      if (rc) {
+        fdpc_free(pc);
+        if (rc == SPEC_BC_COND) return chebhip_fail(CHEBHIP_ERR_ARG, "bc of dimension %d: (alpha, beta) must be finite, >= 0 and not both 0", k);
+        if (rc == SPEC_BC_SINGULAR) return chebhip_fail(CHEBHIP_ERR_ARG, "bc of dimension %d: the end rows are singular", k);
+        return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point spectral line operator (bc of dimension %d) failed", P, k);
+      }
+      lm.parity = par;
+      std::vector<double> h((size_t)4 * M + 4);
+      for (int j = 0; j < M; j++) {
+        h[j] = (double)Qb[j]; h[(size_t)M + j] = (double)Qb[(size_t)M + j];
+        h[(size_t)2 * M + j] = (double)Lb[(size_t)2 * j]; h[(size_t)3 * M + j] = (double)Lb[(size_t)2 * j + 1];
+      }
+      for (int e = 0; e < 4; e++) h[(size_t)4 * M + e] = (double)Bi[e];
+      PCCHK(hipMalloc((void **)&lm.bcm, h.size() * sizeof(double)));
+      PCCHK(hipMemcpy(lm.bcm, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else if (!(kind == LINE_SPECTRAL ? spec_line(P, S, Si, lam) : fdm_line(P, S, Si, lam))) {
       fdpc_free(pc);
       return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point %s line operator failed", P, kind == LINE_SPECTRAL ? "spectral" : "finite-difference");
     }
@@ -372,7 +405,7 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     centro_part(M, Si, 0, part); PCCHK(diffmat_from_dense(M, part.data(), 0, &lm.Fca));
     centro_part(M, S, 1, part);  PCCHK(diffmat_from_dense(M, part.data(), 1, &lm.Bcs));
     centro_part(M, S, 0, part);  PCCHK(diffmat_from_dense(M, part.data(), 0, &lm.Bca));
-    {
+    if (lm.parity) {
       // The same two transforms as ONE product each.  fdm_line orders the modes by parity (even modes at the positions
       // p < H, the q-th odd mode at M-1-q), so with e, o the parity split of a nodal line
       //   forward:  c_p = sum_j Sinv[p][j] e_j (p < H),  c_{M-1-q} = sum_j Sinv[M-1-q][j] o_j      -> halves stored raw
@@ -396,12 +429,13 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     PCCHK(hipMalloc((void **)&lm.lam, M * sizeof(double)));
     PCCHK(hipMemcpy(lm.lam, ld.data(), M * sizeof(double), hipMemcpyHostToDevice));
     lm.ok = true;
-    pc->lines[P] = lm;
+    pc->lines[key] = lm;
+    pc->ln[k] = &pc->lines[key];
   }
   if (kind == LINE_SPECTRAL) {
     const int M0 = v.dims[0] - 2;
     std::vector<double> l0(M0);
-    PCCHK(hipMemcpy(l0.data(), pc->lines[v.dims[0]].lam, M0 * sizeof(double), hipMemcpyDeviceToHost));
+    PCCHK(hipMemcpy(l0.data(), pc->ln[0]->lam, M0 * sizeof(double), hipMemcpyDeviceToHost));
     for (int i = 0; i < M0; i++) l0[i] += sigma;
     PCCHK(hipMalloc((void **)&pc->lam0, M0 * sizeof(double)));
     PCCHK(hipMemcpy(pc->lam0, l0.data(), M0 * sizeof(double), hipMemcpyHostToDevice));
@@ -474,7 +508,7 @@ static int line_transform(chebhip_fdpc *pc, int k, bool backward, const double *
                           const double *in_mul = nullptr) {
   if (fused) *fused = false;
   if (pc->slab && k == 0) return pc->dim0(pc->dim0_ctx, backward ? 1 : 0, pc->nf, x, y, (void *)st);      // collective: every rank of the slab partition
-  return line_transform_g(pc->lines[pc->geo.dims[k]], pc->ncols_g[k] * (unsigned)pc->nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul);
+  return line_transform_g(*pc->ln[k], pc->ncols_g[k] * (unsigned)pc->nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul);
 }
 static SweepParams line_in_mul_params(unsigned ncols, unsigned inner, const double *x, double *y, const double *in_mul) {
   SweepParams sm = {};
@@ -484,7 +518,7 @@ static SweepParams line_in_mul_params(unsigned ncols, unsigned inner, const doub
 static bool line_in_mul_ok(chebhip_fdpc *pc, int k, const double *x, double *y, const double *in_mul) {
   if ((pc->slab && k == 0) || !in_mul) return false;
   const unsigned ncols = pc->ncols_g[k] * (unsigned)pc->nf;
-  return ncols != 0 && sweep_vec_raw_eligible(pc->lines[pc->geo.dims[k]].Fraw, line_in_mul_params(ncols, pc->inner_g[k], x, y, in_mul));
+  return ncols != 0 && pc->ln[k]->parity && sweep_vec_raw_eligible(pc->ln[k]->Fraw, line_in_mul_params(ncols, pc->inner_g[k], x, y, in_mul));
 }
 static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool backward, const double *x, double *y, hipStream_t st,
                             const double *mul, bool *fused, const double *in_mul) {
@@ -495,11 +529,11 @@ static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool b
   sp.ncols = ncols; sp.inner = inner;
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.alpha = 1.0;
   sp.out_mode = OUT_STORE;
-  if (mul && fused && !backward) {
+  if (mul && fused && !backward && lm.parity) {
     SweepParams sm = sp; sm.out_mode = OUT_MUL; sm.acc = mul; sm.raw = 1;
     if (sweep_vec_raw_eligible(lm.Fraw, sm)) { PHIPCHK(sweep_launch(lm.Fraw, sm, st)); *fused = true; return 0; }
   }
-  if (sweep_vec_raw_eligible(backward ? lm.Braw : lm.Fraw, sp)) {       // one launch: the parity split is the transform's own
+  if (lm.parity && sweep_vec_raw_eligible(backward ? lm.Braw : lm.Fraw, sp)) {       // one launch: the parity split is the transform's own
     sp.raw = backward ? 2 : 1;
     PHIPCHK(sweep_launch(backward ? lm.Braw : lm.Fraw, sp, st));
     return 0;
@@ -532,7 +566,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
       src = pc->t3;
     }
   }
-  LamPtrs lam; for (int k = 0; k < MAXD; k++) lam.p[k] = k < d ? pc->lines[pc->geo.dims[k]].lam : nullptr;
+  LamPtrs lam; for (int k = 0; k < MAXD; k++) lam.p[k] = k < d ? pc->ln[k]->lam : nullptr;
   if (pc->lam0) lam.p[0] = pc->lam0;                      // spectral: sigma + l_0 (every weight path reads dimension 0's array)
   const int nl = pc->geo.dims[d - 1] - 2;
   const long lines = pc->G / nl;
@@ -553,8 +587,8 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
   bool zsolve = false;
   {
     const int M = pc->geo.dims[d - 1] - 2;
-    LineMats &lm = pc->lines[pc->geo.dims[d - 1]];
-    zsolve = w_ok && d >= 2 && !opt(OPT_FDM_Z_SEPARATE) && !opt(OPT_NO_RAW_TRANSFORMS) && !opt(OPT_GENERAL_KERNELS) && (M & 1) == 0 &&
+    LineMats &lm = *pc->ln[d - 1];
+    zsolve = w_ok && d >= 2 && lm.parity && !opt(OPT_FDM_Z_SEPARATE) && !opt(OPT_NO_RAW_TRANSFORMS) && !opt(OPT_GENERAL_KERNELS) && (M & 1) == 0 &&
              lm.Fraw.KS == FZ_KS && lm.Braw.KS == FZ_KS && lm.Braw.sym == 1 && pc->G * pc->nf / M < 0x7fffffffL - FZ_NT;
   }
   bool scaled = false;
@@ -576,7 +610,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
   }
   if (zsolve) {
     const int M = pc->geo.dims[d - 1] - 2;
-    LineMats &lm = pc->lines[pc->geo.dims[d - 1]];
+    LineMats &lm = *pc->ln[d - 1];
     FzParams fp = {};
     fp.M = M; fp.H = (M + 1) / 2; fp.ncols = (unsigned)(pc->G * pc->nf / M); fp.ntiles = (fp.ncols + FZ_NT - 1) / FZ_NT;
     fp.x = src; fp.y = (d == 1) ? z : a;
@@ -702,7 +736,7 @@ extern "C" int chebhip_fdpc_pencil_transform(chebhip_fdpc *pc, int backward, int
   if (!pc || nfields < 1 || ncol < 0 || ((!in_dev || !out_dev) && ncol > 0)) return chebhip_fail(CHEBHIP_ERR_ARG, "bad argument");
   if (ncol == 0) return 0;
   if ((unsigned long long)nfields * (unsigned long long)ncol > 0x7fffffffull) return chebhip_fail(CHEBHIP_ERR_DIMS, "pencil too large");
-  return line_transform_g(pc->lines[pc->geo.dims[0]], (unsigned)(nfields * ncol), (unsigned)ncol, backward != 0, in_dev, out_dev, (hipStream_t)stream);
+  return line_transform_g(*pc->ln[0], (unsigned)(nfields * ncol), (unsigned)ncol, backward != 0, in_dev, out_dev, (hipStream_t)stream);
 }
 
 extern "C" int chebhip_fdpc_destroy(chebhip_fdpc *pc) { fdpc_free(pc); return 0; }
@@ -755,9 +789,175 @@ extern "C" int ell_pc_create_spectral(ell_op *op, double sigma, chebhip_fdpc **o
   return 0;
 }
 
+// ---- boundary conditions (cheb_helmholtz_create_bc): the lift of the boundary data and the full-grid extension -------------------
+namespace {
+
+// full-grid geometry: extents, row-major strides of the full grid (ls) and of the interior (gs), sizes per field (NB = N - G).
+// 32-bit: a boundary-condition handle has nf N <= 2^31 - 1 (cheb_helmholtz_create_bc), so every index below fits.
+struct BcGeo { int d; int P[MAXD]; int ls[MAXD]; int gs[MAXD]; int N, G, NB; };
+struct BcMats { const double *m[MAXD]; };      // per direction: Q row 0, Q row 1, L column 0, L column 1 (M each), B_BB^-1 (4)
+
+// Position of a boundary node in the compact boundary layout (row-major node order, ell_op_set_dirichlet): its full-grid index
+// minus the number of interior nodes before it.  The node is end `last` of direction k on a line whose indices in directions
+// < k are j[]; the count stops at the first non-interior index (0: no interior node of that subtree comes before; n: all do).
+template <int DC>
+__device__ __forceinline__ int bc_before(const BcGeo &g, const int *j, int k, bool last) {
+  int c = 0;
+  bool done = false;
+  for (int m = 0; m < (DC ? DC : MAXD); m++)
+    if (m < k && !done) {
+      if (j[m] == 0) done = true;
+      else if (j[m] == g.P[m] - 1) { c += (g.P[m] - 2) * g.gs[m]; done = true; }
+      else c += (j[m] - 1) * g.gs[m];
+    }
+  return last && !done ? c + (g.P[k] - 2) * g.gs[k] : c;
+}
+
+// t = f + sum_k L_k (g at the two faces of direction k) on nf stacked interior fields (field = blockIdx.y).  One thread per
+// interior node, the last index fastest: for k < d-1 consecutive threads read consecutive face values; for k = d-1 a line's
+// threads share its two values.  (DC: d known at compile time, 0: any d up to MAXD.)
+template <int DC>
+__global__ __launch_bounds__(256) void k_bc_lift(BcGeo geo, BcMats bm, const double *__restrict__ f, const double *__restrict__ g,
+                                                 double *__restrict__ t) {
+  const int d = DC ? DC : geo.d;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= (unsigned)geo.G) return;
+  const int fo = blockIdx.y;
+  const double *gf = g + fo * geo.NB;
+  int i[MAXD];
+  unsigned r = q;
+  for (int m = (DC ? DC : MAXD) - 1; m > 0; m--)
+    if (m < d) { const unsigned Mm = (unsigned)(geo.P[m] - 2); i[m] = (int)(r % Mm); r /= Mm; }
+  i[0] = (int)r;
+  int base = 0;
+  for (int m = 0; m < (DC ? DC : MAXD); m++) if (m < d) base += (i[m] + 1) * geo.ls[m];
+  double s = f[fo * geo.G + (int)q];
+  int c = 0;                                   // interior nodes before the first face node: sum_{m < k} i_m gs_m
+  for (int k = 0; k < (DC ? DC : MAXD); k++)
+    if (k < d) {
+      const int M = geo.P[k] - 2;
+      const double *L = bm.m[k] + 2 * M;
+      const int b0 = base - (i[k] + 1) * geo.ls[k] - c;
+      const int b1 = b0 + (geo.P[k] - 1) * geo.ls[k] - M * geo.gs[k];
+      s += L[i[k]] * gf[b0] + L[M + i[k]] * gf[b1];
+      c += i[k] * geo.gs[k];
+    }
+  t[fo * geo.G + (int)q] = s;
+}
+
+// End values of direction k < d-1 on nf stacked full grids (field = blockIdx.y): u_end = Q_k u_line + B_BB^-1 g_line on every
+// line whose indices in directions < k are any and in directions > k interior.  A workgroup takes 64 lines, consecutive in the
+// last index (a wave reads 64 consecutive values at every step), and splits each line into four segments, one per wave (one
+// thread per line would leave a single wave per SIMD at 256^3); the partial sums meet in LDS.  A Dirichlet end (beta = 0) is
+// B_BB^-1 g, a copy for alpha = 1.  src (k = 0 only): the lines' interior values are read from the interior solution and
+// embedded into u on the way.
+constexpr int BC_SEG = 4;
+template <int DC>
+__global__ __launch_bounds__(256) void k_bc_extend_col(BcGeo geo, int k, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
+  __shared__ double red[2][BC_SEG][64];
+  const int d = DC ? DC : geo.d;
+  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
+  const unsigned t = blockIdx.x * 64u + lane;
+  const bool ok = t < (unsigned)nlines;
+  const int fo = blockIdx.y;
+  double *uf = u + fo * geo.N;
+  const int M = geo.P[k] - 2, ls = geo.ls[k], lend = (geo.P[k] - 1) * ls;
+  int j[MAXD];
+  unsigned r = ok ? t : 0u;
+  int base = 0, ibase = 0;
+  for (int m = (DC ? DC : MAXD) - 1; m >= 0; m--) {
+    if (m >= d || m == k) continue;
+    const unsigned rad = (unsigned)(m < k ? geo.P[m] : geo.P[m] - 2);
+    const int x = (int)(r % rad); r /= rad;
+    j[m] = m < k ? x : x + 1;
+    base += j[m] * geo.ls[m];
+    ibase += (j[m] - 1) * geo.gs[m];
+  }
+  const int per = (M + BC_SEG - 1) / BC_SEG, i0 = seg * per, i1 = i0 + per < M ? i0 + per : M;
+  double s0 = 0.0, s1 = 0.0;
+  if (ok) {
+    if (src) {
+      const double *sf = src + fo * geo.G + ibase;
+      const int gk = geo.gs[k];
+#pragma unroll 4
+      for (int i = i0; i < i1; i++) {
+        const double v = sf[i * gk];
+        uf[base + (i + 1) * ls] = v;
+        s0 += bm[i] * v; s1 += bm[M + i] * v;
+      }
+    } else if (!(dir0 && dir1)) {
+#pragma unroll 4
+      for (int i = i0; i < i1; i++) { const double v = uf[base + (i + 1) * ls]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+    }
+  }
+  red[0][seg][lane] = s0; red[1][seg][lane] = s1;
+  __syncthreads();
+  if (seg != 0 || !ok) return;
+  s0 = red[0][0][lane]; s1 = red[1][0][lane];
+  for (int q = 1; q < BC_SEG; q++) { s0 += red[0][q][lane]; s1 += red[1][q][lane]; }
+  double g0 = 0.0, g1 = 0.0;
+  if (g) {
+    const double *gf = g + fo * geo.NB;
+    g0 = gf[base - bc_before<DC>(geo, j, k, false)];
+    g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
+  }
+  const double *Bi = bm + 4 * M;
+  uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
+  uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
+}
+
+// The same for the last direction, whose lines are contiguous: one wave per line (four per workgroup) reduces Q_k u_line across its
+// lanes.  src (d = 1 only): embed the interior solution on the way.
+template <int DC>
+__global__ __launch_bounds__(256) void k_bc_extend_row(BcGeo geo, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
+  const int d = DC ? DC : geo.d, k = d - 1;
+  const unsigned t = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (t >= (unsigned)nlines) return;           // (wave-uniform)
+  const int fo = blockIdx.y;
+  double *uf = u + fo * geo.N;
+  const int M = geo.P[k] - 2, lane = threadIdx.x & 63, lend = geo.P[k] - 1;
+  int j[MAXD];
+  unsigned r = t;
+  int base = 0;
+  for (int m = (DC ? DC : MAXD) - 2; m >= 0; m--) {
+    if (m >= k) continue;
+    const int x = (int)(r % (unsigned)geo.P[m]); r /= (unsigned)geo.P[m];
+    j[m] = x; base += x * geo.ls[m];
+  }
+  double s0 = 0.0, s1 = 0.0;
+  if (src) {
+    const double *sf = src + fo * geo.G;
+    for (int i = lane; i < M; i += 64) { const double v = sf[i]; uf[base + 1 + i] = v; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+  } else if (!(dir0 && dir1)) {
+    for (int i = lane; i < M; i += 64) { const double v = uf[base + 1 + i]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64); }
+  if (lane == 0) {
+    double g0 = 0.0, g1 = 0.0;
+    if (g) {
+      const double *gf = g + fo * geo.NB;
+      g0 = gf[base - bc_before<DC>(geo, j, k, false)];
+      g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
+    }
+    const double *Bi = bm + 4 * M;
+    uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
+    uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
+  }
+}
+
+}  // namespace
+
 struct cheb_helmholtz {
   chebhip_fdpc *pc = nullptr;
   long n = 0;                                  // nfields * prod(dims - 2)
+  // cheb_helmholtz_create_bc only: full-grid geometry, per-direction end flags (beta = 0), the singular flag, two nf * G buffers
+  bool bc = false; int singular = 0; int nf = 1;
+  BcGeo geo = {};
+  int dir[MAXD][2] = {};
+  double *t = nullptr, *z = nullptr;
 };
 
 extern "C" int cheb_helmholtz_create(int d, const int *dims, double sigma, int nfields, cheb_helmholtz **out) {
@@ -798,6 +998,8 @@ extern "C" int cheb_helmholtz_apply(void *h, const double *x_dev, double *y_dev,
 extern "C" int cheb_helmholtz_destroy(cheb_helmholtz *h) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   fdpc_free(h->pc);
+  if (h->t) (void)hipFree(h->t);
+  if (h->z) (void)hipFree(h->z);
   delete h;
   return 0;
 }
@@ -813,5 +1015,129 @@ extern "C" int cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *
   const int M = P - 2;
   for (size_t i = 0; i < (size_t)M * M; i++) { S[i] = (double)s[i]; Sinv[i] = (double)si[i]; }
   for (int i = 0; i < M; i++) lam[i] = (double)l[i];
+  return 0;
+}
+
+// ---- C ABI: the Helmholtz solve with Dirichlet, Neumann or Robin ends --------------------------------------------
+extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc, double sigma, int nfields, cheb_helmholtz **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  if (!bc) return chebhip_fail(CHEBHIP_ERR_ARG, "bc is NULL");
+  int rc = check_sigma(sigma); if (rc) return rc;
+  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  for (int k = 0; k < d; k++)
+    for (int e = 0; e < 2; e++) {
+      const double a = bc[4 * k + 2 * e], b = bc[4 * k + 2 * e + 1];
+      if (!std::isfinite(a) || !std::isfinite(b) || a < 0.0 || b < 0.0 || (a == 0.0 && b == 0.0))
+        return chebhip_fail(CHEBHIP_ERR_ARG, "bc[%d] %s end: (alpha, beta) = (%g, %g) must be finite, >= 0 and not both 0", k, e ? "last" : "first", a, b);
+    }
+  long N = 1, G = 1;
+  for (int k = 0; k < d; k++) {
+    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
+    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
+    G *= dims[k] - 2;
+    N *= dims[k];
+    if (N * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 full-grid values");
+  }
+  FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
+  cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc);
+  if (rc) { delete h; return rc; }
+  h->n = G * nfields; h->nf = nfields; h->bc = true;
+  h->geo.d = d; h->geo.N = (int)N; h->geo.G = (int)G; h->geo.NB = (int)(N - G);
+  {
+    int s = 1, si = 1;
+    for (int k = d - 1; k >= 0; k--) { h->geo.P[k] = dims[k]; h->geo.ls[k] = s; h->geo.gs[k] = si; s *= dims[k]; si *= dims[k] - 2; }
+  }
+  bool neumann = true;
+  for (int k = 0; k < d; k++) {
+    h->dir[k][0] = bc[4 * k + 1] == 0.0; h->dir[k][1] = bc[4 * k + 3] == 0.0;
+    neumann = neumann && bc[4 * k] == 0.0 && bc[4 * k + 2] == 0.0;
+  }
+  h->singular = sigma == 0.0 && neumann;
+  if (hipMalloc((void **)&h->t, (size_t)G * nfields * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&h->z, (size_t)G * nfields * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    cheb_helmholtz_destroy(h);
+    return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of device memory (%ld values)", 2 * G * nfields);
+  }
+  *out = h;
+  return 0;
+}
+
+#define BC_LAUNCH(KERNEL, grid, ...)                                                                          \
+  do {                                                                                                       \
+    switch (h->geo.d) {                                                                                      \
+      case 1: hipLaunchKernelGGL(KERNEL<1>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
+      case 2: hipLaunchKernelGGL(KERNEL<2>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
+      case 3: hipLaunchKernelGGL(KERNEL<3>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
+      default: hipLaunchKernelGGL(KERNEL<0>, grid, dim3(256), 0, st, __VA_ARGS__); break;                    \
+    }                                                                                                        \
+  } while (0)
+
+static bool overlaps(const double *a, long na, const double *b, long nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)nb * sizeof(double) && pb < pa + (uintptr_t)na * sizeof(double);
+}
+
+extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, const double *g_dev, double *u_dev, void *stream) {
+  if (!h || !h->pc) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!h->bc) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_helmholtz_solve_bc: a handle from cheb_helmholtz_create_bc");
+  if (!f_dev || !u_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL vector");
+  const int d = h->geo.d, nf = h->nf;
+  const long G = h->geo.G, N = h->geo.N, NB = h->geo.NB;
+  if (overlaps(u_dev, nf * N, f_dev, nf * G) || (g_dev && overlaps(u_dev, nf * N, g_dev, nf * NB)))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "u may not alias f or g");
+  hipStream_t st = (hipStream_t)stream;
+  BcMats bm;
+  for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
+  const double *rhs = f_dev;
+  if (g_dev) {                                 // (g = NULL: zero data, nothing to lift)
+    BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), h->geo, bm, f_dev, g_dev, h->t);
+    PHIPCHK(hipGetLastError());
+    rhs = h->t;
+  }
+  int rc = fdm_solve(h->pc, rhs, h->z, st); if (rc) return rc;
+  // end values direction by direction: the lines of direction k read the edges direction k - 1 has written
+  long before = 1;                             // prod_{m < k} P_m
+  for (int k = 0; k < d; k++) {
+    const double *src = k == 0 ? h->z : nullptr;
+    if (k < d - 1) {
+      long nl = before;
+      for (int m = k + 1; m < d; m++) nl *= h->geo.P[m] - 2;
+      BC_LAUNCH(k_bc_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), h->geo, k, bm.m[k], h->dir[k][0], h->dir[k][1], (int)nl, src,
+                g_dev, u_dev);
+    } else {
+      BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), h->geo, bm.m[k], h->dir[k][0], h->dir[k][1], (int)before,
+                src, g_dev, u_dev);
+    }
+    PHIPCHK(hipGetLastError());
+    before *= h->geo.P[k];
+  }
+  return 0;
+}
+#undef BC_LAUNCH
+
+extern "C" long cheb_helmholtz_full_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * h->pc->N : -1; }
+extern "C" long cheb_helmholtz_boundary_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * (h->pc->N - h->pc->G) : -1; }
+extern "C" int cheb_helmholtz_singular(const cheb_helmholtz *h) { return h ? h->singular : -1; }
+
+extern "C" int cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam, double *Q, double *L, double *Binv) {
+  if (P < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "P = %d: a line needs interior nodes (P >= 3)", P);
+  if (P > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "P = %d: at most 258 points per line", P);
+  if (!bc4 || !S || !Sinv || !lam || !Q || !L || !Binv) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  std::vector<long double> s, si, l, q, lf, bi;
+  bool parity = true;
+  const int rc = spec_line_bc(P, bc4, s, si, l, q, lf, bi, parity);
+  if (rc == SPEC_BC_COND) return chebhip_fail(CHEBHIP_ERR_ARG, "bc = (%g, %g, %g, %g): each (alpha, beta) must be finite, >= 0 and not both 0", bc4[0], bc4[1], bc4[2], bc4[3]);
+  if (rc == SPEC_BC_SINGULAR) return chebhip_fail(CHEBHIP_ERR_ARG, "bc: the end rows are singular");
+  if (rc) return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point spectral line operator with bc failed", P);
+  const int M = P - 2;
+  for (size_t i = 0; i < (size_t)M * M; i++) { S[i] = (double)s[i]; Sinv[i] = (double)si[i]; }
+  for (int i = 0; i < M; i++) lam[i] = (double)l[i];
+  for (int i = 0; i < 2 * M; i++) { Q[i] = (double)q[i]; L[i] = (double)lf[i]; }
+  for (int i = 0; i < 4; i++) Binv[i] = (double)bi[i];
   return 0;
 }

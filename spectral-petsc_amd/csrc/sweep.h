@@ -218,6 +218,11 @@ bool fdm_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv
 // The same layout for the spectral line operator A_1 = -(D D)[1..n-1, 1..n-1] (nonsymmetric; real, simple, positive spectrum):
 // A_1 = S diag(lam) S^-1, false on complex / repeated eigenvalues (diffmat.cpp)
 bool spec_line(int P, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam);
+// The line operator with the ends eliminated by bc4 = {alpha_first, beta_first, alpha_last, beta_last} (Dirichlet: 1, 0): S, Sinv,
+// lam of A~ (parity: spec_line's layout, equal ends; otherwise ascending), Q (2 x M), L (M x 2), Binv (2 x 2).  0 or SPEC_BC_*
+enum { SPEC_BC_SIZE = 1, SPEC_BC_COND, SPEC_BC_SINGULAR, SPEC_BC_EIG };
+int spec_line_bc(int P, const double *bc4, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam,
+                 std::vector<long double> &Q, std::vector<long double> &L, std::vector<long double> &Binv, bool &parity);
 void centro_part(int M, const std::vector<long double> &A, int part, std::vector<long double> &out);
 
 }  // namespace chebhip

@@ -78,6 +78,30 @@ def poisson_solve(sp, op, b, x, sigma=0.0, solver=None):
     return x
 
 
+def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None):
+    """sigma u - Laplace u = f with alpha u + beta du/dnu = g on every face (sp.HelmholtzSolver's `bc`), solved directly.
+    f_full: full-grid device tensor (its boundary entries are ignored); g: the compact boundary values in row-major node order
+    (the ell_op_set_dirichlet layout) or None for zero data.  solver: a caller's HelmholtzSolver(dims, sigma, bc=bc) to use and
+    keep (its nfields stacked fields); None: one is made and destroyed here.  Returns the full-grid u (a new tensor)."""
+    dims = tuple(int(d) for d in dims)
+    own = solver is None
+    if own:
+        solver = sp.HelmholtzSolver(dims, sigma, bc=bc)
+    elif solver.dims != dims or solver.sigma != float(sigma) or solver.bc is None or solver.bc != tuple(tuple(sp.bc_array(bc, len(dims))[4 * k:4 * k + 4]) for k in range(len(dims))):
+        raise ValueError("solver: a HelmholtzSolver of the grid with sigma = %g and the same bc" % sigma)
+    try:
+        if f_full.numel() != solver.full_size:
+            raise ValueError("f_full has %d elements, expected %d" % (f_full.numel(), solver.full_size))
+        inner = tuple(slice(1, -1) for _ in dims)
+        f = f_full.reshape((solver.nfields,) + dims)[(slice(None),) + inner].contiguous().reshape(-1)
+        u = torch.empty_like(f_full).contiguous()
+        solver.solve_full(f, g, u)
+    finally:
+        if own:
+            solver.destroy()
+    return u
+
+
 def continuation_schedule(exponent, regularization, cont0=0, cont=1):
     """The (exponent, regularization) pairs of the Newton continuation loop, stokes.C:217-221:
     exponent_i = 1 + (i/cont)^0.8 (exponent - 1), regularization_i = exp(log(regularization) i/cont)."""
