@@ -25,20 +25,32 @@ namespace chebhip {
 
 static const long double PI_L = 3.14159265358979323846264338327950288L;
 
+// sin(k pi / 2n) for |k| <= 2n with the argument folded into [0, pi/2] (sin(pi - t) = sin t): PI_L carries a rounding error of
+// 2^-65 pi, and near t = pi that absolute error is relative to a SMALL sine -- unfolded, the entries of D next to the far
+// corner were off by up to 4e-17 of their size, and D D, which cancels by four orders of magnitude at P = 256, turned that into
+// 5e-14 of an entry of the second-derivative matrix.
+static long double sin_half(int k, int n) {
+  int a = k < 0 ? -k : k;
+  if (a > n) a = 2 * n - a;
+  const long double s = sinl(PI_L * a / (2.0L * n));
+  return k < 0 ? -s : s;
+}
+
 // D[i][j] in long double.  Off-diagonal: (c_i/c_j) (-1)^(i+j) / (x_i - x_j) with
 // x_i - x_j = -2 sin((i+j) pi/2n) sin((i-j) pi/2n) (no cancellation); diagonal from the
-// closed forms  D00 = (2n^2+1)/6 = -Dnn,  Dii = -x_i / (2 sin^2(i pi/n)).
+// closed forms  D00 = (2n^2+1)/6 = -Dnn,  Dii = -x_i / (2 sin^2(i pi/n)),  x_i = sin((n-2i) pi/2n).
 static long double dentry(int i, int j, int n) {
   if (i == j) {
     if (i == 0) return (2.0L * n * n + 1.0L) / 6.0L;
     if (i == n) return -(2.0L * n * n + 1.0L) / 6.0L;
-    long double s = sinl(PI_L * i / n);
-    return -cosl(PI_L * i / n) / (2.0L * s * s);
+    if (2 * i == n) return 0.0L;                 // x_i = 0 exactly
+    long double s = sin_half(2 * i, n);
+    return -sin_half(n - 2 * i, n) / (2.0L * s * s);
   }
   long double ci = (i == 0 || i == n) ? 2.0L : 1.0L;
   long double cj = (j == 0 || j == n) ? 2.0L : 1.0L;
   long double sgn = ((i + j) & 1) ? -1.0L : 1.0L;
-  long double dx = -2.0L * sinl(PI_L * (i + j) / (2.0L * n)) * sinl(PI_L * (i - j) / (2.0L * n));
+  long double dx = -2.0L * sin_half(i + j, n) * sin_half(i - j, n);
   return (ci / cj) * sgn / dx;
 }
 
