@@ -22,7 +22,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CHEBHIP_LIB_PATH: a diagnostic build of the same library (tools/v4_ablate.sh, tools/f4_ablate.sh); production uses the in-tree one
+# CHEBHIP_LIB_PATH: a diagnostic build of the same library (`make -C csrc diag`, or the parent commit's build for an A/B); production uses the in-tree one
 LIB_PATH = os.environ.get("CHEBHIP_LIB_PATH") or os.path.join(_HERE, "libchebhip.so")
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 

@@ -15,21 +15,13 @@
 // (2 * P flop/point).  The matrix halves stay in registers as in sweep.hip; tile t+1 is loaded into
 // registers during stage 1 of tile t and parked into IN during stage 2 (IN is dead by then).
 #include "sweep.h"
+#include "tile.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace chebhip {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double d2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32;
-
 template <int M> using mode_c = std::integral_constant<int, M>;
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt(0): every
-// wave would wait at each tile boundary for its own prefetch loads and result stores, which
-// serialises the HBM stream with the MFMA phases.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Branch-free fetch with NO use of the loaded value: an invalid slot reads from a zero word
 // (p.zero) instead of being masked afterwards.  Any arithmetic on the value here would make the
@@ -44,23 +36,12 @@ __device__ __forceinline__ double fetch_u(const SweepParams &p, u32 a, int j, in
 
 template <int KS, bool JFAST, int COEF>
 __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
-  constexpr int MTP = KS / 4;
-  constexpr int NG = 8 / MTP;
-  constexpr int HP = 4 * KS;
-  constexpr int NSUB = (KS >= 16) ? 2 : 1;
-  constexpr int NT = 16 * NG * NSUB;
-  constexpr int LDJ = HP + 1;   // odd pitch: conflict-free operand reads (sweep_vec.hip V_LDJ_PAD; this kernel's LDS accesses are all 8-byte)
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int ITEMS = HP * NT / 512;
-  constexpr int CH = ITEMS / NSUB;
-  constexpr int QSTEP = JFAST ? 512 / HP : 512 / NT;
-  constexpr int LDS_QSTEP = JFAST ? QSTEP * LDJ : QSTEP * NT;
-  constexpr int KSTR = JFAST ? 4 : 4 * NT;
-  __shared__ double smem[4 * LDS_ELEMS];           // IN (E,O) and F (E,O)
-  double *inE = smem, *inO = smem + LDS_ELEMS, *fE_ = smem + 2 * LDS_ELEMS, *fO_ = smem + 3 * LDS_ELEMS;
+  using G = TileGeom<KS, JFAST, 8>;                // 8-byte loader slots; every LDS access of this kernel is 8-byte
+  __shared__ double smem[4 * G::LDS_ELEMS];           // IN (E,O) and F (E,O)
+  double *inE = smem, *inO = smem + G::LDS_ELEMS, *fE_ = smem + 2 * G::LDS_ELEMS, *fO_ = smem + 3 * G::LDS_ELEMS;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int mt = w % MTP, ng = w / MTP;
+  const int mt = w % G::MTP, ng = w / G::MTP;
   const int kq = lane >> 4, l16 = lane & 15;
   const int nn = p.P - 1, H = p.H;
   const u32 inner = p.inner, ncols = p.ncols;
@@ -80,26 +61,24 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): see sweep.hip
 
-  const u32 tpo = JFAST ? 1u : (inner + NT - 1) / NT;
-  // XCD-aware tile walk: workgroups b and b+8 share an XCD (and its L2).  Give each XCD one
-  // contiguous range of tiles and let its CUs take neighbouring tiles at the same time, so that a
-  // 128-B line straddled by two neighbouring row pieces is fetched from HBM once, not once per XCD.
+  const u32 tpo = JFAST ? 1u : (inner + G::NT - 1) / G::NT;
+  // (tile.h's tile_walk, written out: through the helper hipcc emits this kernel's scalar prologue in another order -- profiles/tile_refactor/)
   const u32 nxcd = (gridDim.x % 8 == 0) ? 8u : 1u;
   const u32 t_per = (p.ntiles + nxcd - 1) / nxcd;
   const u32 t_lo = (blockIdx.x % nxcd) * t_per;
   const u32 t_hi = (t_lo + t_per < p.ntiles) ? t_lo + t_per : p.ntiles;
   const u32 t_step = gridDim.x / nxcd;
-  const int ld_n = JFAST ? tid / HP : tid % NT;
-  const int ld_j = JFAST ? tid % HP : tid / NT;
-  const int ld_lds0 = JFAST ? ld_n * LDJ + ld_j : ld_j * NT + (ld_n ^ ((ld_j & 1) << 4));
+  const int ld_n = JFAST ? tid / G::HP : tid % G::NT;
+  const int ld_j = JFAST ? tid % G::HP : tid / G::NT;
+  const int ld_lds0 = JFAST ? ld_n * G::LDJ + ld_j : ld_j * G::NT + (ld_n ^ ((ld_j & 1) << 4));
   const int i0 = mt * 16 + (JFAST ? l16 : kq);
 
-  double rj[CH], rm[CH];   // one chunk of the next tile in flight at a time
+  double rj[G::CH], rm[G::CH];   // one chunk of the next tile in flight at a time
 
-  auto issue_loads = [&](auto MODE, u32 tile, int chunk, double (&xj_)[CH], double (&xm_)[CH]) {
+  auto issue_loads = [&](auto MODE, u32 tile, int chunk, double (&xj_)[G::CH], double (&xm_)[G::CH]) {
     constexpr int IM = decltype(MODE)::value;
     if (!JFAST) {
-      const u32 o = tile / tpo, q0 = (tile - o * tpo) * NT;
+      const u32 o = tile / tpo, q0 = (tile - o * tpo) * G::NT;
       const u32 q = q0 + ld_n;
       const bool cv = q < inner;
       const u32 base = o * lineLen + q - joff;
@@ -107,12 +86,12 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
       if (IM == IN_GATHER) gb = p.gcol[cv ? o * inner + q : 0u];
       // running offsets, made opaque so that the optimiser does not hoist one precomputed
       // address pair per slot out of the tile loop (that costs ~60 VGPRs and spills)
-      int jp = ld_j + chunk * CH * QSTEP;
+      int jp = ld_j + chunk * G::CH * G::QSTEP;
       u32 rel = (u32)jp * inner;
       const u32 top = base + (u32)nn * inner;
       asm volatile("" : "+v"(rel), "+v"(jp));
 #pragma unroll
-      for (int s = 0; s < CH; s++, jp += QSTEP, rel += QSTEP * inner) {
+      for (int s = 0; s < G::CH; s++, jp += G::QSTEP, rel += G::QSTEP * inner) {
         const int jm = nn - jp;
         const bool ok = cv && jp < H && jp >= jlo;
         xj_[s] = fetch_u<IM>(p, base + rel, jp, gb, ok);
@@ -121,8 +100,8 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
     } else {
       const int jp = ld_j, jm = nn - jp;
 #pragma unroll
-      for (int s = 0; s < CH; s++) {
-        const u32 c = tile * NT + ld_n + (chunk * CH + s) * QSTEP;
+      for (int s = 0; s < G::CH; s++) {
+        const u32 c = tile * G::NT + ld_n + (chunk * G::CH + s) * G::QSTEP;
         const bool ok = c < ncols && jp < H && jp >= jlo;
         const u32 cc = ok ? c : 0u;
         const u32 base = ((inner == 1) ? cc * lineLen : (cc / inner) * lineLen + (cc % inner)) - joff;
@@ -132,16 +111,16 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
       }
     }
   };
-  auto issue_loads_any = [&](u32 tile, int chunk, double (&xj_)[CH], double (&xm_)[CH]) {
+  auto issue_loads_any = [&](u32 tile, int chunk, double (&xj_)[G::CH], double (&xm_)[G::CH]) {
     if (p.in_mode == IN_GATHER) issue_loads(mode_c<IN_GATHER>{}, tile, chunk, xj_, xm_);
     else issue_loads(mode_c<IN_PLAIN>{}, tile, chunk, xj_, xm_);
   };
-  auto park_chunk = [&](int chunk, const double (&xj_)[CH], const double (&xm_)[CH]) {
+  auto park_chunk = [&](int chunk, const double (&xj_)[G::CH], const double (&xm_)[G::CH]) {
     const bool mid = JFAST && (2 * ld_j == nn);
 #pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int idx = ld_lds0 + (chunk * CH + s) * LDS_QSTEP;
-      const bool m2 = JFAST ? mid : (2 * (ld_j + (chunk * CH + s) * QSTEP) == nn);
+    for (int s = 0; s < G::CH; s++) {
+      const int idx = ld_lds0 + (chunk * G::CH + s) * G::LDS_QSTEP;
+      const bool m2 = JFAST ? mid : (2 * (ld_j + (chunk * G::CH + s) * G::QSTEP) == nn);
       inE[idx] = xj_[s] + xm_[s];
       inO[idx] = m2 ? 0.0 : xj_[s] - xm_[s];
     }
@@ -149,17 +128,18 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
 
   // two accumulator chains over one 16-line sub-tile of an (E,O) LDS image
   auto chains = [&](const double *sE, const double *sO, int nb, v4d &ce, v4d &co) {
-    const int frag = JFAST ? (nb + l16) * LDJ + kq : kq * NT + ((nb + l16) ^ ((kq & 1) << 4));
+    const int frag = G::frag(nb, l16, kq);
     const double *fE = sE + frag, *fO = sO + frag;
+    // (tile.h's mfma_chain with sched_group_barriers behind each group in place of its fence: this kernel's own schedule)
     ce = v4d{0.0, 0.0, 0.0, 0.0}; co = v4d{0.0, 0.0, 0.0, 0.0};
     double fb[2][4];
-    fb[0][0] = fE[0]; fb[0][1] = fE[KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[KSTR];
+    fb[0][0] = fE[0]; fb[0][1] = fE[G::KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[G::KSTR];
 #pragma unroll
     for (int g = 0; g < KS / 2; g++) {
       const int cb = g & 1, nbuf = cb ^ 1;
       if (g + 1 < KS / 2) {
-        fb[nbuf][0] = fE[(2 * g + 2) * KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * KSTR];
-        fb[nbuf][2] = fO[(2 * g + 2) * KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * KSTR];
+        fb[nbuf][0] = fE[(2 * g + 2) * G::KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * G::KSTR];
+        fb[nbuf][2] = fO[(2 * g + 2) * G::KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * G::KSTR];
       }
       if (!JFAST) {
         ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g], fb[cb][0], ce, 0, 0, 0);
@@ -181,7 +161,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
 
   // addressing of this lane's accumulator rows in sub-tile `sub` of tile `tile`
   auto out_geom = [&](u32 tile, int nb, u32 (&ob)[4], bool (&ov)[4], int (&og)[4]) {
-    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * NT;
+    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * G::NT;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       u32 b, cidx; bool lv;
@@ -190,7 +170,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
         lv = q < inner; b = t_o * lineLen + q - joff; cidx = t_o * inner + q;
         ov[r] = lv && (i0 + 4 * r < H);
       } else {
-        const u32 c = tile * NT + nb + 4 * r + kq;
+        const u32 c = tile * G::NT + nb + 4 * r + kq;
         lv = c < ncols; cidx = c;
         b = ((inner == 1) ? c * lineLen : (c / inner) * lineLen + (c % inner)) - joff;
         ov[r] = lv && (i0 < H);
@@ -203,7 +183,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
   u32 tile = t_lo + blockIdx.x / nxcd;
   if (tile < t_hi) {
 #pragma unroll 1
-    for (int ch = 0; ch < NSUB; ch++) { issue_loads_any(tile, ch, rj, rm); park_chunk(ch, rj, rm); }
+    for (int ch = 0; ch < G::NSUB; ch++) { issue_loads_any(tile, ch, rj, rm); park_chunk(ch, rj, rm); }
   }
   lds_barrier();
   for (; tile < t_hi; tile += t_step) {
@@ -212,11 +192,11 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
 
     // ======================= stage 1: g = D u, f = coef(g) -> F =======================
 #pragma unroll 1
-    for (int sub = 0; sub < NSUB; sub++) {
+    for (int sub = 0; sub < G::NSUB; sub++) {
       // chunk 0 of the next tile is issued under the last chain of stage 1 and parked after the
       // first chain of stage 2; later chunks are issued when the previous one has been parked.
-      if (has_next && sub == NSUB - 1) issue_loads_any(nxt, 0, rj, rm);
-      const int nb = (ng * NSUB + sub) * 16;
+      if (has_next && sub == G::NSUB - 1) issue_loads_any(nxt, 0, rj, rm);
+      const int nb = (ng * G::NSUB + sub) * 16;
       u32 ob[4]; bool ov[4]; int og[4];
       out_geom(tile, nb, ob, ov, og);
       // eta (and c = deta * du0) at (line, i) and (line, n-i): requested BEFORE the chain, so that the
@@ -233,8 +213,8 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
         }
         if (COEF == COEF_FULL && ov[r]) {                  // in2 holds the pairs {eta, c}: one 16-B load per point
           const int i = i0 + (JFAST ? 0 : 4 * r);
-          const d2v ei = *(const d2v *)(p.in2 + 2 * (size_t)(ob[r] + (u32)i * inner));
-          const d2v em = *(const d2v *)(p.in2 + 2 * (size_t)(ob[r] + (u32)(nn - i) * inner));
+          const d2 ei = *(const d2 *)(p.in2 + 2 * (size_t)(ob[r] + (u32)i * inner));
+          const d2 em = *(const d2 *)(p.in2 + 2 * (size_t)(ob[r] + (u32)(nn - i) * inner));
           cv[2 * r] = ei[0]; cc[2 * r] = ei[1];
           cv[2 * r + 1] = em[0]; cc[2 * r + 1] = em[1];
         }
@@ -252,7 +232,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
           double fi = cv[2 * r] * gi, fm = cv[2 * r + 1] * gm;               // eta * g
           if (COEF == COEF_FULL) {                                     // + deta * u * du0 (elliptic.C:321)
             // u is on chip: the parity-split tile holds e = u_i + u_{n-i} and o = u_i - u_{n-i}
-            const int uidx = JFAST ? (nb + 4 * r + kq) * LDJ + i : i * NT + ((nb + l16) ^ ((i & 1) << 4));
+            const int uidx = G::at(i, JFAST ? nb + 4 * r + kq : nb + l16);
             const double ue = inE[uidx], uo = inO[uidx];
             const double ui = (im != i) ? ue + uo : 2.0 * ue, um = ue - uo;   // 2 u: in2 carries c / 2
             fi = fi + cc[2 * r] * ui;
@@ -261,7 +241,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
           if (im != i) { e2 = fi + fm; o2 = fi - fm; } else { e2 = fi; o2 = 0.0; }
         }
         // every (row < HP, line < NT) slot of F is written by exactly one lane (zeros in the padding)
-        const int fidx = JFAST ? (nb + 4 * r + kq) * LDJ + i : i * NT + ((nb + l16) ^ ((i & 1) << 4));
+        const int fidx = G::at(i, JFAST ? nb + 4 * r + kq : nb + l16);
         fE_[fidx] = e2; fO_[fidx] = o2;
       }
     }
@@ -269,8 +249,8 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
 
     // ======================= stage 2: t = D f, out = acc + alpha t =======================
 #pragma unroll 1
-    for (int sub = 0; sub < NSUB; sub++) {
-      const int nb = (ng * NSUB + sub) * 16;
+    for (int sub = 0; sub < G::NSUB; sub++) {
+      const int nb = (ng * G::NSUB + sub) * 16;
       u32 ob[4]; bool ov[4]; int og[4];
       out_geom(tile, nb, ob, ov, og);
       double accv[8];
@@ -291,7 +271,7 @@ __global__ __launch_bounds__(512) void cheb_fused_kernel(const SweepParams p) {
       // the stores would also wait for them to reach memory).
       if (has_next) {
         park_chunk(sub, rj, rm);
-        if (sub + 1 < NSUB) issue_loads_any(nxt, sub + 1, rj, rm);
+        if (sub + 1 < G::NSUB) issue_loads_any(nxt, sub + 1, rj, rm);
       }
       {
         const double alpha = p.alpha;
@@ -334,7 +314,7 @@ static hipError_t launch_c(const SweepParams &p, unsigned grid, hipStream_t stre
 
 template <int KS, bool JFAST>
 static hipError_t launch_f(const SweepParams &p0, hipStream_t stream) {
-  constexpr int MTP = KS / 4, NG = 8 / MTP, NSUB = (KS >= 16) ? 2 : 1, NT = 16 * NG * NSUB;
+  constexpr int NT = TileGeom<KS, JFAST, 8>::NT;
   SweepParams p = p0;
   if (JFAST) p.ntiles = (p.ncols + NT - 1) / NT;
   else p.ntiles = (p.ncols / p.inner) * ((p.inner + NT - 1) / NT);

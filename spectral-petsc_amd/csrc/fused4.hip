@@ -19,71 +19,33 @@
 // stores use, 8 DPP broadcasts + selects per sub-tile in place of 8 of the 16 store instructions: FormFunction 256^3 507-512 us
 // against 494-510 us with the 8-byte stores, A/B in one process.  The stores were not what the launch waits for; removed.)
 #include "sweep.h"
+#include "tile.h"
 #include <type_traits>
 
 namespace chebhip {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32;
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void lds_barrier4() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// pitch of a JFAST tile-image line beyond HP doubles (odd: see sweep_vec.hip V_LDJ_PAD)
-#ifndef F4_LDJ_PAD
-#define F4_LDJ_PAD 1
-#endif
-template <int KS, bool JFAST>
-constexpr int f4_lds_doubles() {
-  constexpr int MTP = KS / 4, NG = 8 / MTP, HP = 4 * KS, NT = 32 * NG, LDJ = HP + F4_LDJ_PAD;
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int NFL = (KS == 32) ? (JFAST ? 7 : 8) : 0;
-  return 4 * LDS_ELEMS + 8 * NFL * 64;
-}
-
-// Diagnostic builds only (-DF4_ABLATE=bits; tools/f4_ablate.sh): 1 = no coefficient loads, 2 = no accumulator loads,
-// 4 = no next-tile input loads, 8 = no global stores, 16 = no MFMA chains.  Results are wrong; the timing shows what
-// each stream costs.
-#ifndef F4_ABLATE
-#define F4_ABLATE 0
-#endif
-
-#define AO4(s_) (((s_) < KR) ? ao[((s_) < KR) ? (s_) : 0] : aoL[((s_) - KR) * 64])
+// What each stream costs (coefficient, accumulator, next-tile input loads, stores, MFMA chains compiled out one at a time):
+// DESIGN 4.2, profiles/r02_fused4_ablation.txt.
 
 template <int KS, bool JFAST, bool FULL, bool ACC, bool WIN, bool ETASQ, bool TRIMF>
 __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) {
-  constexpr int MTP = KS / 4;
-  constexpr int NG = 8 / MTP;
-  constexpr int HP = 4 * KS;
-  constexpr int NSUB = 2;
-  constexpr int NT = 16 * NG * NSUB;
-  constexpr int LDJ = HP + F4_LDJ_PAD;   // odd: conflict-free operand reads (sweep_vec.hip V_LDJ_PAD); lines start on 8-byte boundaries
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int ITEMS = HP * NT / 2 / 512;            // 16-B input slots per thread per tile
-  constexpr int CH = ITEMS / NSUB;
-  constexpr int QSTEP = JFAST ? 512 / (HP / 2) : 512 / (NT / 2);
-  constexpr int LDS_QSTEP = JFAST ? QSTEP * LDJ : QSTEP * NT;
-  constexpr int KSTR = JFAST ? 4 : 4 * NT;
-  constexpr int NFL = (KS == 32) ? (JFAST ? 7 : 8) : 0;
-  constexpr int KR = KS - NFL;
+  using G = TileGeom<KS, JFAST>;                      // two sub-tiles per tile, 16-B input slots; LDJ odd: lines start on 8-byte boundaries
   constexpr u32 INVALID = 0x80000000u, T_INVALID = 0x40000000u;     // see sweep_vec.hip: arrays stay below 0x38000000 bytes
   constexpr int IT = (FULL || TRIMF) ? 1 : 0;         // input / accumulator hold interior points only
   constexpr int OT = (FULL || WIN || TRIMF) ? 1 : 0;  // so does the output
   constexpr bool SUB = WIN || (TRIMF && JFAST);       // the last launch of FormFunction: rhs -= b
   constexpr u32 CE = FULL ? 16u : 8u;                 // bytes of one coefficient element
-  static_assert(KS >= 16 && CH >= 1, "two sub-tiles per tile");
+  static_assert(KS >= 16 && G::CH >= 1, "two sub-tiles per tile");
   static_assert(!WIN || (JFAST && ACC && !FULL), "the window mode is the last launch of FormFunction");
   static_assert(!JFAST || ACC, "the contiguous direction is never the first one");
   static_assert(!ETASQ || !FULL, "eta = 1 + gamma u^2 formed on chip: FormFunction only (the line being differentiated is u)");
   static_assert(!TRIMF || (ETASQ && !WIN && !FULL), "FormFunction on the interior line space: eta on chip, homogeneous Dirichlet rows");
 
-  __shared__ double smem[f4_lds_doubles<KS, JFAST>()];
-  double *inE = smem, *inO = smem + LDS_ELEMS, *fE_ = smem + 2 * LDS_ELEMS, *fO_ = smem + 3 * LDS_ELEMS;
+  __shared__ double smem[G::LDS_DOUBLES];
+  double *inE = smem, *inO = smem + G::LDS_ELEMS, *fE_ = smem + 2 * G::LDS_ELEMS, *fO_ = smem + 3 * G::LDS_ELEMS;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int mt = w % MTP, ng = w / MTP;
+  const int mt = w % G::MTP, ng = w / G::MTP;
   const int kq = lane >> 4, l16 = lane & 15;
   const bool odd = l16 & 1; const int l16e = l16 & ~1;
   const int nn = p.P - 1, H = p.H;
@@ -97,32 +59,24 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   const __amdgpu_buffer_rsrc_t r_sub = __builtin_amdgcn_make_buffer_rsrc((void *)((SUB && p.sub) ? p.sub : p.in), 0, (SUB && p.sub) ? p.sub_bytes : 0u, 0x00020000);
   // TRIMF, first direction: the local copy w0 of the state (scatter GL, elliptic.C:486-493) is stored on the way, same geometry as gout
   const __amdgpu_buffer_rsrc_t r_w0 = __builtin_amdgcn_make_buffer_rsrc((void *)((TRIMF && p.w0out) ? (void *)p.w0out : (void *)p.in), 0, (TRIMF && p.w0out) ? p.w0_bytes : 0u, 0x00020000);
-  auto ld16 = [](__amdgpu_buffer_rsrc_t r, u32 off) { return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); };
-  auto st16 = [](__amdgpu_buffer_rsrc_t r, u32 off, d2 v) { if (!(F4_ABLATE & 8) || v.x == 1.2345e300) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)off, 0, 0); };
-  auto ld8 = [](__amdgpu_buffer_rsrc_t r, u32 off) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0)); };
-  auto st8 = [](__amdgpu_buffer_rsrc_t r, u32 off, double v) { if (!(F4_ABLATE & 8) || v == 1.2345e300) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, (int)off, 0, 0); };
 
-  double ae[KS], ao[KR > 0 ? KR : 1];
-  double *aoL = smem + 4 * LDS_ELEMS + (w * NFL) * 64 + lane;
+  double ae[KS], ao[G::KR > 0 ? G::KR : 1];
+  double *aoL = smem + 4 * G::LDS_ELEMS + (w * G::NFL) * 64 + lane;
 
   // XCD-aware tile walk; tile = (block o, NT lines starting at q0)
   const u32 tpo = p.tpo;
-  const u32 nxcd = (gridDim.x % 8 == 0) ? 8u : 1u;
-  const u32 t_per = (p.ntiles + nxcd - 1) / nxcd;
-  const u32 t_lo = (blockIdx.x % nxcd) * t_per;
-  const u32 t_hi = (t_lo + t_per < p.ntiles) ? t_lo + t_per : p.ntiles;
-  const u32 t_step = gridDim.x / nxcd;
+  const TileWalk wk = tile_walk(blockIdx.x, gridDim.x, p.ntiles);
+  const u32 t_hi = wk.t_hi, t_step = wk.t_step;
   auto tile_o = [&](u32 tl) -> u32 { return __umulhi(tl, p.tpo_inv); };
   // byte offset of a tile's origin in an array of geometry g with elements of esz bytes
   auto tile_off = [&](u32 tl, const F4Geom &g, u32 esz) -> u32 {
-    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * NT;
+    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * G::NT;
     return o * (g.os * esz) + q0 * (g.ls * esz);
   };
 
   // ---- loader: COLFAST (line pair 2*ld_a, row ld_b + s*QSTEP and its mirror); JFAST (point pair of line ld_b + s*QSTEP)
-  const int ld_a = JFAST ? tid % (HP / 2) : tid % (NT / 2);
-  const int ld_b = JFAST ? tid / (HP / 2) : tid / (NT / 2);
-  const int ld_lds0 = JFAST ? ld_b * LDJ + 2 * ld_a + IT : ld_b * NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
+  const int ld_a = tid % G::LD_W, ld_b = tid / G::LD_W;
+  const int ld_lds0 = JFAST ? ld_b * G::LDJ + 2 * ld_a + IT : ld_b * G::NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
   const u32 in_ls8 = p.gi.ls * 8u, in_rs8 = p.gi.rs * 8u;
   // JFAST with a trimmed line: the pair is (j, j+1) = (2a+1, 2a+2), stored points (2a, 2a+1): 16-B aligned in memory,
   // 8-B aligned in the LDS image; row 0 of the image stays zero
@@ -130,30 +84,26 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   const u32 lm = JFAST ? (u32)ld_b * in_ls8 + (u32)(nn - 2 * ld_a - 1 - 2 * IT) * 8u : (u32)(2 * ld_a) * 8u + (u32)(nn - ld_b - IT) * in_rs8;
   const u32 lj0 = (!JFAST && IT && ld_b == 0) ? INVALID : lj;          // rows 0 and n of a trimmed line: zeros
   const u32 lm0 = (!JFAST && IT && ld_b == 0) ? INVALID : lm;
-  const u32 slot8 = JFAST ? (u32)QSTEP * in_ls8 : (u32)QSTEP * in_rs8;
+  const u32 slot8 = JFAST ? (u32)G::QSTEP * in_ls8 : (u32)G::QSTEP * in_rs8;
 
-  auto issue_loads = [&](u32 tl, bool valid, int chunk, d2 (&rj)[CH], d2 (&rm)[CH]) {
+  auto issue_loads = [&](u32 tl, bool valid, int chunk, d2 (&rj)[G::CH], d2 (&rm)[G::CH]) {
     const u32 t0 = tile_off(tl, p.gi, 8u);
-    if constexpr (F4_ABLATE & 4) { if (tl != p.ntiles + 12345u) {
 #pragma unroll
-      for (int s = 0; s < CH; s++) { rj[s] = d2{1.0 + s, 2.0}; rm[s] = d2{0.5, 0.25 * chunk}; }
-      return; } }
-#pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int sg = chunk * CH + s;
+    for (int s = 0; s < G::CH; s++) {
+      const int sg = chunk * G::CH + s;
       const u32 so = (u32)sg * slot8;
       rj[s] = ld16(r_in, (sg == 0 ? lj0 : lj) + (valid ? t0 + so : T_INVALID));
       rm[s] = ld16(r_in, (sg == 0 ? lm0 : lm) + (valid ? (JFAST ? t0 + so : t0 - so) : T_INVALID));
     }
   };
-  auto park_chunk = [&](int chunk, const d2 (&rj)[CH], const d2 (&rm)[CH]) {
+  auto park_chunk = [&](int chunk, const d2 (&rj)[G::CH], const d2 (&rm)[G::CH]) {
 #pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int idx = ld_lds0 + (chunk * CH + s) * LDS_QSTEP;
+    for (int s = 0; s < G::CH; s++) {
+      const int idx = ld_lds0 + (chunk * G::CH + s) * G::LDS_QSTEP;
       if (!JFAST) {
         *(d2 *)(inE + idx) = rj[s] + rm[s];
         *(d2 *)(inO + idx) = rj[s] - rm[s];
-      } else if (IT || (LDJ & 1)) {                                      // odd index or odd pitch: two 8-B halves (ds_write2_b64)
+      } else if (IT || (G::LDJ & 1)) {                                      // odd index or odd pitch: two 8-B halves (ds_write2_b64)
         inE[idx] = rj[s].x + rm[s].y; inE[idx + 1] = rj[s].y + rm[s].x;
         inO[idx] = rj[s].x - rm[s].y; inO[idx + 1] = rj[s].y - rm[s].x;
       } else {
@@ -181,10 +131,10 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   }
 
   // LDS index of (row, line) of sub-tile 0 for r = 0; r adds 4 NT (COLFAST) / 4 LDJ (JFAST), the sub-tile 16 lines
-  const int f_r = JFAST ? 4 * LDJ : 4 * NT;
+  const int f_r = JFAST ? 4 * G::LDJ : 4 * G::NT;
   auto f_idx0 = [&](int sub) -> int {
-    const int nb = (ng * NSUB + sub) * 16;
-    return JFAST ? (nb + kq) * LDJ + i0 : i0 * NT + ((nb + l16) ^ ((i0 & 1) << 4));
+    const int nb = (ng * G::NSUB + sub) * 16;
+    return G::at(i0, nb + (JFAST ? kq : l16));
   };
 
   typename std::conditional<FULL, d2, double>::type cv_hi[4], cv_lo[4];  // coefficients of the sub-tile in flight
@@ -192,8 +142,8 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   double ue[(FULL || ETASQ) ? 4 : 1], uo[(FULL || ETASQ) ? 4 : 1];
 
   auto coef_issue = [&](u32 tl, int sub) {
-    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * NT;
-    const int nb = (ng * NSUB + sub) * 16;
+    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * G::NT;
+    const int nb = (ng * G::NSUB + sub) * 16;
     const u32 t0 = o * (p.gc.os * CE) + (q0 + (u32)nb) * c_ls;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -203,10 +153,7 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
       }
       const u32 tv = tv1[JFAST ? r : 0];
       if constexpr (ETASQ) { (void)tv; }                                // eta comes from the tile image, see epi1
-      else if constexpr (F4_ABLATE & 1) {
-        if constexpr (FULL) { cv_hi[r] = d2{1.0, 0.5}; cv_lo[r] = d2{1.0, 0.25}; } else { cv_hi[r] = 1.0; cv_lo[r] = 1.5; }
-        (void)tv;
-      } else if constexpr (FULL) { cv_hi[r] = ld16(r_coef, k_hi[r] + tv); cv_lo[r] = ld16(r_coef, k_lo[r] + tv); }
+      else if constexpr (FULL) { cv_hi[r] = ld16(r_coef, k_hi[r] + tv); cv_lo[r] = ld16(r_coef, k_lo[r] + tv); }
       else { cv_hi[r] = ld8(r_coef, k_hi[r] + tv); cv_lo[r] = ld8(r_coef, k_lo[r] + tv); }
     }
   };
@@ -248,7 +195,7 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   };
 
   // ---- stage 2, COLFAST: after the lane exchange a lane owns, for rp = 0, 1, row i0 + 4 (2 rp + odd) and of it the two
-  // adjacent columns starting at the even lane of its pair (16-B pieces, sweep_vec.hip)
+  // adjacent columns starting at the even lane of its pair (16-B pieces, as in sweep_vec.hip)
   const u32 o_ls8 = p.go.ls * 8u, o_rs8 = p.go.rs * 8u, a_ls8 = p.ga.ls * 8u, a_rs8 = p.ga.rs * 8u;
   u32 o_hi[JFAST ? 1 : 2], o_lo[JFAST ? 1 : 2], c_hi[JFAST ? 1 : 2], c_lo[JFAST ? 1 : 2];
   if (!JFAST) {
@@ -277,12 +224,12 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   d2 sub_hi[SUB ? 2 : 1], sub_lo[SUB ? 2 : 1];
   u32 tv2[JFAST ? 4 : 1];                              // masked tile offsets of `out`
   auto acc_issue = [&](u32 tl, int sub) {
-    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * NT;
-    const u32 nb = (u32)(ng * NSUB + sub) * 16u;
+    const u32 o = tile_o(tl), q0 = (tl - o * tpo) * G::NT;
+    const u32 nb = (u32)(ng * G::NSUB + sub) * 16u;
     if (!JFAST) {
       const u32 q = q0 + nb + (u32)l16e;
       tv2[0] = (q < qmax) ? o * (p.go.os * 8u) + (q0 + nb) * 8u : T_INVALID;
-      if (ACC && !(F4_ABLATE & 2)) {
+      if (ACC) {
         const u32 ta = o * (p.ga.os * 8u) + (q0 + nb) * 8u;
 #pragma unroll
         for (int rp = 0; rp < 2; rp++) { acc_hi[rp] = ld16(r_acc, c_hi[rp] + ta); acc_lo[rp] = ld16(r_acc, c_lo[rp] + ta); }
@@ -297,7 +244,7 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
       for (int r = 0; r < 4; r++) {
         const u32 q = q0 + nb + (u32)(4 * r + kq) - qt;
         tv2[r] = (q < qmax - 2u * qt) ? to + (u32)(4 * r) * o_ls8 : T_INVALID;
-        const double ah = (F4_ABLATE & 2) ? 1.0 : ld8(r_acc, c_hi[0] + ta + (u32)(4 * r) * a_ls8), al = (F4_ABLATE & 2) ? 2.0 : ld8(r_acc, c_lo[0] + ta + (u32)(4 * r) * a_ls8);
+        const double ah = ld8(r_acc, c_hi[0] + ta + (u32)(4 * r) * a_ls8), al = ld8(r_acc, c_lo[0] + ta + (u32)(4 * r) * a_ls8);
         if (r & 1) { acc_hi[r >> 1].y = ah; acc_lo[r >> 1].y = al; } else { acc_hi[r >> 1].x = ah; acc_lo[r >> 1].x = al; }
         if constexpr (SUB) {
           const double sh = ld8(r_sub, o_hi[0] + tv2[r]), sl = ld8(r_sub, o_lo[0] + tv2[r]);
@@ -305,16 +252,6 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
         }
       }
     }
-  };
-  auto bc_even = [](double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0xA0, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xA0, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-  };
-  auto bc_odd = [](double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0xF5, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xF5, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
   };
   auto epi2 = [&](const v4d &ce, const v4d &co) {
     double hi[4], lo[4];
@@ -351,51 +288,24 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
   // three hooks at fixed k-steps of a chain: global loads, LDS parking, late LDS reads
   auto chain = [&](const double *sE, const double *sO, int sub, int g_a, int g_b, int g_c, v4d &ce, v4d &co,
                    auto &&fn_a, auto &&fn_b, auto &&fn_c) {
-    const int nb = (ng * NSUB + sub) * 16;
+    const int nb = (ng * G::NSUB + sub) * 16;
     ce = v4d{0.0, 0.0, 0.0, 0.0}; co = v4d{0.0, 0.0, 0.0, 0.0};
-    const int frag = JFAST ? (nb + l16) * LDJ + kq : kq * NT + ((nb + l16) ^ ((kq & 1) << 4));
-    const double *fE = sE + frag, *fO = sO + frag;
-    if constexpr (F4_ABLATE & 16) {                    // no matrix work: what the memory streams cost alone
-      fn_a(); fn_b(); fn_c();
-      ce[0] = fE[0] + ae[0]; co[0] = fO[KSTR] + AO4(KS - 1); ce[1] = fE[2 * KSTR]; co[2] = fO[3 * KSTR];
-      return;
-    }
-    double fb[2][4];
-    fb[0][0] = fE[0]; fb[0][1] = fE[KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[KSTR];
-#pragma unroll
-    for (int g = 0; g < KS / 2; g++) {
-      const int cb = g & 1, nbuf = cb ^ 1;
-      if (g + 1 < KS / 2) {
-        fb[nbuf][0] = fE[(2 * g + 2) * KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * KSTR];
-        fb[nbuf][2] = fO[(2 * g + 2) * KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * KSTR];
-      }
-      __builtin_amdgcn_sched_barrier(0);               // fragment reads stay one group ahead of their MFMAs
-      if (g == g_a) fn_a();
-      if (g == g_b) fn_b();
-      if (g == g_c) fn_c();
-      if (!JFAST) {
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g], fb[cb][0], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(AO4(2 * g), fb[cb][2], co, 0, 0, 0);
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g + 1], fb[cb][1], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(AO4(2 * g + 1), fb[cb][3], co, 0, 0, 0);
-      } else {
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][0], ae[2 * g], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][2], AO4(2 * g), co, 0, 0, 0);
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][1], ae[2 * g + 1], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][3], AO4(2 * g + 1), co, 0, 0, 0);
-      }
-    }
+    const int frag = G::frag(nb, l16, kq);
+    mfma_chain<KS, JFAST, G::KSTR>(sE + frag, sO + frag, ce, co, [&](int k) { return ae[k]; }, [&](int k) { return frag_odd<G::KR>(k, ao, aoL); },
+                                   [&](int g) { if (g == g_a) fn_a(); if (g == g_b) fn_b(); if (g == g_c) fn_c(); });
   };
 
-  u32 tile = t_lo + blockIdx.x / nxcd;
+  u32 tile = wk.first();
   if (tile >= t_hi) return;                            // whole workgroup: no barrier is skipped by part of it
-  d2 rj[CH], rm[CH];
+  d2 rj[G::CH], rm[G::CH];
   {
     // first tile: both chunks requested BEFORE the matrix fragments (one memory round trip instead of two)
-    d2 rjB[CH], rmB[CH];
+    d2 rjB[G::CH], rmB[G::CH];
     issue_loads(tile, true, 0, rj, rm); issue_loads(tile, true, 1, rjB, rmB);
-    if (JFAST && IT) { if (tid < NT) { inE[tid * LDJ] = 0.0; inO[tid * LDJ] = 0.0; } }
-    // the CUs of an XCD start at four different places of the fragment set (sweep_vec.hip)
+    if (JFAST && IT) { if (tid < G::NT) { inE[tid * G::LDJ] = 0.0; inO[tid * G::LDJ] = 0.0; } }
+    // Every workgroup of the chip fetches the same 256 KiB at the same moment.  The CUs of an XCD start at four
+    // different places of their fragment sets (a static rotation per code path: the registers are fixed), which
+    // spreads the requests over the L2 channels instead of queueing them on one line at a time.
     auto load_frags = [&](auto ROT_) {
       constexpr int ROT = decltype(ROT_)::value;
 #pragma unroll
@@ -404,11 +314,11 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
         const d2 ve = ((const d2 *)p.fragE2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
         const d2 vo = ((const d2 *)p.fragO2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
         ae[2 * g] = ve.x; ae[2 * g + 1] = ve.y;
-        if (2 * g < KR) ao[2 * g] = vo.x; else aoL[(2 * g - KR) * 64] = vo.x;
-        if (2 * g + 1 < KR) ao[2 * g + 1] = vo.y; else aoL[(2 * g + 1 - KR) * 64] = vo.y;
+        if (2 * g < G::KR) ao[2 * g] = vo.x; else aoL[(2 * g - G::KR) * 64] = vo.x;
+        if (2 * g + 1 < G::KR) ao[2 * g + 1] = vo.y; else aoL[(2 * g + 1 - G::KR) * 64] = vo.y;
       }
     };
-    switch ((blockIdx.x / nxcd) & 3u) {
+    switch (wk.rank() & 3u) {
       case 0: load_frags(std::integral_constant<int, 0>{}); break;
       case 1: load_frags(std::integral_constant<int, KS / 8>{}); break;
       case 2: load_frags(std::integral_constant<int, KS / 4>{}); break;
@@ -422,7 +332,7 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
     // the two waves of a SIMD (w, w + 4) do their vector work at different k-steps of their chains
     constexpr bool GRPB = decltype(GRPB_)::value;
     constexpr int G_A = GRPB ? 0 : KS / 8, G_B = GRPB ? KS / 4 : 3 * KS / 8, G_C = KS / 2 - 2;
-    lds_barrier4();
+    lds_barrier();
     for (; tile < t_hi; tile += t_step) {
       const u32 nxt = tile + t_step;
       const bool v1 = nxt < t_hi;
@@ -432,14 +342,14 @@ __global__ __launch_bounds__(512) void cheb_fused4_kernel(const Fused4Params p) 
       epi1(0, ce, co);
       chain(inE, inO, 1, G_A, G_B, G_C, ce, co, [&] { coef_issue(tile, 1); issue_loads(nxt, v1, 0, rj, rm); }, [] {}, [&] { u_read(1); });
       epi1(1, ce, co);
-      lds_barrier4();                                  // F complete, IN dead
+      lds_barrier();                                  // F complete, IN dead
       // ---- stage 2: t = D f, out = acc + alpha t; the next tile goes into IN
       chain(fE_, fO_, 0, G_A, G_B, G_C, ce, co, [&] { acc_issue(tile, 0); },
             [&] { park_chunk(0, rj, rm); issue_loads(nxt, v1, 1, rj, rm); }, [] {});
       epi2(ce, co);
       chain(fE_, fO_, 1, G_A, G_B, G_C, ce, co, [&] { acc_issue(tile, 1); }, [&] { park_chunk(1, rj, rm); }, [] {});
       epi2(ce, co);
-      lds_barrier4();                                  // IN complete, F dead
+      lds_barrier();                                  // IN complete, F dead
     }
   };
   if (w >= 4) run(std::true_type{}); else run(std::false_type{});
@@ -456,7 +366,7 @@ static hipError_t launch4(const Fused4Params &p, unsigned grid, hipStream_t stre
 
 template <int KS>
 static hipError_t launch4_ks(Fused4Params &p, bool jfast, bool full, bool acc, bool win, hipStream_t stream) {
-  constexpr int NT = 32 * (8 / (KS / 4));
+  constexpr int NT = TileGeom<KS, false>::NT;
   p.tpo = (p.qmax + NT - 1) / NT;
   p.tpo_inv = (unsigned)((0x100000000ull + p.tpo - 1) / p.tpo);
   p.ntiles = p.nouter * p.tpo;

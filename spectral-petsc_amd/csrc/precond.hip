@@ -185,9 +185,7 @@ struct FzParams { int M, H; unsigned ncols, ntiles; const double *x; double *y; 
                   // bits as its array W, which cost this launch a third of its bytes): line -> (i, j) within a field of `flines` lines
                   int d, n1; unsigned flines; const double *l0, *l1, *lz; };
 // (image row pitch: odd, as in sweep_vec.hip / stokes.hip -- conflict-free operand reads, 8-byte-aligned lines)
-#ifndef FZ_PAD
-#define FZ_PAD 1
-#endif
+constexpr int FZ_PAD = 1;
 constexpr int FZ_KS = 16, FZ_LDJ = 4 * FZ_KS + FZ_PAD, FZ_NT = 32;
 __device__ __forceinline__ void fz_put2(double *dst, double2 v) {
   if (FZ_LDJ % 2 == 0) *(double2 *)dst = v; else { dst[0] = v.x; dst[1] = v.y; }

@@ -627,12 +627,10 @@ struct ZfParams {
 };
 // Image row pitch HP + ZF_PAD doubles.  With an ODD pad the MFMA operand reads (lane (l16, kq) reads points kq + 4k, kq + 4k + 4 of line
 // l16: ds_read2_b64) are free of bank conflicts, with pitch = 2 mod 32 each is a 2-way conflict (tools/lds_probe.hip,
-// profiles/r06_lds_probe.txt).  Measured here (tools/ldspad_ab.sh, profiles/r06_lds_probe.txt): the callback does not change (255.8 / 257.2
+// profiles/r06_lds_probe.txt).  Measured here (profiles/r06_lds_probe.txt, DESIGN_history.md "LDS pitch of the other contiguous-line kernels"): the callback does not change (255.8 / 257.2
 // against 256.9 / 255.6 us at 128^3) -- the launch is a byte stream, the reads sit under it -- while the 8-byte park of an odd pitch costs the
 // FOLD variants four spilled VGPRs at their 256-register limit.  Shipped: 2 (ZF_PAD = 1 builds and passes the suite).
-#ifndef ZF_PAD
-#define ZF_PAD 2
-#endif
+constexpr int ZF_PAD = 2;
 constexpr int ZF_KS = 16, ZF_LDJ = 4 * ZF_KS + ZF_PAD, ZF_NT = 16, ZF_PG = 130;   // k-steps; image row pitch; lines per tile; row pitch of G_z
 __device__ __forceinline__ void zf_put2(double *dst, double2 v) {
   if (ZF_LDJ % 2 == 0) *(double2 *)dst = v; else { dst[0] = v.x; dst[1] = v.y; }
@@ -1258,9 +1256,7 @@ static void st_out_full(stokes_op *op, const double *force, double *out, hipStre
   const int d = op->d;                                      // no_gp: grad p is inside the y terms (the folded pressure route: pair kernel only)
   if (p3) {                                                 // (the caller has checked st_out_pairs)
     // one pair per thread here too (round 6; rounds 4-5: two): at 64^3 the launch is 256 workgroups either way
-#ifndef ST_OUT_P3_UN
-#define ST_OUT_P3_UN 1
-#endif
+    constexpr int ST_OUT_P3_UN = 1;
     hipLaunchKernelGGL((k_st_out4p<ST_OUT_P3_UN>), dim3(ugrid(op->N >> 1, ST_OUT_P3_UN)), dim3(256), 0, st, op->N, (const int *)op->ixL, y0, y1, y2,
                        (const double *)op->gp[0], (const double *)op->gp[1], (const double *)op->gp[2], p3, force, out, G, p3 + op->N, p3 + 2 * op->N, st_grid(op));
     return;

@@ -23,6 +23,7 @@
 // MFMA is kept off the per-element path: offsets are 32-bit and tile-invariant, the mode
 // switches are hoisted around the unrolled loops, LDS fragment reads run one group ahead.
 #include "sweep.h"
+#include "tile.h"
 #include <map>
 #include <mutex>
 #include <utility>
@@ -32,9 +33,6 @@
 #include <cstdlib>
 
 namespace chebhip {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef unsigned u32;
 
 static std::atomic<long> g_launches{0};
 long sweep_launch_count() { return g_launches.load(); }
@@ -55,11 +53,6 @@ int sweep_num_cus(hipError_t *err) {
 void sweep_note_launch() { g_launches.fetch_add(1); }
 
 template <int M> using mode_c = std::integral_constant<int, M>;
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt(0): every
-// wave would wait at each tile boundary for its own prefetch loads and result stores, which
-// serialises the HBM stream with the MFMA phases.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // One input element at local element offset `a` (point j of its line; gb = global index of the
 // line's j = 1 node in the interior vector, or -1).
@@ -83,20 +76,11 @@ __device__ __forceinline__ double fetch_in(const SweepParams &p, u32 a, int j, i
 
 template <int KS, bool JFAST>
 __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
-  constexpr int MTP = KS / 4;                      // m-tiles of 16 output rows (padded)
-  constexpr int NG = 8 / MTP;                      // wave groups along the line index
-  constexpr int HP = 4 * KS;                       // padded half length
-  constexpr int NSUB = (KS >= 16) ? 2 : 1;         // 16-line sub-tiles per wave per tile
-  constexpr int NT = 16 * NG * NSUB;               // lines per tile: 32, 64, 64, 128
-  constexpr int LDJ = HP + 1;                      // JFAST row pitch: ODD -> conflict-free operand reads (round 6: tools/lds_probe.hip; == 2 mod 32 was a 2-way conflict)
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int ITEMS = HP * NT / 512;             // (j-pair, line) slots per thread per tile
-  constexpr int CH = ITEMS / NSUB;                 // slots per chunk (one chunk rides under one sub-tile)
-  constexpr int QSTEP = JFAST ? 512 / HP : 512 / NT;  // line step (JFAST) / j-pair step (COLFAST) between slots
-  __shared__ double smem[4 * LDS_ELEMS];           // two buffers of (E, O)
+  using G = TileGeom<KS, JFAST, 8>;                // 8-byte loader slots: one (point pair, line) per slot
+  __shared__ double smem[4 * G::LDS_ELEMS];           // two buffers of (E, O)
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int mt = w % MTP, ng = w / MTP;
+  const int mt = w % G::MTP, ng = w / G::MTP;
   const int kq = lane >> 4, l16 = lane & 15;
   const int nn = p.P - 1, H = p.H;
   const u32 inner = p.inner, ncols = p.ncols;
@@ -119,10 +103,8 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
   // COLFAST: a tile is NT consecutive lines q0..q0+NT-1 of ONE outer block o (tiles never
   //          straddle blocks, so a line's offset is uniform base + lane term: no per-lane divide).
   // JFAST  : a tile is NT consecutive lines c of the flattened (outer, inner) line index.
-  const u32 tpo = JFAST ? 1u : (inner + NT - 1) / NT;    // tiles per outer block (COLFAST)
-  // XCD-aware tile walk: workgroups b and b+8 share an XCD (and its L2).  Give each XCD one
-  // contiguous range of tiles and let its CUs take neighbouring tiles at the same time, so that a
-  // 128-B line straddled by two neighbouring row pieces is fetched from HBM once, not once per XCD.
+  const u32 tpo = JFAST ? 1u : (inner + G::NT - 1) / G::NT;    // tiles per outer block (COLFAST)
+  // (tile.h's tile_walk, written out: through the helper hipcc emits this kernel's scalar prologue in another order -- profiles/tile_refactor/)
   const u32 nxcd = (gridDim.x % 8 == 0) ? 8u : 1u;
   const u32 t_per = (p.ntiles + nxcd - 1) / nxcd;
   const u32 t_lo = (blockIdx.x % nxcd) * t_per;
@@ -130,18 +112,17 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
   const u32 t_step = gridDim.x / nxcd;
 
   // loader slots of this thread
-  const int ld_n = JFAST ? tid / HP : tid % NT;          // first line slot (JFAST) / line (COLFAST)
-  const int ld_j = JFAST ? tid % HP : tid / NT;          // j-pair (JFAST) / first j-pair slot (COLFAST)
-  const int ld_lds0 = JFAST ? ld_n * LDJ + ld_j : ld_j * NT + (ld_n ^ ((ld_j & 1) << 4));
-  constexpr int LDS_QSTEP = JFAST ? QSTEP * LDJ : QSTEP * NT;   // QSTEP even -> swizzle parity unchanged
+  const int ld_n = JFAST ? tid / G::HP : tid % G::NT;          // first line slot (JFAST) / line (COLFAST)
+  const int ld_j = JFAST ? tid % G::HP : tid / G::NT;          // j-pair (JFAST) / first j-pair slot (COLFAST)
+  const int ld_lds0 = JFAST ? ld_n * G::LDJ + ld_j : ld_j * G::NT + (ld_n ^ ((ld_j & 1) << 4));
 
-  double rj[CH], rm[CH];                   // x_j and x_{n-j} of the chunk in flight
+  double rj[G::CH], rm[G::CH];                   // x_j and x_{n-j} of the chunk in flight
 
   // Issue the loads of chunk `chunk` of tile `tile` into rj/rm.
   auto issue_loads = [&](auto MODE, u32 tile, int chunk) {
     constexpr int IM = decltype(MODE)::value;
     if (!JFAST) {
-      const u32 o = tile / tpo, q0 = (tile - o * tpo) * NT;
+      const u32 o = tile / tpo, q0 = (tile - o * tpo) * G::NT;
       const u32 q = q0 + ld_n;
       const bool cv = q < inner;
       const u32 base = o * lineLen + q;
@@ -149,12 +130,12 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
       if (IM == IN_GATHER) gb = p.gcol[cv ? o * inner + q : 0u];
       // running offsets, made opaque so that the optimiser does not hoist one precomputed
       // address pair per slot out of the tile loop (that costs ~60 VGPRs and spills)
-      int jp = ld_j + chunk * CH * QSTEP;
+      int jp = ld_j + chunk * G::CH * G::QSTEP;
       u32 rel = (u32)jp * inner;
       const u32 top = base + (u32)nn * inner;
       asm volatile("" : "+v"(rel), "+v"(jp));
 #pragma unroll
-      for (int s = 0; s < CH; s++, jp += QSTEP, rel += QSTEP * inner) {
+      for (int s = 0; s < G::CH; s++, jp += G::QSTEP, rel += G::QSTEP * inner) {
         const int jm = nn - jp;
         const bool ok = cv && jp < H;
         rj[s] = fetch_in<IM>(p, base + rel, jp, gb, ok);
@@ -163,8 +144,8 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
     } else {
       const int jp = ld_j, jm = nn - jp;
 #pragma unroll
-      for (int s = 0; s < CH; s++) {
-        const u32 c = tile * NT + ld_n + (chunk * CH + s) * QSTEP;
+      for (int s = 0; s < G::CH; s++) {
+        const u32 c = tile * G::NT + ld_n + (chunk * G::CH + s) * G::QSTEP;
         const bool ok = c < ncols && jp < H;
         const u32 cc = ok ? c : 0u;
         const u32 base = (inner == 1) ? cc * lineLen : (cc / inner) * lineLen + (cc % inner);
@@ -186,12 +167,12 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
   // Parity split of the chunk in registers -> LDS buffer `buf`.  For the self-paired middle
   // point (2j == n) xm was left 0, so e = x_j; o is forced to 0 there.
   auto park_chunk = [&](int buf, int chunk) {
-    double *dE = smem + buf * (2 * LDS_ELEMS), *dO = dE + LDS_ELEMS;
+    double *dE = smem + buf * (2 * G::LDS_ELEMS), *dO = dE + G::LDS_ELEMS;
     const bool mid = JFAST && (2 * ld_j == nn);
 #pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int idx = ld_lds0 + (chunk * CH + s) * LDS_QSTEP;
-      const bool m2 = JFAST ? mid : (2 * (ld_j + (chunk * CH + s) * QSTEP) == nn);
+    for (int s = 0; s < G::CH; s++) {
+      const int idx = ld_lds0 + (chunk * G::CH + s) * G::LDS_QSTEP;
+      const bool m2 = JFAST ? mid : (2 * (ld_j + (chunk * G::CH + s) * G::QSTEP) == nn);
       dE[idx] = rj[s] + rm[s];
       dO[idx] = m2 ? 0.0 : rj[s] - rm[s];
     }
@@ -203,20 +184,20 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
   u32 tile = t_lo + blockIdx.x / nxcd;
   if (tile < t_hi) {
 #pragma unroll 1
-    for (int ch = 0; ch < NSUB; ch++) { issue_loads_any(tile, ch); park_chunk(0, ch); }
+    for (int ch = 0; ch < G::NSUB; ch++) { issue_loads_any(tile, ch); park_chunk(0, ch); }
   }
   lds_barrier();
   int cur = 0;
   for (; tile < t_hi; tile += t_step) {
     const u32 nxt = tile + t_step;
     const bool has_next = nxt < t_hi;
-    const double *sE = smem + cur * (2 * LDS_ELEMS), *sO = sE + LDS_ELEMS;
+    const double *sE = smem + cur * (2 * G::LDS_ELEMS), *sO = sE + G::LDS_ELEMS;
     // tile base (COLFAST): uniform
-    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * NT;
+    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * G::NT;
 #pragma unroll 1
-    for (int sub = 0; sub < NSUB; sub++) {
+    for (int sub = 0; sub < G::NSUB; sub++) {
       if (has_next) issue_loads_any(nxt, sub);             // in flight during this sub-tile's MFMA chain
-      const int nb = (ng * NSUB + sub) * 16;
+      const int nb = (ng * G::NSUB + sub) * 16;
 
       // ---- where this lane's 4 accumulator rows go ----
       u32 ob[4];        // element offset of output (line, i = 0)
@@ -231,7 +212,7 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
           lv = q < inner; b = t_o * lineLen + q; cidx = t_o * inner + q;
           ov[r] = lv && (i0 + 4 * r < H);
         } else {
-          const u32 c = tile * NT + nb + 4 * r + kq;
+          const u32 c = tile * G::NT + nb + 4 * r + kq;
           lv = c < ncols; cidx = c;
           b = (inner == 1) ? c * lineLen : (c / inner) * lineLen + (c % inner);
           ov[r] = lv && (i0 < H);
@@ -251,18 +232,17 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
 
       // ---- MFMA chains; LDS fragment reads run one group (2 k-steps) ahead ----
       v4d ce = {0.0, 0.0, 0.0, 0.0}, co = {0.0, 0.0, 0.0, 0.0};
-      const int frag = JFAST ? (nb + l16) * LDJ + kq : kq * NT + ((nb + l16) ^ ((kq & 1) << 4));
+      const int frag = G::frag(nb, l16, kq);
       const double *fE = sE + frag, *fO = sO + frag;
-      constexpr int KSTR = JFAST ? 4 : 4 * NT;             // LDS stride of one k-step
-      {
+      {   // (tile.h's mfma_chain without its fence: adding one changes this kernel's schedule)
         double fb[2][4];
-        fb[0][0] = fE[0]; fb[0][1] = fE[KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[KSTR];
+        fb[0][0] = fE[0]; fb[0][1] = fE[G::KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[G::KSTR];
 #pragma unroll
         for (int g = 0; g < KS / 2; g++) {
           const int cb = g & 1, nbuf = cb ^ 1;
           if (g + 1 < KS / 2) {
-            fb[nbuf][0] = fE[(2 * g + 2) * KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * KSTR];
-            fb[nbuf][2] = fO[(2 * g + 2) * KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * KSTR];
+            fb[nbuf][0] = fE[(2 * g + 2) * G::KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * G::KSTR];
+            fb[nbuf][2] = fO[(2 * g + 2) * G::KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * G::KSTR];
           }
           if (!JFAST) {   // rows = outputs i, cols = lines
             ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g], fb[cb][0], ce, 0, 0, 0);
@@ -319,7 +299,7 @@ __global__ __launch_bounds__(512) void cheb_sweep_kernel(const SweepParams p) {
 
 template <int KS, bool JFAST>
 static hipError_t launch_t(const SweepParams &p0, hipStream_t stream) {
-  constexpr int MTP = KS / 4, NG = 8 / MTP, NSUB = (KS >= 16) ? 2 : 1, NT = 16 * NG * NSUB;
+  constexpr int NT = TileGeom<KS, JFAST, 8>::NT;
   SweepParams p = p0;
   if (JFAST) p.ntiles = (p.ncols + NT - 1) / NT;
   else p.ntiles = (p.ncols / p.inner) * ((p.inner + NT - 1) / NT);

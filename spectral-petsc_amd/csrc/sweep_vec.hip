@@ -14,6 +14,7 @@
 // Preconditions (checked on the host, otherwise sweep.hip runs): COLFAST: even line stride;
 // JFAST: stride 1 and even line length; all arrays 16-B aligned.
 #include "sweep.h"
+#include "tile.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -22,45 +23,11 @@ int chebhip_stamp_next();
 
 namespace chebhip {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32;
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-// Pitch of a line of the JFAST tile image in LDS, in doubles beyond the half length HP.  ODD (1): the MFMA operand reads -- lane
-// (l16, kq) reads points kq + 4k, kq + 4k + 4 of line l16 as one ds_read2_b64 -- are free of bank conflicts; with the pitch = 2 mod 32
-// of rounds 1-5 every such read is a 2-way conflict (tools/lds_probe.hip under --pmc, profiles/r06_lds_probe.txt: SQ_LDS_BANK_CONFLICT
-// = half of SQ_LDS_IDX_ACTIVE at pitch 130, 0 at 129, three quarters at 132 -- the 8.26 M conflict cycles of the JFAST launch in every
-// counter record since round 3).  The price: lines start on 8-byte boundaries only, so the parity split parks its 16-byte pieces as
-// ds_write2_b64 instead of ds_write_b128.
-#ifndef V_LDJ_PAD
-#define V_LDJ_PAD 1
-#endif
 // one 16-byte piece into an LDS image whose lines may start on 8-byte boundaries
 template <bool ALIGNED16>
 __device__ __forceinline__ void lds_put2(double *dst, double __attribute__((ext_vector_type(2))) v) {
   if (ALIGNED16) *(double __attribute__((ext_vector_type(2))) *)dst = v;
   else { dst[0] = v.x; dst[1] = v.y; }
-}
-
-__device__ __forceinline__ void lds_barrier_v() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// exchange with the neighbouring lane (lane ^ 1): DPP quad_perm [1,0,3,2]
-__device__ __forceinline__ double swap1(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-
-// LDS doubles of the 16-byte kernels for a (KS, tiling) pair: two (E, O) tile images, double-buffered, plus the
-// LDS-resident matrix fragments at KS = 32
-template <int KS, bool JFAST>
-constexpr int vec_lds_doubles() {
-  constexpr int MTP = KS / 4, NG = 8 / MTP, HP = 4 * KS, NSUB = (KS >= 16) ? 2 : 1, NT = 16 * NG * NSUB, LDJ = HP + V_LDJ_PAD;
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int NFL = (KS == 32) ? (JFAST ? 7 : 8) : 0;
-  return 4 * LDS_ELEMS + 8 * NFL * 64;
 }
 
 // Body of cheb_sweep_vec_kernel (lines of at most 64 points, KS <= 8): workgroup BID of NBLK (the launch's, or those of one job
@@ -84,30 +51,22 @@ template <int KS, bool JFAST, bool SUM3 = false, bool ACC = true>
 __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, const u32 BID, const u32 NBLK) {
   static_assert(KS <= 8, "lines of more than 64 points run vec4_body");
   static_assert(!SUM3 || !ACC, "IN_SUM3 exists for plain stores only");
-  constexpr int MTP = KS / 4;
-  constexpr int NG = 8 / MTP;
-  constexpr int HP = 4 * KS;
-  constexpr int NT = 16 * NG;
-  constexpr int LDJ = HP + V_LDJ_PAD;
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int CH = HP * NT / 2 / 512;               // 16-B slots per thread per tile
-  constexpr int QSTEP = JFAST ? 512 / (HP / 2) : 512 / (NT / 2);   // line step (JFAST) / j-pair step (COLFAST)
-  constexpr int LDS_QSTEP = JFAST ? QSTEP * LDJ : QSTEP * NT;
-  constexpr int KSTR = JFAST ? 4 : 4 * NT;
-  static_assert(CH >= 1 && (QSTEP % 2 == 0 || JFAST), "tile geometry");
+  using G = TileGeom<KS, JFAST>;                     // CH 16-B slots per thread per tile
+  static_assert(G::CH >= 1 && (G::QSTEP % 2 == 0 || JFAST), "tile geometry");
 
 #ifdef CHEB_STAMPS
   const unsigned long long st_entry = __builtin_amdgcn_s_memtime(), rt_entry = __builtin_amdgcn_s_memrealtime();
 #endif
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int mt = w % MTP, ng = w / MTP;
+  const int mt = w % G::MTP, ng = w / G::MTP;
   const int kq = lane >> 4, l16 = lane & 15;
   const int odd = l16 & 1, l16e = l16 & ~1;
   const int nn = p.P - 1, H = p.H;
   const u32 inner = p.inner, ncols = p.ncols;
   const u32 lineLen = (u32)p.P * inner;
 
-  const u32 tpo = JFAST ? 1u : (inner + NT - 1) / NT;
+  const u32 tpo = JFAST ? 1u : (inner + G::NT - 1) / G::NT;
+  // (tile.h's tile_walk, written out: through the helper hipcc emits this kernel's scalar prologue in another order -- profiles/tile_refactor/)
   const u32 nxcd = (NBLK % 8 == 0) ? 8u : 1u;
   const u32 t_per = (p.ntiles + nxcd - 1) / nxcd;
   const u32 t_lo = (BID % nxcd) * t_per;
@@ -117,22 +76,21 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
   if (tile >= t_hi) return;                             // the whole workgroup: no barrier is skipped by part of it
 
   // loader slots: COLFAST (line pair 2*ld_a, j-pair ld_b + s*QSTEP); JFAST (points 2*ld_a, 2*ld_a+1 of line ld_b + s*QSTEP)
-  const int ld_a = JFAST ? tid % (HP / 2) : tid % (NT / 2);
-  const int ld_b = JFAST ? tid / (HP / 2) : tid / (NT / 2);
-  const int ld_lds0 = JFAST ? ld_b * LDJ + 2 * ld_a : ld_b * NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
+  const int ld_a = tid % G::LD_W, ld_b = tid / G::LD_W;
+  const int ld_lds0 = JFAST ? ld_b * G::LDJ + 2 * ld_a : ld_b * G::NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
 
   // two register sets of prefetched lines where the register file allows it at two workgroups per CU (128 VGPRs): plain stores
   constexpr bool TWO = !SUM3 && !ACC;
-  struct Lines { d2 j[CH], m[CH]; };
+  struct Lines { d2 j[G::CH], m[G::CH]; };
   Lines LA, LB;
   const d2 *zero2 = (const d2 *)p.zero;
 
   const bool raw_in = p.raw == 2, raw_out = p.raw == 1;   // the line transforms of precond.hip (sweep.h)
   // the lines of tile `tl` -> registers; !valid (past the workgroup's last tile): every lane reads the zero line
   auto issue_loads = [&](u32 tl, bool valid, Lines &L) {
-    d2 j1[SUM3 ? CH : 1], m1[SUM3 ? CH : 1], j2[SUM3 ? CH : 1], m2[SUM3 ? CH : 1];
+    d2 j1[SUM3 ? G::CH : 1], m1[SUM3 ? G::CH : 1], j2[SUM3 ? G::CH : 1], m2[SUM3 ? G::CH : 1];
     if (!JFAST) {
-      const u32 o = tl / tpo, q0 = (tl - o * tpo) * NT;
+      const u32 o = tl / tpo, q0 = (tl - o * tpo) * G::NT;
       const u32 q = q0 + 2 * ld_a;
       const bool cv = valid && q < inner;                   // inner is even: the pair is in or out together
       const u32 base = o * lineLen + q;
@@ -141,7 +99,7 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
       const u32 top = base + (u32)nn * inner;
       asm volatile("" : "+v"(rel), "+v"(jp));
 #pragma unroll
-      for (int s = 0; s < CH; s++, jp += QSTEP, rel += QSTEP * inner) {
+      for (int s = 0; s < G::CH; s++, jp += G::QSTEP, rel += G::QSTEP * inner) {
         const bool ok = cv && jp < H, okm = ok && nn - jp != jp;
         L.j[s] = *(ok ? (const d2 *)(p.in0 + (base + rel)) : zero2);
         L.m[s] = *(okm ? (const d2 *)(p.in0 + (top - rel)) : zero2);
@@ -153,8 +111,8 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
     } else {
       const int j = 2 * ld_a;                               // points j, j+1 and their mirrors n-j-1, n-j
 #pragma unroll
-      for (int s = 0; s < CH; s++) {
-        const u32 c = tl * NT + ld_b + s * QSTEP;
+      for (int s = 0; s < G::CH; s++) {
+        const u32 c = tl * G::NT + ld_b + s * G::QSTEP;
         const bool ok = valid && c < ncols && j < H;
         const u32 base = (ok ? c : 0u) * lineLen;
         L.j[s] = *(ok ? (const d2 *)(p.in0 + (base + (u32)j)) : zero2);
@@ -167,20 +125,20 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
     }
     if (SUM3) {                                               // all the loads of the tile are in flight together; the sums wait for them here
 #pragma unroll
-      for (int s = 0; s < CH; s++) { L.j[s] = (L.j[s] + j1[s]) + j2[s]; L.m[s] = (L.m[s] + m1[s]) + m2[s]; }
+      for (int s = 0; s < G::CH; s++) { L.j[s] = (L.j[s] + j1[s]) + j2[s]; L.m[s] = (L.m[s] + m1[s]) + m2[s]; }
     }
   };
 
   // parity split of a register set into tile image `buf`
   auto park_chunk = [&](int buf, const Lines &L) {
-    double *dE = smem + buf * (2 * LDS_ELEMS), *dO = dE + LDS_ELEMS;
+    double *dE = smem + buf * (2 * G::LDS_ELEMS), *dO = dE + G::LDS_ELEMS;
 #pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int idx = ld_lds0 + s * LDS_QSTEP;
+    for (int s = 0; s < G::CH; s++) {
+      const int idx = ld_lds0 + s * G::LDS_QSTEP;
       const d2 rj = L.j[s], rm = L.m[s];
       d2 e, o;
       if (!JFAST) {
-        const bool mid = 2 * (ld_b + s * QSTEP) == nn;                  // rm was left 0 there
+        const bool mid = 2 * (ld_b + s * G::QSTEP) == nn;                  // rm was left 0 there
         if (raw_in) { e = rj; o = rm; }                                 // already split: e_j = x_j, o_j = x_{n-j}
         else { e = rj + rm; o = rj - rm; }
         if (mid) o = d2{0.0, 0.0};
@@ -193,8 +151,8 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
           o = d2{rj.x - rm.y, v1 ? rj.y - rm.x : 0.0};
         }
       }
-      lds_put2<!JFAST || (LDJ % 2 == 0)>(dE + idx, e);
-      lds_put2<!JFAST || (LDJ % 2 == 0)>(dO + idx, o);
+      lds_put2<!JFAST || (G::LDJ % 2 == 0)>(dE + idx, e);
+      lds_put2<!JFAST || (G::LDJ % 2 == 0)>(dO + idx, o);
     }
   };
 
@@ -228,7 +186,7 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
 #endif
   park_chunk(0, LA);
   if (!TWO && tile + t_step < t_hi) issue_loads(tile + t_step, true, LA);   // one register set: the next request follows the split
-  lds_barrier_v();
+  lds_barrier();
 #ifdef CHEB_STAMPS
   STAMP(st_loop);
 #endif
@@ -236,8 +194,8 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
   // one tile: chain on image `cur`, results out; `issue_fn` asks for the tile after next at the top, `park_fn` splits the next
   // tile's lines into image cur ^ 1 after the chain (before the stores: its wait covers loads only)
   auto tile_body = [&](int cur, auto &&issue_fn, auto &&park_fn) {
-    const double *sE = smem + cur * (2 * LDS_ELEMS), *sO = sE + LDS_ELEMS;
-    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * NT;
+    const double *sE = smem + cur * (2 * G::LDS_ELEMS), *sO = sE + G::LDS_ELEMS;
+    const u32 t_o = tile / tpo, t_q0 = (tile - t_o * tpo) * G::NT;
 #ifdef CHEB_STAMPS
     STAMP(st_t0); st_tiles++;
 #endif
@@ -262,7 +220,7 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
         a_hi[rp] = b + (u32)i * inner;
         a_lo[rp] = b + (u32)(nn - i) * inner;
       } else {
-        const u32 c = tile * NT + nb + 4 * r + kq;
+        const u32 c = tile * G::NT + nb + 4 * r + kq;
         const int ie = mt * 16 + l16e;                   // points ie, ie+1 of line c; mirrors n-ie-1, n-ie
         const u32 b = (c < ncols ? c : 0u) * lineLen;
         ok_hi[rp] = c < ncols && ie < H;
@@ -291,19 +249,19 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
 #endif
     v4d ce = {0.0, 0.0, 0.0, 0.0}, co = {0.0, 0.0, 0.0, 0.0};
     {
-      const int frag = JFAST ? (nb + l16) * LDJ + kq : kq * NT + ((nb + l16) ^ ((kq & 1) << 4));
+      const int frag = G::frag(nb, l16, kq);
+      // (the chain of tile.h's mfma_chain, written out: through the helper hipcc orders the first two groups' fragment reads
+      // differently and waits for all four in front of the first MFMA)
       const double *fE = sE + frag, *fO = sO + frag;
       double fb[2][4];
-      fb[0][0] = fE[0]; fb[0][1] = fE[KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[KSTR];
+      fb[0][0] = fE[0]; fb[0][1] = fE[G::KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[G::KSTR];
 #pragma unroll
       for (int g = 0; g < KS / 2; g++) {
         const int cb = g & 1, nbuf = cb ^ 1;
         if (g + 1 < KS / 2) {
-          fb[nbuf][0] = fE[(2 * g + 2) * KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * KSTR];
-          fb[nbuf][2] = fO[(2 * g + 2) * KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * KSTR];
+          fb[nbuf][0] = fE[(2 * g + 2) * G::KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * G::KSTR];
+          fb[nbuf][2] = fO[(2 * g + 2) * G::KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * G::KSTR];
         }
-        // fence: keep the fragment reads of group g+1 ABOVE the MFMAs of group g (hipcc otherwise sinks
-        // them to just before their use and every group starts with an exposed LDS round trip)
         __builtin_amdgcn_sched_barrier(0);
         if (!JFAST) {
           ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g], fb[cb][0], ce, 0, 0, 0);
@@ -350,7 +308,7 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
 #ifdef CHEB_STAMPS
     STAMP(st_t1); st_post += st_t1 - st_t0;
 #endif
-    lds_barrier_v();
+    lds_barrier();
 #ifdef CHEB_STAMPS
     STAMP(st_t0); st_bar += st_t0 - st_t1;
 #endif
@@ -388,12 +346,9 @@ __device__ __forceinline__ void vec1_body(const SweepParams &p, double *smem, co
 // (second launch bound: four waves per SIMD = two workgroups per CU, wgs_per_cu: at most 128 VGPRs)
 template <int KS, bool JFAST, bool ACC>
 __global__ __launch_bounds__(512, 4) void cheb_sweep_vec_kernel(const SweepParams p) {
-  __shared__ double smem[vec_lds_doubles<KS, JFAST>()];
+  __shared__ double smem[TileGeom<KS, JFAST>::LDS_DOUBLES];
   vec1_body<KS, JFAST, false, ACC>(p, smem, blockIdx.x, gridDim.x);
 }
-
-// odd-half fragment s of a wave: a register, or (KS = 32: the last NFL of them) its slot in LDS
-#define AO(s_) (((s_) < KR) ? ao[((s_) < KR) ? (s_) : 0] : aoL[((s_) - KR) * 64])
 
 // Diagnostic builds only (make diag, tools/stamp_probe3.py): in-kernel cycle stamps kept in SGPRs
 #ifdef CHEB_STAMPS
@@ -433,26 +388,12 @@ __global__ __launch_bounds__(512, 4) void cheb_sweep_vec_kernel(const SweepParam
 //     the end of the array), which only meet zero entries of the matrix or feed columns that are never stored;
 //   * the lane exchange that makes 16-byte pieces is one DPP broadcast + one select per dword;
 //   * the centro-symmetry sign rides in the scalar factor of the mirror row.
-// Diagnostic builds only (-DV4_ABLATE=bits; tools/v4_ablate.sh): 1 = no input loads, 2 = no accumulator loads, 8 = no global
-// stores, 16 = no MFMA chains.  Results are wrong; the timing shows what each stream costs.
-#ifndef V4_ABLATE
-#define V4_ABLATE 0
-#endif
-// cache policy of the result stores (aux operand of the raw buffer store: 1 = sc0, 2 = nt, 16 = sc1)
-#ifndef V4_STORE_AUX
-#define V4_STORE_AUX 0
-#endif
-// 1 (shipped): the matrix fragments are requested in the order the chains consume them and the first tile's chains
-// start on the k-steps that have landed (no wait for the whole set); 0: the round 2-5 prologue (rotated fetch order,
-// vmcnt(0) before the first tile) -- kept for the A/B builds of tools/v4_overlap_ab.sh
-#ifndef V4_OVERLAP
-#define V4_OVERLAP 1
-#endif
+// What each stream costs (input loads, accumulator loads, stores, MFMA chains compiled out one at a time): DESIGN 4.2b,
+// profiles/r02_v4_ablation.txt.  Cache policies on the result stores (sc1, nt) all lose: DESIGN_history.md, "write-through result stores".
+//
 // fragment pairs requested ahead of the first tile's first chain; the rest is requested INSIDE that chain, one pair
 // per MFMA group, V4_FRAG_AHEAD groups ahead of its use (KS / 2 and more: all of them up front)
-#ifndef V4_FRAG_AHEAD
-#define V4_FRAG_AHEAD 2
-#endif
+constexpr int V4_FRAG_AHEAD = 2;
 
 // MODE: 0 = STORE, 1 = ACC (out = acc + alpha r), 3 = ACC2 (out = (acc + acc2) + alpha r), 2 = MUL (out = acc * (alpha r): OUT_MUL, the modal scaling of the
 // preconditioner's fast diagonalisation folded into its last forward transform -- RAW = 1 only)
@@ -474,24 +415,11 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   static_assert(INM == 0 || (RAW == 1 && MODE == 0), "IN_MUL exists for the raw forward transform with a plain store only");
   static_assert(RAW == 0 || MODE != 1, "the raw modes (sweep.h) are STORE / MUL only");
   static_assert(!MUL || RAW == 1, "OUT_MUL exists for the raw forward transform only");
-  constexpr int MTP = KS / 4;
-  constexpr int NG = 8 / MTP;
-  constexpr int HP = 4 * KS;
-  constexpr int NSUB = 2;
-  constexpr int NT = 16 * NG * NSUB;
-  constexpr int LDJ = HP + V_LDJ_PAD;
-  constexpr int LDS_ELEMS = JFAST ? NT * LDJ : HP * NT;
-  constexpr int ITEMS = HP * NT / 2 / 512;
-  constexpr int CH = ITEMS / NSUB;
-  constexpr int QSTEP = JFAST ? 512 / (HP / 2) : 512 / (NT / 2);
-  constexpr int LDS_QSTEP = JFAST ? QSTEP * LDJ : QSTEP * NT;
-  constexpr int KSTR = JFAST ? 4 : 4 * NT;
-  constexpr int NFL = (KS == 32) ? (JFAST ? 7 : 8) : 0;
-  constexpr int KR = KS - NFL;
+  using G = TileGeom<KS, JFAST>;
   // offsets beyond every buffer (the launcher keeps them < 1 GiB): a per-lane constant may carry INVALID, the scalar
   // part of an offset T_INVALID, and their sum must not wrap back into range
   constexpr u32 INVALID = 0x80000000u, T_INVALID = 0x40000000u;
-  static_assert(KS >= 16 && CH >= 1, "v4 needs two sub-tiles per tile");
+  static_assert(KS >= 16 && G::CH >= 1, "v4 needs two sub-tiles per tile");
 
 #ifdef CHEB_STAMPS
   unsigned long long st_seg[5] = {0, 0, 0, 0, 0}, st_prev = 0, st_begin = 0, st_loop = 0, st_first = 0;   // diagnostic build only (tools/stamp_probe3.py)
@@ -499,7 +427,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
 #endif
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   STAMP3_MARK(st_begin);
-  const int mt = w % MTP, ng = w / MTP;
+  const int mt = w % G::MTP, ng = w / G::MTP;
   const int kq = lane >> 4, l16 = lane & 15;
   const bool odd = l16 & 1; const int l16e = l16 & ~1;
   const int nn = p.P - 1, H = p.H;
@@ -510,32 +438,26 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   const __amdgpu_buffer_rsrc_t r_acc = __builtin_amdgcn_make_buffer_rsrc((void *)(ACC ? p.acc : p.in0), 0, ACC ? p.acc_bytes : 0u, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_acc2 = __builtin_amdgcn_make_buffer_rsrc((void *)(ACC2 ? p.acc2 : p.in0), 0, ACC2 ? p.acc_bytes : 0u, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc((void *)p.out, 0, p.out_bytes, 0x00020000);
-  auto ld16 = [](__amdgpu_buffer_rsrc_t r, u32 off) { return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); };
-  auto st16 = [](__amdgpu_buffer_rsrc_t r, u32 off, d2 v) { if (!(V4_ABLATE & 8) || v.x == 1.2345e300) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)off, 0, V4_STORE_AUX); };
 
-  double ae[KS], ao[KR > 0 ? KR : 1];
-  double *aoL = smem + 4 * LDS_ELEMS + (w * NFL) * 64 + lane;
+  double ae[KS], ao[G::KR > 0 ? G::KR : 1];
+  double *aoL = smem + 4 * G::LDS_ELEMS + (w * G::NFL) * 64 + lane;
 
-  const u32 tpo = JFAST ? 1u : (qmax + NT - 1) / NT;
-  const u32 nxcd = (NBLK % 8 == 0) ? 8u : 1u;
-  const u32 t_per = (p.ntiles + nxcd - 1) / nxcd;
-  const u32 t_lo = (BID % nxcd) * t_per;
-  const u32 t_hi = (t_lo + t_per < p.ntiles) ? t_lo + t_per : p.ntiles;
-  const u32 t_step = NBLK / nxcd;
+  const u32 tpo = JFAST ? 1u : (qmax + G::NT - 1) / G::NT;
+  const TileWalk wk = tile_walk(BID, NBLK, p.ntiles);
+  const u32 t_hi = wk.t_hi, t_step = wk.t_step;
 
   // loader slots as in v1: COLFAST (line pair 2*ld_a, point pair ld_b + s*QSTEP); JFAST (points 2*ld_a, 2*ld_a+1 of
   // line ld_b + s*QSTEP).  Per-lane byte offsets of slot 0 (point / mirror); a slot adds a scalar
-  const int ld_a = JFAST ? tid % (HP / 2) : tid % (NT / 2);
-  const int ld_b = JFAST ? tid / (HP / 2) : tid / (NT / 2);
-  const int ld_lds0 = JFAST ? ld_b * LDJ + 2 * ld_a : ld_b * NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
+  const int ld_a = tid % G::LD_W, ld_b = tid / G::LD_W;
+  const int ld_lds0 = JFAST ? ld_b * G::LDJ + 2 * ld_a : ld_b * G::NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
   const u32 in_os8 = p.in_os * 8u, in_rs8 = p.in_rs * 8u;
   const u32 lj = JFAST ? (u32)ld_b * in_os8 + (u32)(2 * ld_a) * 8u : (u32)(2 * ld_a) * 8u + (u32)ld_b * in_rs8;
   const u32 lm = JFAST ? (u32)ld_b * in_os8 + (u32)(nn - 2 * ld_a - 1) * 8u : (u32)(2 * ld_a) * 8u + (u32)(nn - ld_b) * in_rs8;
-  const u32 slot8 = JFAST ? (u32)QSTEP * in_os8 : (u32)QSTEP * in_rs8;      // byte step between two slots of a lane
+  const u32 slot8 = JFAST ? (u32)G::QSTEP * in_os8 : (u32)G::QSTEP * in_rs8;      // byte step between two slots of a lane
   // byte offset of a tile's origin in an array of geometry (os8, rs8), or INVALID past the workgroup's last tile
   auto tile_off = [&](u32 tl, bool valid, u32 os8) -> u32 {
-    if (JFAST) return valid ? tl * NT * os8 : T_INVALID;
-    const u32 o = tl / tpo, q0 = (tl - o * tpo) * NT;
+    if (JFAST) return valid ? tl * G::NT * os8 : T_INVALID;
+    const u32 o = tl / tpo, q0 = (tl - o * tpo) * G::NT;
     return valid ? o * os8 + q0 * 8u : T_INVALID;
   };
 
@@ -543,15 +465,15 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   const u32 fb = p.in_fblocks, fskip8 = p.in_fskip * 8u;
   auto in_tile_off = [&](u32 tl) -> u32 {
     u32 off = tile_off(tl, true, in_os8);
-    if (fb) off += __umulhi(JFAST ? tl * NT : tl / tpo, p.in_fblocks_inv) * fskip8;
+    if (fb) off += __umulhi(JFAST ? tl * G::NT : tl / tpo, p.in_fblocks_inv) * fskip8;
     return off;
   };
 
   // GATH: byte address of (row, first column) in vector 0 of the array that holds the row, and that array's doubles per vector,
   // for the thread's ITEMS loader slots (row ld_b + sg QSTEP) and their mirrors
   typedef const d2 __attribute__((address_space(1))) *gd2p;
-  unsigned long long gb_j[GATH ? ITEMS : 1], gb_m[GATH ? ITEMS : 1];
-  u32 glq_j[GATH ? ITEMS : 1], glq_m[GATH ? ITEMS : 1];
+  unsigned long long gb_j[GATH ? G::ITEMS : 1], gb_m[GATH ? G::ITEMS : 1];
+  u32 glq_j[GATH ? G::ITEMS : 1], glq_m[GATH ? G::ITEMS : 1];
   // PUSH: the same for the rows the lane STORES (accumulator rows 2 rp + odd of its 16-row block, and their mirrors), in the owners'
   // result arrays; psink: where a lane with nothing to store writes (the sweep's own output array: straight-line stores keep the
   // loop's wait counts exact)
@@ -564,9 +486,9 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
     // eight rows up.  History (tools/stamp_probe_rank.py, profiles/r06_dist/rank_stamps.txt; the local jobs of the same launch reach
     // their first tile after 8.7 k cycles): a while loop over the ranges per row 15.0 k, eight compare chains with per-lane loads of
     // the owner's entries 12.1 k, with an LDS copy of the kernel argument's table 10.6 k.
-    unsigned long long *gRB = (unsigned long long *)(smem + 2 * LDS_ELEMS);
-    u32 *gRL = (u32 *)(gRB + 2 * HP);
-    unsigned long long *gDB = (unsigned long long *)(gRL + 2 * HP);    // PUSH: the row's place in its owner's result array
+    unsigned long long *gRB = (unsigned long long *)(smem + 2 * G::LDS_ELEMS);
+    u32 *gRL = (u32 *)(gRB + 2 * G::HP);
+    unsigned long long *gDB = (unsigned long long *)(gRL + 2 * G::HP);    // PUSH: the row's place in its owner's result array
     if (tid <= nn) {
       const int gG = gs->G;
       unsigned long long pb = (unsigned long long)gs->p[0], db = PUSH ? (unsigned long long)gs->dp[0] : 0ull; u32 lq = gs->lq[0]; int s0v = gs->s0[0], pmv = gs->pmax[0];
@@ -593,29 +515,29 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       psink = (unsigned long long)p.out + (unsigned long long)tid * 16ull;
     }
 #pragma unroll
-    for (int sg = 0; sg < ITEMS; sg++) {
-      int row = ld_b + sg * QSTEP; if (row > nn) row = nn;       // (rows past the half meet zero columns of the matrix; they stay inside the line)
+    for (int sg = 0; sg < G::ITEMS; sg++) {
+      int row = ld_b + sg * G::QSTEP; if (row > nn) row = nn;       // (rows past the half meet zero columns of the matrix; they stay inside the line)
       gb_j[sg] = gRB[row]; glq_j[sg] = gRL[row];
       gb_m[sg] = gRB[nn - row]; glq_m[sg] = gRL[nn - row];
     }
   }
-  d2 rjA[CH], rmA[CH], rjB[CH], rmB[CH];
-  constexpr int ECH = INM ? CH : 1;
+  d2 rjA[G::CH], rmA[G::CH], rjB[G::CH], rmB[G::CH];
+  constexpr int ECH = INM ? G::CH : 1;
   d2 ejA[ECH], emA[ECH], ejB[ECH], emB[ECH];           // IN_MUL: the multipliers of chunk A / B, in flight beside them
   d2 accX_hi[2], accX_lo[2], accY_hi[2], accY_lo[2];
   d2 acc2X_hi[2], acc2X_lo[2], acc2Y_hi[2], acc2Y_lo[2];   // ACC2 only
 
-  auto issue_loads = [&](u32 tl, bool valid, int chunk, d2 (&rj)[CH], d2 (&rm)[CH]) {
+  auto issue_loads = [&](u32 tl, bool valid, int chunk, d2 (&rj)[G::CH], d2 (&rm)[G::CH]) {
     if constexpr (GATH) {
       // a tile past the workgroup's last re-reads tile 0 (never used); lanes past the last column of the block re-read its last pair
       // (they feed columns that are never stored) -- every address stays inside the arrays
       const u32 tle = valid ? tl : 0u;
       const u32 gf0 = p.gfield0;
-      const u32 o = tle / tpo, q0 = (tle - o * tpo) * NT;
+      const u32 o = tle / tpo, q0 = (tle - o * tpo) * G::NT;
       u32 qq = q0 + 2u * (u32)ld_a; if (qq > qmax - 2u) qq = qmax - 2u;
 #pragma unroll
-      for (int s = 0; s < CH; s++) {
-        const int sg = chunk * CH + s;
+      for (int s = 0; s < G::CH; s++) {
+        const int sg = chunk * G::CH + s;
         rj[s] = *(gd2p)(gb_j[sg] + ((unsigned long long)(o + gf0) * glq_j[sg] + qq) * 8ull);
         rm[s] = *(gd2p)(gb_m[sg] + ((unsigned long long)(o + gf0) * glq_m[sg] + qq) * 8ull);
       }
@@ -625,29 +547,25 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
     if constexpr (INM != 0) {
       d2 (&ej)[ECH] = (&rj == &rjA) ? ejA : ejB; d2 (&em)[ECH] = (&rj == &rjA) ? emA : emB;
 #pragma unroll
-      for (int s = 0; s < CH; s++) {
-        const u32 so = (u32)(chunk * CH + s) * slot8;
+      for (int s = 0; s < G::CH; s++) {
+        const u32 so = (u32)(chunk * G::CH + s) * slot8;
         ej[s] = ld16(r_in1, lj + (valid ? t0 + so : T_INVALID));
         em[s] = ld16(r_in1, lm + (valid ? (JFAST ? t0 + so : t0 - so) : T_INVALID));
       }
     }
-    if constexpr (V4_ABLATE & 1) { if (tl != p.ntiles + 12345u) {
 #pragma unroll
-      for (int s = 0; s < CH; s++) { rj[s] = d2{1.0 + s, 2.0}; rm[s] = d2{0.5, 0.25 * chunk}; }
-      return; } }
-#pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const u32 so = (u32)(chunk * CH + s) * slot8;                          // scalar
+    for (int s = 0; s < G::CH; s++) {
+      const u32 so = (u32)(chunk * G::CH + s) * slot8;                          // scalar
       rj[s] = ld16(r_in, lj + (valid ? t0 + so : T_INVALID));
       rm[s] = ld16(r_in, lm + (valid ? (JFAST ? t0 + so : t0 - so) : T_INVALID));
     }
   };
   const bool oddP = (p.P & 1) != 0;                    // a self-paired middle point exists (COLFAST only; JFAST needs even P)
-  auto park_chunk = [&](int buf, int chunk, const d2 (&rj)[CH], const d2 (&rm)[CH]) {
-    double *dE = smem + buf * (2 * LDS_ELEMS), *dO = dE + LDS_ELEMS;
+  auto park_chunk = [&](int buf, int chunk, const d2 (&rj)[G::CH], const d2 (&rm)[G::CH]) {
+    double *dE = smem + buf * (2 * G::LDS_ELEMS), *dO = dE + G::LDS_ELEMS;
 #pragma unroll
-    for (int s = 0; s < CH; s++) {
-      const int idx = ld_lds0 + (chunk * CH + s) * LDS_QSTEP;
+    for (int s = 0; s < G::CH; s++) {
+      const int idx = ld_lds0 + (chunk * G::CH + s) * G::LDS_QSTEP;
       d2 e, o;
       d2 xj = rj[s], xm = rm[s];
       if constexpr (INM != 0) {
@@ -660,13 +578,13 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       } else if (!JFAST) {
         e = xj + xm;
         o = xj - xm;                                   // the middle point of an odd line is its own mirror: o = 0
-        if (oddP) { const bool mid = 2 * (ld_b + (chunk * CH + s) * QSTEP) == nn; if (mid) e = xj; }
+        if (oddP) { const bool mid = 2 * (ld_b + (chunk * G::CH + s) * G::QSTEP) == nn; if (mid) e = xj; }
       } else {
         e = d2{xj.x + xm.y, xj.y + xm.x};
         o = d2{xj.x - xm.y, xj.y - xm.x};
       }
-      lds_put2<!JFAST || (LDJ % 2 == 0)>(dE + idx, e);
-      lds_put2<!JFAST || (LDJ % 2 == 0)>(dO + idx, o);
+      lds_put2<!JFAST || (G::LDJ % 2 == 0)>(dE + idx, e);
+      lds_put2<!JFAST || (G::LDJ % 2 == 0)>(dO + idx, o);
     }
   };
 
@@ -699,12 +617,11 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   }
   const u32 out_os8 = p.out_os * 8u, acc_os8 = p.acc_os * 8u;
   const u32 sub8_out = JFAST ? 16u * out_os8 : 16u * 8u, sub8_acc = JFAST ? 16u * acc_os8 : 16u * 8u;   // sub-tile 1 vs 0
-  const u32 ng8_out = (u32)ng * NSUB * sub8_out, ng8_acc = (u32)ng * NSUB * sub8_acc;
+  const u32 ng8_out = (u32)ng * G::NSUB * sub8_out, ng8_acc = (u32)ng * G::NSUB * sub8_acc;
   const double alpha = p.alpha, alpha_lo = (p.sym || RAW == 1) ? p.alpha : -p.alpha;      // mirror row: D: b - a; D D: a - b
 
   auto acc_issue = [&](u32 tl, bool valid, int sub, d2 (&ah)[2], d2 (&al)[2]) {
     if (!ACC) return;
-    if constexpr (V4_ABLATE & 2) { ah[0] = d2{1.0, 2.0}; ah[1] = ah[0]; al[0] = d2{3.0, 4.0}; al[1] = al[0]; if (tl != p.ntiles + 12345u) return; }
     const u32 t0 = tile_off(tl, valid, acc_os8) + ng8_acc + (u32)sub * sub8_acc;
 #pragma unroll
     for (int rp = 0; rp < 2; rp++) { ah[rp] = ld16(r_acc, c_hi[rp] + t0); al[rp] = ld16(r_acc, c_lo[rp] + t0); }
@@ -715,7 +632,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
     }
   };
 
-  u32 tile = t_lo + BID / nxcd;
+  u32 tile = wk.first();
   if (tile >= t_hi) return;                            // whole workgroup: no barrier is skipped by part of it
   // the first tile's lines are requested BEFORE the matrix fragments: one memory round trip instead of two
   issue_loads(tile, true, 0, rjA, rmA); issue_loads(tile, true, 1, rjB, rmB);
@@ -727,58 +644,33 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   // live in LDS (their ds_write needs them early; temporaries that are dead before the tile loop), behind the first
   // tile's lines; the other pairs are requested inside the first tile's first chain, one pair per MFMA group, FA groups
   // ahead of their use.  The first tile is a peeled copy of the loop body (`run`): in its straight-line code hipcc counts
-  // vmcnt exactly, so MFMA group g waits for pair g only.  (Rounds 2-5, V4_OVERLAP = 0: everything up front in a rotated
-  // order per CU, vmcnt(0).)
+  // vmcnt exactly, so MFMA group g waits for pair g only.  (Rounds 2-5: everything up front in a rotated
+  // order per CU, vmcnt(0); the A/B is in profiles/r06_prologue_stamps.txt and DESIGN_history.md.)
   constexpr int FA = (V4_FRAG_AHEAD < KS / 2) ? V4_FRAG_AHEAD : KS / 2;
   // pair g of both halves -> registers (the odd half's LDS-resident members have been dealt with up front)
   auto frag_pair = [&](int g) {
     const d2 ve = ((const d2 *)p.fragE2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
     ae[2 * g] = ve.x; ae[2 * g + 1] = ve.y;
-    if (2 * g + 1 < KR) {
+    if (2 * g + 1 < G::KR) {
       const d2 vo = ((const d2 *)p.fragO2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
       ao[2 * g] = vo.x; ao[2 * g + 1] = vo.y;
     }
   };
-  if constexpr (V4_OVERLAP != 0) {
-    constexpr int GL = KR / 2;                         // first pair with an LDS-resident member
-    constexpr int NTL = (NFL > 0) ? KS / 2 - GL : 1;
-    d2 tl[NTL];
-    if constexpr (NFL > 0) {
+  constexpr int GL = G::KR / 2;                         // first pair with an LDS-resident member
+  constexpr int NTL = (G::NFL > 0) ? KS / 2 - GL : 1;
+  d2 tl[NTL];
+  if constexpr (G::NFL > 0) {
 #pragma unroll
-      for (int g = GL; g < KS / 2; g++) tl[g - GL] = ((const d2 *)p.fragO2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
-    }
-#pragma unroll
-    for (int g = 0; g < FA; g++) frag_pair(g);
-    if constexpr (NFL > 0) {
-#pragma unroll
-      for (int g = GL; g < KS / 2; g++) {
-        if (2 * g >= KR) aoL[(2 * g - KR) * 64] = tl[g - GL].x; else ao[2 * g] = tl[g - GL].x;
-        if (2 * g + 1 >= KR) aoL[(2 * g + 1 - KR) * 64] = tl[g - GL].y; else ao[2 * g + 1] = tl[g - GL].y;
-      }
-    }
-  } else {
-  // Every workgroup of the chip fetches the same 256 KiB at the same moment.  The CUs of an XCD start at four
-  // different places of their fragment sets (a static rotation per code path: the registers are fixed), which
-  // spreads the requests over the L2 channels instead of queueing them on one line at a time.
-  auto load_frags = [&](auto ROT_) {
-    constexpr int ROT = decltype(ROT_)::value;
-#pragma unroll
-    for (int g0 = 0; g0 < KS / 2; g0++) {              // two fragments per 16-byte load
-      const int g = (g0 + ROT) % (KS / 2);
-      const d2 ve = ((const d2 *)p.fragE2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
-      const d2 vo = ((const d2 *)p.fragO2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
-      ae[2 * g] = ve.x; ae[2 * g + 1] = ve.y;
-      if (2 * g < KR) ao[2 * g] = vo.x; else aoL[(2 * g - KR) * 64] = vo.x;
-      if (2 * g + 1 < KR) ao[2 * g + 1] = vo.y; else aoL[(2 * g + 1 - KR) * 64] = vo.y;
-    }
-  };
-  switch ((BID / nxcd) & 3u) {
-    case 0: load_frags(std::integral_constant<int, 0>{}); break;
-    case 1: load_frags(std::integral_constant<int, KS / 8>{}); break;
-    case 2: load_frags(std::integral_constant<int, KS / 4>{}); break;
-    default: load_frags(std::integral_constant<int, 3 * KS / 8>{}); break;
+    for (int g = GL; g < KS / 2; g++) tl[g - GL] = ((const d2 *)p.fragO2)[((long)(mt * (KS / 2) + g)) * 64 + lane];
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): see sweep.hip
+#pragma unroll
+  for (int g = 0; g < FA; g++) frag_pair(g);
+  if constexpr (G::NFL > 0) {
+#pragma unroll
+    for (int g = GL; g < KS / 2; g++) {
+      if (2 * g >= G::KR) aoL[(2 * g - G::KR) * 64] = tl[g - GL].x; else ao[2 * g] = tl[g - GL].x;
+      if (2 * g + 1 >= G::KR) aoL[(2 * g + 1 - G::KR) * 64] = tl[g - GL].y; else ao[2 * g + 1] = tl[g - GL].y;
+    }
   }
 #ifdef CHEB_STAMPS
   unsigned long long st_wait = 0, st_park = 0;
@@ -790,60 +682,18 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
 #endif
 
   auto chain = [&](const double *sE, const double *sO, int sub, int g_issue, int g_park, v4d &ce, v4d &co, auto &&issue_fn, auto &&park_fn, auto &&grp_fn) {
-    const int nb = (ng * NSUB + sub) * 16;
+    const int nb = (ng * G::NSUB + sub) * 16;
     ce = v4d{0.0, 0.0, 0.0, 0.0}; co = v4d{0.0, 0.0, 0.0, 0.0};
-    const int frag = JFAST ? (nb + l16) * LDJ + kq : kq * NT + ((nb + l16) ^ ((kq & 1) << 4));
-    const double *fE = sE + frag, *fO = sO + frag;
-    if constexpr (V4_ABLATE & 16) {                    // no matrix work: what the memory streams cost alone
-      issue_fn(); park_fn();
-#pragma unroll
-      for (int g = 0; g < KS / 2; g++) grp_fn(g);
-      ce[0] = fE[0] + ae[0]; co[0] = fO[KSTR] + AO(KS - 1); ce[1] = fE[2 * KSTR]; co[2] = fO[3 * KSTR];
-      return;
-    }
-    double fb[2][4];
-    fb[0][0] = fE[0]; fb[0][1] = fE[KSTR]; fb[0][2] = fO[0]; fb[0][3] = fO[KSTR];
-#pragma unroll
-    for (int g = 0; g < KS / 2; g++) {
-      const int cb = g & 1, nbuf = cb ^ 1;
-      if (g + 1 < KS / 2) {
-        fb[nbuf][0] = fE[(2 * g + 2) * KSTR]; fb[nbuf][1] = fE[(2 * g + 3) * KSTR];
-        fb[nbuf][2] = fO[(2 * g + 2) * KSTR]; fb[nbuf][3] = fO[(2 * g + 3) * KSTR];
-      }
-      __builtin_amdgcn_sched_barrier(0);               // fragment reads stay one group ahead of their MFMAs
-      grp_fn(g);
-      if (g == g_issue) issue_fn();
-      if (g == g_park) park_fn();
-      if (!JFAST) {
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g], fb[cb][0], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(AO(2 * g), fb[cb][2], co, 0, 0, 0);
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[2 * g + 1], fb[cb][1], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(AO(2 * g + 1), fb[cb][3], co, 0, 0, 0);
-      } else {
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][0], ae[2 * g], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][2], AO(2 * g), co, 0, 0, 0);
-        ce = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][1], ae[2 * g + 1], ce, 0, 0, 0);
-        co = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[cb][3], AO(2 * g + 1), co, 0, 0, 0);
-      }
-    }
-  };
-  // value of the even lane of each pair / of the odd lane, in both lanes (DPP quad_perm [0,0,2,2] / [1,1,3,3])
-  auto bc_even = [](double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0xA0, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xA0, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-  };
-  auto bc_odd = [](double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0xF5, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xF5, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
+    const int frag = G::frag(nb, l16, kq);
+    mfma_chain<KS, JFAST, G::KSTR>(sE + frag, sO + frag, ce, co, [&](int k) { return ae[k]; }, [&](int k) { return frag_odd<G::KR>(k, ao, aoL); },
+                                   [&](int g) { grp_fn(g); if (g == g_issue) issue_fn(); if (g == g_park) park_fn(); });
   };
   // out = (acc +) alpha * (sums) for sub-tile `sub` of tile tl
   auto epilogue = [&](u32 tl, int sub, const v4d &ce, const v4d &co, const d2 (&acc_hi)[2], const d2 (&acc_lo)[2]) {
     u32 t0 = tile_off(tl, true, out_os8) + ng8_out + (u32)sub * sub8_out;
     u32 t0v = t0;                                      // per-lane: INVALID where the tile's last column block ends early
     if (!JFAST) {
-      const u32 o = tl / tpo, q = (tl - o * tpo) * NT + (ng * NSUB + sub) * 16 + l16e;
+      const u32 o = tl / tpo, q = (tl - o * tpo) * G::NT + (ng * G::NSUB + sub) * 16 + l16e;
       t0v = (q < qmax) ? t0 : T_INVALID;
     }
     double hi[4], lo[4];
@@ -876,7 +726,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
         // sits as in the array the line was read from -- remote stores inside the same launch as the remote loads (the two
         // directions of a link at once); the final sum then reads local memory only (dist.hip)
         typedef d2 __attribute__((address_space(1))) *gd2w;
-        const u32 o = tl / tpo, q = (tl - o * tpo) * NT + (ng * NSUB + sub) * 16 + l16e;
+        const u32 o = tl / tpo, q = (tl - o * tpo) * G::NT + (ng * G::NSUB + sub) * 16 + l16e;
         const bool cv = q < qmax;
         const unsigned long long of = (unsigned long long)(o + p.gfield0);   // (a field keeps its index on the way back: slabx.hip)
         const unsigned long long ah = (cv && o_hi[rp] != INVALID) ? pb_hi[rp] + (of * pl_hi[rp] + q) * 8ull : psink;
@@ -903,14 +753,14 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       for (int q = 0; q < 4; q++) st16(r_out, INVALID, d2{0.0, 0.0});
       if constexpr (ONEBUF) acc_issue(tile, true, 0, accX_hi, accX_lo);
     }
-    lds_barrier_v();
+    lds_barrier();
     STAMP3_MARK(st_loop);
     int cur = 0;
     auto tile_body = [&](auto FIRST_) {
       constexpr bool FIRST = decltype(FIRST_)::value;
       const u32 nxt = tile + t_step, nxt2 = nxt + t_step;
       const bool v1 = nxt < t_hi, v2 = nxt2 < t_hi;
-      const double *sE = smem + cur * (2 * LDS_ELEMS), *sO = sE + LDS_ELEMS;
+      const double *sE = smem + cur * (2 * G::LDS_ELEMS), *sO = sE + G::LDS_ELEMS;
       v4d ce, co;
       chain(sE, sO, 0, G_ISSUE, G_PARK, ce, co,
             [&] { if constexpr (!ONEBUF) acc_issue(tile, true, 1, accY_hi, accY_lo); issue_loads(nxt, v1, 1, rjB, rmB); },
@@ -927,17 +777,15 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       if constexpr (ONEBUF) { epilogue(tile, 1, ce, co, accX_hi, accX_lo); acc_issue(nxt, v1, 0, accX_hi, accX_lo); }
       else epilogue(tile, 1, ce, co, accY_hi, accY_lo);
       STAMP3(3);
-      lds_barrier_v();
+      lds_barrier();
       STAMP3(4);
       cur ^= 1;
     };
-    if constexpr (V4_OVERLAP != 0) {
-      // the first tile, peeled: the same body in straight-line code behind the fragment requests, so that every MFMA
-      // group waits for its own fragments only; the loop below then starts from the state of its own back edge
-      tile_body(std::true_type{});
-      tile += t_step;
-      STAMP3_MARK(st_first);
-    }
+    // the first tile, peeled: the same body in straight-line code behind the fragment requests, so that every MFMA
+    // group waits for its own fragments only; the loop below then starts from the state of its own back edge
+    tile_body(std::true_type{});
+    tile += t_step;
+    STAMP3_MARK(st_first);
 #pragma unroll 1
     for (; tile < t_hi; tile += t_step) tile_body(std::false_type{});
   };
@@ -950,7 +798,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       dbg[0] = st_seg[0]; dbg[1] = st_seg[1]; dbg[2] = st_seg[2]; dbg[3] = st_seg[3]; dbg[4] = st_seg[4];
       // [5] prologue, [6] whole kernel in shader cycles, [7] whole kernel in 100 MHz ticks (MI355X_MICROARCH.md, DVFS note 6)
       dbg[5] = st_loop - st_begin; dbg[6] = st_end - st_begin; dbg[7] = __builtin_amdgcn_s_memrealtime() - rt_begin;
-      // [8] fragments requested (V4_OVERLAP) / landed (0), [9] first tile's lines parked, [10] first tile done (V4_OVERLAP), [11] / [12] begin / end (absolute, s_memtime)
+      // [8] fragments requested, [9] first tile's lines parked, [10] first tile done, [11] / [12] begin / end (absolute, s_memtime)
       dbg[8] = st_wait - st_begin; dbg[9] = st_park - st_begin; dbg[10] = st_first ? st_first - st_begin : 0; dbg[11] = st_begin; dbg[12] = st_end;
     }
   }
@@ -959,13 +807,13 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
 
 template <int KS, bool JFAST, int MODE, int RAW = 0, int INM = 0>
 __global__ __launch_bounds__(512) void cheb_sweep_vec4_kernel(const SweepParams p) {
-  __shared__ double smem[vec_lds_doubles<KS, JFAST>()];
+  __shared__ double smem[TileGeom<KS, JFAST>::LDS_DOUBLES];
   vec4_body<KS, JFAST, MODE, RAW, INM>(p, smem, blockIdx.x, gridDim.x);
 }
 
 template <int KS, bool PUSH>
 __global__ __launch_bounds__(512) void cheb_sweep_vec4_gather_kernel(const SweepParams p, const GatherSrc g) {
-  __shared__ double smem[vec_lds_doubles<KS, false>()];
+  __shared__ double smem[TileGeom<KS, false>::LDS_DOUBLES];
   vec4_body<KS, false, 0, 0, 0, PUSH ? 2 : 1>(p, smem, blockIdx.x, gridDim.x, &g);
 }
 
@@ -980,7 +828,7 @@ struct MultiParams { int njobs; unsigned bstart[MULTI_MAX + 1]; SweepParams job[
 
 template <int KS, bool SUM3 = false>
 __global__ __launch_bounds__(512, (KS <= 8 ? 4 : 2)) void cheb_sweep_multi_kernel(const MultiParams mp) {
-  constexpr int LDS = vec_lds_doubles<KS, true>() > vec_lds_doubles<KS, false>() ? vec_lds_doubles<KS, true>() : vec_lds_doubles<KS, false>();
+  constexpr int LDS = TileGeom<KS, true>::LDS_DOUBLES > TileGeom<KS, false>::LDS_DOUBLES ? TileGeom<KS, true>::LDS_DOUBLES : TileGeom<KS, false>::LDS_DOUBLES;
   __shared__ double smem[LDS];
   int j = 0;
   while (j + 1 < mp.njobs && blockIdx.x >= mp.bstart[j + 1]) j++;
@@ -998,7 +846,7 @@ __global__ __launch_bounds__(512, (KS <= 8 ? 4 : 2)) void cheb_sweep_multi_kerne
 template <int KS, bool PUSH>
 __global__ __launch_bounds__(512) void cheb_sweep_multi_gather_kernel(const MultiParams mp, const GatherSrc g, const unsigned gmask) {
   static_assert(KS >= 16, "the gather loader is part of the long-line kernel");
-  constexpr int LDS = vec_lds_doubles<KS, true>() > vec_lds_doubles<KS, false>() ? vec_lds_doubles<KS, true>() : vec_lds_doubles<KS, false>();
+  constexpr int LDS = TileGeom<KS, true>::LDS_DOUBLES > TileGeom<KS, false>::LDS_DOUBLES ? TileGeom<KS, true>::LDS_DOUBLES : TileGeom<KS, false>::LDS_DOUBLES;
   __shared__ double smem[LDS];
   int j = 0;
   while (j + 1 < mp.njobs && blockIdx.x >= mp.bstart[j + 1]) j++;
@@ -1037,7 +885,7 @@ static hipError_t launch_v4(const SweepParams &p, unsigned grid, hipStream_t str
 // the general kernel of sweep.hip runs those).
 template <int KS, bool JFAST>
 static int prepare_v(SweepParams &p) {
-  constexpr int MTP = KS / 4, NG = 8 / MTP, NSUB = (KS >= 16) ? 2 : 1, NT = 16 * NG * NSUB;
+  constexpr int NT = TileGeom<KS, JFAST>::NT;
   const bool custom = p.qmax != 0 || p.in_os != 0;         // per-array geometry given by the caller (KS >= 16 only)
   if (JFAST) {
     if (!p.in_os) p.in_os = (unsigned)p.P;

@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import torch
 import __graft_entry__ as ge
 sp = ge.load()
-if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic / A-B builds (tools/v4_overlap_ab.sh)
+if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic / A-B builds
     sp.LIB_PATH = os.environ["CHEBHIP_LIB_PATH"]
 for P in [int(a) for a in sys.argv[1:]] or [64, 128, 256]:
     shape = (P, P, P)

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Run the matvec in a loop for a few seconds and sample rocm-smi (sclk, power) beside it.  The stream-ablated
-builds of tools/v4_ablate.sh are selected with CHEBHIP_LIB_PATH (one process per build)."""
+builds are selected with CHEBHIP_LIB_PATH (one process per build)."""
 import os, subprocess, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import __graft_entry__ as ge
 sp = ge.load()
-if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic builds (tools/v4_ablate.sh): then only the first setting is meaningful
+if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic builds: then only the first setting is meaningful
     sp.LIB_PATH = os.environ["CHEBHIP_LIB_PATH"]
 P = 256
 op = sp.EllipticOp((P, P, P))

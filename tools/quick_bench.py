@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Sustained-loop timing of the Poisson matvec: usage quick_bench.py [P] [option=value ...]
-(options: chebhip_set_option names, e.g. general_kernels=1; CHEBHIP_LIB_PATH selects a diagnostic build of tools/v4_ablate.sh)"""
+(options: chebhip_set_option names, e.g. general_kernels=1; CHEBHIP_LIB_PATH selects another build of the library)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import __graft_entry__ as ge
 sp = ge.load()
-if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic builds (tools/v4_ablate.sh)
+if os.environ.get("CHEBHIP_LIB_PATH"):      # diagnostic / A-B builds
     sp.LIB_PATH = os.environ["CHEBHIP_LIB_PATH"]
 P = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 for a in sys.argv[2:]:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic only: the Poisson matvec with a stamped build of the library (tools/v4_overlap_ab.sh or
-`make -C spectral-petsc_amd/csrc diag`: sweep_vec.hip with -DCHEB_STAMPS) -- where a wave of cheb_sweep_vec4_kernel
+"""Diagnostic only: the Poisson matvec with a stamped build of the library
+(`make -C spectral-petsc_amd/csrc diag`: sweep_vec.hip with -DCHEB_STAMPS) -- where a wave of cheb_sweep_vec4_kernel
 spends its cycles, per launch (direction) and wave group: chain 0, epilogue 0, chain 1, epilogue 1, barrier; the
 prologue split (fragments requested / landed, first lines parked, loop entered, first tile done); the spread of
 the waves' begin and end stamps over the launch (dispatch skew and tail).

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic only: where the waves of the multi-job sweep launches of a 64^3 Stokes callback spend their cycles (stamped build:
-tools/v4_overlap_ab.sh / `make diag`; cheb_sweep_multi_kernel -> vec1_body stamps).  Per job of the LAST multi-job launch issued
+`make diag`; cheb_sweep_multi_kernel -> vec1_body stamps).  Per job of the LAST multi-job launch issued
 (a StokesMatMult runs two: nine jobs, then the three grad div v jobs -- the probe stamps them one at a time by call order):
 fragments landed, loop entered, per-tile pre / chain / post / barrier, whole kernel, tiles walked.
 usage: stamp_probe_multi.py [P] [lib.so]"""
