@@ -125,6 +125,50 @@ long cheb_resample_size(const cheb_resample *r, int which);           /* 0: inpu
 int  cheb_resample_matrix_host(int n_in, int nodes_in, int n_out, int nodes_out, double *R);
 
 /* ------------------------------------------------------------------------- */
+/* The modal side of the Chebyshev-Gauss-Lobatto grids (the reference's       */
+/* ChebMult goes values -> DCT -> recurrence -> DCT, chebyshev.c:142-199, but */
+/* never hands the coefficients out): coefficient transforms, modal filters,  */
+/* per-direction spectra and Clenshaw-Curtis quadrature.  Per direction of    */
+/* n points, N = n - 1, x_j = cos(pi j / N), c_0 = c_N = 2, otherwise c = 1:  */
+/*   backward  B[j][k] = T_k(x_j) = cos(pi j k / N)    coefficients -> values */
+/*   forward   T[k][j] = 2 / (N c_k c_j) cos(pi j k / N)          B T = I     */
+/*   weights   w = I^T T, I_k = 2 / (1 - k^2) (k even), 0 (k odd): exact for  */
+/*             polynomials of degree <= N, sum w = 2                          */
+/*   filter    F = B diag(sigma_0 .. sigma_N) T                               */
+/* all built in long double and rounded once.  Fields are `nfields` arrays of */
+/* prod(dims) values, field-major and row-major over ALL nodes (the layout of */
+/* cheb_helmholtz_solve_bc's full-grid arrays); coefficient arrays have the   */
+/* same shape, entry (k_0, .., k_{d-1}) multiplying T_{k_0}(x) T_{k_1}(y) ... */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_modal cheb_modal;
+
+/* 1 <= d <= 10; 2 <= dims[k] <= 1024; 1 <= nfields <= 16; fewer than 2^31 values.  The handle owns its matrices, two work buffers
+ * and the scratch of the reductions: the calls below allocate nothing and do not synchronise the host. */
+int  cheb_modal_create(int d, const int *dims, int nfields, cheb_modal **out);
+int  cheb_modal_destroy(cheb_modal *h);
+long cheb_modal_size(const cheb_modal *h);                 /* nfields * prod(dims); -1: NULL */
+long cheb_modal_spectrum_size(const cheb_modal *h);        /* nfields * sum(dims); -1: NULL */
+/* a = (T_0 (x) .. (x) T_{d-1}) u and u = (B_0 (x) .. (x) B_{d-1}) a: one launch per direction.  Input and output must not overlap. */
+int  cheb_modal_forward (cheb_modal *h, const double *u_dev, double *a_dev, void *stream);
+int  cheb_modal_backward(cheb_modal *h, const double *a_dev, double *u_dev, void *stream);
+/* sigma of direction k: dims[k] HOST values; NULL clears.  Synchronous (see the conventions above). */
+int  cheb_modal_set_filter(cheb_modal *h, int k, const double *sigma_host);
+/* v = (F_0 (x) .. (x) F_{d-1}) u.  A direction whose sigma is unset or all ones is dropped (the values keep their bits along it);
+ * with no direction left this is a copy.  u and v must not overlap. */
+int  cheb_modal_filter  (cheb_modal *h, const double *u_dev, double *v_dev, void *stream);
+/* E[f][k][m] = sum of a^2 over every index except direction k's, held at m: field by field, direction by direction, dims[k] values
+ * each (cheb_modal_spectrum_size doubles). */
+int  cheb_modal_spectrum(cheb_modal *h, const double *a_dev, double *E_dev, void *stream);
+/* out[f] = sum_i W_i u_i, or sum_i W_i u_i v_i when v_dev is not NULL (u == v is allowed), W_i = prod_k w_k[i_k]: nfields DEVICE
+ * values.  spectrum and integrate add in a fixed order: the same input gives the same bits on every run. */
+int  cheb_modal_integrate(cheb_modal *h, const double *u_dev, const double *v_dev, double *out_dev, void *stream);
+/* Host-side builders; they need no device.  n x n row-major (which = 0: T, 1: B), n weights, and F for n values of sigma
+ * (all ones: exactly the identity). */
+int  cheb_modal_matrix_host(int n, int which, double *M);
+int  cheb_modal_weights_host(int n, double *w);
+int  cheb_modal_filter_matrix_host(int n, const double *sigma, double *F);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

@@ -64,6 +64,9 @@ ABI_SYMBOLS = [
     "cheb_helmholtz_line_host", "ell_pc_create_spectral",
     "cheb_helmholtz_create_bc", "cheb_helmholtz_solve_bc", "cheb_helmholtz_full_size", "cheb_helmholtz_boundary_size",
     "cheb_helmholtz_singular", "cheb_helmholtz_line_bc_host",
+    "cheb_modal_create", "cheb_modal_destroy", "cheb_modal_size", "cheb_modal_spectrum_size", "cheb_modal_forward", "cheb_modal_backward",
+    "cheb_modal_set_filter", "cheb_modal_filter", "cheb_modal_spectrum", "cheb_modal_integrate",
+    "cheb_modal_matrix_host", "cheb_modal_weights_host", "cheb_modal_filter_matrix_host",
 ]
 
 
@@ -238,6 +241,18 @@ def lib():
             f.restype = C.c_long
         L.cheb_helmholtz_singular.argtypes = [vp]
         L.cheb_helmholtz_line_bc_host.argtypes = [C.c_int, dp, dp, dp, dp, dp, dp, dp]
+        L.cheb_modal_create.argtypes = [C.c_int, ip, C.c_int, C.POINTER(vp)]
+        L.cheb_modal_destroy.argtypes = [vp]
+        for f in (L.cheb_modal_size, L.cheb_modal_spectrum_size):
+            f.argtypes = [vp]
+            f.restype = C.c_long
+        for f in (L.cheb_modal_forward, L.cheb_modal_backward, L.cheb_modal_filter, L.cheb_modal_spectrum):
+            f.argtypes = [vp, vp, vp, vp]
+        L.cheb_modal_set_filter.argtypes = [vp, C.c_int, dp]
+        L.cheb_modal_integrate.argtypes = [vp, vp, vp, vp, vp]
+        L.cheb_modal_matrix_host.argtypes = [C.c_int, C.c_int, dp]
+        L.cheb_modal_weights_host.argtypes = [C.c_int, dp]
+        L.cheb_modal_filter_matrix_host.argtypes = [C.c_int, dp, dp]
         _lib = L
     return _lib
 
@@ -409,6 +424,133 @@ class Resample:
     def destroy(self):
         if getattr(self, "_h", None):
             lib().cheb_resample_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+MODAL = {"forward": 0, "backward": 1}
+
+
+def modal_matrix(n, which):
+    """One direction's Chebyshev transform matrix (cheb_modal_matrix_host) as an (n, n) numpy array: "forward" T (values ->
+    coefficients, T[k][j] = 2 / (N c_k c_j) cos(pi j k / N)) or "backward" B (B[j][k] = T_k(x_j)); needs no device."""
+    import numpy as np
+    if which not in MODAL:
+        raise ValueError("transform %r: expected one of %s" % (which, sorted(MODAL)))
+    M = np.empty((max(int(n), 0),) * 2)
+    _chk(lib().cheb_modal_matrix_host(int(n), MODAL[which], M.ctypes.data_as(C.POINTER(C.c_double)) if M.size else None))
+    return M
+
+
+def cc_weights(n):
+    """The Clenshaw-Curtis weights of the n CGL nodes (cheb_modal_weights_host): exact up to degree n - 1, sum 2; needs no device."""
+    import numpy as np
+    w = np.empty(max(int(n), 0))
+    _chk(lib().cheb_modal_weights_host(int(n), w.ctypes.data_as(C.POINTER(C.c_double)) if w.size else None))
+    return w
+
+
+def _sigma(n, sigma):
+    import numpy as np
+    s = np.ascontiguousarray(sigma, dtype=np.float64)
+    if s.shape != (int(n),):
+        raise ValueError("sigma: expected %d values, got shape %r" % (int(n), s.shape))
+    return s
+
+
+def filter_matrix(n, sigma):
+    """F = B diag(sigma) T of one direction (cheb_modal_filter_matrix_host); sigma all ones gives exactly the identity."""
+    import numpy as np
+    s = _sigma(n, sigma)
+    F = np.empty((int(n), int(n)))
+    _chk(lib().cheb_modal_filter_matrix_host(int(n), _np_dp(s), _np_dp(F)))
+    return F
+
+
+def exp_filter(n, order=16, alpha=36.0, cutoff=0):
+    """sigma_k = 1 for k < cutoff and exp(-alpha ((k - cutoff) / (N - cutoff))^order) from there on, N = n - 1."""
+    import numpy as np
+    N, kc = int(n) - 1, int(cutoff)
+    if not 0 <= kc < N:
+        raise ValueError("cutoff %d outside 0..%d" % (kc, N - 1))
+    k = np.arange(N + 1, dtype=np.float64)
+    return np.where(k < kc, 1.0, np.exp(-float(alpha) * (np.maximum(k - kc, 0.0) / (N - kc)) ** order))
+
+
+def sharp_filter(n, keep):
+    """sigma_k = 1 for k < keep and 0 otherwise."""
+    import numpy as np
+    return (np.arange(int(n)) < int(keep)).astype(np.float64)
+
+
+class ChebModal:
+    """The modal side of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_modal_*): values <-> Chebyshev
+    coefficients, modal filters, per-direction spectra and Clenshaw-Curtis integrals.  Fields are field-major, row-major over all
+    nodes; size() values per array.  Everything is asynchronous on torch's current stream."""
+
+    def __init__(self, dims, nfields=1):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        h = C.c_void_p()
+        _chk(lib().cheb_modal_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        self._h = h
+
+    def size(self):
+        return lib().cheb_modal_size(self._h)
+
+    def spectrum_size(self):
+        return lib().cheb_modal_spectrum_size(self._h)
+
+    def forward(self, u, a):
+        """a = coefficients of the values u."""
+        _chk(lib().cheb_modal_forward(self._h, _dev_ptr(u, self.size()), _dev_ptr(a, self.size()), _stream()))
+        return a
+
+    def backward(self, a, u):
+        """u = values of the coefficients a."""
+        _chk(lib().cheb_modal_backward(self._h, _dev_ptr(a, self.size()), _dev_ptr(u, self.size()), _stream()))
+        return u
+
+    def set_filter(self, k, sigma):
+        """sigma of direction k (dims[k] host values, e.g. exp_filter / sharp_filter); None clears."""
+        if sigma is None:
+            _chk(lib().cheb_modal_set_filter(self._h, int(k), None))
+        else:
+            if not 0 <= int(k) < len(self.dims):
+                raise ChebhipError(2, "direction %d out of range 0..%d" % (int(k), len(self.dims) - 1))
+            _chk(lib().cheb_modal_set_filter(self._h, int(k), _np_dp(_sigma(self.dims[int(k)], sigma))))
+
+    def filter(self, u, v):
+        """v = (F_0 x ... x F_{d-1}) u over the directions with a filter set."""
+        _chk(lib().cheb_modal_filter(self._h, _dev_ptr(u, self.size()), _dev_ptr(v, self.size()), _stream()))
+        return v
+
+    def spectrum(self, a, E=None):
+        """E[f][k][m] = sum of a^2 with direction k's index held at m: a device tensor of spectrum_size() values, field by field,
+        direction by direction."""
+        import torch
+        if E is None:
+            E = torch.empty(self.spectrum_size(), dtype=torch.float64, device=a.device)
+        _chk(lib().cheb_modal_spectrum(self._h, _dev_ptr(a, self.size()), _dev_ptr(E, self.spectrum_size()), _stream()))
+        return E
+
+    def integrate(self, u, v=None, out=None):
+        """The integrals of u (of u v) over the domain, one per field, as a device tensor of nfields values; does not synchronise."""
+        import torch
+        if out is None:
+            out = torch.empty(self.nfields, dtype=torch.float64, device=u.device)
+        _chk(lib().cheb_modal_integrate(self._h, _dev_ptr(u, self.size()), None if v is None else _dev_ptr(v, self.size()),
+                                        _dev_ptr(out, self.nfields), _stream()))
+        return out
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_modal_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -850,6 +850,72 @@ void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior
   }
 }
 
+// Chebyshev coefficient transforms on the n = N + 1 Gauss-Lobatto nodes (cheb_modal_*, modal.hip), c_0 = c_N = 2, otherwise 1:
+//   backward  B[j][k] = T_k(x_j) = cos(pi j k / N)                       (coefficients -> values)
+//   forward   T[k][j] = 2 / (N c_k c_j) cos(pi j k / N)                  (values -> coefficients),  B T = I
+//   weights   w = I^T T,  I_k = 2 / (1 - k^2) for even k, 0 for odd k     (Clenshaw-Curtis: exact up to degree N, sum w = 2)
+//   filter    F = B diag(sigma) T
+// The cosine: j k is reduced modulo 2N in integers and folded into 0 .. N (cos is even and 2 pi-periodic), then
+// cos(pi r / N) = sin(pi (N - 2r) / 2N) with the argument in [-pi/2, pi/2] -- unreduced, PI_L's own rounding error times j k makes
+// the entries of a 1024-point matrix wrong in the 14th digit.  2 j k an odd multiple of N gives N - 2r = 0: an exact 0.
+static long double cos_jk(long j, long k, long N) {
+  long r = (j * k) % (2 * N);
+  if (r > N) r = 2 * N - r;
+  const long m = N - 2 * r;
+  if (m == 0) return 0.0L;
+  if (m == N) return 1.0L;
+  if (m == -N) return -1.0L;
+  const long double s = sinl(PI_L * (long double)(m < 0 ? -m : m) / (2.0L * (long double)N));
+  return m < 0 ? -s : s;
+}
+
+static long double modal_entry(int n, int which, int row, int col) {
+  const long N = n - 1;
+  if (which) return cos_jk(row, col, N);                                     // B[j = row][k = col]
+  const long double ck = (row == 0 || row == N) ? 2.0L : 1.0L, cj = (col == 0 || col == N) ? 2.0L : 1.0L;
+  return 2.0L / ((long double)N * ck * cj) * cos_jk(col, row, N);            // T[k = row][j = col]
+}
+
+void modal_matrix_host(int n, int which, double *M) {
+  for (int r = 0; r < n; r++)
+    for (int c = 0; c < n; c++) M[(size_t)r * n + c] = (double)modal_entry(n, which, r, c);
+}
+
+void modal_weights_host(int n, double *w) {
+  for (int j = 0; j < n; j++) {
+    long double s = 0.0L;
+    for (int k = 0; k < n; k += 2) s += 2.0L / (1.0L - (long double)k * k) * modal_entry(n, 0, k, j);
+    w[j] = (double)s;
+  }
+}
+
+// sigma all ones: the identity, exactly; modes with sigma = 0 are skipped
+void modal_filter_matrix_host(int n, const double *sigma, double *F) {
+  bool ones = true;
+  for (int k = 0; k < n; k++) ones = ones && sigma[k] == 1.0;
+  if (ones) {
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < n; j++) F[(size_t)i * n + j] = i == j ? 1.0 : 0.0;
+    return;
+  }
+  std::vector<int> act;
+  for (int k = 0; k < n; k++) if (sigma[k] != 0.0) act.push_back(k);
+  const size_t na = act.size();
+  std::vector<long double> Bs((size_t)n * na), Tt((size_t)n * na), acc(n);     // B[i][k] sigma_k and T[k][j] as [j][k], active k only
+  for (int i = 0; i < n; i++)
+    for (size_t a = 0; a < na; a++) {
+      Bs[(size_t)i * na + a] = modal_entry(n, 1, i, act[a]) * (long double)sigma[act[a]];
+      Tt[(size_t)i * na + a] = modal_entry(n, 0, act[a], i);
+    }
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      const long double *b = &Bs[(size_t)i * na], *t = &Tt[(size_t)j * na];
+      long double s = 0.0L;
+      for (size_t a = 0; a < na; a++) s += b[a] * t[a];
+      F[(size_t)i * n + j] = (double)s;
+    }
+}
+
 void diffmat_destroy(DiffMat *m) {
   if (m->fragE) (void)hipFree(m->fragE);
   if (m->fragO) (void)hipFree(m->fragO);

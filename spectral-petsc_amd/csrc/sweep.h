@@ -115,6 +115,11 @@ void diffmat_dense_host(int P, double *D);
 // Host-side Lagrange interpolation matrix between the stored nodes of two CGL grids (resample.hip; arguments checked there):
 // (n_out - 2 out_interior) x (n_in - 2 in_interior), row-major
 void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior, double *R);
+// Host-side Chebyshev transform matrices of a line of n points (modal.hip; arguments checked there): which = 0 forward T (values ->
+// coefficients), 1 backward B; the Clenshaw-Curtis weights; the filter B diag(sigma) T.  n x n row-major, long double rounded once.
+void modal_matrix_host(int n, int which, double *M);
+void modal_weights_host(int n, double *w);
+void modal_filter_matrix_host(int n, const double *sigma, double *F);
 
 // Launches one sweep.  jfast selects the line-contiguous tiling.
 hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream);

@@ -343,3 +343,35 @@ def stokes_solve_sequenced(sp, levels, stage_level=None, rheology=(0, 1.0, 1.0, 
         if stats is not None:
             stats["linear_fails"] = fails[0]
     return out
+
+
+def resolution(dims, u_full):
+    """How well the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields if it holds a multiple
+    of prod(dims) values) is resolved: per direction sqrt(E over the top third of the modes / total E), E the direction's energy
+    spectrum of the Chebyshev coefficients (one ChebModal.forward + spectrum); a (nfields, d) host array for several fields, d values
+    for one.  The number to look at before choosing the next level of a grid sequence: ~1e-16 for a resolved field, O(1) for noise.
+    Nothing here is wired into the sequenced solvers."""
+    from . import ChebModal
+    dims = tuple(int(n) for n in dims)
+    size = 1
+    for n in dims:
+        size *= n
+    if u_full.numel() == 0 or u_full.numel() % size:
+        raise ValueError("u_full: %d values are no multiple of prod(dims) = %d" % (u_full.numel(), size))
+    nf = u_full.numel() // size
+    m = ChebModal(dims, nf)
+    try:
+        a = m.forward(u_full.reshape(-1), torch.empty(m.size(), dtype=torch.float64, device=u_full.device))
+        E = m.spectrum(a).cpu().view(nf, -1)
+    finally:
+        m.destroy()
+    out = torch.zeros((nf, len(dims)), dtype=torch.float64)
+    o = 0
+    for k, n in enumerate(dims):
+        Ek = E[:, o:o + n]
+        o += n
+        top = n - max(1, n // 3)
+        tot = Ek.sum(dim=1)
+        out[:, k] = torch.where(tot > 0, torch.sqrt(Ek[:, top:].sum(dim=1) / torch.where(tot > 0, tot, torch.ones_like(tot))), torch.zeros_like(tot))
+    out = out.numpy()
+    return out[0] if nf == 1 else out
