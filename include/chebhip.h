@@ -169,6 +169,49 @@ int  cheb_modal_weights_host(int n, double *w);
 int  cheb_modal_filter_matrix_host(int n, const double *sigma, double *F);
 
 /* ------------------------------------------------------------------------- */
+/* Evaluation at arbitrary points of the reference cube [-1, 1]^d (no         */
+/* counterpart in the reference): probes, line and plane cuts, plotting grids */
+/* and tracer positions that live on the device.  Fields use the full-grid,   */
+/* field-major layout of cheb_modal_*.  Per direction of n points, N = n - 1, */
+/* x_j = cos(pi j / N) (index 0 is x = +1), barycentric weights w_j = (-1)^j, */
+/* halved at j = 0 and j = N; the row of a coordinate x is                    */
+/*   l_j(x) = (w_j / (x - x_j)) / sum_k w_k / (x - x_k)                       */
+/* evaluated in the nearest-node form, which cannot overflow: s = the node    */
+/* nearest to x, d_j = x - x_j, r_s = 1, r_j = (w_j / w_s) (d_s / d_j),       */
+/* l = r / sum r.  d_s == 0 gives the exact unit row e_s (a point on a node   */
+/* returns the field's own bits); a NaN or infinite coordinate gives NaN for  */
+/* that point only; |x| > 1 is EXTRAPOLATED by the same formula, not clamped  */
+/* (the interpolant grows like T_N outside the cube).  The sums run in an     */
+/* order that depends on the shape alone: results repeat bit for bit.         */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_points cheb_points;
+
+/* 1 <= d <= 10; 2 <= dims[k] <= 1024; 1 <= nfields <= 16; fewer than 2^31 values.  The handle owns the node tables (long double,
+ * rounded once, shared by equal extents) and the work memory of one chunk of cheb_points_chunk points -- the rows and direction
+ * 0's output, at most max(bytes of the fields, 32 MiB): cheb_points_rows and cheb_points_eval allocate nothing and do not
+ * synchronise the host. */
+int  cheb_points_create(int d, const int *dims, int nfields, cheb_points **out);
+int  cheb_points_destroy(cheb_points *h);
+long cheb_points_chunk(const cheb_points *h);              /* points per chunk: a multiple of 64 where memory allows, <= 1024; -1: NULL */
+/* R[i][j] = l_j(x[i]) of direction k: m x dims[k] DEVICE values, row-major, from m DEVICE coordinates. */
+int  cheb_points_rows(cheb_points *h, int k, const double *x_dev, long m, double *R_dev, void *stream);
+/* out[f][p] = sum l_{i0}(xi[p][0]) .. l_{i(d-1)}(xi[p][d-1]) u[f][i0 .. i(d-1)]: xi is npts x d (point-major), out nfields x npts.
+ * Per chunk: the rows, direction 0 as one line product on the FP64 matrix cores, one contraction per (field, point).
+ * npts = 0 is a no-op; out must not overlap u. */
+int  cheb_points_eval(cheb_points *h, const double *u_dev, const double *xi_dev, long npts, double *out_dev, void *stream);
+/* Tensor grids of arbitrary coordinates: direction k takes m[k] coordinates (HOST counts), the DEVICE array `coords` holds them
+ * direction after direction (sum of m[k] values); out is nfields x m[0] x .. x m[d-1], field-major and row-major.  One line
+ * product per direction, shrinking directions first.  A plane cut is m[k] = 1, a line cut has d - 1 of them.
+ * cheb_points_grid_reserve (synchronous, d HOST ints >= 1) allocates the rows and the two intermediates for every grid with
+ * m[k] <= m_max[k]; cheb_points_eval_grid allocates nothing and refuses a larger grid (CHEBHIP_ERR_ARG).  A count of 0 is a no-op. */
+int  cheb_points_grid_reserve(cheb_points *h, const int *m_max);
+int  cheb_points_eval_grid(cheb_points *h, const double *u_dev, const double *coords_dev, const int *m, double *out_dev, void *stream);
+/* Host-side twins; they need no device.  The n nodes, and the m x n rows (row-major) of m HOST coordinates by the same formula in
+ * long double on the DOUBLE node table, rounded once. */
+int  cheb_nodes_host(int n, double *x);
+int  cheb_points_matrix_host(int n, int m, const double *x_host, double *R);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

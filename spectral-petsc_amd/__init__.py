@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "cheb_modal_create", "cheb_modal_destroy", "cheb_modal_size", "cheb_modal_spectrum_size", "cheb_modal_forward", "cheb_modal_backward",
     "cheb_modal_set_filter", "cheb_modal_filter", "cheb_modal_spectrum", "cheb_modal_integrate",
     "cheb_modal_matrix_host", "cheb_modal_weights_host", "cheb_modal_filter_matrix_host",
+    "cheb_points_create", "cheb_points_destroy", "cheb_points_chunk", "cheb_points_rows", "cheb_points_eval",
+    "cheb_points_grid_reserve", "cheb_points_eval_grid", "cheb_nodes_host", "cheb_points_matrix_host",
 ]
 
 
@@ -253,6 +255,16 @@ def lib():
         L.cheb_modal_matrix_host.argtypes = [C.c_int, C.c_int, dp]
         L.cheb_modal_weights_host.argtypes = [C.c_int, dp]
         L.cheb_modal_filter_matrix_host.argtypes = [C.c_int, dp, dp]
+        L.cheb_points_create.argtypes = [C.c_int, ip, C.c_int, C.POINTER(vp)]
+        L.cheb_points_destroy.argtypes = [vp]
+        L.cheb_points_chunk.argtypes = [vp]
+        L.cheb_points_chunk.restype = C.c_long
+        L.cheb_points_rows.argtypes = [vp, C.c_int, vp, C.c_long, vp, vp]
+        L.cheb_points_eval.argtypes = [vp, vp, vp, C.c_long, vp, vp]
+        L.cheb_points_grid_reserve.argtypes = [vp, ip]
+        L.cheb_points_eval_grid.argtypes = [vp, vp, vp, ip, vp, vp]
+        L.cheb_nodes_host.argtypes = [C.c_int, dp]
+        L.cheb_points_matrix_host.argtypes = [C.c_int, C.c_int, dp, dp]
         _lib = L
     return _lib
 
@@ -551,6 +563,117 @@ class ChebModal:
     def destroy(self):
         if getattr(self, "_h", None):
             lib().cheb_modal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def cgl_nodes(n):
+    """The n Chebyshev-Gauss-Lobatto nodes x_j = cos(pi j / (n - 1)) (cheb_nodes_host), x_0 = +1: long double, rounded once; the
+    table the device interpolates on.  Needs no device."""
+    import numpy as np
+    x = np.empty(max(int(n), 0))
+    _chk(lib().cheb_nodes_host(int(n), x.ctypes.data_as(C.POINTER(C.c_double)) if x.size else None))
+    return x
+
+
+def interp_matrix(n, x):
+    """The barycentric rows l_j(x_i) of the coordinates x on the n CGL nodes (cheb_points_matrix_host) as an (len(x), n) numpy
+    array: long double on the double node table, rounded once.  A coordinate on a node gives the exact unit row, a NaN or infinite
+    one a row of NaN, |x| > 1 extrapolates.  Needs no device."""
+    import numpy as np
+    xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    R = np.empty((xs.size, max(int(n), 0)))
+    _chk(lib().cheb_points_matrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
+    return R
+
+
+class ChebPoints:
+    """Values of `nfields` stacked full-grid fields on the CGL grid `dims` (field-major, row-major over all nodes, as ChebModal) at
+    arbitrary points of [-1, 1]^d (cheb_points_*): scattered points (eval) and tensor grids of arbitrary coordinates (eval_grid:
+    plane and line cuts, plotting grids).  Coordinates are device tensors; |x| > 1 extrapolates, a NaN coordinate gives NaN at that
+    point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream."""
+
+    def __init__(self, dims, nfields=1):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        h = C.c_void_p()
+        _chk(lib().cheb_points_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        self._h = h
+        self._reserved = None
+
+    def size(self):
+        n = self.nfields
+        for d in self.dims:
+            n *= d
+        return n
+
+    @property
+    def chunk(self):
+        """Points per chunk of eval: the rows and direction 0's output of one chunk are the handle's work memory."""
+        return lib().cheb_points_chunk(self._h)
+
+    def rows(self, k, x, out=None):
+        """The rows l_j(x_i) of direction k for the device coordinates x: a (len(x), dims[k]) device tensor."""
+        import torch
+        if not 0 <= int(k) < len(self.dims):
+            raise ChebhipError(2, "direction %d out of range 0..%d" % (int(k), len(self.dims) - 1))
+        m, n = x.numel(), self.dims[int(k)]
+        if out is None:
+            out = torch.empty((m, n), dtype=torch.float64, device=x.device)
+        if m:
+            _chk(lib().cheb_points_rows(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
+        return out
+
+    def eval(self, u, pts, out=None):
+        """out[f][p] = the value of field f at the point pts[p]: pts is an (npts, d) device tensor, out (nfields, npts)."""
+        import torch
+        d = len(self.dims)
+        if pts.dim() != 2 or pts.shape[1] != d:
+            raise ValueError("pts: expected shape (npts, %d), got %r" % (d, tuple(pts.shape)))
+        npts = pts.shape[0]
+        if out is None:
+            out = torch.empty((self.nfields, npts), dtype=torch.float64, device=u.device)
+        if npts:
+            _chk(lib().cheb_points_eval(self._h, _dev_ptr(u, self.size()), _dev_ptr(pts, npts * d), npts,
+                                        _dev_ptr(out, self.nfields * npts), _stream()))
+        return out
+
+    def reserve_grid(self, m_max):
+        """Allocates eval_grid's buffers for every grid of at most m_max[k] coordinates in direction k (synchronous)."""
+        m_max = tuple(int(v) for v in m_max)
+        if len(m_max) != len(self.dims):
+            raise ValueError("m_max: expected %d counts" % len(self.dims))
+        _chk(lib().cheb_points_grid_reserve(self._h, _ints(m_max)))
+        self._reserved = m_max
+
+    def eval_grid(self, u, coords, out=None):
+        """The fields on the tensor grid coords[0] x .. x coords[d-1] (one 1-d device tensor of coordinates per direction): a device
+        tensor of shape (nfields, len(coords[0]), .., len(coords[d-1])).  Without an earlier reserve_grid the buffers are
+        reserved for this grid's size; a grid larger than the reserved one is refused."""
+        import torch
+        if len(coords) != len(self.dims):
+            raise ValueError("coords: expected %d coordinate arrays" % len(self.dims))
+        m = tuple(int(c.numel()) for c in coords)
+        if self._reserved is None:
+            self.reserve_grid(tuple(max(v, 1) for v in m))
+        nout = self.nfields
+        for v in m:
+            nout *= v
+        if out is None:
+            out = torch.empty((self.nfields,) + m, dtype=torch.float64, device=u.device)
+        xs = torch.cat([c.reshape(-1) for c in coords]) if len(coords) > 1 else coords[0].reshape(-1).contiguous()
+        _chk(lib().cheb_points_eval_grid(self._h, _dev_ptr(u, self.size()), _dev_ptr(xs, sum(m)) if sum(m) else None, _ints(m),
+                                         _dev_ptr(out, nout) if nout else None, _stream()))
+        return out
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_points_destroy(self._h)
             self._h = None
 
     def __del__(self):

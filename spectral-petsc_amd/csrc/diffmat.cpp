@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
+#include <limits>
 #include <vector>
 
 namespace chebhip {
@@ -914,6 +915,46 @@ void modal_filter_matrix_host(int n, const double *sigma, double *F) {
       for (size_t a = 0; a < na; a++) s += b[a] * t[a];
       F[(size_t)i * n + j] = (double)s;
     }
+}
+
+// Evaluation at arbitrary points (cheb_points_*, points.hip).  The node table x_j = cos(pi j / N) comes from cos_jk, so x_0 = 1,
+// x_N = -1, x_j = -x_{N-j} and the middle node of an odd n are exact.
+void points_nodes_host(int n, double *x) {
+  for (int j = 0; j < n; j++) x[j] = (double)cos_jk(j, 1, n - 1);
+}
+
+// Row of a coordinate x: l_j = (w_j / (x - x_j)) / sum_k w_k / (x - x_k), w_j = (-1)^j, halved at both ends, in the nearest-node
+// form: s = the node nearest to x (the lowest index on a tie), d_j = x - x_j, r_s = 1, r_j = (w_j / w_s) (d_s / d_j) otherwise
+// (|d_s / d_j| <= 1: nothing overflows), l = r / sum r, the sum in ascending j.  w_j / w_s is +-1/2, +-1 or +-2, so an entry
+// costs one rounding for d_j, one for the quotient and one for the division by the sum.  d_s == 0: the exact unit row; a NaN or
+// infinite coordinate: a row of NaN; |x| > 1 extrapolates by the same formula.  Long double on the DOUBLE node table (the
+// polynomial the device interpolates is the one through the rounded nodes), rounded once.
+void points_matrix_host(int n, int m, const double *x, double *R) {
+  std::vector<double> xn(n);
+  points_nodes_host(n, xn.data());
+  const int N = n - 1;
+  std::vector<long double> r(n);
+  for (int t = 0; t < m; t++) {
+    double *row = R + (size_t)t * n;
+    const long double xt = x[t];
+    if (!std::isfinite(x[t])) { for (int j = 0; j < n; j++) row[j] = std::numeric_limits<double>::quiet_NaN(); continue; }
+    int s = 0;
+    long double best = fabsl(xt - (long double)xn[0]);
+    for (int j = 1; j < n; j++) { const long double a = fabsl(xt - (long double)xn[j]); if (a < best) { best = a; s = j; } }
+    const long double ds = xt - (long double)xn[s];
+    if (ds == 0.0L) { for (int j = 0; j < n; j++) row[j] = j == s ? 1.0 : 0.0; continue; }
+    const long double hs = (s == 0 || s == N) ? 0.5L : 1.0L;
+    long double sum = 0.0L;
+    for (int j = 0; j < n; j++) {
+      if (j == s) r[j] = 1.0L;
+      else {
+        const long double hj = (j == 0 || j == N) ? 0.5L : 1.0L;
+        r[j] = (((j - s) & 1) ? -hj : hj) / hs * (ds / (xt - (long double)xn[j]));
+      }
+      sum += r[j];
+    }
+    for (int j = 0; j < n; j++) row[j] = (double)(r[j] / sum);
+  }
 }
 
 void diffmat_destroy(DiffMat *m) {

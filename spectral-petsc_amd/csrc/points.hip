@@ -1,0 +1,420 @@
+// points.hip -- values of `nfields` stacked full-grid Chebyshev-Gauss-Lobatto fields (field-major, row-major, all nodes: the
+// layout of cheb_modal_* and cheb_helmholtz_solve_bc) at arbitrary points of the reference cube (cheb_points_*,
+// include/chebhip.h): scattered points whose coordinates live on the device, and tensor grids of arbitrary coordinates (plane
+// and line cuts, uniform plotting grids).
+//
+// Per direction of n points the interpolant is evaluated in barycentric form with the weights w_j = (-1)^j, halved at both ends.
+// The row of a coordinate x is built on the device (k_points_rows) in the nearest-node form, which cannot overflow:
+//   s = the node nearest to x,  d_j = x - x_j,  r_s = 1,  r_j = (w_j / w_s) (d_s / d_j),  l = r / sum r
+// from the node table the handle uploaded at create (long double, rounded once, diffmat.cpp).  d_s == 0 gives the exact unit row,
+// a NaN or infinite coordinate a row of NaN, |x| > 1 is extrapolated by the same formula.  A row is built by G lanes (the power
+// of two >= n, at most 64), lane l taking j = l, l + G, ...; the lanes' sums meet by a butterfly of shuffles, so the order of the
+// sum depends on n alone and rows repeat bit for bit.
+//
+// Scattered points run in chunks of C points (cheb_points_chunk), three launches a chunk:
+//   1. k_points_rows: the C x n_k rows of every direction;
+//   2. direction 0 on the FP64 matrix cores: the line product of linegemm.h with R = the chunk's C x n_0 rows, O = nfields,
+//      Q = n_1 .. n_{d-1} -- the fields are read once per chunk; the result is [field][point][i_1 .. i_{d-1}];
+//   3. k_points_contract: one workgroup per (field, point) contracts the point's contiguous block with the product of the other
+//      directions' rows: the last direction's row in LDS, 16-byte loads where a block row starts on a 16-byte boundary, no
+//      atomics, a fixed order of additions.
+// Tensor grids take the same rows and one line product per direction, shrinking directions first, as resample.hip does.
+#include "../../include/chebhip.h"
+#include "sweep.h"
+#include "ops.h"
+#include "linegemm.h"
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <new>
+#include <vector>
+
+using namespace chebhip;
+
+namespace {
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+constexpr int MD = 10;               // directions
+constexpr long WORK_MIN = 32L << 20; // bytes of work memory a handle may always take
+
+// one launch of k_points_rows: direction k (blockIdx.y) has m[k] coordinates x[k][i stride[k]] and writes m[k] rows of n[k]
+struct RowsJob {
+  int nd;
+  int n[MD], lg[MD];                 // extent; log2 of the lanes that share a row
+  unsigned m[MD];
+  long stride[MD];
+  const double *x[MD], *nodes[MD];
+  double *R[MD];
+};
+
+struct PtGeo {
+  int d, lg;                         // directions; log2 of the lanes per block row in k_points_contract
+  int n[MD];
+  unsigned off[MD];                  // sum of the extents before direction k: its rows start at rows + C off[k]
+  unsigned rpb, B;                   // rows of n_{d-1} values per block; values per block, n_1 .. n_{d-1}
+};
+
+__global__ __launch_bounds__(256) void k_points_rows(const RowsJob g) {
+  const int k = blockIdx.y, n = g.n[k], N = n - 1, lg = g.lg[k];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
+  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
+  const bool ok = row < g.m[k];
+  const double *__restrict__ xn = g.nodes[k];
+  const double x = ok ? g.x[k][(size_t)row * (size_t)g.stride[k]] : 0.0;
+
+  // the nearest node, the lowest index on a tie
+  double best = INFINITY;
+  int s = 0x7fffffff;
+  for (int j = l; j < n; j += G) { const double a = fabs(x - xn[j]); if (a < best) { best = a; s = j; } }
+  for (int mm = 1; mm < G; mm <<= 1) {
+    const double ob = __shfl_xor(best, mm);
+    const int os = __shfl_xor(s, mm);
+    if (ob < best || (ob == best && os < s)) { best = ob; s = os; }
+  }
+  const bool fin = fabs(x) < INFINITY;                     // (false for a NaN as well)
+  if (!fin) s = 0;
+  const double ds = x - xn[s], ihs = (s == 0 || s == N) ? 2.0 : 1.0;
+  auto entry = [&](int j) -> double {
+    if (j == s) return 1.0;
+    const double hj = (j == 0 || j == N) ? 0.5 : 1.0;
+    return (((j - s) & 1) ? -hj : hj) * ihs * (ds / (x - xn[j]));
+  };
+  double sum = 0.0;
+  for (int j = l; j < n; j += G) sum += entry(j);
+  for (int mm = 1; mm < G; mm <<= 1) sum += __shfl_xor(sum, mm);
+  if (!ok) return;
+  double *__restrict__ out = g.R[k] + (size_t)row * (size_t)n;
+  for (int j = l; j < n; j += G)
+    out[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : entry(j) / sum;
+}
+
+// the pair (j, j + 1) of a row; the second value is 0 past the end of the row
+__device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
+  if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
+  d2 v; v.x = row[j]; v.y = j + 1 < n ? row[j + 1] : 0.0;
+  return v;
+}
+
+__device__ __forceinline__ double wave_sum(double s) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+  return s;
+}
+
+// out[f][p0 + p] = sum over the block W[f][p][i_1 .. i_{d-1}] of l_1[i_1] .. l_{d-1}[i_{d-1}] W: workgroup (p, f), 1 or 4 waves
+// (blockDim.x).  The block is rpb rows of n = n_{d-1} values; LPR lanes walk a row by pairs, a wave takes 64 / LPR rows at a
+// time, a row's weight is the product of the middle directions' entries (DC: d known at compile time, 0: any d up to MD).
+template <int DC>
+__global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const double *__restrict__ rows, unsigned C,
+                                                         const double *__restrict__ W, unsigned cnt, double *__restrict__ out,
+                                                         size_t npts) {
+  __shared__ double swl[1024];
+  __shared__ double red[4];
+  const int d = DC ? DC : g.d;
+  const unsigned n = (unsigned)g.n[d - 1];
+  const unsigned p = blockIdx.x, f = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
+  const double *rl = rows + (size_t)C * g.off[d - 1] + (size_t)p * n;
+  for (unsigned j = tid; j < n; j += blockDim.x) swl[j] = rl[j];
+  __syncthreads();
+  const unsigned lpr = 1u << g.lg, rpw = 64u >> g.lg, grp = (unsigned)lane >> g.lg, l = (unsigned)lane & (lpr - 1);
+  const double *blk = W + ((size_t)f * cnt + p) * g.B;
+  double acc = 0.0;
+  for (unsigned r = (unsigned)wv * rpw + grp; r < g.rpb; r += (unsigned)nw * rpw) {
+    double wr = 1.0;
+    if (DC == 3) wr = rows[(size_t)C * g.off[1] + (size_t)p * g.n[1] + r];
+    if (DC == 0) {
+      unsigned q = r;
+      for (int m = d - 2; m >= 1; m--) {
+        const unsigned nm = (unsigned)g.n[m], i = m > 1 ? q % nm : q;
+        q /= nm;
+        wr *= rows[(size_t)C * g.off[m] + (size_t)p * nm + i];
+      }
+    }
+    const double *pr = blk + (size_t)r * n;
+    const bool al = ((size_t)pr & 15) == 0;
+    double s = 0.0;
+    for (unsigned j = 2 * l; j < n; j += 2 * lpr) {
+      const d2 a = load_pair(pr, al, j, n);
+      s += swl[j] * a.x + (j + 1 < n ? swl[j + 1] : 0.0) * a.y;
+    }
+    acc += wr * s;
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) red[wv] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = red[0];
+    for (int q = 1; q < nw; q++) s += red[q];
+    out[(size_t)f * npts + p] = s;
+  }
+}
+
+int require_device_pt() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
+                        e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+  return 0;
+}
+
+int check_n(int n) {
+  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
+  if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
+  return 0;
+}
+
+int rows_lg(int n) {                 // log2 of the power of two >= n, at most 6
+  int lg = 0;
+  while (lg < 6 && (1 << lg) < n) lg++;
+  return lg;
+}
+
+int launch_rows(const RowsJob &job, hipStream_t st, const char *what) {
+  unsigned gx = 0;
+  for (int k = 0; k < job.nd; k++) {
+    const unsigned rpb = 4u * (64u >> job.lg[k]);
+    gx = std::max(gx, (job.m[k] + rpb - 1) / rpb);
+  }
+  if (gx == 0) return 0;
+  hipLaunchKernelGGL(k_points_rows, dim3(gx, (unsigned)job.nd), dim3(256), 0, st, job);
+  sweep_note_launch();
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s rows launch: %s", what, hipGetErrorString(e));
+}
+
+}  // namespace
+
+struct cheb_points {
+  int d = 0, nf = 1;
+  long total = 0;                            // nf * prod(dims)
+  unsigned C = 0;                            // points per chunk
+  PtGeo geo{};
+  std::map<int, double *> nodes;             // device node table per distinct extent
+  double *rows = nullptr;                    // C x n_k rows of every direction, direction k at C geo.off[k]
+  double *W = nullptr;                       // nf x C x B: direction 0's output
+  // tensor grids (cheb_points_grid_reserve)
+  int mmax[MD] = {0};
+  size_t goff[MD] = {0};                     // direction k's rows in grows
+  double *grows = nullptr;
+  double *gwork[2] = {nullptr, nullptr};     // ping-pong intermediates
+};
+
+extern "C" int cheb_nodes_host(int n, double *x) {
+  int rc;
+  if ((rc = check_n(n))) return rc;
+  if (!x) return chebhip_fail(CHEBHIP_ERR_ARG, "x is NULL");
+  points_nodes_host(n, x);
+  return 0;
+}
+
+extern "C" int cheb_points_matrix_host(int n, int m, const double *x, double *R) {
+  int rc;
+  if ((rc = check_n(n))) return rc;
+  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  points_matrix_host(n, m, x, R);
+  return 0;
+}
+
+namespace {
+void free_grid(cheb_points *h) {
+  if (h->grows) (void)hipFree(h->grows);
+  for (double *&b : h->gwork) { if (b) (void)hipFree(b); b = nullptr; }
+  h->grows = nullptr;
+  for (int k = 0; k < MD; k++) h->mmax[k] = 0;
+}
+}  // namespace
+
+extern "C" int cheb_points_destroy(cheb_points *h) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  for (auto &t : h->nodes) if (t.second) (void)hipFree(t.second);
+  if (h->rows) (void)hipFree(h->rows);
+  if (h->W) (void)hipFree(h->W);
+  free_grid(h);
+  delete h;
+  return 0;
+}
+
+extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_points **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  int rc;
+  long total = nfields, S = 0;
+  for (int k = 0; k < d; k++) {
+    if ((rc = check_n(dims[k]))) return rc;
+    total *= dims[k]; S += dims[k];
+    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
+  }
+  if ((rc = require_device_pt())) return rc;
+  cheb_points *h = new (std::nothrow) cheb_points;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  h->d = d; h->nf = nfields; h->total = total;
+  PtGeo &g = h->geo;
+  g.d = d;
+  for (int k = 0, o = 0; k < d; o += dims[k], k++) { g.n[k] = dims[k]; g.off[k] = (unsigned)o; }
+  g.B = (unsigned)(total / nfields / dims[0]);
+  g.rpb = g.B / (unsigned)dims[d - 1];
+  g.lg = 0;
+  while (g.lg < 6 && (1 << g.lg) < (dims[d - 1] + 1) / 2) g.lg++;
+
+  // the chunk: rows and direction 0's output within max(bytes of the fields, 32 MiB); a multiple of 128 (the line product's
+  // tile of output points), of 64 below that, whatever fits below 64
+  const long cap = std::max(total * (long)sizeof(double), WORK_MIN) / (long)sizeof(double);
+  const long per = S + (long)nfields * g.B;
+  long C = std::min(1024L, cap / per);
+  if (C >= 128) C -= C % 128; else if (C >= 64) C = 64;
+  if (C < 1) { delete h; return chebhip_fail(CHEBHIP_ERR_DIMS, "no room for one point's work memory"); }
+  h->C = (unsigned)C;
+
+#define POINTS_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cheb_points_destroy(h); \
+    return chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e_)); } } while (0)
+  std::vector<double> x;
+  for (int k = 0; k < d; k++) {
+    const int nk = dims[k];
+    if (h->nodes.count(nk)) continue;
+    x.resize(nk);
+    points_nodes_host(nk, x.data());
+    double *dev = nullptr;
+    POINTS_TRY(hipMalloc(&dev, nk * sizeof(double)), "node table");
+    h->nodes[nk] = dev;
+    POINTS_TRY(hipMemcpy(dev, x.data(), nk * sizeof(double), hipMemcpyHostToDevice), "node table");
+  }
+  POINTS_TRY(hipMalloc(&h->rows, (size_t)C * S * sizeof(double)), "interpolation rows");
+  POINTS_TRY(hipMalloc(&h->W, (size_t)C * nfields * g.B * sizeof(double)), "points work buffer");
+#undef POINTS_TRY
+  *out = h;
+  return 0;
+}
+
+extern "C" long cheb_points_chunk(const cheb_points *h) { return h ? (long)h->C : -1; }
+
+extern "C" int cheb_points_rows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
+  if (m < 0 || m >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %ld must be in 0..2^31-1", m);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  RowsJob job{};
+  const int n = h->geo.n[k];
+  job.nd = 1; job.n[0] = n; job.lg[0] = rows_lg(n); job.m[0] = (unsigned)m; job.stride[0] = 1;
+  job.x[0] = x; job.nodes[0] = h->nodes[n]; job.R[0] = R;
+  return launch_rows(job, (hipStream_t)stream, "points");
+}
+
+extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *xi, long npts, double *out, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
+  if (npts == 0) return 0;
+  if (!u || !xi || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (u < out + (size_t)h->nf * npts && out < u + h->total) return chebhip_fail(CHEBHIP_ERR_ARG, "eval: fields and output must not overlap");
+  hipStream_t st = (hipStream_t)stream;
+  const PtGeo &g = h->geo;
+  const int d = h->d;
+  const long C = h->C;
+  int rc;
+  for (long p0 = 0; p0 < npts; p0 += C) {
+    const unsigned cnt = (unsigned)std::min(C, npts - p0);
+    RowsJob job{};
+    job.nd = d;
+    for (int k = 0; k < d; k++) {
+      job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
+      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->rows + (size_t)C * g.off[k];
+    }
+    if ((rc = launch_rows(job, st, "eval"))) return rc;
+    // d == 1: the line product's [field][point] is the result where it is one chunk or one field
+    const bool direct = d == 1 && (h->nf == 1 || cnt == npts);
+    ResampleDir p{h->rows, u, direct ? out + p0 : h->W, (unsigned)h->nf, (unsigned)g.n[0], cnt, g.B, (unsigned)h->nf * g.B};
+    hipError_t e = resample_launch(p, st);
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval line product launch: %s", hipGetErrorString(e));
+    if (d == 1) {
+      if (!direct) {
+        e = hipMemcpy2DAsync(out + p0, (size_t)npts * sizeof(double), h->W, (size_t)cnt * sizeof(double), (size_t)cnt * sizeof(double),
+                             (size_t)h->nf, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval copy: %s", hipGetErrorString(e));
+      }
+      continue;
+    }
+    const dim3 grid(cnt, (unsigned)h->nf), block(g.B <= 1024 ? 64 : 256);
+#define POINTS_CON(DC) hipLaunchKernelGGL(k_points_contract<DC>, grid, block, 0, st, g, h->rows, (unsigned)C, h->W, cnt, out + p0, (size_t)npts)
+    switch (d) { case 2: POINTS_CON(2); break; case 3: POINTS_CON(3); break; default: POINTS_CON(0); }
+#undef POINTS_CON
+    sweep_note_launch();
+    e = hipGetLastError();
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval contraction launch: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+extern "C" int cheb_points_grid_reserve(cheb_points *h, const int *m_max) {
+  if (!h || !m_max) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  const int d = h->d;
+  long bound = h->nf;
+  size_t nrows = 0;
+  for (int k = 0; k < d; k++) {
+    if (m_max[k] < 1) return chebhip_fail(CHEBHIP_ERR_ARG, "m_max[%d] = %d must be >= 1", k, m_max[k]);
+    bound *= std::max(m_max[k], h->geo.n[k]);
+    if (bound >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "a grid of 2^31 values or more");
+    nrows += (size_t)m_max[k] * h->geo.n[k];
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "grid_reserve: device synchronisation failed");
+  free_grid(h);
+  // an intermediate has m_k or n_k points in direction k: at most `bound` values, whatever order the directions run in
+  hipError_t e = hipMalloc(&h->grows, nrows * sizeof(double));
+  for (int b = 0; b < 2 && b < d - 1 && e == hipSuccess; b++) e = hipMalloc(&h->gwork[b], (size_t)bound * sizeof(double));
+  if (e != hipSuccess) { free_grid(h); return chebhip_fail(CHEBHIP_ERR_MEMORY, "grid buffers: %s", hipGetErrorString(e)); }
+  size_t o = 0;
+  for (int k = 0; k < d; k++) { h->mmax[k] = m_max[k]; h->goff[k] = o; o += (size_t)m_max[k] * h->geo.n[k]; }
+  return 0;
+}
+
+extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const double *coords, const int *m, double *out, void *stream) {
+  if (!h || !m) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  const int d = h->d;
+  const PtGeo &g = h->geo;
+  long nout = h->nf;
+  for (int k = 0; k < d; k++) {
+    if (m[k] < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m[%d] = %d is negative", k, m[k]);
+    if (m[k] > h->mmax[k]) return chebhip_fail(CHEBHIP_ERR_ARG, "m[%d] = %d exceeds the reserved %d (cheb_points_grid_reserve)", k, m[k], h->mmax[k]);
+    nout *= m[k];
+  }
+  if (nout == 0) return 0;
+  if (!u || !coords || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (u < out + nout && out < u + h->total) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grid: fields and output must not overlap");
+  hipStream_t st = (hipStream_t)stream;
+  RowsJob job{};
+  job.nd = d;
+  size_t co = 0;
+  for (int k = 0; k < d; co += m[k], k++) {
+    job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = (unsigned)m[k]; job.stride[k] = 1;
+    job.x[k] = coords + co; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->grows + h->goff[k];
+  }
+  int rc;
+  if ((rc = launch_rows(job, st, "eval_grid"))) return rc;
+  // shrinking directions first: every intermediate is then as small as it can be
+  int order[MD];
+  for (int k = 0; k < d; k++) order[k] = k;
+  std::stable_sort(order, order + d, [&](int a, int b) { return (long)m[a] * g.n[b] < (long)m[b] * g.n[a]; });
+  long cur[MD];
+  for (int k = 0; k < d; k++) cur[k] = g.n[k];
+  const double *src = u;
+  for (int s = 0; s < d; s++) {
+    const int k = order[s];
+    long O = h->nf, Q = 1;
+    for (int j = 0; j < k; j++) O *= cur[j];
+    for (int j = k + 1; j < d; j++) Q *= cur[j];
+    double *dst = s + 1 == d ? out : h->gwork[s & 1];
+    ResampleDir p{h->grows + h->goff[k], src, dst, (unsigned)O, (unsigned)g.n[k], (unsigned)m[k], (unsigned)Q, (unsigned)(O * Q)};
+    hipError_t e = resample_launch(p, st);
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grid launch: %s", hipGetErrorString(e));
+    cur[k] = m[k];
+    src = dst;
+  }
+  return 0;
+}

@@ -120,6 +120,10 @@ void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior
 void modal_matrix_host(int n, int which, double *M);
 void modal_weights_host(int n, double *w);
 void modal_filter_matrix_host(int n, const double *sigma, double *F);
+// Host side of the evaluation at arbitrary points (points.hip; arguments checked there): the n CGL nodes (long double, rounded
+// once), and the m x n barycentric rows of m coordinates in long double on that double table, rounded once.
+void points_nodes_host(int n, double *x);
+void points_matrix_host(int n, int m, const double *x, double *R);
 
 // Launches one sweep.  jfast selects the line-contiguous tiling.
 hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream);

@@ -375,3 +375,36 @@ def resolution(dims, u_full):
         out[:, k] = torch.where(tot > 0, torch.sqrt(Ek[:, top:].sum(dim=1) / torch.where(tot > 0, tot, torch.ones_like(tot))), torch.zeros_like(tot))
     out = out.numpy()
     return out[0] if nf == 1 else out
+
+
+def sample_plane(sp, dims, u_full, axis, coord, m=None):
+    """The plane x_axis = coord of the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields if it
+    holds a multiple of prod(dims) values): one ChebPoints.eval_grid with a single coordinate along `axis`.  The other directions
+    keep their CGL nodes (m = None) or take m uniform points from -1 to +1 each.  Returns a device tensor of shape
+    (nfields, points of the other directions ...), the direction `axis` dropped."""
+    dims = tuple(int(n) for n in dims)
+    axis = int(axis)
+    if not 0 <= axis < len(dims):
+        raise ValueError("axis %d out of range 0..%d" % (axis, len(dims) - 1))
+    size = 1
+    for n in dims:
+        size *= n
+    if u_full.numel() == 0 or u_full.numel() % size:
+        raise ValueError("u_full: %d values are no multiple of prod(dims) = %d" % (u_full.numel(), size))
+    nf = u_full.numel() // size
+    dev = u_full.device
+    coords = []
+    for k, n in enumerate(dims):
+        if k == axis:
+            coords.append(torch.tensor([float(coord)], dtype=torch.float64, device=dev))
+        elif m is None:
+            coords.append(torch.from_numpy(sp.cgl_nodes(n)).to(dev))
+        else:
+            coords.append(torch.linspace(-1.0, 1.0, int(m), dtype=torch.float64, device=dev))
+    pts = sp.ChebPoints(dims, nf)
+    try:
+        out = pts.eval_grid(u_full.reshape(-1), coords)
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        pts.destroy()
+    return out.squeeze(axis + 1)
