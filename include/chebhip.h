@@ -212,6 +212,48 @@ int  cheb_nodes_host(int n, double *x);
 int  cheb_points_matrix_host(int n, int m, const double *x_host, double *R);
 
 /* ------------------------------------------------------------------------- */
+/* Dealiased products and advection terms (no counterpart in the reference):  */
+/* the nonlinear terms of the explicit side of a time-dependent problem.  The */
+/* nodal product of two degree-N interpolants has degree 2N and its upper     */
+/* half folds back onto the retained modes (u = T_N: the nodal square is 1,   */
+/* the truncation of T_N^2 = (T_0 + T_2N) / 2 is 1/2).  Per direction of n    */
+/* coarse points (N = n - 1) and m >= n fine points (M = m - 1):              */
+/*   R (m x n)  Lagrange interpolation coarse -> fine nodes: the matrix of    */
+/*              cheb_resample_matrix_host(n, ALL, m, ALL), bit for bit        */
+/*   P (n x m)  = B_n T_m[0:n, :]: fine values -> fine coefficients, modes    */
+/*              0 .. N kept and evaluated at the coarse nodes (m == n: I)     */
+/*   G (m x n)  = R D_n: differentiate on the coarse grid and interpolate     */
+/* built in long double and rounded once.  For M > 3N/2                       */
+/*   (P_0 (x) ..) (((R_0 (x) ..) u) o ((R_0 (x) ..) v))                       */
+/* is exactly the truncation to degree N per direction of the polynomial      */
+/* product (the aliases of the modes k > M land at 2M - k > N); the smallest  */
+/* such m is ceil(3n/2), the default.  Fields use the full-grid, field-major  */
+/* layout of cheb_modal_*.                                                    */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_dealias cheb_dealias;
+
+/* ceil(3n/2) for 2 <= n <= 1024, -1 otherwise; and R, P or G (which = 0, 1, 2) of n coarse and m >= n fine points, row-major, into
+ * a HOST buffer of n m doubles.  Neither needs a device. */
+int  cheb_dealias_fine_size(int n);
+int  cheb_dealias_matrix_host(int n, int m, int which, double *A);
+/* 1 <= d <= 10; 2 <= dims[k] <= 1024; 1 <= nfields <= 16; dims_fine NULL: the 3/2 rule (n <= 682), otherwise dims[k] <= dims_fine[k]
+ * <= 1024 (equal: that direction runs unpadded); every array the handle touches holds fewer than 2^31 values.  The handle owns its
+ * matrices and work memory -- the product on the fine grid (nfields prod(m) values: the only array of that size, no operand ever
+ * exists on the fine grid) and the operands taken to the fine grid in every direction but one; cheb_dealias_work_bytes reports
+ * it.  multiply and advect allocate nothing and do not synchronise the host; outputs must not overlap inputs. */
+int  cheb_dealias_create(int d, const int *dims, const int *dims_fine, int nfields, cheb_dealias **out);
+int  cheb_dealias_destroy(cheb_dealias *h);
+int  cheb_dealias_fine_dims(const cheb_dealias *h, int *dims_fine);     /* d HOST ints */
+long cheb_dealias_size(const cheb_dealias *h);                          /* nfields * prod(dims); -1: NULL */
+long cheb_dealias_work_bytes(const cheb_dealias *h);                    /* device bytes the handle owns now; -1: NULL */
+/* out[f] = Pi_N (u[f] v[f]), f < nfields; u == v is allowed (squares). */
+int  cheb_dealias_multiply(cheb_dealias *h, const double *u_dev, const double *v_dev, double *out_dev, void *stream);
+/* out[f] = Pi_N (sum_k vel[k] d_k c[f]): vel holds d fields, c and out nfields.  Its work memory (the d (1 + nfields) operand
+ * images) is allocated by cheb_dealias_reserve_advect (synchronous); without it advect returns CHEBHIP_ERR_ARG. */
+int  cheb_dealias_reserve_advect(cheb_dealias *h);
+int  cheb_dealias_advect(cheb_dealias *h, const double *vel_dev, const double *c_dev, double *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

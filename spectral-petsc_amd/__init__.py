@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "cheb_modal_matrix_host", "cheb_modal_weights_host", "cheb_modal_filter_matrix_host",
     "cheb_points_create", "cheb_points_destroy", "cheb_points_chunk", "cheb_points_rows", "cheb_points_eval",
     "cheb_points_grid_reserve", "cheb_points_eval_grid", "cheb_nodes_host", "cheb_points_matrix_host",
+    "cheb_dealias_fine_size", "cheb_dealias_matrix_host", "cheb_dealias_create", "cheb_dealias_destroy", "cheb_dealias_fine_dims",
+    "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
 ]
 
 
@@ -265,6 +267,17 @@ def lib():
         L.cheb_points_eval_grid.argtypes = [vp, vp, vp, ip, vp, vp]
         L.cheb_nodes_host.argtypes = [C.c_int, dp]
         L.cheb_points_matrix_host.argtypes = [C.c_int, C.c_int, dp, dp]
+        L.cheb_dealias_fine_size.argtypes = [C.c_int]
+        L.cheb_dealias_matrix_host.argtypes = [C.c_int, C.c_int, C.c_int, dp]
+        L.cheb_dealias_create.argtypes = [C.c_int, ip, ip, C.c_int, C.POINTER(vp)]
+        L.cheb_dealias_destroy.argtypes = [vp]
+        L.cheb_dealias_fine_dims.argtypes = [vp, ip]
+        for f in (L.cheb_dealias_size, L.cheb_dealias_work_bytes):
+            f.argtypes = [vp]
+            f.restype = C.c_long
+        L.cheb_dealias_reserve_advect.argtypes = [vp]
+        for f in (L.cheb_dealias_multiply, L.cheb_dealias_advect):
+            f.argtypes = [vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -674,6 +687,93 @@ class ChebPoints:
     def destroy(self):
         if getattr(self, "_h", None):
             lib().cheb_points_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+DEALIAS = {"R": 0, "P": 1, "G": 2}
+
+
+def dealias_size(n):
+    """The 3/2 rule's fine size ceil(3n/2) of a direction of n points (cheb_dealias_fine_size)."""
+    m = lib().cheb_dealias_fine_size(int(n))
+    if m < 0:
+        raise ChebhipError(4, lib().chebhip_last_error().decode())
+    return m
+
+
+def dealias_matrix(n, which, m=None):
+    """One direction's dealiasing matrix (cheb_dealias_matrix_host) for n coarse and m fine points (default dealias_size(n)):
+    "R" (m, n) interpolation to the fine nodes, "P" (n, m) = B_n T_m[0:n, :] back to the coarse nodes keeping n modes, "G" (m, n)
+    = R D; needs no device."""
+    import numpy as np
+    if which not in DEALIAS:
+        raise ValueError("matrix %r: expected one of %s" % (which, sorted(DEALIAS)))
+    n = int(n)
+    m = dealias_size(n) if m is None else int(m)
+    A = np.empty((max(n, 0), max(m, 0)) if which == "P" else (max(m, 0), max(n, 0)))
+    _chk(lib().cheb_dealias_matrix_host(n, m, DEALIAS[which], A.ctypes.data_as(C.POINTER(C.c_double)) if A.size else None))
+    return A
+
+
+class ChebDealias:
+    """Dealiased products of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_dealias_*; field-major, row-major over
+    all nodes, as ChebModal): multiply(u, v) = the truncation to degree dims[k] - 1 per direction of the polynomial product u v,
+    advect(vel, c) = that of sum_k vel[k] d_k c.  `fine` is the padded grid (default: the 3/2 rule, dealias_size per direction;
+    fine[k] == dims[k] leaves direction k unpadded).  Asynchronous on torch's current stream; advect reserves its work memory on
+    first use (synchronous)."""
+
+    def __init__(self, dims, nfields=1, fine=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        if fine is not None and len(fine) != len(self.dims):
+            raise ValueError("fine: expected %d sizes" % len(self.dims))
+        h = C.c_void_p()
+        _chk(lib().cheb_dealias_create(len(self.dims), _ints(self.dims), None if fine is None else _ints(fine), self.nfields, C.byref(h)))
+        self._h = h
+        m = (C.c_int * len(self.dims))()
+        _chk(lib().cheb_dealias_fine_dims(self._h, m))
+        self.fine = tuple(m)
+        self._advect = False
+
+    def size(self):
+        return lib().cheb_dealias_size(self._h)
+
+    def work_bytes(self):
+        """Device bytes the handle owns (matrices included); grows once, at the first advect."""
+        return lib().cheb_dealias_work_bytes(self._h)
+
+    def multiply(self, u, v, out=None):
+        """out[f] = the dealiased product u[f] v[f]; `u is v` gives squares."""
+        import torch
+        if out is None:
+            out = torch.empty_like(u)
+        _chk(lib().cheb_dealias_multiply(self._h, _dev_ptr(u, self.size()), _dev_ptr(v, self.size()), _dev_ptr(out, self.size()), _stream()))
+        return out
+
+    def reserve_advect(self):
+        _chk(lib().cheb_dealias_reserve_advect(self._h))
+        self._advect = True
+
+    def advect(self, vel, c, out=None):
+        """out[f] = the dealiased sum_k vel[k] d_k c[f]; vel holds len(dims) fields."""
+        import torch
+        if not self._advect:
+            self.reserve_advect()
+        if out is None:
+            out = torch.empty_like(c)
+        nv = self.size() // self.nfields * len(self.dims)
+        _chk(lib().cheb_dealias_advect(self._h, _dev_ptr(vel, nv), _dev_ptr(c, self.size()), _dev_ptr(out, self.size()), _stream()))
+        return out
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_dealias_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -817,7 +817,8 @@ void centro_part(int M, const std::vector<long double> &A, int part, std::vector
 // exact integer ratios), so the nodes never lose digits to cancellation.  A row whose output node IS an input node (angle
 // indices i (n_in-1) == j (n_out-1), decided in integers) is an exact unit row: equal grids give I, and coarse values are
 // injected unchanged into a finer grid that contains their nodes.
-void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior, double *R) {
+// (the rows in long double: resample_matrix_host rounds them once, dealias_matrix_host multiplies them by D first)
+static void resample_rows_ld(int n_in, int in_interior, int n_out, int out_interior, long double *R) {
   const int a_in = in_interior ? 1 : 0, a_out = out_interior ? 1 : 0;
   const int K = n_in - 2 * a_in, M = n_out - 2 * a_out;
   const long ni = n_in - 1, no = n_out - 1;
@@ -837,18 +838,25 @@ void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior
   std::vector<long double> c(K);
   for (int t = 0; t < M; t++) {
     const long i = t + a_out;
-    double *row = R + (size_t)t * K;
+    long double *row = R + (size_t)t * K;
     int hit = -1;
     for (int s = 0; s < K && hit < 0; s++)
       if (i * ni == (long)(s + a_in) * no) hit = s;
     if (hit >= 0) {
-      for (int s = 0; s < K; s++) row[s] = s == hit ? 1.0 : 0.0;
+      for (int s = 0; s < K; s++) row[s] = s == hit ? 1.0L : 0.0L;
       continue;
     }
     long double sum = 0.0L;
     for (int s = 0; s < K; s++) { c[s] = w[s] / diff(i, no, s + a_in, ni); sum += c[s]; }
-    for (int s = 0; s < K; s++) row[s] = (double)(c[s] / sum);
+    for (int s = 0; s < K; s++) row[s] = c[s] / sum;
   }
+}
+
+void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior, double *R) {
+  const size_t K = n_in - (in_interior ? 2 : 0), M = n_out - (out_interior ? 2 : 0);
+  std::vector<long double> Rl(M * K);
+  resample_rows_ld(n_in, in_interior, n_out, out_interior, Rl.data());
+  for (size_t e = 0; e < M * K; e++) R[e] = (double)Rl[e];
 }
 
 // Chebyshev coefficient transforms on the n = N + 1 Gauss-Lobatto nodes (cheb_modal_*, modal.hip), c_0 = c_N = 2, otherwise 1:
@@ -914,6 +922,51 @@ void modal_filter_matrix_host(int n, const double *sigma, double *F) {
       long double s = 0.0L;
       for (size_t a = 0; a < na; a++) s += b[a] * t[a];
       F[(size_t)i * n + j] = (double)s;
+    }
+}
+
+// Dealiased products (cheb_dealias_*, dealias.hip): n coarse and m >= n fine points of one direction, N = n - 1, M = m - 1.
+//   which = 0  R (m x n): resample_matrix_host(n, m), bit for bit
+//   which = 1  P (n x m) = B_n T_m[0:n, :]: fine values -> fine coefficients, modes 0 .. N kept, evaluated at the coarse nodes
+//              (m == n: B T = I, written as the exact identity)
+//   which = 2  G (m x n) = R D_n: differentiate on the coarse grid and interpolate, one matrix
+// For M > 3N/2 the aliases of the modes M < k <= 2N of a product of two degree-N interpolants land at 2M - k > N, which P drops:
+// P ((R u) o (R v)) is then the exact degree-N truncation of the product.  The smallest such m is ceil(3n/2).
+int dealias_fine_size(int n) { return (3 * n + 1) / 2; }
+
+void dealias_matrix_host(int n, int m, int which, double *A) {
+  if (which == 0) { resample_matrix_host(n, 0, m, 0, A); return; }
+  const size_t sn = n, sm = m;
+  if (which == 1) {
+    if (m == n) {
+      for (size_t i = 0; i < sn; i++)
+        for (size_t j = 0; j < sn; j++) A[i * sn + j] = i == j ? 1.0 : 0.0;
+      return;
+    }
+    std::vector<long double> B(sn * sn), Tt(sm * sn);                         // B_n[i][k]; T_m[k][j] as [j][k], k < n
+    for (int i = 0; i < n; i++)
+      for (int k = 0; k < n; k++) B[i * sn + k] = modal_entry(n, 1, i, k);
+    for (int j = 0; j < m; j++)
+      for (int k = 0; k < n; k++) Tt[j * sn + k] = modal_entry(m, 0, k, j);
+    for (size_t i = 0; i < sn; i++)
+      for (size_t j = 0; j < sm; j++) {
+        const long double *b = &B[i * sn], *t = &Tt[j * sn];
+        long double s = 0.0L;
+        for (size_t k = 0; k < sn; k++) s += b[k] * t[k];
+        A[i * sm + j] = (double)s;
+      }
+    return;
+  }
+  std::vector<long double> R(sm * sn), Dt(sn * sn);                           // D_n as [j][s]
+  resample_rows_ld(n, 0, m, 0, R.data());
+  for (int s = 0; s < n; s++)
+    for (int j = 0; j < n; j++) Dt[j * sn + s] = dentry(s, j, n - 1);
+  for (size_t i = 0; i < sm; i++)
+    for (size_t j = 0; j < sn; j++) {
+      const long double *r = &R[i * sn], *dd = &Dt[j * sn];
+      long double s = 0.0L;
+      for (size_t k = 0; k < sn; k++) s += r[k] * dd[k];
+      A[i * sn + j] = (double)s;
     }
 }
 

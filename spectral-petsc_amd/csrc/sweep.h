@@ -120,6 +120,11 @@ void resample_matrix_host(int n_in, int in_interior, int n_out, int out_interior
 void modal_matrix_host(int n, int which, double *M);
 void modal_weights_host(int n, double *w);
 void modal_filter_matrix_host(int n, const double *sigma, double *F);
+// Host side of the dealiased products (dealias.hip; arguments checked there): the 3/2 rule's fine size ceil(3n/2), and of a
+// direction of n coarse and m fine points R (which = 0, m x n, = resample_matrix_host), P = B_n T_m[0:n, :] (1, n x m) or
+// G = R D_n (2, m x n), row-major, long double rounded once.
+int dealias_fine_size(int n);
+void dealias_matrix_host(int n, int m, int which, double *A);
 // Host side of the evaluation at arbitrary points (points.hip; arguments checked there): the n CGL nodes (long double, rounded
 // once), and the m x n barycentric rows of m coordinates in long double on that double table, rounded once.
 void points_nodes_host(int n, double *x);
