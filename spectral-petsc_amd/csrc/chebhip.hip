@@ -123,15 +123,6 @@ extern "C" int chebhip_timers_read(int stage, double *total_ms, long *calls) {
 }
 extern "C" const char *chebhip_stage_name(int stage) { return (stage >= 0 && stage < CHEBHIP_NSTAGES) ? g_tm_names[stage] : ""; }
 
-static int require_device() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
-                e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // kernel-level plan (MatCreateCheb / ChebMult / ChebDestroy, chebyshev.c:89-235)
 struct cheb_plan {

@@ -8,7 +8,8 @@
 //
 // Schedule.  No operand ever exists at the fine size.  The direction l with the largest m_l / n_l (the last one on a tie) runs
 // last on the way up: every operand is first taken to the fine grid in all the OTHER directions by plain line products
-// (linegemm.h, fields as the outer extent, shrinking ratios first), which leaves images of prod(m) n_l / m_l values per field.
+// (line_chain of linegemm.hip, fields as the outer extent, shrinking ratios first), which leaves images of prod(m) n_l / m_l
+// values per field.
 // cheb_pair_kernel below then runs direction l for two images at once, multiplies the two results in registers, adds such
 // products over a run-time list of pairs and stores that one array of prod(m) values per field.  multiply has one pair
 // (R u, R v); advect has d pairs (R vel_k, G_k c): G sits in direction k of the second operand, so for k != l it is one of the
@@ -17,7 +18,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
-#include "linegemm.h"
+#include "linetile.h"
 #include <algorithm>
 #include <map>
 #include <new>
@@ -42,7 +43,8 @@ struct PairDir {
 };
 
 // y = sum over the pairs of (Ra xa) o (Rb xb) along one direction.  The tiling, the LDS layout and the order of the MFMA chain are
-// those of cheb_resample_kernel (linegemm.h) with BM = 64, run for two line images side by side: three accumulator sets (a, b and
+// those of cheb_resample_kernel (linegemm.hip; linetile.h describes them) with BM = 64, run for two line images side by side:
+// three accumulator sets (a, b and
 // the sum of products) of 2 x 2 C/D tiles each are 96 registers a lane: 206 .. 232 VGPRs in all, two waves per SIMD (which the launch
 // bounds ask for); with BM = 128 the sets are 192 registers, the kernel 464 .. 493, one wave per SIMD.  SAME: every pair has Ra == Rb (multiply): one matrix chunk is loaded, staged and read.  Otherwise both
 // copies exist and a pair whose two matrices are the same pointer stages and reads the first one only.
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void cheb_pair_kernel(const PairDir p) {
     int kk, ll;
     if (LINES_A) { ll = t / RS_KC; kk = t % RS_KC; } else { kk = t / RS_BN; ll = t % RS_BN; }
     const unsigned line = l0 + ll, o = line / Q;
-    xl[e] = line < L; xk[e] = kk; xo[e] = kk * RS_XP + ll;
+    xl[e] = line < L; xk[e] = kk; xo[e] = lds_x(kk, ll);
     xbb[e] = o * K * Q + (line - o * Q);
     const unsigned la = line % p.La, oa = la / Q;
     xba[e] = oa * K * Q + (la - oa * Q);
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void cheb_pair_kernel(const PairDir p) {
 #pragma unroll
   for (int e = 0; e < RN; e++) {
     const int t = tid + 256 * e, ii = t / RS_KC, kk = t % RS_KC;
-    rl[e] = i0 + ii < M; rk[e] = kk; ro[e] = ii * RS_RP + kk; rb[e] = (i0 + ii) * K;
+    rl[e] = i0 + ii < M; rk[e] = kk; ro[e] = lds_r(ii, kk); rb[e] = (i0 + ii) * K;
   }
 
   v4d sum[MT][2];
@@ -135,22 +137,20 @@ __global__ __launch_bounds__(256, 2) void cheb_pair_kernel(const PairDir p) {
         double aa[MT], ab[MT], ba[2], bb[2];
 #pragma unroll
         for (int u = 0; u < MT; u++) {
-          aa[u] = sRa[(pw + 16 * u + l16) * RS_RP + 4 * ks + kq];                                // Ra[point][k]
-          ab[u] = SAME ? aa[u] : sRb2[(pw + 16 * u + l16) * RS_RP + 4 * ks + kq];                // Rb[point][k]
+          aa[u] = sRa[lds_r(pw + 16 * u + l16, 4 * ks + kq)];
+          ab[u] = SAME ? aa[u] : sRb2[lds_r(pw + 16 * u + l16, 4 * ks + kq)];
         }
 #pragma unroll
         for (int t = 0; t < 2; t++) {
-          ba[t] = sXa[(4 * ks + kq) * RS_XP + lw + 16 * t + l16];                                // Xa[k][line]
-          bb[t] = sXb[(4 * ks + kq) * RS_XP + lw + 16 * t + l16];                                // Xb[k][line]
+          ba[t] = sXa[lds_x(4 * ks + kq, lw + 16 * t + l16)];
+          bb[t] = sXb[lds_x(4 * ks + kq, lw + 16 * t + l16)];
         }
 #pragma unroll
         for (int u = 0; u < MT; u++)
 #pragma unroll
           for (int t = 0; t < 2; t++) {
-            acca[u][t] = LINES_A ? __builtin_amdgcn_mfma_f64_16x16x4f64(ba[t], aa[u], acca[u][t], 0, 0, 0)
-                                 : __builtin_amdgcn_mfma_f64_16x16x4f64(aa[u], ba[t], acca[u][t], 0, 0, 0);
-            accb[u][t] = LINES_A ? __builtin_amdgcn_mfma_f64_16x16x4f64(bb[t], ab[u], accb[u][t], 0, 0, 0)
-                                 : __builtin_amdgcn_mfma_f64_16x16x4f64(ab[u], bb[t], accb[u][t], 0, 0, 0);
+            acca[u][t] = line_mfma<LINES_A>(aa[u], ba[t], acca[u][t]);
+            accb[u][t] = line_mfma<LINES_A>(ab[u], bb[t], accb[u][t]);
           }
       }
     }
@@ -192,21 +192,6 @@ hipError_t pair_launch(const PairDir &p, hipStream_t st) {
   return la ? pair_launch_t<true, false>(p, st) : pair_launch_t<false, false>(p, st);
 }
 
-int require_device_da() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
-                        e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-  return 0;
-}
-
-int check_n_da(int n) {
-  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
-  if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
-  return 0;
-}
-
 }  // namespace
 
 struct cheb_dealias {
@@ -232,14 +217,12 @@ struct cheb_dealias {
 };
 
 extern "C" int cheb_dealias_fine_size(int n) {
-  if (n < 2) { (void)chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n); return -1; }
-  if (n > 1024) { (void)chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n); return -1; }
-  return dealias_fine_size(n);
+  return check_extent(n) ? -1 : dealias_fine_size(n);
 }
 
 extern "C" int cheb_dealias_matrix_host(int n, int m, int which, double *A) {
   int rc;
-  if ((rc = check_n_da(n)) || (rc = check_n_da(m))) return rc;
+  if ((rc = check_extent(n)) || (rc = check_extent(m))) return rc;
   if (m < n) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is smaller than n = %d", m, n);
   if (which < 0 || which > 2) return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d is none of 0 (R), 1 (P), 2 (G)", which);
   if (!A) return chebhip_fail(CHEBHIP_ERR_ARG, "matrix is NULL");
@@ -292,7 +275,7 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
   int rc, mk[MD];
   long coarse = 1, fine = 1;
   for (int k = 0; k < d; k++) {
-    if ((rc = check_n_da(dims[k]))) return rc;
+    if ((rc = check_extent(dims[k]))) return rc;
     mk[k] = dims_fine ? dims_fine[k] : dealias_fine_size(dims[k]);
     if (mk[k] < dims[k]) return chebhip_fail(CHEBHIP_ERR_ARG, "direction %d: fine size %d is smaller than %d", k, mk[k], dims[k]);
     if (mk[k] > 1024)
@@ -301,7 +284,7 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
     coarse *= dims[k]; fine *= mk[k];
     if (nfields * fine >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more on the fine grid");
   }
-  if ((rc = require_device_da())) return rc;
+  if ((rc = require_device())) return rc;
   cheb_dealias *h = new (std::nothrow) cheb_dealias;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->coarse = coarse; h->fine = fine;
@@ -312,11 +295,10 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
   }
   h->l = l;
   h->img = fine / mk[l] * dims[l];
-  auto ratio_less = [&](int a, int b) { return (long)h->m[a] * h->n[b] < (long)h->m[b] * h->n[a]; };
   for (int k = 0; k < d; k++) if (k != l) h->up.push_back(k);
-  std::stable_sort(h->up.begin(), h->up.end(), ratio_less);                // growing least first: small intermediates
+  order_by_ratio(h->up.data(), h->up.data() + h->up.size(), h->m, h->n);           // growing least first: small intermediates
   for (int k = 0; k < d; k++) if (k != l && mk[k] != dims[k]) h->down.push_back(k);
-  std::stable_sort(h->down.begin(), h->down.end(), [&](int a, int b) { return ratio_less(b, a); });   // shrinking most first
+  order_by_ratio(h->down.data(), h->down.data() + h->down.size(), h->n, h->m);     // shrinking most first
   if (mk[l] != dims[l]) h->down.insert(h->down.begin(), l);
   // an operand's intermediates: stage s of its line products writes tmp[s & 1], the last one its image.  An operand may skip
   // directions with m == n, which shifts the stages: both buffers take the largest intermediate.
@@ -331,24 +313,21 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
     if (h->up.size() >= 3) h->tmp_len[1] = len;
   }
 
-#define DEALIAS_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cheb_dealias_destroy(h); \
-    return chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e_)); } } while (0)
   std::vector<double> buf;
-  for (int k = 0; k < d; k++) {
+  for (int k = 0; k < d && !rc; k++) {
     const std::pair<int, int> key{dims[k], mk[k]};
     if (h->mats.count(key)) continue;
     const size_t nm = (size_t)dims[k] * mk[k];
     buf.resize(3 * nm);
     for (int which = 0; which < 3; which++) dealias_matrix_host(dims[k], mk[k], which, buf.data() + which * nm);
     double *dev = nullptr;
-    DEALIAS_TRY(hipMalloc(&dev, 3 * nm * sizeof(double)), "dealias matrices");
+    if ((rc = device_array(&dev, 3 * nm, buf.data(), "dealias matrices"))) break;
     h->mats[key] = dev;
     h->mat_bytes += 3 * nm * sizeof(double);
-    DEALIAS_TRY(hipMemcpy(dev, buf.data(), 3 * nm * sizeof(double), hipMemcpyHostToDevice), "dealias matrices");
   }
-  DEALIAS_TRY(hipMalloc(&h->prod, (size_t)nfields * fine * sizeof(double)), "dealias product buffer");
-#undef DEALIAS_TRY
-  if ((rc = dealias_reserve(h, 2L * nfields, nfields))) { cheb_dealias_destroy(h); return rc; }
+  if (!rc) rc = device_array(&h->prod, (size_t)nfields * fine, nullptr, "dealias product buffer");
+  if (!rc) rc = dealias_reserve(h, 2L * nfields, nfields);
+  if (rc) { cheb_dealias_destroy(h); return rc; }
   *out = h;
   return 0;
 }
@@ -373,29 +352,17 @@ extern "C" long cheb_dealias_work_bytes(const cheb_dealias *h) { return h ? (lon
 
 namespace {
 
-bool overlap(const double *a, long na, const double *b, long nb) { return a < b + nb && b < a + na; }
-
 // `fields` coarse fields at x to the fine grid in every direction but l, direction g (-1: none) through G instead of R: the
 // result is written to `image` (fields * img values), or IS x when no direction is left to run
 int dealias_lift(cheb_dealias *h, const double *x, long fields, int g, double *image, const double **res, hipStream_t st) {
   long cur[MD];
   for (int k = 0; k < h->d; k++) cur[k] = h->n[k];
-  std::vector<int> run;
-  for (int k : h->up) if (k == g || h->m[k] != h->n[k]) run.push_back(k);
-  const double *src = x;
-  for (size_t s = 0; s < run.size(); s++) {
-    const int k = run[s];
-    long O = fields, Q = 1;
-    for (int j = 0; j < k; j++) O *= cur[j];
-    for (int j = k + 1; j < h->d; j++) Q *= cur[j];
-    double *dst = s + 1 == run.size() ? image : h->tmp[s & 1];
-    ResampleDir p{h->mat(k, k == g ? 2 : 0), src, dst, (unsigned)O, (unsigned)h->n[k], (unsigned)h->m[k], (unsigned)Q, (unsigned)(O * Q)};
-    hipError_t e = resample_launch(p, st);
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "dealias launch: %s", hipGetErrorString(e));
-    cur[k] = h->m[k];
-    src = dst;
-  }
-  *res = src;
+  LineStep run[MD];
+  int nr = 0;
+  for (int k : h->up) if (k == g || h->m[k] != h->n[k]) run[nr++] = LineStep{k, h->mat(k, k == g ? 2 : 0), h->m[k]};
+  hipError_t e = line_chain(h->d, cur, fields, 1, nr, run, x, image, h->tmp, st);
+  if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "dealias launch: %s", hipGetErrorString(e));
+  *res = nr ? image : x;
   return 0;
 }
 
@@ -405,7 +372,7 @@ int dealias_finish(cheb_dealias *h, PairDir &p, bool a_shared, double *out, hipS
   long O = h->nf, Q = 1;
   for (int j = 0; j < l; j++) O *= h->m[j];
   for (int j = l + 1; j < h->d; j++) Q *= h->m[j];
-  const size_t nd = h->down.size();
+  const int nd = (int)h->down.size();
   p.y = nd ? h->prod : out;
   p.O = (unsigned)O; p.K = (unsigned)h->n[l]; p.M = (unsigned)h->m[l]; p.Q = (unsigned)Q; p.L = (unsigned)(O * Q);
   p.La = a_shared ? p.L / (unsigned)h->nf : p.L;
@@ -414,20 +381,11 @@ int dealias_finish(cheb_dealias *h, PairDir &p, bool a_shared, double *out, hipS
   // the way down: stage s writes half s & 1 of the image buffer (nf * img values each: stage 0 shrinks direction l or something smaller)
   long cur[MD];
   for (int k = 0; k < h->d; k++) cur[k] = h->m[k];
-  const double *src = h->prod;
-  for (size_t s = 0; s < nd; s++) {
-    const int k = h->down[s];
-    O = h->nf; Q = 1;
-    for (int j = 0; j < k; j++) O *= cur[j];
-    for (int j = k + 1; j < h->d; j++) Q *= cur[j];
-    double *dst = s + 1 == nd ? out : h->image + (s & 1) * (size_t)h->nf * h->img;
-    ResampleDir r{h->mat(k, 1), src, dst, (unsigned)O, (unsigned)h->m[k], (unsigned)h->n[k], (unsigned)Q, (unsigned)(O * Q)};
-    e = resample_launch(r, st);
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "dealias launch: %s", hipGetErrorString(e));
-    cur[k] = h->n[k];
-    src = dst;
-  }
-  return 0;
+  LineStep down[MD];
+  for (int s = 0; s < nd; s++) down[s] = LineStep{h->down[s], h->mat(h->down[s], 1), h->n[h->down[s]]};
+  double *const halves[2] = {h->image, h->image ? h->image + (size_t)h->nf * h->img : nullptr};
+  e = line_chain(h->d, cur, h->nf, 1, nd, down, h->prod, out, halves, st);
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "dealias launch: %s", hipGetErrorString(e));
 }
 
 }  // namespace

@@ -1,39 +1,11 @@
-// linegemm.h -- the batched line product on the FP64 matrix cores that resample.hip (interpolation matrices) and modal.hip
-// (Chebyshev transform and filter matrices) share: every line of a row-major tensor along one direction is multiplied by a
-// dense M x K matrix R.
-//
-// In a direction of K -> M points the tensor is (O outer, K, Q inner) and every one of the L = O Q lines (o, q) -- element k at
-// o K Q + k Q + q -- is multiplied by R.  A workgroup computes BM output points x 64 lines; R and the line image are
-// staged in LDS by chunks of 16 points of the contracted index (a 1024-point R does not fit), the next chunk's loads in flight
-// while the current one is multiplied.  Two tilings, selected by the stride Q of the contracted index:
-//   Q > 4 (COLFAST): R is the A operand, the lines the B operand -- the 16 lanes of a quarter-wave load and store 16 neighbouring
-//                    lines at one point (contiguous for Q >= 16);
-//   Q <= 4 (the last direction, stride = ncomp): the lines are the A operand, R^T the B operand -- the 16 lanes of a quarter-wave
-//                    load and store 16 consecutive points of one line.
-// Both read the same LDS fragments (R[i][k] and X[k][line]); only the operand order of the MFMA and the meaning of the C/D
-// rows and columns change.  C/D of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 reg.
-//
-// Everything here sits in an anonymous namespace: each translation unit that includes the header compiles its own copy of the
-// kernel into its own code object (the library is built without relocatable device code), with internal linkage on both sides.
-#pragma once
-#include <hip/hip_runtime.h>
+// linegemm.hip -- the batched line product on the FP64 matrix cores that resample.hip (interpolation matrices), modal.hip
+// (Chebyshev transform and filter matrices), points.hip (barycentric rows) and dealias.hip (the 3/2 rule's matrices) share, and
+// the host driver of a chain of such products, one direction after the other.  The tiling is described in linetile.h; this is
+// the only unit that compiles cheb_resample_kernel.
 #include "sweep.h"
+#include "linetile.h"
 
-namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-constexpr int RS_BN = 64;            // lines per workgroup tile
-constexpr int RS_KC = 16;            // points of the contracted index per LDS chunk (4 k-steps)
-constexpr int RS_XP = RS_BN + 16;    // pitch (doubles) of a row of the line image: the 4 rows a wave reads at once sit 128 B apart
-constexpr int RS_RP = RS_KC + 2;     // pitch (doubles) of a row of the matrix chunk: 16 rows x 2 k of a half-wave on distinct banks
-
-struct ResampleDir {
-  const double *R;                   // n_out x n_in, row-major
-  const double *x;
-  double *y;
-  unsigned O, K, M, Q, L;            // outer extent, n_in, n_out, stride of the contracted index, lines O Q
-};
+namespace chebhip {
 
 // LINES_A: the lines are the A operand (Q <= 4); BM = 64 or 128 output points per workgroup (4 waves as 2 x 2: BM/2 points x 32 lines each)
 template <bool LINES_A, int BM>
@@ -57,14 +29,14 @@ __global__ __launch_bounds__(256) void cheb_resample_kernel(const ResampleDir p)
     int kk, ll;
     if (LINES_A) { ll = t / RS_KC; kk = t % RS_KC; } else { kk = t / RS_BN; ll = t % RS_BN; }
     const unsigned line = l0 + ll, o = line / Q;
-    xl[e] = line < L; xk[e] = kk; xo[e] = kk * RS_XP + ll;
+    xl[e] = line < L; xk[e] = kk; xo[e] = lds_x(kk, ll);
     xb[e] = o * K * Q + (line - o * Q);
   }
   int rk[RN], ro[RN]; bool rl[RN]; unsigned rb[RN];
 #pragma unroll
   for (int e = 0; e < RN; e++) {
     const int t = tid + 256 * e, ii = t / RS_KC, kk = t % RS_KC;
-    rl[e] = i0 + ii < M; rk[e] = kk; ro[e] = ii * RS_RP + kk; rb[e] = (i0 + ii) * K;
+    rl[e] = i0 + ii < M; rk[e] = kk; ro[e] = lds_r(ii, kk); rb[e] = (i0 + ii) * K;
   }
   double xv[XN], rv[RN];
   auto load = [&](unsigned k0) {
@@ -93,15 +65,13 @@ __global__ __launch_bounds__(256) void cheb_resample_kernel(const ResampleDir p)
     for (int ks = 0; ks < RS_KC / 4; ks++) {
       double a[MT], b[2];
 #pragma unroll
-      for (int u = 0; u < MT; u++) a[u] = sR[(pw + 16 * u + l16) * RS_RP + 4 * ks + kq];      // R[point][k]
+      for (int u = 0; u < MT; u++) a[u] = sR[lds_r(pw + 16 * u + l16, 4 * ks + kq)];
 #pragma unroll
-      for (int t = 0; t < 2; t++) b[t] = sX[(4 * ks + kq) * RS_XP + lw + 16 * t + l16];       // X[k][line]
+      for (int t = 0; t < 2; t++) b[t] = sX[lds_x(4 * ks + kq, lw + 16 * t + l16)];
 #pragma unroll
       for (int u = 0; u < MT; u++)
 #pragma unroll
-        for (int t = 0; t < 2; t++)
-          acc[u][t] = LINES_A ? __builtin_amdgcn_mfma_f64_16x16x4f64(b[t], a[u], acc[u][t], 0, 0, 0)   // (line x k) (k x point)
-                              : __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[t], acc[u][t], 0, 0, 0);  // (point x k) (k x line)
+        for (int t = 0; t < 2; t++) acc[u][t] = line_mfma<LINES_A>(a[u], b[t], acc[u][t]);
     }
   }
 
@@ -122,18 +92,35 @@ __global__ __launch_bounds__(256) void cheb_resample_kernel(const ResampleDir p)
 }
 
 template <bool LINES_A, int BM>
-hipError_t launch_t(const ResampleDir &p, hipStream_t st) {
+static hipError_t launch_t(const ResampleDir &p, hipStream_t st) {
   const dim3 grid((p.L + RS_BN - 1) / RS_BN, (p.M + BM - 1) / BM);
   hipLaunchKernelGGL((cheb_resample_kernel<LINES_A, BM>), grid, dim3(256), 0, st, p);
-  chebhip::sweep_note_launch();
+  sweep_note_launch();
   return hipGetLastError();
 }
 
-[[maybe_unused]] hipError_t resample_launch(const ResampleDir &p, hipStream_t st) {
+hipError_t resample_launch(const ResampleDir &p, hipStream_t st) {
   if (p.L == 0) return hipSuccess;
   const bool la = p.Q <= 4;
   if (p.M > 64) return la ? launch_t<true, 128>(p, st) : launch_t<false, 128>(p, st);
   return la ? launch_t<true, 64>(p, st) : launch_t<false, 64>(p, st);
 }
 
-}  // namespace
+hipError_t line_chain(int d, long *cur, long outer, long inner, int nsteps, const LineStep *steps, const double *src, double *dst,
+                      double *const *work, hipStream_t st) {
+  for (int s = 0; s < nsteps; s++) {
+    const int k = steps[s].dir;
+    long O = outer, Q = inner;
+    for (int j = 0; j < k; j++) O *= cur[j];
+    for (int j = k + 1; j < d; j++) Q *= cur[j];
+    double *out = s + 1 == nsteps ? dst : work[s & 1];
+    const ResampleDir p{steps[s].R, src, out, (unsigned)O, (unsigned)cur[k], (unsigned)steps[s].m, (unsigned)Q, (unsigned)(O * Q)};
+    const hipError_t e = resample_launch(p, st);
+    if (e != hipSuccess) return e;
+    cur[k] = steps[s].m;
+    src = out;
+  }
+  return hipSuccess;
+}
+
+}  // namespace chebhip

@@ -3,7 +3,7 @@
 // (field-major, row-major, all nodes: the layout of cheb_helmholtz_solve_bc's full-grid arrays).
 //
 // forward / backward / filter are tensor products of n x n matrices (diffmat.cpp: T, B, F = B diag(sigma) T): one launch of the
-// line GEMM of linegemm.h per direction, the fields as one more outer extent, intermediates in the handle's two ping-pong buffers.
+// line product of linegemm.hip per direction (line_chain), the fields as one more outer extent, intermediates in the handle's two ping-pong buffers.
 //
 // integrate and spectrum are one pass over the data each.  Both see a field as rpf = prod_{k < d-1} n_k rows of n = n_{d-1}
 // contiguous values.  A row is walked by LPR lanes (the power of two >= ceil(n / 2), at most 64), each lane taking the pairs
@@ -14,7 +14,6 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
-#include "linegemm.h"
 #include <algorithm>
 #include <map>
 #include <new>
@@ -208,21 +207,6 @@ __global__ __launch_bounds__(256) void k_modal_fold(const double *__restrict__ p
   }
 }
 
-int require_device_md() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
-                        e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-  return 0;
-}
-
-int check_n(int n) {
-  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
-  if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
-  return 0;
-}
-
 }  // namespace
 
 struct cheb_modal {
@@ -240,7 +224,7 @@ struct cheb_modal {
 
 extern "C" int cheb_modal_matrix_host(int n, int which, double *M) {
   int rc;
-  if ((rc = check_n(n))) return rc;
+  if ((rc = check_extent(n))) return rc;
   if (which != 0 && which != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d is neither 0 (forward) nor 1 (backward)", which);
   if (!M) return chebhip_fail(CHEBHIP_ERR_ARG, "M is NULL");
   modal_matrix_host(n, which, M);
@@ -249,7 +233,7 @@ extern "C" int cheb_modal_matrix_host(int n, int which, double *M) {
 
 extern "C" int cheb_modal_weights_host(int n, double *w) {
   int rc;
-  if ((rc = check_n(n))) return rc;
+  if ((rc = check_extent(n))) return rc;
   if (!w) return chebhip_fail(CHEBHIP_ERR_ARG, "w is NULL");
   modal_weights_host(n, w);
   return 0;
@@ -257,7 +241,7 @@ extern "C" int cheb_modal_weights_host(int n, double *w) {
 
 extern "C" int cheb_modal_filter_matrix_host(int n, const double *sigma, double *F) {
   int rc;
-  if ((rc = check_n(n))) return rc;
+  if ((rc = check_extent(n))) return rc;
   if (!sigma || !F) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   modal_filter_matrix_host(n, sigma, F);
   return 0;
@@ -282,11 +266,11 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   int rc;
   long total = nfields, S = 0;
   for (int k = 0; k < d; k++) {
-    if ((rc = check_n(dims[k]))) return rc;
+    if ((rc = check_extent(dims[k]))) return rc;
     total *= dims[k]; S += dims[k];
     if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
   }
-  if ((rc = require_device_md())) return rc;
+  if ((rc = require_device())) return rc;
   cheb_modal *h = new (std::nothrow) cheb_modal;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->total = total;
@@ -308,10 +292,8 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   if (h->lds_spec > 64 * 1024) { delete h; return chebhip_fail(CHEBHIP_ERR_DIMS, "extents sum to %ld: the spectrum's bins do not fit in LDS", S); }
   const size_t npart = std::max((size_t)nfields * h->gx_int, (size_t)nfields * h->gx_spec * S);
 
-#define MODAL_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cheb_modal_destroy(h); \
-    return chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e_)); } } while (0)
   std::vector<double> m;
-  for (int k = 0; k < d; k++) {
+  for (int k = 0; k < d && !rc; k++) {
     const int nk = dims[k];
     if (h->mats.count(nk)) continue;
     const size_t nn = (size_t)nk * nk;
@@ -319,15 +301,12 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
     modal_matrix_host(nk, 0, m.data());
     modal_matrix_host(nk, 1, m.data() + nn);
     double *dev = nullptr;
-    MODAL_TRY(hipMalloc(&dev, 2 * nn * sizeof(double)), "modal matrices");
-    h->mats[nk] = dev;
-    MODAL_TRY(hipMemcpy(dev, m.data(), 2 * nn * sizeof(double), hipMemcpyHostToDevice), "modal matrices");
+    if (!(rc = device_array(&dev, 2 * nn, m.data(), "modal matrices"))) h->mats[nk] = dev;
   }
-  MODAL_TRY(hipMalloc(&h->w, S * sizeof(double)), "quadrature weights");
-  MODAL_TRY(hipMemcpy(h->w, w.data(), S * sizeof(double), hipMemcpyHostToDevice), "quadrature weights");
-  for (int b = 0; b < 2 && b < d - 1; b++) MODAL_TRY(hipMalloc(&h->work[b], total * sizeof(double)), "modal work buffer");
-  MODAL_TRY(hipMalloc(&h->partial, npart * sizeof(double)), "modal partial sums");
-#undef MODAL_TRY
+  if (!rc) rc = device_array(&h->w, S, w.data(), "quadrature weights");
+  for (int b = 0; b < 2 && b < d - 1 && !rc; b++) rc = device_array(&h->work[b], total, nullptr, "modal work buffer");
+  if (!rc) rc = device_array(&h->partial, npart, nullptr, "modal partial sums");
+  if (rc) { cheb_modal_destroy(h); return rc; }
   *out = h;
   return 0;
 }
@@ -340,29 +319,21 @@ namespace {
 // y = (M_0 (x) ... (x) M_{d-1}) x over the directions with a matrix (null: identity), one launch each, the last one into y
 int modal_product(cheb_modal *h, const double *const *M, const double *x, double *y, void *stream, const char *what) {
   if (!h || !x || !y) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (x < y + h->total && y < x + h->total) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: input and output must not overlap", what);
+  if (overlap(x, h->total, y, h->total)) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: input and output must not overlap", what);
   hipStream_t st = (hipStream_t)stream;
+  LineStep steps[MD];
+  long cur[MD];
   int nd = 0;
-  for (int k = 0; k < h->d; k++) nd += M[k] != nullptr;
+  for (int k = 0; k < h->d; k++) {
+    cur[k] = h->geo.n[k];
+    if (M[k]) steps[nd++] = LineStep{k, M[k], h->geo.n[k]};
+  }
   if (nd == 0) {
     hipError_t e = hipMemcpyAsync(y, x, h->total * sizeof(double), hipMemcpyDeviceToDevice, st);
     return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s copy: %s", what, hipGetErrorString(e));
   }
-  const double *src = x;
-  unsigned O = (unsigned)h->nf, Q = h->geo.N;
-  for (int k = 0, s = 0; k < h->d; k++) {
-    const unsigned n = (unsigned)h->geo.n[k];
-    Q /= n;
-    if (M[k]) {
-      double *dst = s + 1 == nd ? y : h->work[s & 1];
-      ResampleDir p{M[k], src, dst, O, n, n, Q, O * Q};
-      hipError_t e = resample_launch(p, st);
-      if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
-      src = dst; s++;
-    }
-    O *= n;
-  }
-  return 0;
+  hipError_t e = line_chain(h->d, cur, h->nf, 1, nd, steps, x, y, h->work, st);
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
 }
 
 int modal_transform(cheb_modal *h, int which, const double *x, double *y, void *stream) {

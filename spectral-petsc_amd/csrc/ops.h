@@ -1,6 +1,9 @@
-// ops.h -- what the preconditioner module (precond.hip) needs to see of the operator handles.
+// ops.h -- what the preconditioner module (precond.hip) needs to see of the operator handles, and the plumbing that the
+// handle modules share (chebhip.hip, resample.hip, modal.hip, points.hip, dealias.hip).
 #pragma once
 #include "../../include/chebhip.h"
+#include <hip/hip_runtime.h>
+#include <algorithm>
 
 namespace chebhip {
 
@@ -24,3 +27,40 @@ int ell_op_fd_view_any(ell_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view_any(stokes_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view(stokes_op *op, chebhip::FdView *v);    // stokes.hip
 int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip
+
+namespace chebhip {
+
+inline int require_device() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
+                        e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+  return 0;
+}
+
+// the extent of one direction of a full Chebyshev-Gauss-Lobatto grid
+inline int check_extent(int n) {
+  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
+  if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
+  return 0;
+}
+
+inline bool overlap(const double *a, long na, const double *b, long nb) { return a < b + nb && b < a + na; }
+
+// *dev = n doubles on the device, filled from `host` unless that is null; on failure *dev is null and the error is set
+inline int device_array(double **dev, size_t n, const double *host, const char *what) {
+  hipError_t e = hipMalloc(dev, n * sizeof(double));
+  if (e != hipSuccess) *dev = nullptr;
+  else if (host && (e = hipMemcpy(*dev, host, n * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) { (void)hipFree(*dev); *dev = nullptr; }
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e));
+}
+
+// directions first..last in ascending order of out[k] / in[k], ties in their given order.  A chain of line products that runs its
+// shrinking directions first keeps every prefix product of out / in, hence every intermediate, as small as it can be.
+template <class Out, class In>
+void order_by_ratio(int *first, int *last, const Out &out, const In &in) {
+  std::stable_sort(first, last, [&](int a, int b) { return (long)out[a] * in[b] < (long)out[b] * in[a]; });
+}
+
+}  // namespace chebhip

@@ -13,16 +13,15 @@
 //
 // Scattered points run in chunks of C points (cheb_points_chunk), three launches a chunk:
 //   1. k_points_rows: the C x n_k rows of every direction;
-//   2. direction 0 on the FP64 matrix cores: the line product of linegemm.h with R = the chunk's C x n_0 rows, O = nfields,
+//   2. direction 0 on the FP64 matrix cores: the line product of linegemm.hip with R = the chunk's C x n_0 rows, O = nfields,
 //      Q = n_1 .. n_{d-1} -- the fields are read once per chunk; the result is [field][point][i_1 .. i_{d-1}];
 //   3. k_points_contract: one workgroup per (field, point) contracts the point's contiguous block with the product of the other
 //      directions' rows: the last direction's row in LDS, 16-byte loads where a block row starts on a 16-byte boundary, no
 //      atomics, a fixed order of additions.
-// Tensor grids take the same rows and one line product per direction, shrinking directions first, as resample.hip does.
+// Tensor grids take the same rows and one line product per direction (line_chain), shrinking directions first, as resample.hip does.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
-#include "linegemm.h"
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -152,21 +151,6 @@ __global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const do
   }
 }
 
-int require_device_pt() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device (%s); libchebhip has no CPU fallback",
-                        e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-  return 0;
-}
-
-int check_n(int n) {
-  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
-  if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
-  return 0;
-}
-
 int rows_lg(int n) {                 // log2 of the power of two >= n, at most 6
   int lg = 0;
   while (lg < 6 && (1 << lg) < n) lg++;
@@ -205,7 +189,7 @@ struct cheb_points {
 
 extern "C" int cheb_nodes_host(int n, double *x) {
   int rc;
-  if ((rc = check_n(n))) return rc;
+  if ((rc = check_extent(n))) return rc;
   if (!x) return chebhip_fail(CHEBHIP_ERR_ARG, "x is NULL");
   points_nodes_host(n, x);
   return 0;
@@ -213,7 +197,7 @@ extern "C" int cheb_nodes_host(int n, double *x) {
 
 extern "C" int cheb_points_matrix_host(int n, int m, const double *x, double *R) {
   int rc;
-  if ((rc = check_n(n))) return rc;
+  if ((rc = check_extent(n))) return rc;
   if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
   if (m == 0) return 0;
   if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
@@ -248,11 +232,11 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   int rc;
   long total = nfields, S = 0;
   for (int k = 0; k < d; k++) {
-    if ((rc = check_n(dims[k]))) return rc;
+    if ((rc = check_extent(dims[k]))) return rc;
     total *= dims[k]; S += dims[k];
     if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
   }
-  if ((rc = require_device_pt())) return rc;
+  if ((rc = require_device())) return rc;
   cheb_points *h = new (std::nothrow) cheb_points;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->total = total;
@@ -273,22 +257,18 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   if (C < 1) { delete h; return chebhip_fail(CHEBHIP_ERR_DIMS, "no room for one point's work memory"); }
   h->C = (unsigned)C;
 
-#define POINTS_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cheb_points_destroy(h); \
-    return chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e_)); } } while (0)
   std::vector<double> x;
-  for (int k = 0; k < d; k++) {
+  for (int k = 0; k < d && !rc; k++) {
     const int nk = dims[k];
     if (h->nodes.count(nk)) continue;
     x.resize(nk);
     points_nodes_host(nk, x.data());
     double *dev = nullptr;
-    POINTS_TRY(hipMalloc(&dev, nk * sizeof(double)), "node table");
-    h->nodes[nk] = dev;
-    POINTS_TRY(hipMemcpy(dev, x.data(), nk * sizeof(double), hipMemcpyHostToDevice), "node table");
+    if (!(rc = device_array(&dev, nk, x.data(), "node table"))) h->nodes[nk] = dev;
   }
-  POINTS_TRY(hipMalloc(&h->rows, (size_t)C * S * sizeof(double)), "interpolation rows");
-  POINTS_TRY(hipMalloc(&h->W, (size_t)C * nfields * g.B * sizeof(double)), "points work buffer");
-#undef POINTS_TRY
+  if (!rc) rc = device_array(&h->rows, (size_t)C * S, nullptr, "interpolation rows");
+  if (!rc) rc = device_array(&h->W, (size_t)C * nfields * g.B, nullptr, "points work buffer");
+  if (rc) { cheb_points_destroy(h); return rc; }
   *out = h;
   return 0;
 }
@@ -313,7 +293,7 @@ extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *x
   if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
   if (npts == 0) return 0;
   if (!u || !xi || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (u < out + (size_t)h->nf * npts && out < u + h->total) return chebhip_fail(CHEBHIP_ERR_ARG, "eval: fields and output must not overlap");
+  if (overlap(u, h->total, out, h->nf * npts)) return chebhip_fail(CHEBHIP_ERR_ARG, "eval: fields and output must not overlap");
   hipStream_t st = (hipStream_t)stream;
   const PtGeo &g = h->geo;
   const int d = h->d;
@@ -386,7 +366,7 @@ extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const doub
   }
   if (nout == 0) return 0;
   if (!u || !coords || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (u < out + nout && out < u + h->total) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grid: fields and output must not overlap");
+  if (overlap(u, h->total, out, nout)) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grid: fields and output must not overlap");
   hipStream_t st = (hipStream_t)stream;
   RowsJob job{};
   job.nd = d;
@@ -397,24 +377,12 @@ extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const doub
   }
   int rc;
   if ((rc = launch_rows(job, st, "eval_grid"))) return rc;
-  // shrinking directions first: every intermediate is then as small as it can be
   int order[MD];
-  for (int k = 0; k < d; k++) order[k] = k;
-  std::stable_sort(order, order + d, [&](int a, int b) { return (long)m[a] * g.n[b] < (long)m[b] * g.n[a]; });
   long cur[MD];
-  for (int k = 0; k < d; k++) cur[k] = g.n[k];
-  const double *src = u;
-  for (int s = 0; s < d; s++) {
-    const int k = order[s];
-    long O = h->nf, Q = 1;
-    for (int j = 0; j < k; j++) O *= cur[j];
-    for (int j = k + 1; j < d; j++) Q *= cur[j];
-    double *dst = s + 1 == d ? out : h->gwork[s & 1];
-    ResampleDir p{h->grows + h->goff[k], src, dst, (unsigned)O, (unsigned)g.n[k], (unsigned)m[k], (unsigned)Q, (unsigned)(O * Q)};
-    hipError_t e = resample_launch(p, st);
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grid launch: %s", hipGetErrorString(e));
-    cur[k] = m[k];
-    src = dst;
-  }
-  return 0;
+  for (int k = 0; k < d; k++) { order[k] = k; cur[k] = g.n[k]; }
+  order_by_ratio(order, order + d, m, g.n);                    // shrinking directions first
+  LineStep steps[MD];
+  for (int s = 0; s < d; s++) steps[s] = LineStep{order[s], h->grows + h->goff[order[s]], m[order[s]]};
+  hipError_t e = line_chain(d, cur, h->nf, 1, d, steps, u, out, h->gwork, st);
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grid launch: %s", hipGetErrorString(e));
 }

@@ -138,6 +138,22 @@ hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream);
 hipError_t fused_launch(const DiffMat &m, SweepParams p, hipStream_t stream);
 void sweep_note_launch();
 
+// One batched line product on the FP64 matrix cores (linegemm.hip): every line of a row-major tensor (O outer, K, Q inner) along
+// the middle direction is multiplied by the dense M x K matrix R; nothing is launched for L == 0.
+struct ResampleDir {
+  const double *R;                   // n_out x n_in, row-major
+  const double *x;
+  double *y;
+  unsigned O, K, M, Q, L;            // outer extent, n_in, n_out, stride of the contracted index, lines O Q
+};
+hipError_t resample_launch(const ResampleDir &p, hipStream_t stream);
+// A chain of line products over a row-major tensor of `outer` x cur[0] x .. x cur[d-1] x `inner` values: step s multiplies
+// direction `dir` (of cur[dir] points at that time) by R (m x cur[dir]), reads src (s == 0) or the previous stage and writes
+// work[s & 1], the last step dst; cur[] follows the extents.  Nothing happens for nsteps == 0.
+struct LineStep { int dir; const double *R; int m; };
+hipError_t line_chain(int d, long *cur, long outer, long inner, int nsteps, const LineStep *steps, const double *src, double *dst,
+                      double *const *work, hipStream_t stream);
+
 // Straight-line fused kernel (fused4.hip).  The launch walks a line space of nouter blocks x qmax lines; element
 // (block o, line q, point j) of array X sits at o * X.os + q * X.ls + j * X.rs, counted in elements of X (COLFAST: ls = 1,
 // JFAST: rs = 1).  Arrays marked "trimmed" hold the points 1..n-1 of a line only (point j at (j-1) * rs): the interior
