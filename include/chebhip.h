@@ -254,6 +254,55 @@ int  cheb_dealias_reserve_advect(cheb_dealias *h);
 int  cheb_dealias_advect(cheb_dealias *h, const double *vel_dev, const double *c_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Partial contractions (no counterpart in the reference): the numbers a run  */
+/* is made for -- mean profiles, plane-averaged fluxes <w T>(z), the flux     */
+/* through a wall, the value or normal derivative of a field on a face, a     */
+/* marginal of a density.  A SUBSET of the directions of u, or of the product */
+/* u v, is summed against one weight vector per contracted direction:         */
+/*   out[f][kept indices] = sum over the contracted indices of                */
+/*                          prod_{k contracted} w_k[i_k] u[f][i] (v[f][i])    */
+/* with the kept indices row-major in the original order of the directions.   */
+/* Fields use the full-grid, field-major layout of cheb_modal_*.  Contracting */
+/* every direction with the default weights is cheb_modal_integrate.  The     */
+/* weight vectors of one direction of n points (index 0 is x = +1):           */
+/*   CHEB_W_INTEGRAL     the Clenshaw-Curtis weights (cheb_modal_weights_host)*/
+/*   CHEB_W_MEAN         half of them: the mean over [-1, 1]                  */
+/*   CHEB_W_NODE   j     e_j: the value on the grid plane i_k = j             */
+/*   CHEB_W_DNODE  j     row j of D_n: d/dx_k on that plane.  The OUTWARD     */
+/*                       derivative is + this at j = 0 and - this at j = n-1  */
+/*                       (the convention of cheb_helmholtz_create_bc); the    */
+/*                       sign is the caller's                                 */
+/*   CHEB_W_POINT  x     the barycentric row of cheb_points_matrix_host: the  */
+/*                       value on the plane x_k = x                           */
+/*   CHEB_W_DPOINT x     r(x)^T D_n: d/dx_k on the plane x_k = x              */
+/* built in long double and rounded once.  No atomics: the additions run in   */
+/* an order that depends on (dims, nfields, contract) alone, so results       */
+/* repeat bit for bit, and an output reads only the values it owns (a NaN in  */
+/* u stays in its own outputs).  With T terms per output over S contracted    */
+/* directions every output is within (T + S + 4) 2^-53 sum |W_i u_i v_i| of   */
+/* the exact sum with the weights as uploaded.                                */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_reduce cheb_reduce;
+enum { CHEB_W_INTEGRAL = 0, CHEB_W_MEAN = 1, CHEB_W_NODE = 2, CHEB_W_DNODE = 3, CHEB_W_POINT = 4, CHEB_W_DPOINT = 5 };
+
+/* n HOST values; arg is the node index j or the coordinate x (ignored by INTEGRAL and MEAN).  A j that is no index of the line or
+ * an unknown kind is CHEBHIP_ERR_ARG; a NaN or infinite x gives a row of NaN.  Needs no device. */
+int  cheb_reduce_weights_host(int n, int kind, double arg, double *w);
+/* 1 <= d <= 10; 2 <= dims[k] <= 1024; 1 <= nfields <= 16; fewer than 2^31 input values; contract: d flags, at least one of them
+ * nonzero (CHEBHIP_ERR_ARG otherwise).  Contracted directions start with CHEB_W_INTEGRAL.  The handle owns its weights and the
+ * scratch of the partial sums: cheb_reduce_apply allocates nothing and does not synchronise the host. */
+int  cheb_reduce_create(int d, const int *dims, int nfields, const int *contract, cheb_reduce **out);
+int  cheb_reduce_destroy(cheb_reduce *h);
+/* The weights of the contracted direction k: dims[k] HOST values, NULL restores the default; a kept direction is CHEBHIP_ERR_ARG.
+ * Synchronous, like cheb_modal_set_filter. */
+int  cheb_reduce_set_weights(cheb_reduce *h, int k, const double *w_host);
+long cheb_reduce_size(const cheb_reduce *h, int which);    /* 0: input values nfields * prod(dims), 1: output values; -1 on a bad argument */
+int  cheb_reduce_slices(const cheb_reduce *h);             /* partial sums per output value (1: stored directly, no fold launch); -1: NULL */
+/* v_dev NULL: the contraction of u; otherwise of u v (u == v is allowed).  out: cheb_reduce_size(h, 1) DEVICE values, field-major;
+ * it must not overlap u or v. */
+int  cheb_reduce_apply(cheb_reduce *h, const double *u_dev, const double *v_dev, double *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "cheb_points_grid_reserve", "cheb_points_eval_grid", "cheb_nodes_host", "cheb_points_matrix_host",
     "cheb_dealias_fine_size", "cheb_dealias_matrix_host", "cheb_dealias_create", "cheb_dealias_destroy", "cheb_dealias_fine_dims",
     "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
+    "cheb_reduce_weights_host", "cheb_reduce_create", "cheb_reduce_destroy", "cheb_reduce_set_weights", "cheb_reduce_size",
+    "cheb_reduce_slices", "cheb_reduce_apply",
 ]
 
 
@@ -278,6 +280,14 @@ def lib():
         L.cheb_dealias_reserve_advect.argtypes = [vp]
         for f in (L.cheb_dealias_multiply, L.cheb_dealias_advect):
             f.argtypes = [vp, vp, vp, vp, vp]
+        L.cheb_reduce_weights_host.argtypes = [C.c_int, C.c_int, C.c_double, dp]
+        L.cheb_reduce_create.argtypes = [C.c_int, ip, C.c_int, ip, C.POINTER(vp)]
+        L.cheb_reduce_destroy.argtypes = [vp]
+        L.cheb_reduce_set_weights.argtypes = [vp, C.c_int, dp]
+        L.cheb_reduce_size.argtypes = [vp, C.c_int]
+        L.cheb_reduce_size.restype = C.c_long
+        L.cheb_reduce_slices.argtypes = [vp]
+        L.cheb_reduce_apply.argtypes = [vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -774,6 +784,101 @@ class ChebDealias:
     def destroy(self):
         if getattr(self, "_h", None):
             lib().cheb_dealias_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+REDUCE_W = {"integral": 0, "mean": 1, "node": 2, "dnode": 3, "point": 4, "dpoint": 5}
+
+
+def reduce_weights(n, kind, arg=None):
+    """The n weights one contracted direction of n points is summed against (cheb_reduce_weights_host), long double rounded once:
+    "integral" (the Clenshaw-Curtis weights), "mean" (half of them), ("node", j) the unit vector e_j (the value on the grid plane
+    i = j; j = 0 is x = +1), ("dnode", j) row j of D (d/dx on that plane; the outward derivative is + at j = 0, - at j = n - 1),
+    ("point", x) the barycentric row of x, ("dpoint", x) r(x)^T D.  A kind with an argument is a pair, or `arg` carries it.
+    Needs no device."""
+    import numpy as np
+    if isinstance(kind, (tuple, list)):
+        if len(kind) != 2 or arg is not None:
+            raise ValueError("weights %r: expected a name or a (name, argument) pair" % (kind,))
+        kind, arg = kind
+    if kind not in REDUCE_W:
+        raise ValueError("weights %r: expected one of %s" % (kind, sorted(REDUCE_W)))
+    if (arg is None) != (REDUCE_W[kind] < 2):
+        raise ValueError("weights %r take %s argument" % (kind, "no" if REDUCE_W[kind] < 2 else "one"))
+    w = np.empty(max(int(n), 0))
+    _chk(lib().cheb_reduce_weights_host(int(n), REDUCE_W[kind], 0.0 if arg is None else float(arg),
+                                        w.ctypes.data_as(C.POINTER(C.c_double)) if w.size else None))
+    return w
+
+
+class ChebReduce:
+    """Partial contractions of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_reduce_*; field-major, row-major over
+    all nodes, as ChebModal): the directions listed in `over` are summed against one weight vector each, the others are kept --
+    out[f][kept indices] = sum prod_k w_k[i_k] u[f][i] (v[f][i]).  Every contracted direction starts with the Clenshaw-Curtis
+    weights (a partial integral); `weights` maps a direction to what set_weights takes.  apply is asynchronous on torch's current
+    stream, adds in a fixed order (the same input gives the same bits) and uses no vendor GEMM."""
+
+    def __init__(self, dims, nfields=1, over=(), weights=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        over = (over,) if isinstance(over, int) else tuple(int(k) for k in over)
+        for k in over:
+            if not 0 <= k < len(self.dims):
+                raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(self.dims) - 1))
+        self.over = tuple(sorted(set(over)))
+        self.out_dims = tuple(n for k, n in enumerate(self.dims) if k not in self.over)
+        h = C.c_void_p()
+        _chk(lib().cheb_reduce_create(len(self.dims), _ints(self.dims), self.nfields,
+                                      _ints([int(k in self.over) for k in range(len(self.dims))]), C.byref(h)))
+        self._h = h
+        for k, w in (weights or {}).items():
+            self.set_weights(k, w)
+
+    def size(self, which=0):
+        """Values of the input (which = 0) or of the output (1)."""
+        return lib().cheb_reduce_size(self._h, int(which))
+
+    @property
+    def slices(self):
+        """Partial sums per output value: 1 = the kernel stores the outputs itself, more = one fold launch adds them."""
+        return lib().cheb_reduce_slices(self._h)
+
+    def set_weights(self, k, w):
+        """The weights of the contracted direction k: dims[k] host values, or what reduce_weights takes as `kind` ("mean",
+        ("dnode", 0), ..); None restores the default.  Synchronous."""
+        import numpy as np
+        k = int(k)
+        if not 0 <= k < len(self.dims):
+            raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(self.dims) - 1))
+        if w is None:
+            _chk(lib().cheb_reduce_set_weights(self._h, k, None))
+            return
+        if isinstance(w, str) or (isinstance(w, (tuple, list)) and len(w) == 2 and isinstance(w[0], str)):
+            w = reduce_weights(self.dims[k], w)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.dims[k],):
+            raise ValueError("weights of direction %d: expected %d values, got shape %r" % (k, self.dims[k], w.shape))
+        _chk(lib().cheb_reduce_set_weights(self._h, k, _np_dp(w)))
+
+    def apply(self, u, v=None, out=None):
+        """The contraction of u (of u v; `v is u` gives squares) as a device tensor of shape (nfields,) + out_dims; does not
+        synchronise.  `out` must not overlap the inputs."""
+        import torch
+        if out is None:
+            out = torch.empty((self.nfields,) + self.out_dims, dtype=torch.float64, device=u.device)
+        _chk(lib().cheb_reduce_apply(self._h, _dev_ptr(u, self.size(0)), None if v is None else _dev_ptr(v, self.size(0)),
+                                     _dev_ptr(out, self.size(1)), _stream()))
+        return out
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            lib().cheb_reduce_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -982,32 +982,75 @@ void points_nodes_host(int n, double *x) {
 // costs one rounding for d_j, one for the quotient and one for the division by the sum.  d_s == 0: the exact unit row; a NaN or
 // infinite coordinate: a row of NaN; |x| > 1 extrapolates by the same formula.  Long double on the DOUBLE node table (the
 // polynomial the device interpolates is the one through the rounded nodes), rounded once.
+// the row of one finite coordinate in long double, before the rounding
+static void points_row_ld(int n, const double *xn, double x, long double *l) {
+  const int N = n - 1;
+  const long double xt = x;
+  int s = 0;
+  long double best = fabsl(xt - (long double)xn[0]);
+  for (int j = 1; j < n; j++) { const long double a = fabsl(xt - (long double)xn[j]); if (a < best) { best = a; s = j; } }
+  const long double ds = xt - (long double)xn[s];
+  if (ds == 0.0L) { for (int j = 0; j < n; j++) l[j] = j == s ? 1.0L : 0.0L; return; }
+  const long double hs = (s == 0 || s == N) ? 0.5L : 1.0L;
+  long double sum = 0.0L;
+  for (int j = 0; j < n; j++) {
+    if (j == s) l[j] = 1.0L;
+    else {
+      const long double hj = (j == 0 || j == N) ? 0.5L : 1.0L;
+      l[j] = (((j - s) & 1) ? -hj : hj) / hs * (ds / (xt - (long double)xn[j]));
+    }
+    sum += l[j];
+  }
+  for (int j = 0; j < n; j++) l[j] = l[j] / sum;
+}
+
 void points_matrix_host(int n, int m, const double *x, double *R) {
   std::vector<double> xn(n);
   points_nodes_host(n, xn.data());
-  const int N = n - 1;
   std::vector<long double> r(n);
   for (int t = 0; t < m; t++) {
     double *row = R + (size_t)t * n;
-    const long double xt = x[t];
     if (!std::isfinite(x[t])) { for (int j = 0; j < n; j++) row[j] = std::numeric_limits<double>::quiet_NaN(); continue; }
-    int s = 0;
-    long double best = fabsl(xt - (long double)xn[0]);
-    for (int j = 1; j < n; j++) { const long double a = fabsl(xt - (long double)xn[j]); if (a < best) { best = a; s = j; } }
-    const long double ds = xt - (long double)xn[s];
-    if (ds == 0.0L) { for (int j = 0; j < n; j++) row[j] = j == s ? 1.0 : 0.0; continue; }
-    const long double hs = (s == 0 || s == N) ? 0.5L : 1.0L;
-    long double sum = 0.0L;
-    for (int j = 0; j < n; j++) {
-      if (j == s) r[j] = 1.0L;
-      else {
-        const long double hj = (j == 0 || j == N) ? 0.5L : 1.0L;
-        r[j] = (((j - s) & 1) ? -hj : hj) / hs * (ds / (xt - (long double)xn[j]));
-      }
-      sum += r[j];
-    }
-    for (int j = 0; j < n; j++) row[j] = (double)(r[j] / sum);
+    points_row_ld(n, xn.data(), x[t], r.data());
+    for (int j = 0; j < n; j++) row[j] = (double)r[j];
   }
+}
+
+// Weight vectors of the partial contractions (cheb_reduce_*, reduce.hip): what one contracted direction of n points is summed
+// against.  INTEGRAL: modal_weights_host; MEAN: half of it (the interval has length 2; the halving is exact); NODE j: the unit
+// vector e_j; DNODE j: row j of D_n; POINT x: the row of points_matrix_host; DPOINT x: r(x)^T D_n, r the long double row on the
+// double node table, the product formed before the one rounding (as G in dealias_matrix_host).  Returns 0, 1 (kind) or 2 (j).
+int reduce_weights_host(int n, int kind, double arg, double *w) {
+  if (kind == REDUCE_W_INTEGRAL) { modal_weights_host(n, w); return 0; }
+  if (kind == REDUCE_W_MEAN) {
+    for (int j = 0; j < n; j++) {
+      long double s = 0.0L;
+      for (int k = 0; k < n; k += 2) s += 2.0L / (1.0L - (long double)k * k) * modal_entry(n, 0, k, j);
+      w[j] = (double)(0.5L * s);
+    }
+    return 0;
+  }
+  if (kind == REDUCE_W_NODE || kind == REDUCE_W_DNODE) {
+    if (!(arg >= 0.0 && arg <= (double)(n - 1)) || arg != (double)(int)arg) return 2;
+    const int i = (int)arg;
+    for (int j = 0; j < n; j++) w[j] = kind == REDUCE_W_NODE ? (j == i ? 1.0 : 0.0) : (double)dentry(i, j, n - 1);
+    return 0;
+  }
+  if (kind == REDUCE_W_POINT) { points_matrix_host(n, 1, &arg, w); return 0; }
+  if (kind == REDUCE_W_DPOINT) {
+    if (!std::isfinite(arg)) { for (int j = 0; j < n; j++) w[j] = std::numeric_limits<double>::quiet_NaN(); return 0; }
+    std::vector<double> xn(n);
+    points_nodes_host(n, xn.data());
+    std::vector<long double> r(n);
+    points_row_ld(n, xn.data(), arg, r.data());
+    for (int k = 0; k < n; k++) {
+      long double s = 0.0L;
+      for (int j = 0; j < n; j++) s += r[j] * dentry(j, k, n - 1);
+      w[k] = (double)s;
+    }
+    return 0;
+  }
+  return 1;
 }
 
 void diffmat_destroy(DiffMat *m) {

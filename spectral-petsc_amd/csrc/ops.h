@@ -1,5 +1,5 @@
 // ops.h -- what the preconditioner module (precond.hip) needs to see of the operator handles, and the plumbing that the
-// handle modules share (chebhip.hip, resample.hip, modal.hip, points.hip, dealias.hip).
+// handle modules share (chebhip.hip, resample.hip, modal.hip, points.hip, dealias.hip, reduce.hip).
 #pragma once
 #include "../../include/chebhip.h"
 #include <hip/hip_runtime.h>

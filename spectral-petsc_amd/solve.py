@@ -408,3 +408,55 @@ def sample_plane(sp, dims, u_full, axis, coord, m=None):
     finally:
         pts.destroy()
     return out.squeeze(axis + 1)
+
+
+def _stacked(dims, u_full):
+    dims = tuple(int(n) for n in dims)
+    size = 1
+    for n in dims:
+        size *= n
+    if u_full.numel() == 0 or u_full.numel() % size:
+        raise ValueError("u_full: %d values are no multiple of prod(dims) = %d" % (u_full.numel(), size))
+    return dims, u_full.numel() // size
+
+
+def profile(sp, dims, u_full, axis):
+    """The mean profile along `axis` of the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields
+    if it holds a multiple of prod(dims) values): the mean over every other direction (one ChebReduce.apply with "mean" weights),
+    a device tensor of shape (nfields, dims[axis])."""
+    dims, nf = _stacked(dims, u_full)
+    axis = int(axis)
+    if not 0 <= axis < len(dims):
+        raise ValueError("axis %d out of range 0..%d" % (axis, len(dims) - 1))
+    if len(dims) == 1:
+        return u_full.reshape(nf, dims[0]).clone()
+    over = [k for k in range(len(dims)) if k != axis]
+    red = sp.ChebReduce(dims, nf, over=over, weights={k: "mean" for k in over})
+    try:
+        out = red.apply(u_full.reshape(-1))
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        red.destroy()
+    return out
+
+
+def face_flux(sp, dims, u_full, axis, side, integrate=True):
+    """The outward normal derivative du/dnu of the full-grid field u_full (layout as profile) on the face x_axis = +1 (side = 0,
+    grid index 0) or x_axis = -1 (side = 1, the last index): one pass over the field with a row of D as the weights of `axis`,
+    + at side 0 and - at side 1 (the convention of HelmholtzSolver's boundary conditions).  integrate = True: its integral over
+    the face, a device tensor of nfields values; False: the face field, shape (nfields, the other directions ...)."""
+    dims, nf = _stacked(dims, u_full)
+    axis, side = int(axis), int(side)
+    if not 0 <= axis < len(dims):
+        raise ValueError("axis %d out of range 0..%d" % (axis, len(dims) - 1))
+    if side not in (0, 1):
+        raise ValueError("side %d: 0 (x = +1) or 1 (x = -1)" % side)
+    w = sp.reduce_weights(dims[axis], "dnode", 0 if side == 0 else dims[axis] - 1)
+    over = list(range(len(dims))) if integrate else [axis]
+    red = sp.ChebReduce(dims, nf, over=over, weights={axis: w if side == 0 else -w})
+    try:
+        out = red.apply(u_full.reshape(-1))
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        red.destroy()
+    return out
