@@ -376,8 +376,28 @@ def allreduce_trampoline(group=None):
     return REDUCE_FN(red)
 
 
-class ChebPlan:
+class _Handle:
+    """Owner of one library handle `_h`; a subclass names its destroy entry point in `_destroy`.  destroy() may be called any number
+    of times, also after a constructor that raised before `_h` was set; a borrowed handle (`_owned` false) is dropped, not destroyed."""
+    _destroy = None
+    _owned = True
+
+    def destroy(self):
+        if getattr(self, "_h", None):
+            if self._owned:
+                getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class ChebPlan(_Handle):
     """y = d/dx_tr x on a row-major tensor of shape dims (MatCreateCheb, chebyshev.c:89-138)."""
+    _destroy = "cheb_plan_destroy"
 
     def __init__(self, dims, tr):
         self.dims = tuple(int(d) for d in dims)
@@ -399,17 +419,6 @@ class ChebPlan:
         y = np.empty_like(x)
         _chk(lib().cheb_apply_host(self._h, _np_dp(x), _np_dp(y)))
         return y
-
-    def destroy(self):
-        if self._h:
-            lib().cheb_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 NODES = {"all": 0, "interior": 1}
@@ -433,9 +442,10 @@ def resample_matrix(n_in, n_out, nodes_in="all", nodes_out="all"):
     return R
 
 
-class Resample:
+class Resample(_Handle):
     """y = (R_0 x ... x R_{d-1}) x: a field on the CGL grid dims_in (node set nodes_in: "all" or "interior") interpolated to the
     grid dims_out (cheb_resample_*); ncomp components innermost.  Sizes: size(0) input values, size(1) output values."""
+    _destroy = "cheb_resample_destroy"
 
     def __init__(self, dims_in, dims_out, nodes_in="all", nodes_out="all", ncomp=1):
         self.dims_in = tuple(int(d) for d in dims_in)
@@ -455,17 +465,6 @@ class Resample:
         """Asynchronous on torch's current stream."""
         _chk(lib().cheb_resample_apply(self._h, _dev_ptr(x, self.size(0)), _dev_ptr(y, self.size(1)), _stream()))
         return y
-
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_resample_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 MODAL = {"forward": 0, "backward": 1}
@@ -523,10 +522,11 @@ def sharp_filter(n, keep):
     return (np.arange(int(n)) < int(keep)).astype(np.float64)
 
 
-class ChebModal:
+class ChebModal(_Handle):
     """The modal side of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_modal_*): values <-> Chebyshev
     coefficients, modal filters, per-direction spectra and Clenshaw-Curtis integrals.  Fields are field-major, row-major over all
     nodes; size() values per array.  Everything is asynchronous on torch's current stream."""
+    _destroy = "cheb_modal_destroy"
 
     def __init__(self, dims, nfields=1):
         self.dims = tuple(int(d) for d in dims)
@@ -583,17 +583,6 @@ class ChebModal:
                                         _dev_ptr(out, self.nfields), _stream()))
         return out
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_modal_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def cgl_nodes(n):
     """The n Chebyshev-Gauss-Lobatto nodes x_j = cos(pi j / (n - 1)) (cheb_nodes_host), x_0 = +1: long double, rounded once; the
@@ -615,11 +604,12 @@ def interp_matrix(n, x):
     return R
 
 
-class ChebPoints:
+class ChebPoints(_Handle):
     """Values of `nfields` stacked full-grid fields on the CGL grid `dims` (field-major, row-major over all nodes, as ChebModal) at
     arbitrary points of [-1, 1]^d (cheb_points_*): scattered points (eval) and tensor grids of arbitrary coordinates (eval_grid:
     plane and line cuts, plotting grids).  Coordinates are device tensors; |x| > 1 extrapolates, a NaN coordinate gives NaN at that
     point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream."""
+    _destroy = "cheb_points_destroy"
 
     def __init__(self, dims, nfields=1):
         self.dims = tuple(int(d) for d in dims)
@@ -694,17 +684,6 @@ class ChebPoints:
                                          _dev_ptr(out, nout) if nout else None, _stream()))
         return out
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_points_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 DEALIAS = {"R": 0, "P": 1, "G": 2}
 
@@ -731,12 +710,13 @@ def dealias_matrix(n, which, m=None):
     return A
 
 
-class ChebDealias:
+class ChebDealias(_Handle):
     """Dealiased products of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_dealias_*; field-major, row-major over
     all nodes, as ChebModal): multiply(u, v) = the truncation to degree dims[k] - 1 per direction of the polynomial product u v,
     advect(vel, c) = that of sum_k vel[k] d_k c.  `fine` is the padded grid (default: the 3/2 rule, dealias_size per direction;
     fine[k] == dims[k] leaves direction k unpadded).  Asynchronous on torch's current stream; advect reserves its work memory on
     first use (synchronous)."""
+    _destroy = "cheb_dealias_destroy"
 
     def __init__(self, dims, nfields=1, fine=None):
         self.dims = tuple(int(d) for d in dims)
@@ -781,17 +761,6 @@ class ChebDealias:
         _chk(lib().cheb_dealias_advect(self._h, _dev_ptr(vel, nv), _dev_ptr(c, self.size()), _dev_ptr(out, self.size()), _stream()))
         return out
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_dealias_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 REDUCE_W = {"integral": 0, "mean": 1, "node": 2, "dnode": 3, "point": 4, "dpoint": 5}
 
@@ -817,12 +786,13 @@ def reduce_weights(n, kind, arg=None):
     return w
 
 
-class ChebReduce:
+class ChebReduce(_Handle):
     """Partial contractions of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_reduce_*; field-major, row-major over
     all nodes, as ChebModal): the directions listed in `over` are summed against one weight vector each, the others are kept --
     out[f][kept indices] = sum prod_k w_k[i_k] u[f][i] (v[f][i]).  Every contracted direction starts with the Clenshaw-Curtis
     weights (a partial integral); `weights` maps a direction to what set_weights takes.  apply is asynchronous on torch's current
     stream, adds in a fixed order (the same input gives the same bits) and uses no vendor GEMM."""
+    _destroy = "cheb_reduce_destroy"
 
     def __init__(self, dims, nfields=1, over=(), weights=None):
         self.dims = tuple(int(d) for d in dims)
@@ -875,17 +845,6 @@ class ChebReduce:
         _chk(lib().cheb_reduce_apply(self._h, _dev_ptr(u, self.size(0)), None if v is None else _dev_ptr(v, self.size(0)),
                                      _dev_ptr(out, self.size(1)), _stream()))
         return out
-
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_reduce_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def helmholtz_line(P):
@@ -946,7 +905,7 @@ def helmholtz_line_bc(P, bc):
     return S, Si, lam, Q, L, Bi
 
 
-class HelmholtzSolver:
+class HelmholtzSolver(_Handle):
     """u = (sigma I + A)^-1 f with A the EllipticOp operator at eta == 1 (zero Dirichlet values) by fast diagonalisation
     (cheb_helmholtz_*): `nfields` stacked interior fields of the grid `dims` per call; `size` values.  Usable as the M of
     Fgmres.solve.
@@ -955,6 +914,7 @@ class HelmholtzSolver:
     (spec at index 0, spec at index n-1); a spec is "dirichlet", "neumann" or (alpha, beta) for alpha u + beta du/dnu = g,
     du/dnu outward.  Such a solver also has solve_full (full-grid output from interior f and boundary data g), full_size,
     boundary_size and singular (sigma = 0 with Neumann everywhere: the constant-like zero mode is dropped)."""
+    _destroy = "cheb_helmholtz_destroy"
 
     def __init__(self, dims, sigma=0.0, nfields=1, bc=None):
         self.dims = tuple(int(d) for d in dims)
@@ -997,21 +957,11 @@ class HelmholtzSolver:
         _chk(lib().cheb_helmholtz_solve_bc(self._h, f.data_ptr(), None if g is None else g.data_ptr(), u.data_ptr(), _stream()))
         return u
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().cheb_helmholtz_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Lap1dPlan:
+class Lap1dPlan(_Handle):
     """y = acc + alpha * D_tr D_tr x on an interior-layout tensor (cheb_plan_create_trimmed /
     cheb_apply_lap1d): one direction of the linear MatMult_Elliptic, usable on slabs and pencils."""
+    _destroy = "cheb_plan_destroy"
 
     def __init__(self, dims, tr):
         self.dims = tuple(int(d) for d in dims)
@@ -1025,17 +975,6 @@ class Lap1dPlan:
         ap = _dev_ptr(acc, self.size) if acc is not None else None
         _chk(lib().cheb_apply_lap1d(self._h, _dev_ptr(x, self.size), ap, alpha, _dev_ptr(y, self.size), _stream()))
         return y
-
-    def destroy(self):
-        if self._h:
-            lib().cheb_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def slab_pack(slab, buf, m0, M1, R, c1):
@@ -1069,8 +1008,9 @@ def _dim0_trampoline(dim0):
     return DIM0_FN(tramp)
 
 
-class EllipticOp:
+class EllipticOp(_Handle):
     """The scalar elliptic MatShell (MatCreate_Elliptic, elliptic.C:250-293)."""
+    _destroy = "ell_op_destroy"
 
     def __init__(self, dims, slab=None, dim0=None, handle=None):
         """slab = (lo, hi): the planes [lo, hi) of grid dimension 0 (ell_op_create_slab); dim0 is then the Python
@@ -1145,24 +1085,13 @@ class EllipticOp:
         assert values.size == self.local_size
         _chk(lib().ell_op_set_state(self._h, which, _np_dp(values)))
 
-    def destroy(self):
-        if self._h:
-            if self._owned:
-                lib().ell_op_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class StokesOp:
+class StokesOp(_Handle):
     """The Stokes MatShells (StokesCreate, stokes.C:257-344) with -boundary 0.
 
     mult <-> StokesMatMult (stokes.C:499-519); mult_vv / mult_pv / mult_vp <-> MatVV / MatPV / MatVP
     (:623-676, :557-566, :599-619); function <-> StokesFunction (:680-758)."""
+    _destroy = "stokes_op_destroy"
 
     def __init__(self, dims, slab=None, dim0=None, handle=None):
         """slab = (lo, hi): the planes [lo, hi) of grid dimension 0 (stokes_op_create_slab); dim0 is then the Python
@@ -1293,18 +1222,6 @@ class StokesOp:
         assert values.size == n
         _chk(lib().stokes_op_set_state(self._h, which, _np_dp(values)))
 
-    def destroy(self):
-        if self._h:
-            if self._owned:
-                lib().stokes_op_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def timers(enable=None, reset=False):
     """Per-stage device timers of the library (chebhip_timers_*): timers(True) switches them on, timers() returns
@@ -1328,11 +1245,12 @@ def timers(enable=None, reset=False):
     return out
 
 
-class FdPc:
+class FdPc(_Handle):
     """The finite-difference preconditioner of the reference on the device: FormJacobian's matrix P
     (elliptic.C:537-590) for an EllipticOp, MatVVPC (stokes.C:1160-1241) on velocity vectors for a StokesOp.
     `apply` is an approximate solve with P (fast diagonalisation + `sweeps` defect corrections); pass the object as
     the `M` of Fgmres.solve."""
+    _destroy = "chebhip_fdpc_destroy"
 
     def __init__(self, op, sweeps=1, handle=None):
         """handle: a slab-mode handle owned by a slab driver (dist.py: DistStokesC.pc / DistEllipticC.pc) -- borrowed."""
@@ -1365,23 +1283,12 @@ class FdPc:
         _chk(lib().chebhip_fdpc_apply_cm(self._h, _dev_ptr(r, self.n), _dev_ptr(z, self.n), _stream()))
         return z
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            if self._owned:
-                lib().chebhip_fdpc_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class SpectralPc:
+class SpectralPc(_Handle):
     """z = (sigma I + A)^-1 (r / eta) for an EllipticOp (ell_pc_create_spectral): the direct solve of the constant-coefficient
     operator after division by the viscosity.  `update` refreshes eta from the operator's last FormFunction; pass the object as
     the `M` of Fgmres.solve."""
+    _destroy = "chebhip_fdpc_destroy"
 
     def __init__(self, op, sigma=0.0):
         h = C.c_void_p()
@@ -1398,22 +1305,12 @@ class SpectralPc:
         _chk(lib().chebhip_fdpc_apply(self._h, _dev_ptr(r, self.n), _dev_ptr(z, self.n), _stream()))
         return z
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().chebhip_fdpc_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class StokesSaddlePc:
+class StokesSaddlePc(_Handle):
     """StokesPCApply0..3 (stokes.C:1714-1817) on the device: block LU / upper / diagonal / lower preconditioners of the
     saddle-point system, with the inner solves KSPVelocity, KSPSchur, KSPSchurVelocity (stokes.C:328-341).
     Pass the object as the `M` of Fgmres.solve around StokesOp.mult."""
+    _destroy = "stokes_saddle_destroy"
 
     def __init__(self, op, saddle_type=0, vel=(4, 1e-5), schur=(3, 1e-5), svel=(0, 1e-5), pc_sweeps=0, schur_jacobi=True, slab=None):
         """schur_jacobi: KSPSchur's PCJACOBI with 1/eta on the diagonal (stokes.C:330-331, 538-553); False = -schur_pc_type none.
@@ -1445,24 +1342,14 @@ class StokesSaddlePc:
 
     inner_iterations = property(lambda self: (lib().stokes_saddle_iterations(self._h, 0), lib().stokes_saddle_iterations(self._h, 1)))
 
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().stokes_saddle_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Fgmres:
+class Fgmres(_Handle):
     """Restarted flexible GMRES on device vectors (KSPFGMRES's role, elliptic.C:181-185).
 
     `A` and the optional right preconditioner `M` are operator objects of this module (EllipticOp,
     StokesOp): their C entry points are handed to the solver directly, no Python in the loop.
     """
+    _destroy = "chebhip_fgmres_destroy"
 
     def __init__(self, n, restart=30, rtol=1e-5, atol=1e-50, max_it=10000):
         self.n = int(n)
@@ -1523,14 +1410,3 @@ class Fgmres:
     iterations = property(lambda self: lib().chebhip_fgmres_iterations(self._h))
     residual = property(lambda self: lib().chebhip_fgmres_residual(self._h))
     reason = property(lambda self: lib().chebhip_fgmres_reason(self._h))
-
-    def destroy(self):
-        if getattr(self, "_h", None):
-            lib().chebhip_fgmres_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass

@@ -22,24 +22,13 @@ using namespace chebhip;
 // error plumbing
 // ---------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  g_err = buf;
-  return code;
-}
-// shared with stokes.hip
+// declared in ops.h: every module reports through it
 int chebhip_fail(int code, const char *fmt, ...) {
   char buf[512];
   va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
   g_err = buf;
   return code;
 }
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 extern "C" const char *chebhip_last_error(void) { return g_err.c_str(); }
 extern "C" int chebhip_version(void) { return 100; }
@@ -50,18 +39,18 @@ extern "C" long chebhip_launch_count(void) { return sweep_launch_count(); }
 // run-time options (include/chebhip.h; registry in options.cpp): the only switches of the library; the environment is never read
 // ---------------------------------------------------------------------------------------------
 extern "C" int chebhip_set_option(const char *name, int value) {
-  if (!name) return fail(CHEBHIP_ERR_ARG, "NULL option name");
+  if (!name) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL option name");
   if (!strcmp(name, "no_rocblas")) { opt_set(OPT_VENDOR_GEMM, value ? 0 : 1); return 0; }   // deprecated name (rounds 1-3), inverted meaning
   const int id = opt_find(name);
-  if (id < 0) return fail(CHEBHIP_ERR_ARG, "unknown option '%s'", name);
+  if (id < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "unknown option '%s'", name);
   opt_set(id, value);
   return 0;
 }
 extern "C" int chebhip_get_option(const char *name, int *value) {
-  if (!name || !value) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!name || !value) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   if (!strcmp(name, "no_rocblas")) { *value = opt(OPT_VENDOR_GEMM) ? 0 : 1; return 0; }
   const int id = opt_find(name);
-  if (id < 0) return fail(CHEBHIP_ERR_ARG, "unknown option '%s'", name);
+  if (id < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "unknown option '%s'", name);
   *value = opt(id);
   return 0;
 }
@@ -115,7 +104,7 @@ extern "C" int chebhip_timers_reset(void) {
   return 0;
 }
 extern "C" int chebhip_timers_read(int stage, double *total_ms, long *calls) {
-  if (stage < 0 || stage >= CHEBHIP_NSTAGES || !total_ms || !calls) return fail(CHEBHIP_ERR_ARG, "stage %d out of range", stage);
+  if (stage < 0 || stage >= CHEBHIP_NSTAGES || !total_ms || !calls) return chebhip_fail(CHEBHIP_ERR_ARG, "stage %d out of range", stage);
   std::lock_guard<std::mutex> lk(g_tm_mu);
   tm_drain_locked();
   *total_ms = g_tm_ms[stage]; *calls = g_tm_calls[stage];
@@ -137,37 +126,37 @@ struct cheb_plan {
 };
 
 static int check_geom(int rank, int tr, const int *dims, long *N, unsigned *inner, bool allow_long = false) {
-  if (!dims || rank < 1 || rank > 16) return fail(CHEBHIP_ERR_DIMS, "rank = %d must be in 1..16", rank);
-  if (!(0 <= tr && tr < rank)) return fail(CHEBHIP_ERR_TDIM, "tdim out of range");              // chebyshev.c:106
+  if (!dims || rank < 1 || rank > 16) return chebhip_fail(CHEBHIP_ERR_DIMS, "rank = %d must be in 1..16", rank);
+  if (!(0 <= tr && tr < rank)) return chebhip_fail(CHEBHIP_ERR_TDIM, "tdim out of range");              // chebyshev.c:106
   long n = 1, in = 1;
   for (int r = 0; r < rank; r++) {
-    if (dims[r] < 1) return fail(CHEBHIP_ERR_DIMS, "dims[%d] = %d must be >= 1", r, dims[r]);
+    if (dims[r] < 1) return chebhip_fail(CHEBHIP_ERR_DIMS, "dims[%d] = %d must be >= 1", r, dims[r]);
     n *= dims[r];
     if (r > tr) in *= dims[r];
-    if (n > 0x7fffffffL) return fail(CHEBHIP_ERR_DIMS, "tensor of more than 2^31-1 points");
+    if (n > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "tensor of more than 2^31-1 points");
   }
-  if (n < 2 || dims[tr] < 2) return fail(CHEBHIP_ERR_SIZE, "n = %ld but must be >= 2", n);       // chebyshev.c:18,98
+  if (n < 2 || dims[tr] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %ld but must be >= 2", n);       // chebyshev.c:18,98
   if (dims[tr] > 256 && !allow_long)
-    return fail(CHEBHIP_ERR_ARG, "dims[tr] = %d: the interior-layout (slab) plans support <= 256 points per line", dims[tr]);
-  if (dims[tr] > 4096) return fail(CHEBHIP_ERR_ARG, "dims[tr] = %d: at most 4096 points per line", dims[tr]);
+    return chebhip_fail(CHEBHIP_ERR_ARG, "dims[tr] = %d: the interior-layout (slab) plans support <= 256 points per line", dims[tr]);
+  if (dims[tr] > 4096) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[tr] = %d: at most 4096 points per line", dims[tr]);
   *N = n; *inner = (unsigned)in;
   return 0;
 }
 
 extern "C" int cheb_plan_create(int rank, int tr, const int *dims, cheb_plan **out) {
-  if (!out) return fail(CHEBHIP_ERR_ARG, "out is NULL");
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   long N; unsigned inner;
   int rc = check_geom(rank, tr, dims, &N, &inner, true);
   if (rc) return rc;
   if ((rc = require_device())) return rc;
   cheb_plan *p = new (std::nothrow) cheb_plan;
-  if (!p) return fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  if (!p) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   p->rank = rank; p->tr = tr; p->dims.assign(dims, dims + rank);
   p->N = N; p->inner = inner; p->ncols = (unsigned)(N / dims[tr]);
   hipError_t e = hipSuccess;
   e = diffmat_create(dims[tr], &p->mat);          // > 256 points: dense matrix for cheb_sweep_long_kernel
-  if (e != hipSuccess) { delete p; return fail(CHEBHIP_ERR_DEVICE, "plan matrices: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { delete p; return chebhip_fail(CHEBHIP_ERR_DEVICE, "plan matrices: %s", hipGetErrorString(e)); }
   *out = p;
   return 0;
 }
@@ -178,24 +167,24 @@ extern "C" long cheb_plan_size(const cheb_plan *p) { return p ? p->N : -1; }
 // (dims[tr] = P-2 stored points, the two end points are implicit zeros): the layout of the
 // reference's global vectors (SetupBC, elliptic.C:372-434) and of any slab or pencil cut from them.
 extern "C" int cheb_plan_create_trimmed(int rank, int tr, const int *dims, cheb_plan **out) {
-  if (!out) return fail(CHEBHIP_ERR_ARG, "out is NULL");
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || rank < 1 || rank > 16) return fail(CHEBHIP_ERR_DIMS, "rank = %d must be in 1..16", rank);
-  if (!(0 <= tr && tr < rank)) return fail(CHEBHIP_ERR_TDIM, "tdim out of range");
+  if (!dims || rank < 1 || rank > 16) return chebhip_fail(CHEBHIP_ERR_DIMS, "rank = %d must be in 1..16", rank);
+  if (!(0 <= tr && tr < rank)) return chebhip_fail(CHEBHIP_ERR_TDIM, "tdim out of range");
   std::vector<int> full(dims, dims + rank);
-  if (dims[tr] < 1) return fail(CHEBHIP_ERR_SIZE, "dims[tr] = %d stored points but must be >= 1", dims[tr]);
+  if (dims[tr] < 1) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[tr] = %d stored points but must be >= 1", dims[tr]);
   full[tr] = dims[tr] + 2;
   long N; unsigned inner;
   int rc = check_geom(rank, tr, full.data(), &N, &inner);
   if (rc) return rc;
   if ((rc = require_device())) return rc;
   cheb_plan *p = new (std::nothrow) cheb_plan;
-  if (!p) return fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  if (!p) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   p->rank = rank; p->tr = tr; p->dims.assign(dims, dims + rank); p->trimmed = true;
   p->N = N / full[tr] * dims[tr]; p->inner = inner; p->ncols = (unsigned)(N / full[tr]);
   hipError_t e = diffmat_create(full[tr], &p->mat);
   if (e == hipSuccess) e = diffmat_create_lap(full[tr], &p->lap);
-  if (e != hipSuccess) { diffmat_destroy(&p->mat); delete p; return fail(CHEBHIP_ERR_DEVICE, "diffmat_create: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { diffmat_destroy(&p->mat); delete p; return chebhip_fail(CHEBHIP_ERR_DEVICE, "diffmat_create: %s", hipGetErrorString(e)); }
   *out = p;
   return 0;
 }
@@ -205,15 +194,15 @@ extern "C" int cheb_plan_create_trimmed(int rank, int tr, const int *dims, cheb_
 // acc may be NULL (treated as 0) and may alias y.
 extern "C" int cheb_apply_lap1d(cheb_plan *p, const double *x, const double *acc, double alpha,
                                 double *y, void *stream) {
-  if (!p || !x || !y) return fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (!p->trimmed) return fail(CHEBHIP_ERR_ARG, "cheb_apply_lap1d needs a plan from cheb_plan_create_trimmed");
-  if (x == y) return fail(CHEBHIP_ERR_ARG, "x and y must be distinct");
+  if (!p || !x || !y) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!p->trimmed) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_apply_lap1d needs a plan from cheb_plan_create_trimmed");
+  if (x == y) return chebhip_fail(CHEBHIP_ERR_ARG, "x and y must be distinct");
   SweepParams sp = {};
   sp.ncols = p->ncols; sp.inner = p->inner;
   sp.in0 = x; sp.in_mode = IN_PLAIN;
   sp.alpha = alpha; sp.out = y;
   if (acc) { sp.out_mode = OUT_ACC; sp.acc = acc; } else sp.out_mode = OUT_STORE;
-  HIPCHK(sweep_launch(p->lap, sp, (hipStream_t)stream));
+  HIP_TRY(sweep_launch(p->lap, sp, (hipStream_t)stream));
   return 0;
 }
 
@@ -226,7 +215,7 @@ int lap1d_gather_try(cheb_plan *p, const GatherSrc &g, double alpha, double *y, 
   SweepParams sp = {};
   sp.ncols = p->ncols; sp.inner = p->inner;
   sp.in_mode = IN_PLAIN; sp.alpha = alpha; sp.out = y; sp.out_mode = OUT_STORE;
-  HIPCHK(sweep_launch_gather(p->lap, sp, g, st, done));
+  HIP_TRY(sweep_launch_gather(p->lap, sp, g, st, done));
   return 0;
 }
 }  // namespace chebhip
@@ -247,7 +236,7 @@ int lap1d_multi_gather_try(int n, cheb_plan *const *plans, const double *x, doub
   sp[n] = SweepParams{};
   sp[n].ncols = gp->ncols; sp[n].inner = gp->inner; sp[n].in_mode = IN_PLAIN; sp[n].alpha = alpha; sp[n].out = gout; sp[n].out_mode = OUT_STORE;
   m[n] = &gp->lap;
-  HIPCHK(sweep_launch_multi_gather_try(n + 1, m, sp, 1u << n, g, st, done));
+  HIP_TRY(sweep_launch_multi_gather_try(n + 1, m, sp, 1u << n, g, st, done));
   return 0;
 }
 }  // namespace chebhip
@@ -266,32 +255,32 @@ int lap1d_multi_try(int n, cheb_plan *const *plans, const double *x, double *con
     sp[k].in0 = x; sp[k].in_mode = IN_PLAIN; sp[k].alpha = alpha; sp[k].out = outs[k]; sp[k].out_mode = OUT_STORE;
     m[k] = &plans[k]->lap;
   }
-  HIPCHK(sweep_launch_multi_try(n, m, sp, st, done));
+  HIP_TRY(sweep_launch_multi_try(n, m, sp, st, done));
   return 0;
 }
 }  // namespace chebhip
 
 extern "C" int cheb_apply(cheb_plan *p, const double *x, double *y, void *stream) {
-  if (!p || !x || !y) return fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (x == y) return fail(CHEBHIP_ERR_ARG, "x and y must be distinct (as every ChebMult call site)");
-  if (p->trimmed) return fail(CHEBHIP_ERR_ARG, "plan is trimmed: use cheb_apply_lap1d");
+  if (!p || !x || !y) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (x == y) return chebhip_fail(CHEBHIP_ERR_ARG, "x and y must be distinct (as every ChebMult call site)");
+  if (p->trimmed) return chebhip_fail(CHEBHIP_ERR_ARG, "plan is trimmed: use cheb_apply_lap1d");
   StageTimer tm(CHEBHIP_STAGE_CHEB_APPLY, stream);
   SweepParams sp = {};
   sp.ncols = p->ncols; sp.inner = p->inner;
   sp.in0 = x; sp.out = y; sp.alpha = 1.0;
   sp.in_mode = IN_PLAIN; sp.out_mode = OUT_STORE;
-  HIPCHK(sweep_launch(p->mat, sp, (hipStream_t)stream));
+  HIP_TRY(sweep_launch(p->mat, sp, (hipStream_t)stream));
   return 0;
 }
 
 extern "C" int cheb_apply_host(cheb_plan *p, const double *x, double *y) {
-  if (!p || !x || !y) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!p || !x || !y) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   const size_t bytes = (size_t)p->N * sizeof(double);
-  if (!p->hx) { HIPCHK(hipMalloc((void **)&p->hx, bytes)); HIPCHK(hipMalloc((void **)&p->hy, bytes)); }
-  HIPCHK(hipMemcpy(p->hx, x, bytes, hipMemcpyHostToDevice));
+  if (!p->hx) { HIP_TRY(hipMalloc((void **)&p->hx, bytes)); HIP_TRY(hipMalloc((void **)&p->hy, bytes)); }
+  HIP_TRY(hipMemcpy(p->hx, x, bytes, hipMemcpyHostToDevice));
   int rc = cheb_apply(p, p->hx, p->hy, nullptr);
   if (rc) return rc;
-  HIPCHK(hipMemcpy(y, p->hy, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(y, p->hy, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -339,36 +328,36 @@ __global__ void k_slab_unpack_add(SlabSplit sp, long m0, long M1, long R, const 
 }
 
 static int slab_split(int G, const long *c1, long M1, SlabSplit *sp) {
-  if (G < 1 || G > 64 || !c1) return fail(CHEBHIP_ERR_ARG, "G = %d must be in 1..64", G);
+  if (G < 1 || G > 64 || !c1) return chebhip_fail(CHEBHIP_ERR_ARG, "G = %d must be in 1..64", G);
   sp->G = G;
   for (int s = 0; s <= G; s++) {
     sp->c1[s] = c1[s];
-    if (c1[s] < 0 || c1[s] > M1 || (s > 0 && c1[s] < c1[s - 1])) return fail(CHEBHIP_ERR_ARG, "column splits must be non-decreasing in 0..M1");
+    if (c1[s] < 0 || c1[s] > M1 || (s > 0 && c1[s] < c1[s - 1])) return chebhip_fail(CHEBHIP_ERR_ARG, "column splits must be non-decreasing in 0..M1");
   }
-  if (c1[0] != 0 || c1[G] != M1) return fail(CHEBHIP_ERR_ARG, "column splits must cover 0..M1");
+  if (c1[0] != 0 || c1[G] != M1) return chebhip_fail(CHEBHIP_ERR_ARG, "column splits must cover 0..M1");
   return 0;
 }
 
 extern "C" int cheb_slab_pack(long m0, long M1, long R, int G, const long *c1, const double *slab, double *buf, void *stream) {
-  if (!slab || !buf || m0 < 0 || M1 < 0 || R < 1) return fail(CHEBHIP_ERR_ARG, "bad argument");
+  if (!slab || !buf || m0 < 0 || M1 < 0 || R < 1) return chebhip_fail(CHEBHIP_ERR_ARG, "bad argument");
   SlabSplit sp; int rc = slab_split(G, c1, M1, &sp); if (rc) return rc;
   const long n = m0 * M1 * R;
   if (n == 0) return 0;
   long g = (n + 255) / 256; if (g > 4096) g = 4096;
   hipLaunchKernelGGL(k_slab_pack, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sp, m0, M1, R, slab, buf);
-  HIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 extern "C" int cheb_slab_unpack_add(long m0, long M1, long R, int G, const long *c1, const double *buf, const double *acc,
                                     double alpha, double *out, void *stream) {
-  if (!buf || !out || m0 < 0 || M1 < 0 || R < 1) return fail(CHEBHIP_ERR_ARG, "bad argument");
+  if (!buf || !out || m0 < 0 || M1 < 0 || R < 1) return chebhip_fail(CHEBHIP_ERR_ARG, "bad argument");
   SlabSplit sp; int rc = slab_split(G, c1, M1, &sp); if (rc) return rc;
   const long n = m0 * M1 * R;
   if (n == 0) return 0;
   long g = (n + 255) / 256; if (g > 4096) g = 4096;
   hipLaunchKernelGGL(k_slab_unpack_add, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sp, m0, M1, R, buf, acc, alpha, out);
-  HIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -495,20 +484,15 @@ __global__ void k_cprod_sq(long N, const double *__restrict__ w0, double gamma, 
   }
 }
 
-static inline unsigned pw_grid(long N) { long g = (N + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g)); }
-
 // ---------------------------------------------------------------------------------------------
 // operator level: MatElliptic (elliptic.C:78-86)
 // ---------------------------------------------------------------------------------------------
 enum CoeffMode { COEFF_UNIT = 0, COEFF_FULL = 1 };
 
-struct ell_op {
-  int d = 0;
-  std::vector<int> dims;
-  long N = 0, G = 0;
+struct ell_op : BoxGrid {                // d, dims, N, gP0, lo: the handle's box (slab mode: see `slab` below)
+  long G = 0;                           // interior nodes
   std::map<int, DiffMat> mats;          // one matrix per distinct extent
   std::map<int, DiffMat> laps;          // interior (D D) per distinct extent: the constant-coefficient path
-  std::vector<unsigned> inner, ncols;   // per direction
   std::vector<unsigned> inner_g, ncols_g; // per direction, in the interior (global-vector) layout
   std::vector<int *> gcol;              // per direction: device [ncols_k]
   std::vector<long> gstride;            // per direction, in the global (interior) layout
@@ -523,7 +507,6 @@ struct ell_op {
   // slab mode (multi-GPU): the handle owns the planes [lo, lo + dims[0]) of a grid whose dimension 0 has
   // gP0 points; sweeps along dimension 0 go through `dim0` (transposes + pencil sweep in the driver)
   bool slab = false;
-  int gP0 = 0, lo = 0;
   ell_dim0_fn dim0 = nullptr;
   void *dim0_ctx = nullptr;
   bool has_long = false;                // some extent > 256: every sweep goes through the unfused path (cheb_sweep_long_kernel)
@@ -552,47 +535,47 @@ static int ell_alloc_state(ell_op *op) {
   // that allocates waits for them (once per handle).  Without this the clear of w0 / gradu could land AFTER the first
   // kernels of the caller's stream had written them (seen with thread ranks, each on a stream of its own).
   const bool fresh = !op->w0 || !op->eta || op->gradu.empty();
-  if (!op->w0) { HIPCHK(hipMalloc((void **)&op->w0_alloc, sbytes)); HIPCHK(hipMemset(op->w0_alloc, 0, sbytes)); op->w0 = op->w0_alloc; op->w0_shift = 0; }   // boundary nodes read as zero until a pass writes them
+  if (!op->w0) { HIP_TRY(hipMalloc((void **)&op->w0_alloc, sbytes)); HIP_TRY(hipMemset(op->w0_alloc, 0, sbytes)); op->w0 = op->w0_alloc; op->w0_shift = 0; }   // boundary nodes read as zero until a pass writes them
   if (!op->eta) {
-    HIPCHK(hipMalloc((void **)&op->eta, bytes));
-    HIPCHK(hipMalloc((void **)&op->deta, bytes));
-    hipLaunchKernelGGL(k_fill, dim3(pw_grid(op->N)), dim3(256), 0, nullptr, op->N, 1.0, op->eta);   // VecSet(eta,1) elliptic.C:265
-    HIPCHK(hipMemset(op->deta, 0, bytes));                                                           // VecSet(deta,0) :266
+    HIP_TRY(hipMalloc((void **)&op->eta, bytes));
+    HIP_TRY(hipMalloc((void **)&op->deta, bytes));
+    hipLaunchKernelGGL(k_fill, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, nullptr, op->N, 1.0, op->eta);   // VecSet(eta,1) elliptic.C:265
+    HIP_TRY(hipMemset(op->deta, 0, bytes));                                                           // VecSet(deta,0) :266
   }
   if (op->gradu.empty()) {
     op->gradu.assign(op->d, nullptr); op->cprod.assign(op->d, nullptr); op->gradu_alloc.assign(op->d, nullptr); op->g_shift.assign(op->d, 0); op->cprod_alloc.assign(op->d, nullptr);
     for (int k = 0; k < op->d; k++) {
-      HIPCHK(hipMalloc((void **)&op->gradu_alloc[k], sbytes));
-      HIPCHK(hipMemset(op->gradu_alloc[k], 0, sbytes));
+      HIP_TRY(hipMalloc((void **)&op->gradu_alloc[k], sbytes));
+      HIP_TRY(hipMemset(op->gradu_alloc[k], 0, sbytes));
       op->gradu[k] = op->gradu_alloc[k];
-      HIPCHK(hipMalloc((void **)&op->cprod_alloc[k], 2 * sbytes));
+      HIP_TRY(hipMalloc((void **)&op->cprod_alloc[k], 2 * sbytes));
       op->cprod[k] = op->cprod_alloc[k] + 2 * (k < op->d - 1 ? 15 : 0);   // the pairs of local column 1 on a 128-byte boundary for the strided directions (see w0_alloc): Jacobian apply 502 -> 495 us
     }
     op->cdirty = true;
   }
-  if (fresh) HIPCHK(hipStreamSynchronize(nullptr));
+  if (fresh) HIP_TRY(hipStreamSynchronize(nullptr));
   return 0;
 }
 
 // eta / deta as the reference would hold them after the last FormFunction (elliptic.C:508-509), for whoever reads the arrays
 static int ell_sync_coeffs(ell_op *op, hipStream_t st) {
   if (!op->coef_stale) return 0;
-  hipLaunchKernelGGL(k_coeff_sq, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->w0, op->coef_gamma, op->eta, op->deta);
-  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_coeff_sq, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->w0, op->coef_gamma, op->eta, op->deta);
+  HIP_TRY(hipGetLastError());
   op->coef_stale = false;
   return 0;
 }
 int ell_op_sync_coeffs(ell_op *op, void *stream) { return op ? ell_sync_coeffs(op, (hipStream_t)stream) : 0; }   // precond.hip, before it reads the view
 
 int ell_op_fd_view(ell_op *op, chebhip::FdView *v) {
-  if (!op || !v) return fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (op->slab) return fail(CHEBHIP_ERR_ARG, "slab-mode handle: the preconditioner comes from chebhip_dist_ell_pc");
+  if (!op || !v) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (op->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "slab-mode handle: the preconditioner comes from chebhip_dist_ell_pc");
   return ell_op_fd_view_any(op, v, nullptr);
 }
 int ell_op_fd_view_any(ell_op *op, chebhip::FdView *v, int *gP0) {
-  if (!op || !v) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !v) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   if (gP0) *gP0 = op->gP0;
-  if (op->d > 10) return fail(CHEBHIP_ERR_DIMS, "d > 10");
+  if (op->d > 10) return chebhip_fail(CHEBHIP_ERR_DIMS, "d > 10");
   int rc = ell_alloc_state(op); if (rc) return rc;
   v->d = op->d; v->dims = op->dims.data(); v->N = op->N; v->G = op->G; v->ixL = op->ixL;
   v->eta = op->eta; v->deta = op->deta;
@@ -600,87 +583,61 @@ int ell_op_fd_view_any(ell_op *op, chebhip::FdView *v, int *gP0) {
   return 0;
 }
 
-static inline bool ell_is_bdy(const ell_op *op, const int *ind) {
-  const int g0 = ind[0] + op->lo;
-  if (g0 == 0 || g0 == op->gP0 - 1) return true;
-  for (int j = 1; j < op->d; j++) if (ind[j] == 0 || ind[j] == op->dims[j] - 1) return true;
-  return false;
-}
-
 static int ell_create(int d, const int *gdims, int lo, int hi, ell_dim0_fn dim0, void *dim0_ctx, ell_op **out) {
-  if (!out) return fail(CHEBHIP_ERR_ARG, "out is NULL");
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   const bool slab = dim0 != nullptr;
-  if (slab && (!gdims || d < 2)) return fail(CHEBHIP_ERR_DIMS, "slab mode needs d >= 2");
-  std::vector<int> dimv;
-  if (gdims && d >= 1 && d <= 10) {
-    dimv.assign(gdims, gdims + d);
-    if (slab) {
-      if (!(0 <= lo && lo < hi && hi <= gdims[0])) return fail(CHEBHIP_ERR_ARG, "slab planes [%d, %d) outside 0..%d", lo, hi, gdims[0]);
-      if (gdims[0] < 3) return fail(CHEBHIP_ERR_SIZE, "slab mode needs dims[0] >= 3");
-      dimv[0] = hi - lo;
-    } else lo = 0;
+  if (slab && (!gdims || d < 2)) return chebhip_fail(CHEBHIP_ERR_DIMS, "slab mode needs d >= 2");
+  if (slab && d <= 10) {
+    int rc = BoxGrid::check_slab(lo, hi, gdims[0]);
+    if (rc) return rc;
+    if (gdims[0] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "slab mode needs dims[0] >= 3");
   }
-  const int *dims = dimv.empty() ? gdims : dimv.data();
-  if (!dims || d < 1 || d > 10) return fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10 (elliptic.C:137)", d);
-  long N = 1, G = 1;
-  for (int k = 0; k < d; k++) {
+  if (!gdims || d < 1 || d > 10) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10 (elliptic.C:137)", d);
+  for (int k = 0; k < d; k++) {                         // every direction a valid line of a tensor of at most 2^31-1 points
     long nk; unsigned ik;
     int rc = check_geom(d, k, gdims, &nk, &ik, true);
     if (rc) return rc;
-    N *= dims[k];
-    if (!(slab && k == 0)) G *= (dims[k] > 2 ? dims[k] - 2 : 0);
-  }
-  long nint0 = 0;                                       // interior planes of dimension 0 owned by this handle
-  if (slab) {
-    for (int i = lo; i < hi; i++) if (i > 0 && i < gdims[0] - 1) nint0++;
-    G *= nint0;
-    if (N > 0x7fffffffL) return fail(CHEBHIP_ERR_DIMS, "tensor of more than 2^31-1 points");
   }
   int rc = require_device();
   if (rc) return rc;
   ell_op *op = new (std::nothrow) ell_op;
-  if (!op) return fail(CHEBHIP_ERR_MEMORY, "out of host memory");
-  op->d = d; op->dims.assign(dims, dims + d); op->N = N; op->G = G;
-  op->slab = slab; op->gP0 = gdims[0]; op->lo = lo; op->dim0 = dim0; op->dim0_ctx = dim0_ctx;
+  if (!op) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  if (!slab) { lo = 0; hi = gdims[0]; }
+  op->set_box(d, gdims, lo, hi);
+  const std::vector<int> &dims = op->dims;
+  const long N = op->N;
+  op->slab = slab; op->dim0 = dim0; op->dim0_ctx = dim0_ctx;
   // from here on failures go through ell_op_destroy
-#define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ell_op_destroy(op); \
-    return fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
   for (int k = 0; k < d; k++) {      // dimension 0: the global extent (in slab mode it is applied on pencils)
     const int Pk = (k == 0) ? gdims[0] : dims[k];
     if (!op->mats.count(Pk)) {
-      DiffMat m; OPCHK(diffmat_create(Pk, &m)); op->mats[Pk] = m;
+      DiffMat m; HIP_TRY_OR(diffmat_create(Pk, &m), ell_op_destroy(op)); op->mats[Pk] = m;
       if (m.KS == 0) op->has_long = true;
-      else if (Pk > 2 && !slab) { DiffMat l; OPCHK(diffmat_create_lap(Pk, &l)); op->laps[Pk] = l; }
+      else if (Pk > 2 && !slab) { DiffMat l; HIP_TRY_OR(diffmat_create_lap(Pk, &l), ell_op_destroy(op)); op->laps[Pk] = l; }
     }
   }
   // SetupBC (elliptic.C:372-434): ixL in BlockIt order; interior strides of the global vector
   std::vector<long> gs(d, 1);
   for (int k = d - 2; k >= 0; k--) gs[k] = gs[k + 1] * (dims[k + 1] - 2);    // dims[k+1], k+1 >= 1: never the split dimension
   {
-    std::vector<int> ixL((size_t)N);
-    std::vector<int> ind(d, 0);
-    long g = 0;
-    for (long l = 0; l < N; l++) {
-      ixL[l] = ell_is_bdy(op, ind.data()) ? -1 : (int)g++;
-      for (int j = d - 1; j >= 0; j--) { if (++ind[j] < dims[j]) break; ind[j] = 0; }
-    }
-    OPCHK(hipMalloc((void **)&op->ixL, (size_t)N * sizeof(int)));
-    OPCHK(hipMemcpy(op->ixL, ixL.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    std::vector<int> ixL;
+    op->G = op->interior_index(ixL);
+    HIP_TRY_OR(hipMalloc((void **)&op->ixL, (size_t)N * sizeof(int)), ell_op_destroy(op));
+    HIP_TRY_OR(hipMemcpy(op->ixL, ixL.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice), ell_op_destroy(op));
   }
-  op->inner.resize(d); op->ncols.resize(d); op->gcol.assign(d, nullptr); op->gstride = gs;
+  const long G = op->G;
+  op->gcol.assign(d, nullptr); op->gstride = gs;
   op->inner_g.resize(d); op->ncols_g.resize(d);
   for (int k = 0; k < d; k++) {
     op->inner_g[k] = (unsigned)gs[k];
     op->ncols_g[k] = (dims[k] > 2 && !slab) ? (unsigned)(G / (dims[k] - 2)) : 0u;
   }
   for (int k = 0; k < d; k++) {
-    unsigned in = 1; for (int r = k + 1; r < d; r++) in *= dims[r];
-    op->inner[k] = in; op->ncols[k] = (unsigned)(N / dims[k]);
     // line c of direction k <-> multi-index over the other dims (row-major, dim k removed)
-    std::vector<int> tab(op->ncols[k]);
+    std::vector<int> tab(op->ncols(k));
     std::vector<int> ind(d, 0);
-    for (unsigned c = 0; c < op->ncols[k]; c++) {
+    for (unsigned c = 0; c < op->ncols(k); c++) {
       bool interior = true; long gi = 0;
       const int off0 = (lo == 0) ? 1 : 0;               // local plane of the first interior plane of this handle
       for (int r = 0; r < d; r++) {
@@ -692,11 +649,11 @@ static int ell_create(int d, const int *gdims, int lo, int hi, ell_dim0_fn dim0,
       tab[c] = (interior && dims[k] > 2 && !(slab && k == 0)) ? (int)gi : -1;
       for (int r = d - 1; r >= 0; r--) { if (r == k) continue; if (++ind[r] < dims[r]) break; ind[r] = 0; }
     }
-    OPCHK(hipMalloc((void **)&op->gcol[k], tab.size() * sizeof(int)));
-    OPCHK(hipMemcpy(op->gcol[k], tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY_OR(hipMalloc((void **)&op->gcol[k], tab.size() * sizeof(int)), ell_op_destroy(op));
+    HIP_TRY_OR(hipMemcpy(op->gcol[k], tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice), ell_op_destroy(op));
   }
   op->g.assign(d, nullptr);
-  for (int k = 0; k < d; k++) OPCHK(hipMalloc((void **)&op->g[k], (size_t)N * sizeof(double)));
+  for (int k = 0; k < d; k++) HIP_TRY_OR(hipMalloc((void **)&op->g[k], (size_t)N * sizeof(double)), ell_op_destroy(op));
   size_t wsize = (size_t)N;
   if (!slab && !op->has_long && (d == 2 || d == 3)) {
     // padded accumulator of the constant-coefficient path (ell_op_mult): needs the 16-byte kernel's v3
@@ -710,9 +667,8 @@ static int ell_create(int d, const int *gdims, int lo, int hi, ell_dim0_fn dim0,
       if (need > wsize) wsize = need;
     }
   }
-  OPCHK(hipMalloc((void **)&op->W, wsize * sizeof(double)));
+  HIP_TRY_OR(hipMalloc((void **)&op->W, wsize * sizeof(double)), ell_op_destroy(op));
   op->wsize = wsize;
-#undef OPCHK
   *out = op;
   return 0;
 }
@@ -722,18 +678,18 @@ extern "C" int ell_op_create(int d, const int *dims, ell_op **out) { return ell_
 // Slab of the planes [lo, hi) of grid dimension 0 (multi-GPU): vectors are the serial ones restricted to
 // the slab (contiguous pieces, dimension 0 being outermost); sweeps along dimension 0 are delegated to `dim0`.
 extern "C" int ell_op_create_slab(int d, const int *dims, int lo, int hi, ell_dim0_fn dim0, void *dim0_ctx, ell_op **out) {
-  if (!dim0) return fail(CHEBHIP_ERR_ARG, "slab mode needs the dimension-0 callback");
+  if (!dim0) return chebhip_fail(CHEBHIP_ERR_ARG, "slab mode needs the dimension-0 callback");
   return ell_create(d, dims, lo, hi, dim0, dim0_ctx, out);
 }
 
 // Pencil side of the slab mode: out = D_0 in on an array (dims[0], ncol), lines along dimension 0 with stride ncol
 extern "C" int ell_op_pencil_sweep(ell_op *op, long ncol, const double *in, double *out, void *stream) {
-  if (!op || !in || !out || ncol < 0) return fail(CHEBHIP_ERR_ARG, "bad argument");
+  if (!op || !in || !out || ncol < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "bad argument");
   if (ncol == 0) return 0;
   SweepParams sp = {};
   sp.ncols = (unsigned)ncol; sp.inner = (unsigned)ncol;
   sp.in0 = in; sp.in_mode = IN_PLAIN; sp.out = out; sp.out_mode = OUT_STORE; sp.alpha = 1.0;
-  HIPCHK(sweep_launch(op->mats[op->gP0], sp, (hipStream_t)stream));
+  HIP_TRY(sweep_launch(op->mats[op->gP0], sp, (hipStream_t)stream));
   return 0;
 }
 
@@ -750,7 +706,7 @@ int ell_pencil_gather_try(ell_op *op, long ncol, const GatherSrc &g, double *out
   SweepParams sp = {};
   sp.ncols = (unsigned)ncol; sp.inner = (unsigned)ncol;
   sp.in_mode = IN_PLAIN; sp.out = out; sp.out_mode = OUT_STORE; sp.alpha = 1.0;
-  HIPCHK(sweep_launch_gather(op->mats[op->gP0], sp, g, st, done));
+  HIP_TRY(sweep_launch_gather(op->mats[op->gP0], sp, g, st, done));
   return 0;
 }
 }  // namespace chebhip
@@ -813,7 +769,7 @@ static int ell_fused4_jacobian(ell_op *op, int k, const double *U, double *V, hi
     q.acc = op->W; q.acc_bytes = (unsigned)wbytes; q.out = V; q.out_bytes = (unsigned)((size_t)op->G * 8);
   }
   q.coef = (const void *)(op->cprod[k] + 2 * shift); q.coef_bytes = (unsigned)(((size_t)op->N - shift) * 16);
-  HIPCHK(fused4_launch(op->mats[op->dims[k]], q, last, true, k > 0, false, st));
+  HIP_TRY(fused4_launch(op->mats[op->dims[k]], q, last, true, k > 0, false, st));
   return 0;
 }
 
@@ -843,7 +799,7 @@ static int ell_fused4_function(ell_op *op, int k, double gamma, double exponent,
     q.acc = op->W; q.acc_bytes = nbytes; q.out = rhs; q.out_bytes = gbytes;
     q.sub = b; q.sub_bytes = b ? gbytes : 0u;
   }
-  HIPCHK(fused4_launch(op->mats[op->dims[k]], q, last, false, k > 0, last, st));
+  HIP_TRY(fused4_launch(op->mats[op->dims[k]], q, last, false, k > 0, last, st));
   return 0;
 }
 
@@ -860,11 +816,11 @@ static int ell_state_layout(ell_op *op, bool trim, hipStream_t st) {
     *cur = want; *ptr = alloc + want;
     return e;
   };
-  HIPCHK(place(op->w0_alloc, &op->w0, &op->w0_shift, trim ? 15 : 0));
-  for (int k = 0; k < d; k++) HIPCHK(place(op->gradu_alloc[k], &op->gradu[k], &op->g_shift[k], (trim && k < d - 1) ? 15 : 0));
+  HIP_TRY(place(op->w0_alloc, &op->w0, &op->w0_shift, trim ? 15 : 0));
+  for (int k = 0; k < d; k++) HIP_TRY(place(op->gradu_alloc[k], &op->gradu[k], &op->g_shift[k], (trim && k < d - 1) ? 15 : 0));
   if (trim && op->bdy_lines_dirty && !cleared_all) {          // same layout as last time, but the general path left boundary-line values
-    HIPCHK(hipMemsetAsync(op->w0_alloc, 0, sbytes, st));
-    for (int k = 0; k < d; k++) HIPCHK(hipMemsetAsync(op->gradu_alloc[k], 0, sbytes, st));
+    HIP_TRY(hipMemsetAsync(op->w0_alloc, 0, sbytes, st));
+    for (int k = 0; k < d; k++) HIP_TRY(hipMemsetAsync(op->gradu_alloc[k], 0, sbytes, st));
   }
   if (trim) op->bdy_lines_dirty = false;
   return 0;
@@ -904,7 +860,7 @@ static int ell_fused4_function_trim(ell_op *op, int k, double gamma, const doubl
   }
   q.gout = op->gradu[k] + shift; q.gout_bytes = (unsigned)(((size_t)op->N - shift) * 8);
   if (k == 0) { q.w0out = op->w0 + shift; q.w0_bytes = q.gout_bytes; }
-  HIPCHK(fused4_launch(op->mats[op->dims[k]], q, last, false, k > 0, false, st));
+  HIP_TRY(fused4_launch(op->mats[op->dims[k]], q, last, false, k > 0, false, st));
   return 0;
 }
 
@@ -922,9 +878,9 @@ static void ell_out_chain(ell_op *op, int k, double *out_global, SweepParams *sp
 static int ell_slab_sweep(ell_op *op, int k, const double *x, double *y, hipStream_t st) {
   if (k == 0) return op->dim0(op->dim0_ctx, 0, 1, x, nullptr, 1.0, y, st);
   SweepParams sp = {};
-  sp.ncols = op->ncols[k]; sp.inner = op->inner[k];
+  sp.ncols = op->ncols(k); sp.inner = op->inner(k);
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.out_mode = OUT_STORE; sp.alpha = 1.0;
-  HIPCHK(sweep_launch(op->mats[op->dims[k]], sp, st));
+  HIP_TRY(sweep_launch(op->mats[op->dims[k]], sp, st));
   return 0;
 }
 
@@ -933,20 +889,20 @@ static int ell_slab_sweep(ell_op *op, int k, const double *x, double *y, hipStre
 static int ell_slab_divergence(ell_op *op, int in_mode, double *const *src, double *out_global, hipStream_t st) {
   const int d = op->d;
   if (in_mode != IN_PLAIN)
-    hipLaunchKernelGGL(k_flux, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->eta,
+    hipLaunchKernelGGL(k_flux, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->eta,
                        (const double *)(in_mode == IN_FLUX_FULL ? op->deta : nullptr), (const double *)op->w0,
                        (const double *)(in_mode == IN_FLUX_FULL ? op->gradu[0] : nullptr), src[0]);
   int rc = op->dim0(op->dim0_ctx, 0, 1, src[0], nullptr, -1.0, op->W, st);          // W = -D_0 f_0
   if (rc) return rc;
   for (int k = 1; k < d; k++) {
     SweepParams sp = {};
-    sp.ncols = op->ncols[k]; sp.inner = op->inner[k];
+    sp.ncols = op->ncols(k); sp.inner = op->inner(k);
     sp.in0 = src[k]; sp.in1 = op->eta; sp.in2 = op->deta; sp.in3 = op->w0;
     sp.in4 = op->gradu.empty() ? nullptr : op->gradu[k];
     sp.in_mode = in_mode; sp.alpha = -1.0;
     if (k == d - 1) { sp.out_mode = OUT_ACC_SCATTER; sp.out = out_global; sp.acc = op->W; sp.gcol = op->gcol[k]; sp.gstride = op->gstride[k]; }
     else { sp.out_mode = OUT_ACC; sp.out = op->W; sp.acc = op->W; }
-    HIPCHK(sweep_launch(op->mats[op->dims[k]], sp, st));
+    HIP_TRY(sweep_launch(op->mats[op->dims[k]], sp, st));
   }
   return 0;
 }
@@ -955,9 +911,9 @@ static int ell_slab_divergence(ell_op *op, int in_mode, double *const *src, doub
 // sweep_launch; gather, flux and scatter are pointwise passes -- literally the reference's structure.
 static int ell_plain_sweep(ell_op *op, int k, const double *x, double *y, int out_mode, const double *acc, double alpha, hipStream_t st) {
   SweepParams sp = {};
-  sp.ncols = op->ncols[k]; sp.inner = op->inner[k];
+  sp.ncols = op->ncols(k); sp.inner = op->inner(k);
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.out_mode = out_mode; sp.acc = acc; sp.alpha = alpha;
-  HIPCHK(sweep_launch(op->mats[op->dims[k]], sp, st));
+  HIP_TRY(sweep_launch(op->mats[op->dims[k]], sp, st));
   return 0;
 }
 
@@ -965,33 +921,33 @@ static int ell_plain_sweep(ell_op *op, int k, const double *x, double *y, int ou
 static int ell_plain_divergence(ell_op *op, int flux, double *const *src, double *V, hipStream_t st) {
   for (int k = 0; k < op->d; k++) {
     if (flux)
-      hipLaunchKernelGGL(k_flux, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->eta,
+      hipLaunchKernelGGL(k_flux, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->eta,
                          (const double *)(flux == 2 ? op->deta : nullptr), (const double *)op->w0,
                          (const double *)(flux == 2 ? op->gradu[k] : nullptr), src[k]);
     int rc = ell_plain_sweep(op, k, src[k], op->W, k == 0 ? OUT_STORE : OUT_ACC, op->W, -1.0, st);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_scatter_lg, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const int *)op->ixL, (const double *)op->W, V);
-  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_scatter_lg, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const int *)op->ixL, (const double *)op->W, V);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 static int ell_mult_plain(ell_op *op, const double *U, double *V, hipStream_t st) {
   int rc = ell_alloc_state(op); if (rc) return rc;
-  hipLaunchKernelGGL(k_gather_bc, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, op->ixL, U, (const double *)nullptr, op->w0);
+  hipLaunchKernelGGL(k_gather_bc, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, op->ixL, U, (const double *)nullptr, op->w0);
   for (int k = 0; k < op->d; k++) if ((rc = ell_plain_sweep(op, k, op->w0, op->g[k], OUT_STORE, nullptr, 1.0, st))) return rc;
   return ell_plain_divergence(op, op->mode == COEFF_UNIT ? 0 : 2, op->g.data(), V, st);
 }
 
 static int ell_mult_slab(ell_op *op, const double *U, double *V, hipStream_t st) {
   int rc = ell_alloc_state(op); if (rc) return rc;                    // w0
-  hipLaunchKernelGGL(k_gather_bc, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, op->ixL, U, (const double *)nullptr, op->w0);
+  hipLaunchKernelGGL(k_gather_bc, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, op->ixL, U, (const double *)nullptr, op->w0);
   for (int k = 0; k < op->d; k++) if ((rc = ell_slab_sweep(op, k, op->w0, op->g[k], st))) return rc;
   // a rank without interior nodes still takes part in the exchanges of the others
   // (its boundary plane carries the flux f_0 = eta g_0 of the lines that cross it: w0 is zero there, elliptic.C:305-308)
   if (op->G == 0) {
     if (op->mode != COEFF_UNIT)
-      hipLaunchKernelGGL(k_flux, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)op->deta,
+      hipLaunchKernelGGL(k_flux, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)op->deta,
                          (const double *)op->w0, (const double *)op->gradu[0], op->g[0]);
     return op->dim0(op->dim0_ctx, 0, 1, op->g[0], nullptr, -1.0, op->W, st);
   }
@@ -1004,8 +960,8 @@ constexpr size_t TWO_LAUNCH_MAX = 9000000;
 
 extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream) {
   // empty vectors (a slab that owns only boundary planes) may be NULL
-  if (!op || ((!U || !V) && !(op->slab && op->G == 0))) return fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (U && U == V) return fail(CHEBHIP_ERR_ARG, "U and V must be distinct (MatMult never aliases its vectors)");
+  if (!op || ((!U || !V) && !(op->slab && op->G == 0))) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (U && U == V) return chebhip_fail(CHEBHIP_ERR_ARG, "U and V must be distinct (MatMult never aliases its vectors)");
   StageTimer tm(CHEBHIP_STAGE_ELL_MULT, stream);
   if (op->slab) return ell_mult_slab(op, U, V, (hipStream_t)stream);
   if (op->G == 0) return 0;
@@ -1029,8 +985,8 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
       const int d = op->d;
       if (d >= 2 && d <= 3 && mode != 2 && (mode == 1 || op->G < 6000000L) && aligned16(U) && aligned16(V)) {
         if (!op->Wj[0]) {
-          HIPCHK(hipMalloc((void **)&op->Wj[0], (size_t)(op->G + 2) * sizeof(double)));
-          HIPCHK(hipMalloc((void **)&op->Wj[1], (size_t)(op->G + 2) * sizeof(double)));
+          HIP_TRY(hipMalloc((void **)&op->Wj[0], (size_t)(op->G + 2) * sizeof(double)));
+          HIP_TRY(hipMalloc((void **)&op->Wj[1], (size_t)(op->G + 2) * sizeof(double)));
         }
         const DiffMat *m[3]; SweepParams sp[3];
         double *term[3] = {op->W, op->Wj[0], op->Wj[1]};
@@ -1051,8 +1007,8 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
               m[k] = &op->laps[op->dims[k]];
             }
             bool done2 = false;
-            HIPCHK(sweep_launch_multi_try(2, m, sp, st, &done2));
-            if (done2) { HIPCHK(sweep_launch(op->laps[op->dims[2]], last, st)); return 0; }
+            HIP_TRY(sweep_launch_multi_try(2, m, sp, st, &done2));
+            if (done2) { HIP_TRY(sweep_launch(op->laps[op->dims[2]], last, st)); return 0; }
           }
         }
         for (int k = 0; k < d; k++) {
@@ -1062,11 +1018,11 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
           m[k] = &op->laps[op->dims[k]];
         }
         bool done = false;
-        HIPCHK(sweep_launch_multi_try(d, m, sp, st, &done));
+        HIP_TRY(sweep_launch_multi_try(d, m, sp, st, &done));
         if (done) {
-          hipLaunchKernelGGL(k_sum_terms, dim3(pw_grid((op->G + 1) >> 1)), dim3(256), 0, st, op->G, (const double *)term[0], (const double *)term[1],
+          hipLaunchKernelGGL(k_sum_terms, dim3(grid1d((op->G + 1) >> 1, 256, 2048)), dim3(256), 0, st, op->G, (const double *)term[0], (const double *)term[1],
                              (const double *)(d == 3 ? term[2] : nullptr), V);
-          HIPCHK(hipGetLastError());
+          HIP_TRY(hipGetLastError());
           return 0;
         }
       }
@@ -1102,7 +1058,7 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
       // kernel keeps ONE set of the two operands (sweep_vec.hip, ONEBUF).  Option poisson_launches = 2: a launch per direction (A/B).
       const int pl = opt(OPT_POISSON_LAUNCHES);
       if (d == 3 && pl != 2 && (pl == 3 || op->wsize <= (size_t)TWO_LAUNCH_MAX) && !opt(OPT_SEPARATE_LAUNCHES) && !opt(OPT_GENERAL_KERNELS)) {
-        if (!op->W2) HIPCHK(hipMalloc((void **)&op->W2, op->wsize * sizeof(double)));
+        if (!op->W2) HIP_TRY(hipMalloc((void **)&op->W2, op->wsize * sizeof(double)));
         SweepParams last = dir_params(2);
         last.out_mode = OUT_ACC2; last.acc = op->W; last.acc2 = op->W2; last.out = V;
         if (sweep_vec_eligible(op->laps[op->dims[2]], last)) {
@@ -1113,8 +1069,8 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
             m[k] = &op->laps[op->dims[k]];
           }
           bool done2 = false;
-          HIPCHK(sweep_launch_multi_try(2, m, sp, st, &done2));
-          if (done2) { HIPCHK(sweep_launch(op->laps[op->dims[2]], last, st)); return 0; }
+          HIP_TRY(sweep_launch_multi_try(2, m, sp, st, &done2));
+          if (done2) { HIP_TRY(sweep_launch(op->laps[op->dims[2]], last, st)); return 0; }
         }
       }
       for (int k = 0; k < d; k++) {
@@ -1122,7 +1078,7 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
         if (k == 0) { sp.out_mode = OUT_STORE; sp.out = op->W; }
         else if (k == d - 1) { sp.out_mode = OUT_ACC; sp.out = V; sp.acc = op->W; }
         else { sp.out_mode = OUT_ACC; sp.out = op->W; sp.acc = op->W; }
-        HIPCHK(sweep_launch(op->laps[op->dims[k]], sp, st));
+        HIP_TRY(sweep_launch(op->laps[op->dims[k]], sp, st));
       }
       return 0;
     }
@@ -1135,7 +1091,7 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
       else if (k == 0) { sp.out_mode = OUT_STORE; sp.out = V; }
       else if (k == op->d - 1) { sp.out_mode = OUT_ACC; sp.out = V; sp.acc = op->W; }
       else { sp.out_mode = OUT_ACC; sp.out = op->W; sp.acc = op->W; }
-      HIPCHK(sweep_launch(op->laps[op->dims[k]], sp, st));
+      HIP_TRY(sweep_launch(op->laps[op->dims[k]], sp, st));
     }
     return 0;
   }
@@ -1147,10 +1103,10 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
   if (op->cdirty) {
     for (int k = 0; k < op->d; k++) {
       if (op->coef_stale)     // state left by the interior-line FormFunction: the pairs come straight from w0
-        hipLaunchKernelGGL(k_cprod_sq, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->w0, op->coef_gamma,
+        hipLaunchKernelGGL(k_cprod_sq, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->w0, op->coef_gamma,
                            (const double *)op->gradu[k], (double2 *)op->cprod[k]);
       else
-        hipLaunchKernelGGL(k_cprod, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)op->deta,
+        hipLaunchKernelGGL(k_cprod, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)op->deta,
                            (const double *)op->gradu[k], (double2 *)op->cprod[k]);
     }
     op->cdirty = false;
@@ -1161,19 +1117,19 @@ extern "C" int ell_op_mult(ell_op *op, const double *U, double *V, void *stream)
   }
   for (int k = 0; k < op->d; k++) {
     SweepParams sp = {};
-    sp.ncols = op->ncols[k]; sp.inner = op->inner[k];
+    sp.ncols = op->ncols(k); sp.inner = op->inner(k);
     sp.in0 = U; sp.in_mode = IN_GATHER;
     sp.coef_mode = COEF_FULL; sp.in1 = op->eta; sp.in2 = op->cprod[k];
     ell_out_chain(op, k, V, &sp);
-    HIPCHK(fused_launch(op->mats[op->dims[k]], sp, st));
+    HIP_TRY(fused_launch(op->mats[op->dims[k]], sp, st));
   }
   return 0;
 }
 
 extern "C" int ell_op_function(ell_op *op, double gamma, double exponent, const double *U,
                                const double *b, double *rhs, void *stream) {
-  if (!op || ((!U || !rhs) && !(op->slab && op->G == 0))) return fail(CHEBHIP_ERR_ARG, "NULL argument");
-  if (U && (U == rhs || b == rhs)) return fail(CHEBHIP_ERR_ARG, "rhs must not alias U or b");
+  if (!op || ((!U || !rhs) && !(op->slab && op->G == 0))) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (U && (U == rhs || b == rhs)) return chebhip_fail(CHEBHIP_ERR_ARG, "rhs must not alias U or b");
   StageTimer tm(CHEBHIP_STAGE_ELL_FUNCTION, stream);
   hipStream_t st = (hipStream_t)stream;
   int rc = ell_alloc_state(op);
@@ -1196,10 +1152,10 @@ extern "C" int ell_op_function(ell_op *op, double gamma, double exponent, const 
   if ((rc = ell_state_layout(op, false, st))) return rc;
   if (op->dir_nonzero) op->bdy_lines_dirty = true;
   if ((op->N & 1) == 0)
-    hipLaunchKernelGGL(k_gather_coeff2, dim3(pw_grid(op->N >> 1) * 2), dim3(256), 0, st, op->N, (const int *)op->ixL, U,
+    hipLaunchKernelGGL(k_gather_coeff2, dim3(grid1d(op->N >> 1, 256, 2048) * 2), dim3(256), 0, st, op->N, (const int *)op->ixL, U,
                        (const double *)op->dirloc, gamma, exponent, iexp, op->w0, op->eta, op->deta);   // elliptic.C:486-493, 508-509
   else
-    hipLaunchKernelGGL(k_gather_coeff, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const int *)op->ixL, U,
+    hipLaunchKernelGGL(k_gather_coeff, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const int *)op->ixL, U,
                        (const double *)op->dirloc, gamma, exponent, iexp, op->w0, op->eta, op->deta);
   op->cdirty = true;
   // eta stays exactly 1 and deta exactly 0 only when gamma == 0 and no pow() can produce inf/nan
@@ -1208,24 +1164,24 @@ extern "C" int ell_op_function(ell_op *op, double gamma, double exponent, const 
   if (op->slab) {
     for (int k = 0; k < d; k++) if ((rc = ell_slab_sweep(op, k, op->w0, op->gradu[k], st))) return rc;     // :497-499
     // w_k = eta * gradu[k] (:511): dimension 0 needs it as an array (g[0]); the others form it on load
-    HIPCHK(hipMemcpyAsync(op->g[0], op->gradu[0], (size_t)op->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(op->g[0], op->gradu[0], (size_t)op->N * sizeof(double), hipMemcpyDeviceToDevice, st));
     std::vector<double *> src(op->gradu); src[0] = op->g[0];
-    if (op->G == 0) { hipLaunchKernelGGL(k_flux, dim3(pw_grid(op->N)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)nullptr,
+    if (op->G == 0) { hipLaunchKernelGGL(k_flux, dim3(grid1d(op->N, 256, 2048)), dim3(256), 0, st, op->N, (const double *)op->eta, (const double *)nullptr,
                                          (const double *)nullptr, (const double *)nullptr, src[0]);
                       return op->dim0(op->dim0_ctx, 0, 1, src[0], nullptr, -1.0, op->W, st); }
     if ((rc = ell_slab_divergence(op, IN_FLUX_ETA, src.data(), rhs, st))) return rc;
-    if (b) hipLaunchKernelGGL(k_axpy, dim3(pw_grid(op->G)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
-    HIPCHK(hipGetLastError());
+    if (b) hipLaunchKernelGGL(k_axpy, dim3(grid1d(op->G, 256, 2048)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   if (op->has_long) {
     for (int k = 0; k < d; k++) if ((rc = ell_plain_sweep(op, k, op->w0, op->gradu[k], OUT_STORE, nullptr, 1.0, st))) return rc;   // :497-499
     if (op->G == 0) return 0;
     for (int k = 0; k < d; k++)                                                 // w_k = eta * gradu[k] (:511), formed in g[k]
-      HIPCHK(hipMemcpyAsync(op->g[k], op->gradu[k], (size_t)op->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(op->g[k], op->gradu[k], (size_t)op->N * sizeof(double), hipMemcpyDeviceToDevice, st));
     if ((rc = ell_plain_divergence(op, 1, op->g.data(), rhs, st))) return rc;
-    if (b) hipLaunchKernelGGL(k_axpy, dim3(pw_grid(op->G)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
-    HIPCHK(hipGetLastError());
+    if (b) hipLaunchKernelGGL(k_axpy, dim3(grid1d(op->G, 256, 2048)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   if (ell_fused4_ok(op) && aligned16(rhs)) {
@@ -1236,60 +1192,56 @@ extern "C" int ell_op_function(ell_op *op, double gamma, double exponent, const 
     // divergence without leaving the chip (:521-528)
     for (int k = 0; k < d; k++) {
       SweepParams sp = {};
-      sp.ncols = op->ncols[k]; sp.inner = op->inner[k];
+      sp.ncols = op->ncols(k); sp.inner = op->inner(k);
       sp.in0 = op->w0; sp.in_mode = IN_PLAIN;
       sp.coef_mode = COEF_ETA; sp.in1 = op->eta; sp.gout = op->gradu[k];
       ell_out_chain(op, k, rhs, &sp);
       if (op->G == 0) { sp.out_mode = OUT_STORE; sp.out = op->W; sp.acc = nullptr; }
-      HIPCHK(fused_launch(op->mats[op->dims[k]], sp, st));
+      HIP_TRY(fused_launch(op->mats[op->dims[k]], sp, st));
     }
     if (op->G == 0) return 0;
   }
-  if (b) hipLaunchKernelGGL(k_axpy, dim3(pw_grid(op->G)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
-  HIPCHK(hipGetLastError());
+  if (b) hipLaunchKernelGGL(k_axpy, dim3(grid1d(op->G, 256, 2048)), dim3(256), 0, st, op->G, -1.0, b, rhs);  // :530
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 static int ell_stage(ell_op *op) {
   const size_t gb = (size_t)(op->G > 0 ? op->G : 1) * sizeof(double);
-  if (!op->hU) { HIPCHK(hipMalloc((void **)&op->hU, gb)); HIPCHK(hipMalloc((void **)&op->hV, gb)); HIPCHK(hipMalloc((void **)&op->hB, gb)); }
+  if (!op->hU) { HIP_TRY(hipMalloc((void **)&op->hU, gb)); HIP_TRY(hipMalloc((void **)&op->hV, gb)); HIP_TRY(hipMalloc((void **)&op->hB, gb)); }
   return 0;
 }
 
 extern "C" int ell_op_mult_host(ell_op *op, const double *U, double *V) {
-  if (!op || !U || !V) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !U || !V) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   int rc = ell_stage(op); if (rc) return rc;
   const size_t gb = (size_t)op->G * sizeof(double);
-  HIPCHK(hipMemcpy(op->hU, U, gb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(op->hU, U, gb, hipMemcpyHostToDevice));
   if ((rc = ell_op_mult(op, op->hU, op->hV, nullptr))) return rc;
-  HIPCHK(hipMemcpy(V, op->hV, gb, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(V, op->hV, gb, hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int ell_op_function_host(ell_op *op, double gamma, double exponent, const double *U,
                                     const double *b, double *rhs) {
-  if (!op || !U || !rhs) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !U || !rhs) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   int rc = ell_stage(op); if (rc) return rc;
   const size_t gb = (size_t)op->G * sizeof(double);
-  HIPCHK(hipMemcpy(op->hU, U, gb, hipMemcpyHostToDevice));
-  if (b) HIPCHK(hipMemcpy(op->hB, b, gb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(op->hU, U, gb, hipMemcpyHostToDevice));
+  if (b) HIP_TRY(hipMemcpy(op->hB, b, gb, hipMemcpyHostToDevice));
   if ((rc = ell_op_function(op, gamma, exponent, op->hU, b ? op->hB : nullptr, op->hV, nullptr))) return rc;
-  HIPCHK(hipMemcpy(rhs, op->hV, gb, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rhs, op->hV, gb, hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int ell_op_set_dirichlet(ell_op *op, const double *values) {
-  if (!op || !values) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !values) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   // expand the compact BlockIt-ordered boundary vector (elliptic.C:399-403) to the local layout
   std::vector<double> loc((size_t)op->N, 0.0);
-  std::vector<int> ind(op->d, 0);
   long dd = 0;
-  for (long l = 0; l < op->N; l++) {
-    if (ell_is_bdy(op, ind.data())) loc[l] = values[dd++];
-    for (int j = op->d - 1; j >= 0; j--) { if (++ind[j] < op->dims[j]) break; ind[j] = 0; }
-  }
-  if (!op->dirloc) HIPCHK(hipMalloc((void **)&op->dirloc, (size_t)op->N * sizeof(double)));
-  HIPCHK(hipMemcpy(op->dirloc, loc.data(), (size_t)op->N * sizeof(double), hipMemcpyHostToDevice));
+  op->for_each_node([&](long l, const int *, bool bdy) { if (bdy) loc[l] = values[dd++]; });
+  if (!op->dirloc) HIP_TRY(hipMalloc((void **)&op->dirloc, (size_t)op->N * sizeof(double)));
+  HIP_TRY(hipMemcpy(op->dirloc, loc.data(), (size_t)op->N * sizeof(double), hipMemcpyHostToDevice));
   op->dir_nonzero = false;
   for (long i = 0; i < dd && !op->dir_nonzero; i++) op->dir_nonzero = values[i] != 0.0;
   return 0;
@@ -1301,28 +1253,28 @@ static int ell_state_ptr(ell_op *op, int which, double **p) {
   if (which == 0) *p = op->eta;
   else if (which == 1) *p = op->deta;
   else if (which >= 2 && which < 2 + op->d) *p = op->gradu[which - 2];
-  else return fail(CHEBHIP_ERR_ARG, "which = %d out of range", which);
+  else return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d out of range", which);
   return 0;
 }
 
 extern "C" int ell_op_get_state(ell_op *op, int which, double *dst) {
-  if (!op || !dst) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !dst) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   double *p; int rc = ell_state_ptr(op, which, &p); if (rc) return rc;
   // a FormFunction still queued on a non-blocking stream must have written w0 before the null-stream rebuild of eta / deta reads it
-  HIPCHK(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
   if (which < 2 && (rc = ell_sync_coeffs(op, nullptr))) return rc;
-  HIPCHK(hipStreamSynchronize(nullptr));
-  HIPCHK(hipMemcpy(dst, p, (size_t)op->N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(dst, p, (size_t)op->N * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int ell_op_set_state(ell_op *op, int which, const double *src) {
-  if (!op || !src) return fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!op || !src) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   double *p; int rc = ell_state_ptr(op, which, &p); if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());                               // as in ell_op_get_state: callbacks on non-blocking streams first
+  HIP_TRY(hipDeviceSynchronize());                               // as in ell_op_get_state: callbacks on non-blocking streams first
   if ((rc = ell_sync_coeffs(op, nullptr))) return rc;           // the untouched one of eta / deta must be current
-  HIPCHK(hipStreamSynchronize(nullptr));
-  HIPCHK(hipMemcpy(p, src, (size_t)op->N * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(p, src, (size_t)op->N * sizeof(double), hipMemcpyHostToDevice));
   if (which >= 2) op->bdy_lines_dirty = true;
   op->mode = COEFF_FULL; op->cdirty = true;
   return 0;

@@ -18,6 +18,7 @@
 //             segment exchanges and the reductions.
 #include "comm.h"
 #include "sweep.h"
+#include "ops.h"
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <sched.h>
@@ -36,14 +37,6 @@
 #include <string>
 #include <utility>
 #include <vector>
-
-int chebhip_fail(int code, const char *fmt, ...);   // chebhip.hip
-
-#define CHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -129,7 +122,6 @@ struct chebhip_local_group {
   }
   void abort() { std::lock_guard<std::mutex> lk(mu); aborted = true; cv.notify_all(); }
 };
-
 
 // ---- ranks as processes of one node ------------------------------------------------------------------------------
 namespace {
@@ -606,7 +598,7 @@ static int self_copies(const chebhip_comm *c, const XSeg *segs, int nseg, hipStr
   for (int i = 0; i < nseg; i++)
     if (segs[i].peer == c->rank && segs[i].nrecv > 0) {
       if (segs[i].nsend != segs[i].nrecv) return chebhip_fail(CHEBHIP_ERR_ARG, "exchange: a rank's own segment has unequal send / receive counts");
-      CHIPCHK(hipMemcpyAsync(segs[i].recv, segs[i].send, (size_t)segs[i].nrecv * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(segs[i].recv, segs[i].send, (size_t)segs[i].nrecv * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
   return 0;
 }

@@ -30,20 +30,14 @@
 // contract (the CPU tests run the exchange logic under gloo that way).
 #include "comm.h"
 #include "sweep.h"
+#include "ops.h"
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <new>
 #include <vector>
 
-int chebhip_fail(int code, const char *fmt, ...);   // chebhip.hip
 using chebhip::XSeg;
-
-#define DHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -225,11 +219,11 @@ static int dist_work_build(chebhip_dist *D, int nrhs, chebhip_dist::Work *W) {
   long wmax = 0; for (int s = 0; s < D->G; s++) wmax = D->m1[s] > wmax ? D->m1[s] : wmax;
   const size_t lb = (size_t)(D->local > 0 ? D->local : 1) * nrhs * sizeof(double), pb = ((size_t)(D->pencil > 0 ? D->pencil : 1) * nrhs + (size_t)(wmax + 1) * D->R) * sizeof(double);
   W->A.assign(d - 1, nullptr);
-  for (int k = 0; k < d - 1; k++) DHIPCHK(hipMalloc((void **)&W->A[k], lb));
-  DHIPCHK(hipMalloc((void **)&W->sendbuf, lb)); DHIPCHK(hipMalloc((void **)&W->recvbuf, lb));
-  DHIPCHK(hipMalloc((void **)&W->UT, pb)); DHIPCHK(hipMalloc((void **)&W->TT, pb));
-  DHIPCHK(hipMalloc((void **)&W->Tin, lb + 16384));
-  DHIPCHK(hipMemset(W->Tin, 0, lb + 16384));     // (the NULL transport sums blocks of it that nobody writes)
+  for (int k = 0; k < d - 1; k++) HIP_TRY(hipMalloc((void **)&W->A[k], lb));
+  HIP_TRY(hipMalloc((void **)&W->sendbuf, lb)); HIP_TRY(hipMalloc((void **)&W->recvbuf, lb));
+  HIP_TRY(hipMalloc((void **)&W->UT, pb)); HIP_TRY(hipMalloc((void **)&W->TT, pb));
+  HIP_TRY(hipMalloc((void **)&W->Tin, lb + 16384));
+  HIP_TRY(hipMemset(W->Tin, 0, lb + 16384));     // (the NULL transport sums blocks of it that nobody writes)
   return 0;
 }
 
@@ -271,13 +265,10 @@ extern "C" int chebhip_dist_create(int d, const int *dims, int nranks, int rank,
   D->fwd_send.resize(nranks); D->fwd_recv.resize(nranks);
   for (int s = 0; s < nranks; s++) { D->fwd_send[s] = D->m0[rank] * D->m1[s] * D->R; D->fwd_recv[s] = D->m0[s] * D->m1[rank] * D->R; }
   D->split.G = nranks; for (int s = 0; s <= nranks; s++) D->split.c1[s] = D->s1[s];
-#define DHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { chebhip_dist_destroy(D); \
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
   { int rc = dist_work(D, 1, nullptr); if (rc) { chebhip_dist_destroy(D); return rc; } }
-  DHIP(hipStreamCreateWithFlags(&D->side, hipStreamNonBlocking));
-  DHIP(hipEventCreateWithFlags(&D->ev_in, hipEventDisableTiming));
-  DHIP(hipEventCreateWithFlags(&D->ev_out, hipEventDisableTiming));
-#undef DHIP
+  HIP_TRY_OR(hipStreamCreateWithFlags(&D->side, hipStreamNonBlocking), chebhip_dist_destroy(D));
+  HIP_TRY_OR(hipEventCreateWithFlags(&D->ev_in, hipEventDisableTiming), chebhip_dist_destroy(D));
+  HIP_TRY_OR(hipEventCreateWithFlags(&D->ev_out, hipEventDisableTiming), chebhip_dist_destroy(D));
   *out = D;
   return 0;
 }
@@ -463,7 +454,7 @@ static int dist_mult(chebhip_dist *D, chebhip_dist::Work *W, const double *U, do
       if (v2c) hipLaunchKernelGGL((k_pull_combine<true>), dim3(grid), dim3(256), 0, st, D->split, ps, s0r, M1, R, A, V, lq);
       else hipLaunchKernelGGL((k_pull_combine<false>), dim3(grid), dim3(256), 0, st, D->split, ps, s0r, M1, R, A, V, lq);
     }
-    DHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return chebhip::comm_mark(D->comm, 3, st);                                                                          // my reads of the peers' TT end here
   }
 
@@ -491,7 +482,7 @@ static int dist_mult(chebhip_dist *D, chebhip_dist::Work *W, const double *U, do
     if (v2) hipLaunchKernelGGL((k_combine<true>), dim3(grid), dim3(256), 0, st, D->split, m0, M1, R, (const double *)W->recvbuf, own, own_out, A, V, lq, pq);
     else hipLaunchKernelGGL((k_combine<false>), dim3(grid), dim3(256), 0, st, D->split, m0, M1, R, (const double *)W->recvbuf, own, own_out, A, V, lq, pq);
   }
-  DHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 

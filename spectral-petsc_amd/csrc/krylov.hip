@@ -19,18 +19,11 @@
 #include "../../include/chebhip.h"
 #include "timers.h"
 #include "sweep.h"
+#include "ops.h"
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <new>
 #include <vector>
-
-int chebhip_fail(int code, const char *fmt, ...);   // chebhip.hip
-
-#define KHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -558,36 +551,31 @@ extern "C" int chebhip_fgmres_create(long n, int restart, chebhip_fgmres **out) 
   *out = nullptr;
   if (n < 0) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %ld but must be >= 0", n);     // 0: a rank without unknowns
   if (restart < 1 || restart > RT) return chebhip_fail(CHEBHIP_ERR_ARG, "restart = %d must be in 1..%d", restart, RT);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device; libchebhip has no CPU fallback");
+  { int rc = chebhip::require_device(); if (rc) return rc; }
   chebhip_fgmres *k = new (std::nothrow) chebhip_fgmres;
   if (!k) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   const int m = restart;
   k->n = n; k->m = m; k->ld = n > 0 ? ((n + 1) & ~1L) : 2;             // even leading dimension: every basis vector 16-B aligned
-#define KC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { chebhip_fgmres_destroy(k); \
-    return chebhip_fail(e_ == hipErrorOutOfMemory ? CHEBHIP_ERR_MEMORY : CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
-  KC(hipMalloc((void **)&k->V, (size_t)(m + 1) * k->ld * sizeof(double)));
-  KC(hipMalloc((void **)&k->Z, (size_t)m * k->ld * sizeof(double)));
-  KC(hipMalloc((void **)&k->part, (size_t)(m + 2) * RB * sizeof(double)));
-  KC(hipMalloc((void **)&k->ticket, sizeof(int)));
-  KC(hipMemset(k->ticket, 0, sizeof(int)));
-  KC(hipMalloc((void **)&k->scal, 4 * sizeof(double)));
-  KC(hipMalloc((void **)&k->coef, (size_t)(m + 3) * sizeof(double)));
-  KC(hipMalloc((void **)&k->rn, (size_t)(m + 3) * sizeof(double)));
-  KC(hipMalloc((void **)&k->npart, (size_t)RB * sizeof(double)));
-  KC(hipMalloc((void **)&k->hcol, (size_t)(m + 3) * sizeof(double)));
-  KC(hipMalloc((void **)&k->ydev, (size_t)(m + 2) * sizeof(double)));
-  KC(hipMalloc((void **)&k->H, (size_t)m * (m + 1) * sizeof(double)));
-  KC(hipMalloc((void **)&k->cs, (size_t)m * sizeof(double)));
-  KC(hipMalloc((void **)&k->sn, (size_t)m * sizeof(double)));
-  KC(hipMalloc((void **)&k->G, (size_t)(m + 1) * (m + 2) * sizeof(double)));
-  KC(hipMalloc((void **)&k->nsq, sizeof(double)));
-  KC(hipHostMalloc((void **)&k->res, (size_t)(m + 2) * sizeof(double)));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->V, (size_t)(m + 1) * k->ld * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->Z, (size_t)m * k->ld * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->part, (size_t)(m + 2) * RB * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->ticket, sizeof(int)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMemset(k->ticket, 0, sizeof(int)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->scal, 4 * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->coef, (size_t)(m + 3) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->rn, (size_t)(m + 3) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->npart, (size_t)RB * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->hcol, (size_t)(m + 3) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->ydev, (size_t)(m + 2) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->H, (size_t)m * (m + 1) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->cs, (size_t)m * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->sn, (size_t)m * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->G, (size_t)(m + 1) * (m + 2) * sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&k->nsq, sizeof(double)), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipHostMalloc((void **)&k->res, (size_t)(m + 2) * sizeof(double)), chebhip_fgmres_destroy(k));
   k->ev.assign(m, nullptr);
-  for (int j = 0; j < m; j++) KC(hipEventCreateWithFlags(&k->ev[j], hipEventDisableTiming));
-  KC(hipStreamSynchronize(nullptr));      // the ticket was cleared on the null stream, which a caller's non-blocking stream does not wait for
-#undef KC
+  for (int j = 0; j < m; j++) HIP_TRY_MEM_OR(hipEventCreateWithFlags(&k->ev[j], hipEventDisableTiming), chebhip_fgmres_destroy(k));
+  HIP_TRY_MEM_OR(hipStreamSynchronize(nullptr), chebhip_fgmres_destroy(k));      // the ticket was cleared on the null stream, which a caller's non-blocking stream does not wait for
   *out = k;
   return 0;
 }
@@ -620,9 +608,9 @@ static int dev_norm(chebhip_fgmres *k, const double *v, hipStream_t st, double *
     hipLaunchKernelGGL(k_rows_finish, dim3(1), dim3(RT), 0, st, (const double *)k->npart, k->nsq, 0);
     int rc = k->reduce(k->reduce_ctx, k->nsq, 1, st); if (rc) return rc;
     hipLaunchKernelGGL(k_sqrt1, dim3(1), dim3(1), 0, st, k->nsq);
-    KHIPCHK(hipMemcpyAsync(k->res + k->m, k->nsq, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(k->res + k->m, k->nsq, sizeof(double), hipMemcpyDeviceToHost, st));
   }
-  KHIPCHK(hipStreamSynchronize(st));
+  HIP_TRY(hipStreamSynchronize(st));
   *out = k->res[k->m];
   return 0;
 }
@@ -644,7 +632,7 @@ extern "C" int chebhip_fgmres_solve(chebhip_fgmres *k, chebhip_apply_fn A, void 
   // preconditioners (stokes.C:328-341: 1..4 iterations each) are a few dozen vector passes in all.
   bool x_unset = !x_nonzero;
   auto clear_x = [&]() -> int {
-    if (x_unset && n > 0) KHIPCHK(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), st));
+    if (x_unset && n > 0) HIP_TRY(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), st));
     x_unset = false; return 0;
   };
   bool first = true;
@@ -718,10 +706,10 @@ extern "C" int chebhip_fgmres_solve(chebhip_fgmres *k, chebhip_apply_fn A, void 
                                k->H, k->cs, k->sn, k->G, k->res);
           }
         }
-        KHIPCHK(hipGetLastError());
-        KHIPCHK(hipEventRecord(k->ev[j], st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(k->ev[j], st));
         enq = j + 1;
-        if (j >= 1) { KHIPCHK(hipEventSynchronize(k->ev[j - 1])); examine(j - 1); }
+        if (j >= 1) { HIP_TRY(hipEventSynchronize(k->ev[j - 1])); examine(j - 1); }
         continue;
       }
       if ((n & 1) == 0) hipLaunchKernelGGL((k_multidot_grouped<true>), dim3(RB, (j + KB) / KB), dim3(ST), 0, st, n, j + 1, (const double *)k->V, ld, (const double *)w, k->part);
@@ -739,11 +727,11 @@ extern "C" int chebhip_fgmres_solve(chebhip_fgmres *k, chebhip_apply_fn A, void 
         hipLaunchKernelGGL(k_givens_scale, dim3(gsgrid), dim3(RT), 0, st, j, m, (const double *)nullptr, (const double *)k->hcol, k->H, k->cs, k->sn, k->G, k->res,
                            (const double *)k->nsq, n, w, use_next);
       }
-      KHIPCHK(hipEventRecord(k->ev[j], st));
+      HIP_TRY(hipEventRecord(k->ev[j], st));
       enq = j + 1;
-      if (j >= 1) { KHIPCHK(hipEventSynchronize(k->ev[j - 1])); examine(j - 1); }
+      if (j >= 1) { HIP_TRY(hipEventSynchronize(k->ev[j - 1])); examine(j - 1); }
     }
-    if (!stop && enq > 0) { KHIPCHK(hipEventSynchronize(k->ev[enq - 1])); examine(enq - 1); }
+    if (!stop && enq > 0) { HIP_TRY(hipEventSynchronize(k->ev[enq - 1])); examine(enq - 1); }
     // was the last accepted column one whose h_{j+1,j} is the one-pass estimate (no update pass: `use_next` = 0 above)?
     const bool last_est = !k->exact && kk > 0 && !(kk < m && k->its + kk < k->max_it);
     k->its += kk;
@@ -753,7 +741,7 @@ extern "C" int chebhip_fgmres_solve(chebhip_fgmres *k, chebhip_apply_fn A, void 
       hipLaunchKernelGGL(k_multiaxpy, dim3(pgrid(n)), dim3(256), 0, st, n, kk, (const double *)(M ? k->Z : k->V), ld, (const double *)k->ydev, x, x_unset ? 1 : 0);
       x_unset = false;
     }
-    KHIPCHK(hipStreamSynchronize(st));      // a speculative iteration may still be running: drain before V is reused
+    HIP_TRY(hipStreamSynchronize(st));      // a speculative iteration may still be running: drain before V is reused
     if (k->reason == -9) return clear_x();
     // convergence read off an estimated column is checked on the true residual (top of the loop: converged, iteration limit, or on)
     if (k->rnorm <= tol && !last_est) { k->reason = k->rnorm <= k->atol ? 3 : 2; return clear_x(); }

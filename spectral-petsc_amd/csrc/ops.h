@@ -1,9 +1,12 @@
-// ops.h -- what the preconditioner module (precond.hip) needs to see of the operator handles, and the plumbing that the
-// handle modules share (chebhip.hip, resample.hip, modal.hip, points.hip, dealias.hip, reduce.hip).
+// ops.h -- the plumbing every module of the library shares: the error-return macros around HIP calls, the grid-stride loop and the
+// launch size of the pointwise kernels, the argument checks of the handle constructors, BoxGrid (the local box of an operator handle
+// and which of its nodes lie on the boundary of the global grid), and what the preconditioner module (precond.hip) needs to see of
+// the operator handles.
 #pragma once
 #include "../../include/chebhip.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <vector>
 
 namespace chebhip {
 
@@ -26,9 +29,67 @@ int ell_op_fd_view(ell_op *op, chebhip::FdView *v);          // chebhip.hip (all
 int ell_op_fd_view_any(ell_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view_any(stokes_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view(stokes_op *op, chebhip::FdView *v);    // stokes.hip
-int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip
+int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip: sets chebhip_last_error(), returns code
+
+// A failed HIP call ends the calling function: `cleanup` runs, the error text is the call as written plus HIP's reason.
+#define HIP_TRY_AS(expr, text, code, cleanup)                                                           \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) { cleanup; return chebhip_fail(code, "%s: %s", text, hipGetErrorString(e_)); } \
+  } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(expr, #expr, CHEBHIP_ERR_DEVICE, (void)0)
+#define HIP_TRY_OR(expr, cleanup) HIP_TRY_AS(expr, #expr, CHEBHIP_ERR_DEVICE, cleanup)     // constructors: destroy the half-built handle
+#define HIP_TRY_MEM_OR(expr, cleanup) HIP_TRY_AS(expr, #expr, e_ == hipErrorOutOfMemory ? CHEBHIP_ERR_MEMORY : CHEBHIP_ERR_DEVICE, cleanup)
+
+// pointwise kernels: grid-stride loop, and the blocks of a launch that gives each block `per_block` items, at most `cap` blocks
+#define GS_LOOP(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 namespace chebhip {
+
+inline unsigned grid1d(long n, long per_block, long cap) { const long g = (n + per_block - 1) / per_block; return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g)); }
+
+// The local box of an operator handle: d extents in row-major order, of which dimension 0 may be the planes [lo, lo + dims[0]) of a
+// global grid with gP0 planes (slab mode; otherwise lo = 0 and dims[0] = gP0).  Host only.
+struct BoxGrid {
+  int d = 0;
+  std::vector<int> dims;            // local extents, boundary included
+  int gP0 = 0, lo = 0;
+  long N = 0;                       // local nodes
+
+  static int check_slab(int lo, int hi, int P0) {
+    return 0 <= lo && lo < hi && hi <= P0 ? 0 : chebhip_fail(CHEBHIP_ERR_ARG, "slab planes [%d, %d) outside 0..%d", lo, hi, P0);
+  }
+  // the planes [lo_, hi_) of the grid gdims
+  void set_box(int d_, const int *gdims, int lo_, int hi_) {
+    d = d_; dims.assign(gdims, gdims + d_); dims[0] = hi_ - lo_; gP0 = gdims[0]; lo = lo_;
+    N = 1; for (int n : dims) N *= n;
+  }
+  // is the node with local multi-index ind a boundary node of the GLOBAL grid?
+  bool boundary(const int *ind) const {
+    const int g0 = ind[0] + lo;
+    if (g0 == 0 || g0 == gP0 - 1) return true;
+    for (int j = 1; j < d; j++) if (ind[j] == 0 || ind[j] == dims[j] - 1) return true;
+    return false;
+  }
+  // f(l, ind, is_boundary) for every local node l in row-major (BlockIt) order
+  template <class F> void for_each_node(F f) const {
+    std::vector<int> ind(d, 0);
+    for (long l = 0; l < N; l++) {
+      f(l, (const int *)ind.data(), boundary(ind.data()));
+      for (int j = d - 1; j >= 0; j--) { if (++ind[j] < dims[j]) break; ind[j] = 0; }
+    }
+  }
+  // ixL[l]: the number of node l among the interior nodes, or -1 on the boundary; returns the number of interior nodes
+  long interior_index(std::vector<int> &ixL) const {
+    long g = 0;
+    ixL.resize((size_t)N);
+    for_each_node([&](long l, const int *, bool bdy) { ixL[l] = bdy ? -1 : (int)g++; });
+    return g;
+  }
+  // lines along direction k: the stride between their points, and how many there are
+  unsigned inner(int k) const { unsigned in = 1; for (int r = k + 1; r < d; r++) in *= dims[r]; return in; }
+  unsigned ncols(int k) const { return (unsigned)(N / dims[k]); }
+};
 
 inline int require_device() {
   int n = 0;

@@ -34,19 +34,10 @@
 
 using namespace chebhip;
 
-#define PHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
 namespace {
 
 constexpr int MAXD = 10;
 struct Geo { int d; int dims[MAXD]; long gs[MAXD]; };      // local extents, interior strides
-
-static inline unsigned pgrid(long n) { long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-#define GS_LOOP(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 // One row of P per interior node, exactly the arithmetic of elliptic.C:556-579 (gradu[j] null: the deta * du0
 // terms are absent, stokes.C:1217-1222).  cf[0] diagonal, cf[1+2j] / cf[2+2j] the neighbours at -1 / +1 along
@@ -360,8 +351,6 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
   if (kind == LINE_SPECTRAL) { pc->sweeps = 0; pc->assembled = bare; }
   for (int k = 0; k < v.d; k++) pc->geo.dims[k] = v.dims[k];
   { long s = 1; for (int k = v.d - 1; k >= 0; k--) { pc->geo.gs[k] = s; s *= (v.dims[k] - 2); } }
-#define PCCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fdpc_free(pc); \
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
   pc->inner_g.resize(v.d); pc->ncols_g.resize(v.d);
   for (int k = 0; k < v.d; k++) {
     const int P = v.dims[k], M = P - 2;
@@ -369,8 +358,8 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     pc->ncols_g[k] = (unsigned)(v.G / M);                      // (dimension 0 of a slab: unused, its transforms run on pencils)
     std::vector<double> x(P);
     for (int i = 0; i < P; i++) x[i] = cos(i * 3.14159265358979323846 / (P - 1));          // elliptic.C:279, stokes.C:296
-    PCCHK(hipMalloc((void **)&pc->xs[k], P * sizeof(double)));
-    PCCHK(hipMemcpy(pc->xs[k], x.data(), P * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_OR(hipMalloc((void **)&pc->xs[k], P * sizeof(double)), fdpc_free(pc));
+    HIP_TRY_OR(hipMemcpy(pc->xs[k], x.data(), P * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
     std::array<double, 4> bk = BC_DIRICHLET;
     if (bc) for (int e = 0; e < 4; e++) bk[e] = bc[4 * k + e];
     const LineKey key(P, bk);
@@ -393,16 +382,16 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
         h[(size_t)2 * M + j] = (double)Lb[(size_t)2 * j]; h[(size_t)3 * M + j] = (double)Lb[(size_t)2 * j + 1];
       }
       for (int e = 0; e < 4; e++) h[(size_t)4 * M + e] = (double)Bi[e];
-      PCCHK(hipMalloc((void **)&lm.bcm, h.size() * sizeof(double)));
-      PCCHK(hipMemcpy(lm.bcm, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIP_TRY_OR(hipMalloc((void **)&lm.bcm, h.size() * sizeof(double)), fdpc_free(pc));
+      HIP_TRY_OR(hipMemcpy(lm.bcm, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
     } else if (!(kind == LINE_SPECTRAL ? spec_line(P, S, Si, lam) : fdm_line(P, S, Si, lam))) {
       fdpc_free(pc);
       return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point %s line operator failed", P, kind == LINE_SPECTRAL ? "spectral" : "finite-difference");
     }
-    centro_part(M, Si, 1, part); PCCHK(diffmat_from_dense(M, part.data(), 1, &lm.Fcs));
-    centro_part(M, Si, 0, part); PCCHK(diffmat_from_dense(M, part.data(), 0, &lm.Fca));
-    centro_part(M, S, 1, part);  PCCHK(diffmat_from_dense(M, part.data(), 1, &lm.Bcs));
-    centro_part(M, S, 0, part);  PCCHK(diffmat_from_dense(M, part.data(), 0, &lm.Bca));
+    centro_part(M, Si, 1, part); HIP_TRY_OR(diffmat_from_dense(M, part.data(), 1, &lm.Fcs), fdpc_free(pc));
+    centro_part(M, Si, 0, part); HIP_TRY_OR(diffmat_from_dense(M, part.data(), 0, &lm.Fca), fdpc_free(pc));
+    centro_part(M, S, 1, part);  HIP_TRY_OR(diffmat_from_dense(M, part.data(), 1, &lm.Bcs), fdpc_free(pc));
+    centro_part(M, S, 0, part);  HIP_TRY_OR(diffmat_from_dense(M, part.data(), 0, &lm.Bca), fdpc_free(pc));
     if (lm.parity) {
       // The same two transforms as ONE product each.  fdm_line orders the modes by parity (even modes at the positions
       // p < H, the q-th odd mode at M-1-q), so with e, o the parity split of a nodal line
@@ -415,17 +404,17 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
           E[(size_t)q * Hh + j] = Si[(size_t)q * M + j];
           O[(size_t)q * Hh + j] = (2 * q == m || 2 * j == m) ? 0.0L : Si[(size_t)(m - q) * M + j];
         }
-      PCCHK(diffmat_from_blocks(M, E.data(), O.data(), 1, &lm.Fraw));
+      HIP_TRY_OR(diffmat_from_blocks(M, E.data(), O.data(), 1, &lm.Fraw), fdpc_free(pc));
       for (int i = 0; i < Hh; i++)
         for (int j = 0; j < Hh; j++) {
           E[(size_t)i * Hh + j] = S[(size_t)i * M + j];
           O[(size_t)i * Hh + j] = (2 * j == m) ? 0.0L : S[(size_t)i * M + (m - j)];
         }
-      PCCHK(diffmat_from_blocks(M, E.data(), O.data(), 1, &lm.Braw));
+      HIP_TRY_OR(diffmat_from_blocks(M, E.data(), O.data(), 1, &lm.Braw), fdpc_free(pc));
     }
     std::vector<double> ld(M); for (int i = 0; i < M; i++) ld[i] = (double)lam[i];
-    PCCHK(hipMalloc((void **)&lm.lam, M * sizeof(double)));
-    PCCHK(hipMemcpy(lm.lam, ld.data(), M * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_OR(hipMalloc((void **)&lm.lam, M * sizeof(double)), fdpc_free(pc));
+    HIP_TRY_OR(hipMemcpy(lm.lam, ld.data(), M * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
     lm.ok = true;
     pc->lines[key] = lm;
     pc->ln[k] = &pc->lines[key];
@@ -433,18 +422,18 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
   if (kind == LINE_SPECTRAL) {
     const int M0 = v.dims[0] - 2;
     std::vector<double> l0(M0);
-    PCCHK(hipMemcpy(l0.data(), pc->ln[0]->lam, M0 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY_OR(hipMemcpy(l0.data(), pc->ln[0]->lam, M0 * sizeof(double), hipMemcpyDeviceToHost), fdpc_free(pc));
     for (int i = 0; i < M0; i++) l0[i] += sigma;
-    PCCHK(hipMalloc((void **)&pc->lam0, M0 * sizeof(double)));
-    PCCHK(hipMemcpy(pc->lam0, l0.data(), M0 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_OR(hipMalloc((void **)&pc->lam0, M0 * sizeof(double)), fdpc_free(pc));
+    HIP_TRY_OR(hipMemcpy(pc->lam0, l0.data(), M0 * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
   }
   const size_t gb = (size_t)(v.G > 0 ? v.G : 1) * sizeof(double);
-  if (kind == LINE_FD) PCCHK(hipMalloc((void **)&pc->cf, (2 * v.d + 1) * gb));
-  if (!bare) PCCHK(hipMalloc((void **)&pc->eta_g, gb));
-  PCCHK(hipMalloc((void **)&pc->t0, nf * gb)); PCCHK(hipMalloc((void **)&pc->t1, nf * gb));
+  if (kind == LINE_FD) HIP_TRY_OR(hipMalloc((void **)&pc->cf, (2 * v.d + 1) * gb), fdpc_free(pc));
+  if (!bare) HIP_TRY_OR(hipMalloc((void **)&pc->eta_g, gb), fdpc_free(pc));
+  HIP_TRY_OR(hipMalloc((void **)&pc->t0, nf * gb), fdpc_free(pc)); HIP_TRY_OR(hipMalloc((void **)&pc->t1, nf * gb), fdpc_free(pc));
   if (!bare) {
-    PCCHK(hipMalloc((void **)&pc->t2, nf * gb)); PCCHK(hipMalloc((void **)&pc->t3, nf * gb));
-    PCCHK(hipMalloc((void **)&pc->t4, nf * gb)); PCCHK(hipMalloc((void **)&pc->t5, nf * gb));
+    HIP_TRY_OR(hipMalloc((void **)&pc->t2, nf * gb), fdpc_free(pc)); HIP_TRY_OR(hipMalloc((void **)&pc->t3, nf * gb), fdpc_free(pc));
+    HIP_TRY_OR(hipMalloc((void **)&pc->t4, nf * gb), fdpc_free(pc)); HIP_TRY_OR(hipMalloc((void **)&pc->t5, nf * gb), fdpc_free(pc));
   }
   // the operand arrays of the pointwise steps that ride inside the line transforms (fdm_solve: filled on first use / by update);
   // allocated here so that no solve meets a hipMalloc.  A failed allocation only means the separate passes run.
@@ -454,7 +443,6 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     if (v.d >= 2 && v.d <= 3 && hipMalloc((void **)&pc->W, nf * gb) != hipSuccess) { pc->W = nullptr; (void)hipGetLastError(); }
     if (any_long && !bare && hipMalloc((void **)&pc->Einv, nf * gb) != hipSuccess) { pc->Einv = nullptr; (void)hipGetLastError(); }
   }
-#undef PCCHK
   *out = pc;
   return 0;
 }
@@ -467,8 +455,8 @@ static int fdpc_eta_inverse(chebhip_fdpc *pc, hipStream_t st) {
   for (int k = 0; k < pc->geo.d; k++) any_long = any_long || pc->geo.dims[k] - 2 > 64;
   if (!any_long) return 0;
   if (!pc->Einv) return 0;              // (allocated at create)
-  hipLaunchKernelGGL(k_eta_inverse, dim3(pgrid(pc->G), (unsigned)pc->nf), dim3(256), 0, st, pc->G, (const double *)pc->eta_g, pc->Einv);
-  PHIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_eta_inverse, dim3(grid1d(pc->G, 256, 4096), (unsigned)pc->nf), dim3(256), 0, st, pc->G, (const double *)pc->eta_g, pc->Einv);
+  HIP_TRY(hipGetLastError());
   pc->Einv_ok = true;
   return 0;
 }
@@ -481,15 +469,15 @@ static int fdpc_update(chebhip_fdpc *pc, hipStream_t st) {
   if (rc) return rc;
   if (pc->G == 0) { pc->assembled = true; return 0; }
   if (pc->slab || pc->kind == LINE_SPECTRAL) {            // no stencil: only eta at the interior nodes
-    hipLaunchKernelGGL(k_eta_g, dim3(pgrid(pc->N)), dim3(256), 0, st, pc->N, v.ixL, v.eta, pc->eta_g);
-    PHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_eta_g, dim3(grid1d(pc->N, 256, 4096)), dim3(256), 0, st, pc->N, v.ixL, v.eta, pc->eta_g);
+    HIP_TRY(hipGetLastError());
     pc->assembled = true;
     return fdpc_eta_inverse(pc, st);
   }
   GradPtrs gu; CoordPtrs xs;
   for (int k = 0; k < MAXD; k++) { gu.p[k] = k < v.d ? v.gradu[k] : nullptr; xs.p[k] = pc->xs[k]; }
-  hipLaunchKernelGGL(k_fd_assemble, dim3(pgrid(pc->N)), dim3(256), 0, st, pc->geo, pc->N, pc->G, v.ixL, v.eta, v.deta, gu, xs, pc->cf, pc->eta_g);
-  PHIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fd_assemble, dim3(grid1d(pc->N, 256, 4096)), dim3(256), 0, st, pc->geo, pc->N, pc->G, v.ixL, v.eta, v.deta, gu, xs, pc->cf, pc->eta_g);
+  HIP_TRY(hipGetLastError());
   pc->assembled = true;
   return fdpc_eta_inverse(pc, st);
 }
@@ -522,23 +510,23 @@ static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool b
                             const double *mul, bool *fused, const double *in_mul) {
   if (fused) *fused = false;
   if (ncols == 0) return 0;
-  if (in_mul && !backward) { PHIPCHK(sweep_launch(lm.Fraw, line_in_mul_params(ncols, inner, x, y, in_mul), st)); return 0; }
+  if (in_mul && !backward) { HIP_TRY(sweep_launch(lm.Fraw, line_in_mul_params(ncols, inner, x, y, in_mul), st)); return 0; }
   SweepParams sp = {};
   sp.ncols = ncols; sp.inner = inner;
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.alpha = 1.0;
   sp.out_mode = OUT_STORE;
   if (mul && fused && !backward && lm.parity) {
     SweepParams sm = sp; sm.out_mode = OUT_MUL; sm.acc = mul; sm.raw = 1;
-    if (sweep_vec_raw_eligible(lm.Fraw, sm)) { PHIPCHK(sweep_launch(lm.Fraw, sm, st)); *fused = true; return 0; }
+    if (sweep_vec_raw_eligible(lm.Fraw, sm)) { HIP_TRY(sweep_launch(lm.Fraw, sm, st)); *fused = true; return 0; }
   }
   if (lm.parity && sweep_vec_raw_eligible(backward ? lm.Braw : lm.Fraw, sp)) {       // one launch: the parity split is the transform's own
     sp.raw = backward ? 2 : 1;
-    PHIPCHK(sweep_launch(backward ? lm.Braw : lm.Fraw, sp, st));
+    HIP_TRY(sweep_launch(backward ? lm.Braw : lm.Fraw, sp, st));
     return 0;
   }
-  PHIPCHK(sweep_launch(backward ? lm.Bcs : lm.Fcs, sp, st));
+  HIP_TRY(sweep_launch(backward ? lm.Bcs : lm.Fcs, sp, st));
   sp.out_mode = OUT_ACC; sp.acc = y;
-  PHIPCHK(sweep_launch(backward ? lm.Bca : lm.Fca, sp, st));
+  HIP_TRY(sweep_launch(backward ? lm.Bca : lm.Fca, sp, st));
   return 0;
 }
 
@@ -559,7 +547,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
   if (over_eta) {
     if (pc->Einv_ok && !opt(OPT_FDM_PASSES) && d >= 2 && line_in_mul_ok(pc, order[0], r, a, pc->Einv)) in_mul = pc->Einv;
     else {
-      hipLaunchKernelGGL(k_resid_over_eta, dim3(pgrid(pc->G), (unsigned)pc->nf), dim3(256), 0, st, pc->G, pc->nf, r, (const double *)nullptr,
+      hipLaunchKernelGGL(k_resid_over_eta, dim3(grid1d(pc->G, 256, 4096), (unsigned)pc->nf), dim3(256), 0, st, pc->G, pc->nf, r, (const double *)nullptr,
                          (const double *)pc->eta_g, pc->t3);
       src = pc->t3;
     }
@@ -578,7 +566,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
     const int n1 = d == 3 ? pc->geo.dims[1] - 2 : 1;
     hipLaunchKernelGGL(k_modal_weights3, dim3((unsigned)((nl + 255) / 256), (unsigned)lines, (unsigned)pc->nf), dim3(256), 0, st, d, n1, nl, pc->G,
                        lam.p[0], lam.p[1], lam.p[2], pc->W);
-    PHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   // The last forward transform, the scaling and the first backward transform act on the same contiguous lines: one launch
   // (k_fdm_zsolve16) where those lines have 66 .. 128 interior points, an even number of them (option "fdm_z_separate" = 1: A/B)
@@ -604,7 +592,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
                          lam.p[0], lam.p[1], lam.p[2], (double *)src);
     } else if (pc->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "slab-mode preconditioner: d <= 3 and at most 65535 lines per slab");
     else
-      hipLaunchKernelGGL(k_modal_scale, dim3(pgrid(pc->G * pc->nf)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, lam, (double *)src);
+      hipLaunchKernelGGL(k_modal_scale, dim3(grid1d(pc->G * pc->nf, 256, 4096)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, lam, (double *)src);
   }
   if (zsolve) {
     const int M = pc->geo.dims[d - 1] - 2;
@@ -615,10 +603,10 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
     fp.d = d; fp.n1 = d == 3 ? pc->geo.dims[1] - 2 : 1; fp.flines = (unsigned)(pc->G / M);
     fp.l0 = lam.p[0]; fp.l1 = lam.p[1]; fp.lz = lam.p[d - 1];
     fp.FE = lm.Fraw.fragE; fp.FO = lm.Fraw.fragO; fp.BE = lm.Braw.fragE; fp.BO = lm.Braw.fragO;
-    hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); PHIPCHK(cu_err);
+    hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
     const unsigned grid = fp.ntiles < 3u * (unsigned)ncu ? fp.ntiles : 3u * (unsigned)ncu;       // three workgroups per CU
     if (grid) hipLaunchKernelGGL(k_fdm_zsolve16, dim3(grid), dim3(256), 0, st, fp);
-    PHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     src = a; std::swap(a, b);
   }
   for (int k = (zsolve ? d - 2 : d - 1); k >= 0; k--) {
@@ -626,7 +614,7 @@ static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t s
     int rc = line_transform(pc, k, true, src, dst, st); if (rc) return rc;
     src = dst; std::swap(a, b);
   }
-  PHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -637,18 +625,18 @@ static int fdpc_mult(chebhip_fdpc *pc, const double *x, double *y, hipStream_t s
   if (pc->G == 0) return 0;
   const long n = pc->G * pc->nf;
   const double *xin = x; double *yout = y;
-  if (pc->interleaved) { hipLaunchKernelGGL(k_deinterleave, dim3(pgrid(pc->G)), dim3(256), 0, st, pc->G, pc->nf, x, pc->t2); xin = pc->t2; yout = pc->t3; }
-  hipLaunchKernelGGL(k_fd_mult, dim3(pgrid(n)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, (const double *)pc->cf, xin, yout);
-  if (pc->interleaved) hipLaunchKernelGGL(k_interleave, dim3(pgrid(pc->G)), dim3(256), 0, st, pc->G, pc->nf, (const double *)pc->t3, y);
-  PHIPCHK(hipGetLastError());
+  if (pc->interleaved) { hipLaunchKernelGGL(k_deinterleave, dim3(grid1d(pc->G, 256, 4096)), dim3(256), 0, st, pc->G, pc->nf, x, pc->t2); xin = pc->t2; yout = pc->t3; }
+  hipLaunchKernelGGL(k_fd_mult, dim3(grid1d(n, 256, 4096)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, (const double *)pc->cf, xin, yout);
+  if (pc->interleaved) hipLaunchKernelGGL(k_interleave, dim3(grid1d(pc->G, 256, 4096)), dim3(256), 0, st, pc->G, pc->nf, (const double *)pc->t3, y);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // component-major callbacks of the inner solve: y = P x and z = P_1^-1 (r / eta)
 static int cb_fd_mult(void *ctx, const double *x, double *y, void *stream) {
   chebhip_fdpc *pc = (chebhip_fdpc *)ctx;
-  hipLaunchKernelGGL(k_fd_mult, dim3(pgrid(pc->G * pc->nf)), dim3(256), 0, (hipStream_t)stream, pc->geo, pc->G, pc->nf, (const double *)pc->cf, x, y);
-  PHIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_fd_mult, dim3(grid1d(pc->G * pc->nf, 256, 4096)), dim3(256), 0, (hipStream_t)stream, pc->geo, pc->G, pc->nf, (const double *)pc->cf, x, y);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 static int cb_fdm(void *ctx, const double *r, double *z, void *stream) {
@@ -665,12 +653,12 @@ static int fdpc_apply(chebhip_fdpc *pc, const double *r, double *z, hipStream_t 
   const double *rin = r; double *zc = z;
   if (pc->interleaved && pc->sweeps == 0) {    // z = P_1^-1 (r / eta), the division applied while the components are pulled apart
     zc = pc->t4;
-    hipLaunchKernelGGL(k_deinterleave_over_eta, dim3(pgrid(pc->G)), dim3(256), 0, st, pc->G, pc->nf, r, (const double *)pc->eta_g, pc->t3);
+    hipLaunchKernelGGL(k_deinterleave_over_eta, dim3(grid1d(pc->G, 256, 4096)), dim3(256), 0, st, pc->G, pc->nf, r, (const double *)pc->eta_g, pc->t3);
     int rc = fdm_solve(pc, pc->t3, zc, st); if (rc) return rc;
   } else if (pc->sweeps == 0) {                // z = P_1^-1 (r / eta)
     int rc = cb_fdm(pc, rin, zc, st); if (rc) return rc;
   } else {
-    if (pc->interleaved) { hipLaunchKernelGGL(k_deinterleave, dim3(pgrid(pc->G)), dim3(256), 0, st, pc->G, pc->nf, r, pc->t2); rin = pc->t2; zc = pc->t4; }
+    if (pc->interleaved) { hipLaunchKernelGGL(k_deinterleave, dim3(grid1d(pc->G, 256, 4096)), dim3(256), 0, st, pc->G, pc->nf, r, pc->t2); rin = pc->t2; zc = pc->t4; }
     // `sweeps` iterations of GMRES on P z = r, right-preconditioned by P_1^-1 (1/eta): monotone in the residual for
     // any coefficient state (a stationary defect correction diverges once eta varies by more than a factor ~2)
     if (!pc->inner || pc->inner_m != pc->sweeps) {
@@ -682,8 +670,8 @@ static int fdpc_apply(chebhip_fdpc *pc, const double *r, double *z, hipStream_t 
     int rc = chebhip_fgmres_set_tolerances(pc->inner, 1e-12, 1e-300, pc->sweeps); if (rc) return rc;
     if ((rc = chebhip_fgmres_solve(pc->inner, cb_fd_mult, pc, cb_fdm, pc, rin, zc, 0, st))) return rc;
   }
-  if (pc->interleaved) hipLaunchKernelGGL(k_interleave, dim3(pgrid(pc->G)), dim3(256), 0, st, pc->G, pc->nf, (const double *)zc, z);
-  PHIPCHK(hipGetLastError());
+  if (pc->interleaved) hipLaunchKernelGGL(k_interleave, dim3(grid1d(pc->G, 256, 4096)), dim3(256), 0, st, pc->G, pc->nf, (const double *)zc, z);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -1094,7 +1082,7 @@ extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, c
   const double *rhs = f_dev;
   if (g_dev) {                                 // (g = NULL: zero data, nothing to lift)
     BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), h->geo, bm, f_dev, g_dev, h->t);
-    PHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     rhs = h->t;
   }
   int rc = fdm_solve(h->pc, rhs, h->z, st); if (rc) return rc;
@@ -1111,7 +1099,7 @@ extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, c
       BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), h->geo, bm.m[k], h->dir[k][0], h->dir[k][1], (int)before,
                 src, g_dev, u_dev);
     }
-    PHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     before *= h->geo.P[k];
   }
   return 0;

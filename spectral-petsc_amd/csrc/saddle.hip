@@ -17,17 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <new>
 
-int chebhip_fail(int code, const char *fmt, ...);   // chebhip.hip
-
-#define SHIPCHK2(expr)                                                                                  \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
 namespace {
-static inline unsigned sgrid(long n) { long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-#define GS_LOOP(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 // full global vector (I nodes x [v_0 .. v_{d-1}, p]) <-> velocity (I x d) and pressure (I) parts: scatterGV / GP / VG / PG
 // cm: the velocity part is component-major (component c of node n at c I + n; the default of the inner solves, see stokes_saddle)
@@ -142,7 +132,7 @@ static int remove_mean(stokes_saddle *s, const double *in, double *out, hipStrea
   return 0;
 }
 static void eta_scale(stokes_saddle *s, const double *in, double *out, hipStream_t st) {
-  if (s->schur_jacobi) hipLaunchKernelGGL(k_eta_scale, dim3(sgrid(s->view.N)), dim3(256), 0, st, s->view.N, s->view.ixL, s->view.eta, in, out);
+  if (s->schur_jacobi) hipLaunchKernelGGL(k_eta_scale, dim3(chebhip::grid1d(s->view.N, 256, 4096)), dim3(256), 0, st, s->view.N, s->view.ixL, s->view.eta, in, out);
 }
 // One step of KSPSchur's left-preconditioned GMRES (PETSc's default side): y = P (eta .* (S x))
 static int schur_apply(void *ctx, const double *x, double *y, void *stream) {
@@ -151,7 +141,7 @@ static int schur_apply(void *ctx, const double *x, double *y, void *stream) {
   if (rc) return rc;
   eta_scale(s, y, y, (hipStream_t)stream);
   if ((rc = remove_mean(s, y, y, (hipStream_t)stream))) return rc;
-  SHIPCHK2(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 // KSPSolve(KSPVelocity, b, x)
@@ -267,7 +257,7 @@ extern "C" int stokes_saddle_apply(void *ctx, const double *x, double *y, void *
   chebhip::StageTimer tm(CHEBHIP_STAGE_SADDLE_APPLY, stream);
   hipStream_t st = (hipStream_t)stream;
   const long I = s->I; const int d = s->d, cm = s->cm ? 1 : 0;
-  const unsigned gg = sgrid(s->g), gpn = sgrid(s->gp), gvn = sgrid(s->gv);
+  const unsigned gg = chebhip::grid1d(s->g, 256, 4096), gpn = chebhip::grid1d(s->gp, 256, 4096), gvn = chebhip::grid1d(s->gv, 256, 4096);
   s->its_vel = s->its_schur = 0;
   int rc;
 #define SPLIT(V, P) hipLaunchKernelGGL(k_split, dim3(gg), dim3(256), 0, st, I, d, x, V, P, cm)
@@ -318,6 +308,6 @@ extern "C" int stokes_saddle_apply(void *ctx, const double *x, double *y, void *
   }
 #undef SPLIT
 #undef MERGE
-  SHIPCHK2(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -13,18 +13,12 @@
 // the pencil-row side of the backward one need no (un)packing: a peer's block is a run of whole pencil planes.
 #include "comm.h"
 #include "sweep.h"
+#include "ops.h"
 #include <cstdlib>
 #include <new>
 #include <vector>
 
-int chebhip_fail(int code, const char *fmt, ...);   // chebhip.hip
 using chebhip::XSeg;
-
-#define XHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -113,8 +107,8 @@ struct SlabX {
     // (one row of slack behind the pencils: with the NULL transport a rank reads its own pencil result with the peers' column counts)
     long wmax = 0; for (int s = 0; s < G; s++) wmax = m1[s] > wmax ? m1[s] : wmax;
     const size_t sb = (size_t)nf * (size_t)(Ns > 0 ? Ns : 1) * sizeof(double), pb = ((size_t)nf * (size_t)(Np > 0 ? Np : 1) + (size_t)(wmax + 1) * R) * sizeof(double);
-    XHIPCHK(hipMalloc((void **)&sendbuf, sb)); XHIPCHK(hipMalloc((void **)&recvbuf, sb));
-    XHIPCHK(hipMalloc((void **)&pen_in, pb)); XHIPCHK(hipMalloc((void **)&pen_out, pb));
+    HIP_TRY(hipMalloc((void **)&sendbuf, sb)); HIP_TRY(hipMalloc((void **)&recvbuf, sb));
+    HIP_TRY(hipMalloc((void **)&pen_in, pb)); HIP_TRY(hipMalloc((void **)&pen_out, pb));
     return 0;
   }
 
@@ -172,7 +166,7 @@ struct SlabX {
       const long s0r = push ? 0 : s0[rank];
       if (v2) hipLaunchKernelGGL((k_xpull_unpack<true>), grid, dim3(256), 0, st, split, xp, s0r, P1, R, Ns, acc, alpha, out);
       else hipLaunchKernelGGL((k_xpull_unpack<false>), grid, dim3(256), 0, st, split, xp, s0r, P1, R, Ns, acc, alpha, out);
-      XHIPCHK(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
     return chebhip::comm_mark(comm, 3, st);                                   // my reads of the peers' pencil results end here
   }
@@ -200,8 +194,8 @@ struct SlabX {
     Ns = m0[rank] * P1 * R; ncol = m1[rank] * R; Np = P0 * ncol;
     split.G = G; for (int s = 0; s <= G; s++) split.c1[s] = s1[s];
     const size_t sb = (size_t)nf * (size_t)(Ns > 0 ? Ns : 1) * sizeof(double), pb = (size_t)nf * (size_t)(Np > 0 ? Np : 1) * sizeof(double);
-    XHIPCHK(hipMalloc((void **)&sendbuf, sb)); XHIPCHK(hipMalloc((void **)&recvbuf, sb));
-    XHIPCHK(hipMalloc((void **)&pen_in, pb)); XHIPCHK(hipMalloc((void **)&pen_out, pb));
+    HIP_TRY(hipMalloc((void **)&sendbuf, sb)); HIP_TRY(hipMalloc((void **)&recvbuf, sb));
+    HIP_TRY(hipMalloc((void **)&pen_in, pb)); HIP_TRY(hipMalloc((void **)&pen_out, pb));
     return 0;
   }
 
@@ -223,7 +217,7 @@ struct SlabX {
       const dim3 grid((unsigned)(m0[rank] * G), (unsigned)nf);
       if (vec2(in, nullptr, nullptr)) hipLaunchKernelGGL((k_xpack<true>), grid, dim3(256), 0, st, split, m0[rank], P1, R, Ns, in, sendbuf, own(), own_in, Np);
       else hipLaunchKernelGGL((k_xpack<false>), grid, dim3(256), 0, st, split, m0[rank], P1, R, Ns, in, sendbuf, own(), own_in, Np);
-      XHIPCHK(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
     segs.clear();
     for (int s = 0; s < G; s++)
@@ -245,7 +239,7 @@ struct SlabX {
       const double *own_out = pen_out + s0[rank] * ncol;
       if (vec2(out, acc, nullptr)) hipLaunchKernelGGL((k_xunpack<true>), grid, dim3(256), 0, st, split, m0[rank], P1, R, Ns, (const double *)recvbuf, own(), own_out, Np, acc, alpha, out);
       else hipLaunchKernelGGL((k_xunpack<false>), grid, dim3(256), 0, st, split, m0[rank], P1, R, Ns, (const double *)recvbuf, own(), own_out, Np, acc, alpha, out);
-      XHIPCHK(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
     return 0;
   }

@@ -23,16 +23,6 @@
 
 using namespace chebhip;
 
-#define SHIPCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-static inline unsigned sgrid(long n) { long g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-static inline unsigned pgrid(long nlines) { long g = (nlines + 31) / 32; return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-#define GS_LOOP(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
-
 // Work-vector layout.  The reference keeps the d components of a node interleaved (rank d+1 plans with the
 // components innermost, stokes.C:284-290); the global vectors at the ABI keep that layout.  Inside the
 // operator the component index is OUTERMOST (field k occupies [k*N, (k+1)*N)): DV[i] is then DP[i] over d
@@ -893,10 +883,8 @@ __global__ __launch_bounds__(256, 2) void k_st_zfused16(const ZfParams p) {
 __global__ void k_st_fill(long n, double v, double *__restrict__ a) { GS_LOOP(i, n) a[i] = v; }
 
 // ---------------------------------------------------------------------------------------------
-struct stokes_op {
-  int d = 0;
-  std::vector<int> dims;
-  long N = 0, I = 0;
+struct stokes_op : BoxGrid {                                  // d, dims, N, gP0, lo: the handle's box (slab mode: see `slab` below)
+  long I = 0;                                                // interior nodes
   std::map<int, DiffMat> mats;
   // D with the end-point extrapolation of StokesPressureReduceOrder folded in, per extent (every extent of 3 .. 256 points;
   // in slab mode the matrix of dimension 0 is applied on the pencils): gp[i] = matsP * pL needs no extrapolation pass -- see st_pressure_gradient
@@ -947,7 +935,6 @@ struct stokes_op {
   // sweep it calls next (stokes_pencil_gather_try), so that the d directions of a gradient / divergence are ONE launch; what the driver
   // did not take is launched by st_flush_pending
   int npend = 0; const DiffMat *pend_m[8] = {}; SweepParams pend_sp[8] = {};
-  int gP0 = 0, lo = 0;
   stokes_dim0_fn dim0 = nullptr;
   void *dim0_ctx = nullptr;
   bool deta_nonzero = false;                                 // deta == 0 everywhere: the node loop skips S0
@@ -957,7 +944,7 @@ struct stokes_op {
 // Work arrays of one handle.  (Round 4 tried starting every array at a different multiple of 4352 bytes of its allocation, against
 // a suspected HBM channel / bank alignment of the ~30 arrays a node loop streams: 128^3 power-law StokesMatMult 287 -> 305 us,
 // StokesFunction 305 -> 310 us in an A/B in one process -- the 16-MiB-aligned allocations are the better placement.  Removed.)
-static int st_alloc(double **p, size_t n) { SHIPCHK(hipMalloc((void **)p, n * sizeof(double))); SHIPCHK(hipMemset(*p, 0, n * sizeof(double))); return 0; }
+static int st_alloc(double **p, size_t n) { HIP_TRY(hipMalloc((void **)p, n * sizeof(double))); HIP_TRY(hipMemset(*p, 0, n * sizeof(double))); return 0; }
 static void st_free(double *p) { if (p) (void)hipFree(p); }
 
 extern "C" int stokes_op_destroy(stokes_op *op) {
@@ -983,13 +970,6 @@ extern "C" int stokes_op_destroy(stokes_op *op) {
 }
 
 static bool st_zfused_ok(stokes_op *op);
-// boundary node of the GLOBAL grid?  ind: local multi-index (dimension 0 is offset by op->lo in slab mode)
-static inline bool st_is_bdy(const stokes_op *op, const int *ind) {
-  const int g0 = ind[0] + op->lo;
-  if (g0 == 0 || g0 == op->gP0 - 1) return true;
-  for (int j = 1; j < op->d; j++) if (ind[j] == 0 || ind[j] == op->dims[j] - 1) return true;
-  return false;
-}
 
 static int st_create(int d, const int *gdims, int lo, int hi, stokes_dim0_fn dim0, void *dim0_ctx, stokes_op **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
@@ -1000,51 +980,40 @@ static int st_create(int d, const int *gdims, int lo, int hi, stokes_dim0_fn dim
     if (gdims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d but must be >= 3", k, gdims[k]);
     if (gdims[k] > 4096) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: at most 4096 points per line", k, gdims[k]);
   }
-  if (slab && !(0 <= lo && lo < hi && hi <= gdims[0])) return chebhip_fail(CHEBHIP_ERR_ARG, "slab planes [%d, %d) outside 0..%d", lo, hi, gdims[0]);
-  std::vector<int> dims(gdims, gdims + d);
-  if (slab) dims[0] = hi - lo; else { lo = 0; hi = gdims[0]; }
-  long N = 1;
-  for (int k = 0; k < d; k++) {
-    N *= dims[k];
-    if (N * d > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "tensor of more than 2^31-1 values");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "no usable HIP device; libchebhip has no CPU fallback");
+  if (slab) { int rc = BoxGrid::check_slab(lo, hi, gdims[0]); if (rc) return rc; }
+  else { lo = 0; hi = gdims[0]; }
+  BoxGrid box;
+  box.set_box(d, gdims, lo, hi);             // extents of at most 4096 and d <= 3: N cannot overflow
+  const std::vector<int> &dims = box.dims;
+  const long N = box.N;
+  if (N * d > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "tensor of more than 2^31-1 values");
+  { int rc = require_device(); if (rc) return rc; }
   stokes_op *op = new (std::nothrow) stokes_op;
   if (!op) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
-  op->d = d; op->dims = dims; op->N = N;
-  op->slab = slab; op->gP0 = gdims[0]; op->lo = lo; op->dim0 = dim0; op->dim0_ctx = dim0_ctx;
-#define OPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { stokes_op_destroy(op); \
-    return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
+  static_cast<BoxGrid &>(*op) = box;
+  op->slab = slab; op->dim0 = dim0; op->dim0_ctx = dim0_ctx;
 #define OPRC(expr) do { int rc_ = (expr); if (rc_) { stokes_op_destroy(op); return rc_; } } while (0)
   for (int k = 0; k < d; k++)      // dimension 0: the global extent (in slab mode it is applied on pencils)
-    if (!op->mats.count(gdims[k])) { DiffMat m; OPCHK(diffmat_create(gdims[k], &m)); op->mats[gdims[k]] = m; }
+    if (!op->mats.count(gdims[k])) { DiffMat m; HIP_TRY_OR(diffmat_create(gdims[k], &m), stokes_op_destroy(op)); op->mats[gdims[k]] = m; }
   op->pext = !opt(OPT_PRESSURE_PASSES);                     // "pressure_passes": the three extrapolation passes of the reference (A/B)
   for (int k = 0; k < d; k++) op->pext = op->pext && gdims[k] >= 3 && op->mats[gdims[k]].KS != 0;
   if (op->pext)
     for (int k = 0; k < d; k++)
-      if (!op->matsP.count(gdims[k])) { DiffMat m; OPCHK(diffmat_create_pext(gdims[k], &m)); op->matsP[gdims[k]] = m; }
+      if (!op->matsP.count(gdims[k])) { DiffMat m; HIP_TRY_OR(diffmat_create_pext(gdims[k], &m), stokes_op_destroy(op)); op->matsP[gdims[k]] = m; }
   op->uniform_ok = op->pext && !slab && d >= 2 && !opt(OPT_GENERAL_VISCOUS);        // "general_viscous": A/B
   if (op->uniform_ok)
     for (int k = 0; k < d; k++)
-      if (!op->matsDD.count(gdims[k])) { DiffMat m; OPCHK(diffmat_create_dd(gdims[k], &m)); op->matsDD[gdims[k]] = m; }
+      if (!op->matsDD.count(gdims[k])) { DiffMat m; HIP_TRY_OR(diffmat_create_dd(gdims[k], &m), stokes_op_destroy(op)); op->matsDD[gdims[k]] = m; }
   {  // ixLP of StokesSetupDomain (stokes.C:791-879): interior index or -1, BlockIt order (of this slab)
-    std::vector<int> ixL((size_t)N), ind(d, 0);
-    long g = 0;
-    for (long l = 0; l < N; l++) {
-      ixL[l] = st_is_bdy(op, ind.data()) ? -1 : (int)g++;
-      for (int j = d - 1; j >= 0; j--) { if (++ind[j] < dims[j]) break; ind[j] = 0; }
-    }
-    op->I = g;
-    OPCHK(hipMalloc((void **)&op->ixL, (size_t)N * sizeof(int)));
-    OPCHK(hipMemcpy(op->ixL, ixL.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    std::vector<int> ixL;
+    op->I = op->interior_index(ixL);
+    HIP_TRY_OR(hipMalloc((void **)&op->ixL, (size_t)N * sizeof(int)), stokes_op_destroy(op));
+    HIP_TRY_OR(hipMemcpy(op->ixL, ixL.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice), stokes_op_destroy(op));
   }
   op->innerP.resize(d); op->ncolsP.resize(d); op->innerV.resize(d); op->ncolsV.resize(d);
   for (int k = 0; k < d; k++) {
-    unsigned in = 1; for (int r = k + 1; r < d; r++) in *= dims[r];
-    op->innerP[k] = in; op->ncolsP[k] = (unsigned)(N / dims[k]);
-    op->innerV[k] = in; op->ncolsV[k] = (unsigned)(N / dims[k]) * d;          // DV[k]: the same lines for d stacked fields
+    op->innerP[k] = box.inner(k); op->ncolsP[k] = box.ncols(k);
+    op->innerV[k] = box.inner(k); op->ncolsV[k] = box.ncols(k) * d;           // DV[k]: the same lines for d stacked fields
   }
   const size_t nd = (size_t)N * d;
   // Slab mode: the gradient along dimension 0 and the pressure gradient along it share ONE round trip to pencils (d + 1 stacked
@@ -1080,7 +1049,7 @@ static int st_create(int d, const int *gdims, int lo, int hi, stokes_dim0_fn dim
   // what one launch leaves in the caches for the next).  profiles/r05_placement*.txt, r05_arena_sweep*.txt; DESIGN_history.md.)
   for (const Req &r : reqs) OPRC(st_alloc(r.p, r.n));
   if (slab) { op->gp[0] = op->V[0] + nd; op->pL = op->xL + nd; }
-  hipLaunchKernelGGL(k_st_fill, dim3(sgrid(N)), dim3(256), 0, nullptr, N, 1.0, op->eta);
+  hipLaunchKernelGGL(k_st_fill, dim3(grid1d(N, 256, 4096)), dim3(256), 0, nullptr, N, 1.0, op->eta);
   // Lagrange weights of the interior nodes x_1..x_{P-2} at x_0 and x_{P-1} (the polyInterp functional)
   op->w0.assign(d, nullptr); op->w1.assign(d, nullptr);
   for (int k = 0; k < d; k++) {
@@ -1093,10 +1062,10 @@ static int st_create(int d, const int *gdims, int lo, int hi, stokes_dim0_fn dim
       for (int q = 1; q <= m; q++) if (q != j) { l0 *= (x[0] - x[q]) / (x[j] - x[q]); l1 *= (x[P - 1] - x[q]) / (x[j] - x[q]); }
       a[j - 1] = (double)l0; b[j - 1] = (double)l1;
     }
-    OPCHK(hipMalloc((void **)&op->w0[k], (size_t)m * sizeof(double)));
-    OPCHK(hipMalloc((void **)&op->w1[k], (size_t)m * sizeof(double)));
-    OPCHK(hipMemcpy(op->w0[k], a.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(op->w1[k], b.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_OR(hipMalloc((void **)&op->w0[k], (size_t)m * sizeof(double)), stokes_op_destroy(op));
+    HIP_TRY_OR(hipMalloc((void **)&op->w1[k], (size_t)m * sizeof(double)), stokes_op_destroy(op));
+    HIP_TRY_OR(hipMemcpy(op->w0[k], a.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice), stokes_op_destroy(op));
+    HIP_TRY_OR(hipMemcpy(op->w1[k], b.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice), stokes_op_destroy(op));
   }
   {
     // The pressure chain on a second stream pays on large grids (128^3 StokesMatMult 298 against 325 us, 120^3 260 against
@@ -1104,16 +1073,14 @@ static int st_create(int d, const int *gdims, int lo, int hi, stokes_dim0_fn dim
     // 62 us with the one-launch gradients of the one-stream path; 96^3 .. 112^3: a tie), so smaller grids stay on one stream.
     // Round 5: where the fused-z route runs (st_zfused_ok) the pressure-gradient sweeps are jobs of its first launch instead, and
     // the second stream is only made with option "stokes_pressure_stream" = 1 (A/B)
-    op->N = N;
     const bool z1 = st_zfused_ok(op) && !opt(OPT_STOKES_PRESSURE_STREAM);
     if (!opt(OPT_STOKES_SINGLE_STREAM) && !slab && N >= 1200000 && !z1) {         // "stokes_single_stream": read when the handle is created
-      OPCHK(hipStreamCreateWithFlags(&op->aux, hipStreamNonBlocking));
-      OPCHK(hipEventCreateWithFlags(&op->ev_fork, hipEventDisableTiming));
-      OPCHK(hipEventCreateWithFlags(&op->ev_join, hipEventDisableTiming));
+      HIP_TRY_OR(hipStreamCreateWithFlags(&op->aux, hipStreamNonBlocking), stokes_op_destroy(op));
+      HIP_TRY_OR(hipEventCreateWithFlags(&op->ev_fork, hipEventDisableTiming), stokes_op_destroy(op));
+      HIP_TRY_OR(hipEventCreateWithFlags(&op->ev_join, hipEventDisableTiming), stokes_op_destroy(op));
     }
   }
-  OPCHK(hipDeviceSynchronize());
-#undef OPCHK
+  HIP_TRY_OR(hipDeviceSynchronize(), stokes_op_destroy(op));
 #undef OPRC
   *out = op;
   return 0;
@@ -1138,7 +1105,6 @@ extern "C" int stokes_op_create_slab(int d, const int *dims, int lo, int hi, sto
   if (!dim0) return chebhip_fail(CHEBHIP_ERR_ARG, "slab mode needs the dimension-0 callback");
   return st_create(d, dims, lo, hi, dim0, dim0_ctx, out);
 }
-
 
 int stokes_op_fd_view(stokes_op *op, chebhip::FdView *v) {
   if (!op || !v) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
@@ -1177,22 +1143,20 @@ extern "C" int stokes_op_set_dirichlet(stokes_op *op, const double *values) {
   if (!op || !values) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   const int d = op->d;
   std::vector<double> loc((size_t)op->N * d, 0.0);
-  std::vector<int> ind(d, 0);
   long dd = 0;
-  for (long l = 0; l < op->N; l++) {                      // ixDL order: boundary nodes in BlockIt order, d values each
-    if (st_is_bdy(op, ind.data())) for (int k = 0; k < d; k++) loc[(size_t)k * op->N + l] = values[dd++];
-    for (int j = d - 1; j >= 0; j--) { if (++ind[j] < op->dims[j]) break; ind[j] = 0; }
-  }
-  if (!op->dirloc) SHIPCHK(hipMalloc((void **)&op->dirloc, loc.size() * sizeof(double)));
-  SHIPCHK(hipMemcpy(op->dirloc, loc.data(), loc.size() * sizeof(double), hipMemcpyHostToDevice));
+  op->for_each_node([&](long l, const int *, bool bdy) {   // ixDL order: boundary nodes in BlockIt order, d values each
+    if (bdy) for (int k = 0; k < d; k++) loc[(size_t)k * op->N + l] = values[dd++];
+  });
+  if (!op->dirloc) HIP_TRY(hipMalloc((void **)&op->dirloc, loc.size() * sizeof(double)));
+  HIP_TRY(hipMemcpy(op->dirloc, loc.data(), loc.size() * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
 extern "C" int stokes_op_set_force(stokes_op *op, const double *force) {
   if (!op || !force) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   const size_t g = (size_t)op->I * (op->d + 1);
-  if (!op->force) SHIPCHK(hipMalloc((void **)&op->force, (g ? g : 1) * sizeof(double)));
-  SHIPCHK(hipMemcpy(op->force, force, g * sizeof(double), hipMemcpyHostToDevice));
+  if (!op->force) HIP_TRY(hipMalloc((void **)&op->force, (g ? g : 1) * sizeof(double)));
+  HIP_TRY(hipMemcpy(op->force, force, g * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1217,12 +1181,12 @@ static int sweep_plain(stokes_op *op, bool vec, int k, const double *x, double *
   sp.ncols = vec ? op->ncolsV[k] : op->ncolsP[k];
   sp.inner = op->innerP[k];
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.out_mode = out_mode; sp.acc = acc; sp.alpha = alpha;
-  SHIPCHK(sweep_launch(pext ? op->matsP[op->dims[k]] : op->mats[op->dims[k]], sp, st));
+  HIP_TRY(sweep_launch(pext ? op->matsP[op->dims[k]] : op->mats[op->dims[k]], sp, st));
   return 0;
 }
 
-#define ST_D(KERNEL, ...) do { if (d == 2) hipLaunchKernelGGL((KERNEL<2>), dim3(sgrid(op->N)), dim3(256), 0, st, op->N, __VA_ARGS__); \
-                               else hipLaunchKernelGGL((KERNEL<3>), dim3(sgrid(op->N)), dim3(256), 0, st, op->N, __VA_ARGS__); } while (0)
+#define ST_D(KERNEL, ...) do { if (d == 2) hipLaunchKernelGGL((KERNEL<2>), dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, __VA_ARGS__); \
+                               else hipLaunchKernelGGL((KERNEL<3>), dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, __VA_ARGS__); } while (0)
 
 // the grid of st_pair_ix: serial 3-D handles with an even last extent (option "general_kernels": the table)
 static inline StGrid st_grid(const stokes_op *op) {
@@ -1284,7 +1248,7 @@ static void st_out_full(stokes_op *op, const double *force, double *out, hipStre
 static int st_flush_pending(stokes_op *op, hipStream_t st) {
   if (op->npend <= 0) return 0;
   const int n = op->npend; op->npend = 0;
-  SHIPCHK(sweep_launch_multi(n, op->pend_m, op->pend_sp, st));
+  HIP_TRY(sweep_launch_multi(n, op->pend_m, op->pend_sp, st));
   return 0;
 }
 static int sweeps_multi(stokes_op *op, bool vec, int k0, const double *const *x, double *const *y, double alpha, hipStream_t st, bool spaced = false,
@@ -1303,7 +1267,7 @@ static int sweeps_multi(stokes_op *op, bool vec, int k0, const double *const *x,
     m[n] = pext ? &op->matsP[op->dims[k]] : &op->mats[op->dims[k]];
   }
   if (park && op->npend + n <= 8) { for (int j = 0; j < n; j++) { op->pend_m[op->npend] = m[j]; op->pend_sp[op->npend++] = sp[j]; } return 0; }
-  SHIPCHK(sweep_launch_multi(n, m, sp, st));
+  HIP_TRY(sweep_launch_multi(n, m, sp, st));
   return 0;
 }
 
@@ -1357,7 +1321,7 @@ static int st_gradient_and_pressure_gradient(stokes_op *op, double *const *out, 
       sp[n].in0 = vec ? op->xL : op->pL; sp[n].in_mode = IN_PLAIN; sp[n].out = vec ? out[k] : op->gp[k]; sp[n].out_mode = OUT_STORE; sp[n].alpha = 1.0;
       m[n] = (!vec && op->pext) ? &op->matsP[op->dims[k]] : &op->mats[op->dims[k]];
     }
-  SHIPCHK(sweep_launch_multi(n, m, sp, st));
+  HIP_TRY(sweep_launch_multi(n, m, sp, st));
   return 0;
 }
 static inline bool st_one_launch_gradients(const stokes_op *op) { return !op->aux && !op->slab; }
@@ -1413,7 +1377,7 @@ static int st_viscous_uniform(stokes_op *op, bool with_pressure, hipStream_t st,
   for (int k = 0; k < d; k++) job(op->matsDD[op->dims[k]], true, k, xloc, op->V[k], a);
   for (int k = 0; k < d; k++) job(op->mats[op->dims[k]], false, k, xloc + (size_t)k * N, op->yL + (size_t)k * N, 1.0);
   if (with_pressure) for (int k = 0; k < d; k++) job(op->matsP[op->dims[k]], false, k, op->pL, op->gp[k], 1.0);
-  SHIPCHK(sweep_launch_multi(n, m, sp, st));
+  HIP_TRY(sweep_launch_multi(n, m, sp, st));
   // Lines of at most 64 points (the launch-bound sizes): the sweeps of grad div v read div v = (t_0 + t_1) + t_2 from its three
   // terms as they load (IN_SUM3: the same sum in the same order), so the pointwise pass between the two sweep launches -- one
   // more dependent launch on a chain that is all launch latency -- is not run; *split_div tells the caller that p2 was not formed.
@@ -1426,14 +1390,14 @@ static int st_viscous_uniform(stokes_op *op, bool with_pressure, hipStream_t st,
         sp[n - 1].in_mode = IN_SUM3; sp[n - 1].in1 = op->yL + N; sp[n - 1].in2 = op->yL + 2 * N;
       }
       bool done = false;
-      SHIPCHK(sweep_launch_multi_try(n, m, sp, st, &done));
+      HIP_TRY(sweep_launch_multi_try(n, m, sp, st, &done));
       if (done) { *split_div = true; return 0; }
     }
   }
-  hipLaunchKernelGGL(k_st_sum_fields, dim3(sgrid(N)), dim3(256), 0, st, N, d, (const double *)op->yL, op->p2);
+  hipLaunchKernelGGL(k_st_sum_fields, dim3(grid1d(N, 256, 4096)), dim3(256), 0, st, N, d, (const double *)op->yL, op->p2);
   n = 0;
   for (int c = 0; c < d; c++) job(op->mats[op->dims[c]], false, c, op->p2, op->yLx[1] + (size_t)c * N, a);
-  SHIPCHK(sweep_launch_multi(n, m, sp, st));
+  HIP_TRY(sweep_launch_multi(n, m, sp, st));
   return 0;
 }
 
@@ -1455,7 +1419,7 @@ static int st_sync_strain(stokes_op *op, hipStream_t st) {
   int rc = sweeps_multi(op, true, 0, x, op->strain, 1.0, st); if (rc) return rc;
   const int d = op->d;
   ST_D(k_st_symmetrise, op->strain[0], op->strain[1], op->strain[2]);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   op->strain_stale = false;
   return 0;
 }
@@ -1477,7 +1441,7 @@ static int st_zfused_launch(stokes_op *op, int mode, ZfParams zp, hipStream_t st
   zp.yz = op->yLx[2];
   const DiffMat &m = op->mats[zp.P];
   zp.fragE = m.fragE; zp.fragO = m.fragO;
-  hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); SHIPCHK(cu_err);
+  hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
   const unsigned grid = zp.ntiles < 2u * (unsigned)ncu ? zp.ntiles : 2u * (unsigned)ncu;      // two workgroups per CU
   if (zp.pL) {
     if (mode == 2) hipLaunchKernelGGL((k_st_zfused16<2, true>), dim3(grid), dim3(256), 0, st, zp);
@@ -1488,7 +1452,7 @@ static int st_zfused_launch(stokes_op *op, int mode, ZfParams zp, hipStream_t st
     else if (mode == 1) hipLaunchKernelGGL((k_st_zfused16<1, false>), dim3(grid), dim3(256), 0, st, zp);
     else hipLaunchKernelGGL((k_st_zfused16<0, false>), dim3(grid), dim3(256), 0, st, zp);
   }
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 // Round 5: the pressure inside the stress.  -sum_j D_j tau_jk + DP_k p = -(sum_{j != k} D_j tau_jk + D_k (tau_kk - p_ext)) with p_ext the
@@ -1509,7 +1473,7 @@ static int st_pressure_faces(stokes_op *op, hipStream_t st) {
   long g = (lines + 3) / 4; if (g > 4096) g = 4096; if (g < 1) g = 1;
   hipLaunchKernelGGL(k_st_pfaces, dim3((unsigned)g, 3), dim3(256), 0, st, op->pL, P0, P1, P2, (const double *)op->w0[0], (const double *)op->w1[0],
                      (const double *)op->w0[1], (const double *)op->w1[1], (const double *)op->w0[2], (const double *)op->w1[2]);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 // The x / y gradient of the fused-z route, out[0] = D_x xL, out[1] = D_y xL (3 fields each), and -- with_pressure -- the three
@@ -1534,7 +1498,7 @@ static int st_xy_gradient(stokes_op *op, double *const *out, bool with_pressure,
       sp[n].in0 = op->pL; sp[n].in_mode = IN_PLAIN; sp[n].out = op->gp[k]; sp[n].out_mode = OUT_STORE; sp[n].alpha = 1.0;
       m[n] = op->pext ? &op->matsP[op->dims[k]] : &op->mats[op->dims[k]];
     }
-  SHIPCHK(sweep_launch_multi(n, m, sp, st));
+  HIP_TRY(sweep_launch_multi(n, m, sp, st));
   return 0;
 }
 static int st_viscous_jacobian_zfused(stokes_op *op, double *div, hipStream_t st, bool with_pressure = false, bool fold = false) {
@@ -1555,9 +1519,9 @@ static int st_viscous_jacobian(stokes_op *op, double *div, hipStream_t st, bool 
   const int d = op->d;
   if (!have_gradient && st_zfused_ok(op)) return st_viscous_jacobian_zfused(op, div, st);
   if (!have_gradient) { int rc = st_gradient(op, op->V, st); if (rc) return rc; }                                               // :639
-#define NODE_VV(D_, DETA_) hipLaunchKernelGGL((k_st_node_vv<D_, DETA_>), dim3(sgrid(op->N)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
+#define NODE_VV(D_, DETA_) hipLaunchKernelGGL((k_st_node_vv<D_, DETA_>), dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
     (const double *)op->strain[0], (const double *)op->strain[1], (const double *)op->strain[2], (const double *)op->eta, (const double *)op->deta, div)
-#define NODE_VV_PAIR(DETA_, SYM_) hipLaunchKernelGGL((k_st_node_vv_pair<DETA_, SYM_>), dim3(sgrid(op->N >> 1)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
+#define NODE_VV_PAIR(DETA_, SYM_) hipLaunchKernelGGL((k_st_node_vv_pair<DETA_, SYM_>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
     (const double *)op->strain[0], (const double *)op->strain[1], (const double *)op->strain[2], (const double *)op->eta, (const double *)op->deta, div, op->T)
   if (d == 2) { if (op->deta_nonzero) NODE_VV(2, true); else NODE_VV(2, false); }
   else if ((op->N & 1) == 0) { if (op->deta_nonzero) NODE_VV_PAIR(true, false); else NODE_VV_PAIR(false, false); }
@@ -1588,10 +1552,10 @@ static void st_pressure_extrapolate(stokes_op *op, double *pL, hipStream_t st) {
                        (int)p, (const double *)op->w0[2], (const double *)op->w1[2]);
   }
   if (ni > 0)
-    hipLaunchKernelGGL(k_st_preduce, dim3(pgrid(ni * p)), dim3(256), 0, st, pL, ni, i_lo, n * p, p, 0L, 1L, p,
+    hipLaunchKernelGGL(k_st_preduce, dim3(grid1d(ni * p, 32, 8192)), dim3(256), 0, st, pL, ni, i_lo, n * p, p, 0L, 1L, p,
                        (int)n, (const double *)op->w0[1], (const double *)op->w1[1]);
   if (!op->slab)
-    hipLaunchKernelGGL(k_st_preduce, dim3(pgrid(n * p)), dim3(256), 0, st, pL, n, 0L, p, p, 0L, 1L, n * p,
+    hipLaunchKernelGGL(k_st_preduce, dim3(grid1d(n * p, 32, 8192)), dim3(256), 0, st, pL, n, 0L, p, p, 0L, 1L, n * p,
                        (int)m, (const double *)op->w0[0], (const double *)op->w1[0]);
 }
 
@@ -1617,14 +1581,14 @@ static int st_pressure_gradient(stokes_op *op, hipStream_t st) {
 // pressure chain on the second stream, between the gather (already enqueued on st) and the final scatter
 static int st_pressure_gradient_forked(stokes_op *op, hipStream_t st) {
   if (!op->aux) return st_pressure_gradient(op, st);
-  SHIPCHK(hipEventRecord(op->ev_fork, st));
-  SHIPCHK(hipStreamWaitEvent(op->aux, op->ev_fork, 0));
+  HIP_TRY(hipEventRecord(op->ev_fork, st));
+  HIP_TRY(hipStreamWaitEvent(op->aux, op->ev_fork, 0));
   return st_pressure_gradient(op, op->aux);
 }
 static int st_join(stokes_op *op, hipStream_t st) {
   if (!op->aux) return 0;
-  SHIPCHK(hipEventRecord(op->ev_join, op->aux));
-  SHIPCHK(hipStreamWaitEvent(st, op->ev_join, 0));
+  HIP_TRY(hipEventRecord(op->ev_join, op->aux));
+  HIP_TRY(hipStreamWaitEvent(st, op->ev_join, 0));
   return 0;
 }
 
@@ -1663,15 +1627,15 @@ static int st_mult_vv(stokes_op *op, const double *vG, double *out, hipStream_t 
   if (st_uniform(op)) {
     bool split = false;                                    // (no pressure rows here: whether div v was formed as p2 does not matter)
     int rc = st_viscous_uniform(op, false, st, nullptr, 0.0, &split); if (rc) return rc;
-    if (pairs) { st_out_cm(op, 4, op->V[0], op->V[1], op->V[2], op->yLx[1], out, st); SHIPCHK(hipGetLastError()); return 0; }
+    if (pairs) { st_out_cm(op, 4, op->V[0], op->V[1], op->V[2], op->yLx[1], out, st); HIP_TRY(hipGetLastError()); return 0; }
     ST_OUT(gs, (const int *)op->ixL, CDP(op->V[0]), CDP(op->V[1]), CDP(op->V[2]), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), 0, CDP(nullptr), out, CDP(op->yLx[1]), cs);
-    SHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   int rc = st_viscous_jacobian(op, nullptr, st); if (rc) return rc;
-  if (pairs) { st_out_cm(op, 3, op->yL, op->yLx[1], op->yLx[2], nullptr, out, st); SHIPCHK(hipGetLastError()); return 0; }
+  if (pairs) { st_out_cm(op, 3, op->yL, op->yLx[1], op->yLx[2], nullptr, out, st); HIP_TRY(hipGetLastError()); return 0; }
   ST_OUT(gs, (const int *)op->ixL, CDP(op->yL), CDP(op->yLx[1]), CDP(op->yLx[2]), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), 0, CDP(nullptr), out, CDP(nullptr), cs);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 static int st_mult_pv(stokes_op *op, const double *vG, double *pout, hipStream_t st, bool cm) {
@@ -1689,17 +1653,17 @@ static int st_mult_pv(stokes_op *op, const double *vG, double *pout, hipStream_t
       m[k] = &op->mats[op->dims[k]];
     }
     bool done = false;
-    SHIPCHK(sweep_launch_multi_try(d, m, sp, st, &done));
+    HIP_TRY(sweep_launch_multi_try(d, m, sp, st, &done));
     if (done) {
       ST_OUT(1, (const int *)op->ixL, CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(op->yL), 0, CDP(nullptr), pout, CDP(nullptr), 1L,
              CDP(op->yL + op->N), CDP(d == 3 ? op->yL + 2 * op->N : nullptr));
-      SHIPCHK(hipGetLastError());
+      HIP_TRY(hipGetLastError());
       return 0;
     }
   }
   int rc = st_divergence(op, st); if (rc) return rc;
   ST_OUT(1, (const int *)op->ixL, CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(op->p2), 0, CDP(nullptr), pout, CDP(nullptr), 1L);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 static int st_mult_vp(stokes_op *op, const double *pG, double *vout, hipStream_t st, bool cm) {
@@ -1707,10 +1671,10 @@ static int st_mult_vp(stokes_op *op, const double *pG, double *vout, hipStream_t
   st_local(op, 1, 0, pG, nullptr, nullptr, op->pL, st);
   if (op->slab) op->gp[0] = op->V[0] + (size_t)op->d * op->N;
   int rc = st_pressure_gradient(op, st); if (rc) return rc;
-  if (st_cm_pairs(op, cm)) { st_out_cm(op, 1, op->gp[0], op->gp[1], op->gp[2], nullptr, vout, st, true); SHIPCHK(hipGetLastError()); return 0; }
+  if (st_cm_pairs(op, cm)) { st_out_cm(op, 1, op->gp[0], op->gp[1], op->gp[2], nullptr, vout, st, true); HIP_TRY(hipGetLastError()); return 0; }
   ST_OUT(cm ? 1 : d, (const int *)op->ixL, CDP(nullptr), CDP(nullptr), CDP(nullptr), CDP(op->gp[0]), CDP(op->gp[1]), CDP(op->gp[2]), CDP(nullptr), 0, CDP(nullptr), vout, CDP(nullptr),
          cm ? op->I : 1L);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -1760,7 +1724,7 @@ extern "C" int stokes_op_mult(stokes_op *op, const double *xG, double *yG, void 
     const bool pairs = st_out_pairs(op, op->V[0], op->V[1], op->V[2], op->yLx[1], nullptr, yG);
     if ((rc = st_viscous_uniform(op, true, st, nullptr, 0.0, pairs ? &split : nullptr))) return rc;
     st_out_full(op, nullptr, yG, st, op->V[0], op->V[1], op->V[2], op->yLx[1], split ? op->yL : nullptr);
-    SHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   if (op->slab) {
@@ -1769,7 +1733,7 @@ extern "C" int stokes_op_mult(stokes_op *op, const double *xG, double *yG, void 
   } else if (st_fold_pressure(op, yG, nullptr)) {             // the fused-z route with the pressure inside the stress
     if ((rc = st_viscous_jacobian_zfused(op, op->p2, st, false, true))) return rc;                                               // MatVP (:512) + MatVV
     if (!ST_ABL(4)) st_out_full(op, nullptr, yG, st, nullptr, nullptr, nullptr, nullptr, nullptr, true);
-    SHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
   } else if (!op->aux && st_zfused_ok(op)) {                  // the fused-z route with the pressure-gradient sweeps inside its first launch
     if (!op->pext) st_pressure_extrapolate(op, op->pL, st);
@@ -1784,7 +1748,7 @@ extern "C" int stokes_op_mult(stokes_op *op, const double *xG, double *yG, void 
   }
   if (!ST_ABL(5) && (rc = st_join(op, st))) return rc;
   if (!ST_ABL(4)) st_out_full(op, nullptr, yG, st);
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -1799,14 +1763,14 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
     // loop and the second set of d^2 sweeps are not needed (st_viscous_uniform); the symmetrised strain it would leave as
     // state is rebuilt from xF by whoever asks for it (st_sync_strain).  Option "general_viscous" keeps the general route.
     st_local(op, d + 1, d, xG, op->dirloc, op->xF, op->pL, st);
-    if (!(op->eta_uniform && op->eta_value == 1.0)) hipLaunchKernelGGL(k_st_fill, dim3(sgrid(op->N)), dim3(256), 0, st, op->N, 1.0, op->eta);
-    if (op->deta_nonzero) hipLaunchKernelGGL(k_st_fill, dim3(sgrid(op->N)), dim3(256), 0, st, op->N, 0.0, op->deta);
+    if (!(op->eta_uniform && op->eta_value == 1.0)) hipLaunchKernelGGL(k_st_fill, dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, 1.0, op->eta);
+    if (op->deta_nonzero) hipLaunchKernelGGL(k_st_fill, dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, 0.0, op->deta);
     op->eta_uniform = true; op->eta_value = 1.0; op->deta_nonzero = false; op->strain_stale = true;
     bool split = false;
     const bool pairs = st_out_pairs(op, op->V[0], op->V[1], op->V[2], op->yLx[1], op->force, yG);
     int rc = st_viscous_uniform(op, true, st, op->xF, 1.0, pairs ? &split : nullptr); if (rc) return rc;
     st_out_full(op, op->force, yG, st, op->V[0], op->V[1], op->V[2], op->yLx[1], split ? op->yL : nullptr);                        // :750-756
-    SHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   op->strain_stale = false;                               // the node loop below leaves the strain as state
@@ -1833,7 +1797,7 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
     if (!ST_ABL(3) && (rc = sweeps_multi(op, true, 0, t, y, -1.0, st, true, false, 2))) return rc;                               // :737-740 (x, y)
     if (!ST_ABL(5) && (rc = st_join(op, st))) return rc;
     if (!ST_ABL(4)) st_out_full(op, op->force, yG, st, nullptr, nullptr, nullptr, nullptr, nullptr, fold);                          // :750-756
-    SHIPCHK(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
   }
   if (op->slab) {
@@ -1846,10 +1810,10 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
     { int rc = st_gradient(op, op->strain, st); if (rc) return rc; }                                                              // :701
   }
   if (op->sym)
-    hipLaunchKernelGGL((k_st_node_fn_pair<true>), dim3(sgrid(op->N >> 1)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
+    hipLaunchKernelGGL((k_st_node_fn_pair<true>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
                        op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh_kind, op->rh_hard, op->rh_expo, op->rh_eps, op->rh_g0, op->T);
   else if (d == 3 && (op->N & 1) == 0)
-    hipLaunchKernelGGL((k_st_node_fn_pair<false>), dim3(sgrid(op->N >> 1)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
+    hipLaunchKernelGGL((k_st_node_fn_pair<false>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
                        op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh_kind, op->rh_hard, op->rh_expo, op->rh_eps, op->rh_g0, op->T);
   else
     ST_D(k_st_node_fn, op->strain[0], op->strain[1], op->strain[2], op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2,
@@ -1859,7 +1823,7 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
   int rc = st_div_stress(op, st, op->sym); if (rc) return rc;                                                                    // :737-740
   if ((rc = st_join(op, st))) return rc;
   st_out_full(op, op->force, yG, st);                                                                                              // :750-756
-  SHIPCHK(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -1892,7 +1856,7 @@ static int st_mult_schur(stokes_op *op, const double *pG, double *out, chebhip_a
   const size_t gv = (size_t)op->I * op->d;
   if (!op->sv0) {
     int rc = st_alloc(&op->sv0, gv ? gv : 1); if (rc) return rc; if ((rc = st_alloc(&op->sv1, gv ? gv : 1))) return rc;
-    SHIPCHK(hipStreamSynchronize(nullptr));       // st_alloc clears on the null stream, which a non-blocking caller's stream does not wait for
+    HIP_TRY(hipStreamSynchronize(nullptr));       // st_alloc clears on the null stream, which a non-blocking caller's stream does not wait for
   }
   int rc = st_mult_vp(op, pG, op->sv0, st, cm); if (rc) return rc;                            // :530
   if (solve) { if ((rc = solve(solve_ctx, op->sv0, op->sv1, st))) return rc; }               // KSPSolve(KSPSchurVelocity), :531
@@ -1905,8 +1869,8 @@ static int st_mult_schur(stokes_op *op, const double *pG, double *out, chebhip_a
     op->inner_its = chebhip_fgmres_iterations(op->inner);
   }
   if ((rc = st_mult_pv(op, op->sv1, out, st, cm))) return rc;                                // :532
-  hipLaunchKernelGGL(k_st_neg, dim3(sgrid(op->I)), dim3(256), 0, st, op->I, out);
-  SHIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_st_neg, dim3(grid1d(op->I, 256, 4096)), dim3(256), 0, st, op->I, out);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 extern "C" int stokes_op_mult_schur(stokes_op *op, const double *pG, double *out, chebhip_apply_fn solve, void *solve_ctx, void *stream) {
@@ -1928,7 +1892,7 @@ extern "C" int stokes_op_pencil_sweep(stokes_op *op, int nfields, long ncol, con
   SweepParams sp = {};
   sp.ncols = (unsigned)(nfields * ncol); sp.inner = (unsigned)ncol;
   sp.in0 = in; sp.in_mode = IN_PLAIN; sp.out = out; sp.out_mode = OUT_STORE; sp.alpha = 1.0;
-  SHIPCHK(sweep_launch(op->mats[op->gP0], sp, (hipStream_t)stream));
+  HIP_TRY(sweep_launch(op->mats[op->gP0], sp, (hipStream_t)stream));
   return 0;
 }
 
@@ -1949,7 +1913,7 @@ extern "C" int stokes_op_pencil_sweep_pressure(stokes_op *op, int nvel, long nco
     sp[0].in0 = in; sp[0].in_mode = IN_PLAIN; sp[0].out = out; sp[0].out_mode = OUT_STORE; sp[0].alpha = 1.0;
     sp[1].ncols = (unsigned)ncol; sp[1].inner = (unsigned)ncol;
     sp[1].in0 = in + (size_t)nvel * Np; sp[1].in_mode = IN_PLAIN; sp[1].out = out + (size_t)nvel * Np; sp[1].out_mode = OUT_STORE; sp[1].alpha = 1.0;
-    SHIPCHK(sweep_launch_multi(2, m, sp, (hipStream_t)stream));      // (one launch where the 16-byte kernels run, else one each)
+    HIP_TRY(sweep_launch_multi(2, m, sp, (hipStream_t)stream));      // (one launch where the 16-byte kernels run, else one each)
     return 0;
   }
   int rc = stokes_op_pencil_sweep(op, nvel, ncol, in, out, stream); if (rc) return rc;
@@ -1993,11 +1957,11 @@ int stokes_pencil_gather_try(stokes_op *op, int kind, int nf, long ncol, const G
     int n = ng;
     for (int j = 0; j < op->npend; j++, n++) { m[n] = op->pend_m[j]; sp[n] = op->pend_sp[j]; }
     bool all = false;
-    SHIPCHK(sweep_launch_multi_gather_try(n, m, sp, gmask, g, st, &all));
+    HIP_TRY(sweep_launch_multi_gather_try(n, m, sp, gmask, g, st, &all));
     if (all) { op->npend = 0; *done = true; return 0; }
   }
-  if (ng == 1) { SHIPCHK(sweep_launch_gather(*m[0], sp[0], g, st, done)); }
-  else { SHIPCHK(sweep_launch_multi_gather_try(2, m, sp, gmask, g, st, done)); }
+  if (ng == 1) { HIP_TRY(sweep_launch_gather(*m[0], sp[0], g, st, done)); }
+  else { HIP_TRY(sweep_launch_multi_gather_try(2, m, sp, gmask, g, st, done)); }
   return 0;
 }
 }  // namespace chebhip
@@ -2010,10 +1974,10 @@ extern "C" int stokes_op_pencil_pressure(stokes_op *op, long ncol, double *p_pen
     SweepParams sp = {};
     sp.ncols = (unsigned)ncol; sp.inner = (unsigned)ncol;
     sp.in0 = p_pencil; sp.in_mode = IN_PLAIN; sp.out = gp0_pencil; sp.out_mode = OUT_STORE; sp.alpha = 1.0;
-    SHIPCHK(sweep_launch(op->matsP[op->gP0], sp, st));
+    HIP_TRY(sweep_launch(op->matsP[op->gP0], sp, st));
     return 0;
   }
-  hipLaunchKernelGGL(k_st_preduce, dim3(pgrid(ncol)), dim3(256), 0, st, p_pencil, ncol, 0L, 1L, 1L, 0L, 0L, ncol,
+  hipLaunchKernelGGL(k_st_preduce, dim3(grid1d(ncol, 32, 8192)), dim3(256), 0, st, p_pencil, ncol, 0L, 1L, 1L, 0L, 0L, ncol,
                      op->gP0, (const double *)op->w0[0], (const double *)op->w1[0]);
   return stokes_op_pencil_sweep(op, 1, ncol, p_pencil, gp0_pencil, stream);
 }
@@ -2031,16 +1995,16 @@ static int st_state_ptr(stokes_op *op, int which, double **p, size_t *n, bool *s
 extern "C" int stokes_op_get_state(stokes_op *op, int which, double *dst) {
   ARGCHK(op && dst);
   double *p; size_t n; bool soa; int rc = st_state_ptr(op, which, &p, &n, &soa); if (rc) return rc;
-  SHIPCHK(hipDeviceSynchronize());
-  if (soa && op->strain_stale) { if ((rc = st_sync_strain(op, nullptr))) return rc; SHIPCHK(hipStreamSynchronize(nullptr)); }
-  if (!soa) { SHIPCHK(hipMemcpy(dst, p, n * sizeof(double), hipMemcpyDeviceToHost)); return 0; }
+  HIP_TRY(hipDeviceSynchronize());
+  if (soa && op->strain_stale) { if ((rc = st_sync_strain(op, nullptr))) return rc; HIP_TRY(hipStreamSynchronize(nullptr)); }
+  if (!soa) { HIP_TRY(hipMemcpy(dst, p, n * sizeof(double), hipMemcpyDeviceToHost)); return 0; }
   std::vector<double> tmp(n);
   const size_t N = (size_t)op->N; const int d = op->d;
   const int j = which - 2;
   for (int k = 0; k < d; k++) {
     // symmetric storage (stokes_op::sym): only the entries with first index <= second are the symmetrised strain
     const double *src = (op->sym && k < j) ? op->strain[k] + (size_t)j * N : p + (size_t)k * N;
-    SHIPCHK(hipMemcpy(tmp.data() + (size_t)k * N, src, N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tmp.data() + (size_t)k * N, src, N * sizeof(double), hipMemcpyDeviceToHost));
   }
   for (size_t l = 0; l < N; l++) for (int k = 0; k < d; k++) dst[l * d + k] = tmp[k * N + l];
   return 0;
@@ -2049,11 +2013,11 @@ extern "C" int stokes_op_get_state(stokes_op *op, int which, double *dst) {
 extern "C" int stokes_op_set_state(stokes_op *op, int which, const double *src) {
   ARGCHK(op && src);
   double *p; size_t n; bool soa; int rc = st_state_ptr(op, which, &p, &n, &soa); if (rc) return rc;
-  SHIPCHK(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
   // a state set by hand starts from the complete state of the last StokesFunction (an eta' given here will meet the strain)
-  if (op->strain_stale) { if ((rc = st_sync_strain(op, nullptr))) return rc; SHIPCHK(hipStreamSynchronize(nullptr)); }
+  if (op->strain_stale) { if ((rc = st_sync_strain(op, nullptr))) return rc; HIP_TRY(hipStreamSynchronize(nullptr)); }
   if (!soa) {
-    SHIPCHK(hipMemcpy(p, src, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p, src, n * sizeof(double), hipMemcpyHostToDevice));
     if (which == 1) { bool nz = false; for (size_t i = 0; i < n && !nz; i++) nz = (src[i] != 0.0); op->deta_nonzero = nz; }
     if (which == 0) { bool same = n > 0; for (size_t i = 1; i < n && same; i++) same = (src[i] == src[0]); op->eta_uniform = same; op->eta_value = same ? src[0] : 1.0; }
     return 0;
@@ -2061,7 +2025,7 @@ extern "C" int stokes_op_set_state(stokes_op *op, int which, const double *src) 
   std::vector<double> tmp(n);
   const size_t N = (size_t)op->N; const int d = op->d;
   for (size_t l = 0; l < N; l++) for (int k = 0; k < d; k++) tmp[k * N + l] = src[l * d + k];
-  SHIPCHK(hipMemcpy(p, tmp.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p, tmp.data(), n * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -2084,13 +2048,13 @@ __global__ __launch_bounds__(256) void k_minmax(long n, const double *__restrict
 extern "C" int stokes_op_viscosity_range(stokes_op *op, double *eta_min, double *eta_max, void *stream) {
   ARGCHK(op && eta_min && eta_max);
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nb = sgrid(op->N) > 256 ? 256 : sgrid(op->N);
+  const unsigned nb = grid1d(op->N, 256, 4096) > 256 ? 256 : grid1d(op->N, 256, 4096);
   // p2 is free between callbacks: 2 * nb partial results
   if ((long)(2 * nb) > op->N) return chebhip_fail(CHEBHIP_ERR_SIZE, "grid too small");
   hipLaunchKernelGGL(k_minmax, dim3(nb), dim3(256), 0, st, op->N, (const double *)op->eta, op->p2);
   std::vector<double> h(2 * nb);
-  SHIPCHK(hipMemcpyAsync(h.data(), op->p2, 2 * nb * sizeof(double), hipMemcpyDeviceToHost, st));
-  SHIPCHK(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(h.data(), op->p2, 2 * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   double lo = h[0], hi = h[1];
   for (unsigned b = 1; b < nb; b++) { lo = h[2 * b] < lo ? h[2 * b] : lo; hi = h[2 * b + 1] > hi ? h[2 * b + 1] : hi; }
   *eta_min = lo; *eta_max = hi;
@@ -2105,39 +2069,35 @@ extern "C" int stokes_op_write_vtk(stokes_op *op, const double *state_dev, const
   ARGCHK(op && path); ARGCHK(VEC_OK(state_dev));
   if (op->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "stokes_op_write_vtk: serial handles only");
   const int d = op->d; const long N = op->N;
-  SHIPCHK(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
   { int rc = st_sync_strain(op, nullptr); if (rc) return rc; }
   std::vector<double> v(N * d), p(N), fv(N * d, 0.0), fp(N, 0.0), eta(N), deta(N), strain((size_t)d * N * d);
   auto fetch = [&](const double *src, std::vector<double> &vel, std::vector<double> &pre) -> int {
     st_local(op, d + 1, d, src, op->dirloc, op->xL, op->pL, nullptr);                 // scatters + dirichlet (:1827-1838)
     st_pressure_extrapolate(op, op->pL, nullptr);                                       // :1837
-    SHIPCHK(hipMemcpy(vel.data(), op->xL, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost));
-    SHIPCHK(hipMemcpy(pre.data(), op->pL, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vel.data(), op->xL, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pre.data(), op->pL, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
   };
   int rc = fetch(state_dev, v, p); if (rc) return rc;
   if (op->force) { rc = fetch(op->force, fv, fp); if (rc) return rc; }                 // :1840-1851
-  SHIPCHK(hipMemcpy(eta.data(), op->eta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-  SHIPCHK(hipMemcpy(deta.data(), op->deta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(eta.data(), op->eta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(deta.data(), op->deta, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
   for (int j = 0; j < d; j++)
     for (int k = 0; k < d; k++) {       // symmetric storage: entries below the diagonal come from their mirror
       const double *src = (op->sym && k < j) ? op->strain[k] + (size_t)j * N : op->strain[j] + (size_t)k * N;
-      SHIPCHK(hipMemcpy(strain.data() + (size_t)j * N * d + (size_t)k * N, src, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(strain.data() + (size_t)j * N * d + (size_t)k * N, src, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
     }
   FILE *f = fopen(path, "w");
   if (!f) return chebhip_fail(CHEBHIP_ERR_ARG, "cannot open %s", path);
   const int m = op->dims[0], n = op->dims[1], pp = d > 2 ? op->dims[2] : 1;
   fprintf(f, "# vtk DataFile Version 2.0\nStokes Output\nASCII\nDATASET STRUCTURED_GRID\n");
   fprintf(f, "DIMENSIONS %d %d %d\nPOINTS %ld double\n", m, n, pp, N);
-  {  // c->coord: x = cos(i pi/(dim-1)) per dimension (stokes.C:296), three values per line
-    std::vector<int> ind(d, 0);
-    for (long l = 0; l < N; l++) {
-      for (int j = 0; j < d; j++) fprintf(f, "%20e ", cos(ind[j] * 3.14159265358979323846 / (op->dims[j] - 1)));
-      for (int j = d; j < 3; j++) fprintf(f, "0 ");
-      fprintf(f, "\n");
-      for (int j = d - 1; j >= 0; j--) { if (++ind[j] < op->dims[j]) break; ind[j] = 0; }
-    }
-  }
+  op->for_each_node([&](long, const int *ind, bool) {   // c->coord: x = cos(i pi/(dim-1)) per dimension (stokes.C:296), three values per line
+    for (int j = 0; j < d; j++) fprintf(f, "%20e ", cos(ind[j] * 3.14159265358979323846 / (op->dims[j] - 1)));
+    for (int j = d; j < 3; j++) fprintf(f, "0 ");
+    fprintf(f, "\n");
+  });
   auto vec3 = [&](const std::vector<double> &a) {       // component-major work vector, printed node by node (StokesVecView)
     for (long l = 0; l < N; l++) { for (int j = 0; j < d; j++) fprintf(f, "%20e ", a[(size_t)j * N + l]); for (int j = d; j < 3; j++) fprintf(f, "0 "); fprintf(f, "\n"); }
   };

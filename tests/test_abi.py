@@ -60,6 +60,30 @@ def test_argument_errors(L):
     assert h.value is None
 
 
+def test_slab_grid_errors(L):
+    """The checks of the box / slab grid that the elliptic and the Stokes operator share, and the ones in which they differ: codes
+    and messages, all before any device use."""
+    ints = lambda v: (C.c_int * len(v))(*v)
+    cb = sp.DIM0_FN(lambda *a: 0)
+    cbp = C.cast(cb, C.c_void_p)
+    for create in (L.ell_op_create_slab, L.stokes_op_create_slab):
+        for lo, hi in ((-1, 2), (3, 3), (2, 6)):
+            h = C.c_void_p()
+            assert create(3, ints([5, 4, 4]), lo, hi, cbp, None, C.byref(h)) == 4
+            msg = L.chebhip_last_error()
+            assert b"slab planes [" in msg and b"outside 0..5" in msg
+            assert h.value is None
+        h = C.c_void_p()
+        assert create(3, ints([5, 4, 4]), 0, 2, None, None, C.byref(h)) == 4
+        assert b"dimension-0 callback" in L.chebhip_last_error() and h.value is None
+    h = C.c_void_p()
+    assert L.ell_op_create_slab(2, ints([2, 4]), 0, 1, cbp, None, C.byref(h)) == 1          # CHEBHIP_ERR_SIZE
+    assert b"dims[0] >= 3" in L.chebhip_last_error()
+    for d in (1, 4):
+        assert L.stokes_op_create(d, ints([5] * d), C.byref(h)) == 3                        # CHEBHIP_ERR_DIMS
+    assert h.value is None
+
+
 def test_no_cpu_fallback(L):
     """On a box without a GPU the product refuses to run instead of silently computing on the CPU."""
     import torch
