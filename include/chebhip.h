@@ -303,6 +303,99 @@ int  cheb_reduce_slices(const cheb_reduce *h);             /* partial sums per o
 int  cheb_reduce_apply(cheb_reduce *h, const double *u_dev, const double *v_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Vector calculus of full-grid fields (no counterpart in the reference,      */
+/* whose operators differentiate inside their callbacks only).  Fields use    */
+/* the full-grid, field-major layout of cheb_modal_*: field f of an array at  */
+/* f * N, N = prod(dims), row-major over all nodes.  A VECTOR field is d      */
+/* consecutive fields u[v][c], component c along grid direction c.  With      */
+/* d_k = the derivative along direction k and s_k = scale[k] (2 / L_k for a   */
+/* box of length L_k; default 1):                                             */
+/*   grad       out[f*d + k] = s_k d_k s[f]                                   */
+/*   tensor     G[v][c][k]   = s_k d_k u[v][c]       (grad of the nv*d fields)*/
+/*   div        out[v] = ((s_0 d_0 u[v][0]) + s_1 d_1 u[v][1]) + ...          */
+/*   curl       d = 3: w_0 = d_1 u_2 - d_2 u_1, w_1 = d_2 u_0 - d_0 u_2,      */
+/*              w_2 = d_0 u_1 - d_1 u_0 (scales included, index = direction); */
+/*              d = 2: the one field d_0 u_1 - d_1 u_0; other d: ERR_ARG      */
+/*   strain     per vector the d(d+1)/2 fields (0,0), (0,1), .., (d-1,d-1):   */
+/*              S_cc = s_c d_c u_c,  S_ck = 1/2 s_k d_k u_c + 1/2 s_c d_c u_k */
+/*   laplacian  out[f] = sum_k s_k^2 d_k^2 s[f], k ascending: one sweep with  */
+/*              D D (long double, rounded once) for 3 <= n_k <= 256, two D    */
+/*              sweeps through `work` for n_k > 256, nothing for n_k = 2      */
+/*              (D D = 0 there)                                               */
+/* Every output is a list of signed derivative sweeps: the first term is      */
+/* stored, the later ones are added to the same array in the order written    */
+/* above, the factor of a term (sign, 1/2, scale) multiplies the sweep's      */
+/* result.  Results repeat bit for bit.  An output of T terms is within       */
+/* (max n + 8 + T) 2^-53 sum_t B_t of the exact value, B_t = |factor| times   */
+/* the componentwise weight |D| |u| of the term's sweep.                      */
+/* Pointwise invariants of a tensor G[v][c][k] (any array of that layout),    */
+/* per vector the selected fields in the order of the bits:                   */
+/*   CHEB_INV_DIV      sum_c G_cc                                             */
+/*   CHEB_INV_VORT2    sum_{c<k} (G_kc - G_ck)^2      (|curl u|^2 for d = 2,3)*/
+/*   CHEB_INV_STRAIN2  S:S = sum_c G_cc^2 + 1/2 sum_{c<k} (G_ck + G_kc)^2     */
+/*   CHEB_INV_GAMMA    1/2 S:S: the second invariant of stokes.C:711-717      */
+/*   CHEB_INV_Q        1/4 VORT2 - 1/2 STRAIN2                                */
+/*   CHEB_INV_NORM2    sum_{c,k} G_ck^2                                       */
+/* summed in the index order written (pairs c < k row by row; NORM2 row-major */
+/* for d <= 3, and for d > 3 per c: G_cc^2, then G_ck^2, G_kc^2 for k > c).   */
+/* A field of T squared (or, DIV, plain) terms is within (T + 4) 2^-53 A of   */
+/* the formula evaluated exactly on G, A = the formula with every term taken  */
+/* non-negative.  A NaN or Inf at a node stays in that node's outputs.        */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_grad cheb_grad;
+enum { CHEB_INV_DIV = 1, CHEB_INV_VORT2 = 2, CHEB_INV_STRAIN2 = 4, CHEB_INV_GAMMA = 8, CHEB_INV_Q = 16, CHEB_INV_NORM2 = 32 };
+
+/* 1 <= d <= 10; 2 <= dims[k] <= 1024; fewer than 2^31 nodes; scale: d finite HOST values or NULL (all 1).  The handle owns the
+ * differentiation matrices and no work arrays: the calls below allocate nothing on the device and do not synchronise the host. */
+int  cheb_grad_create(int d, const int *dims, const double *scale, cheb_grad **out);
+int  cheb_grad_destroy(cheb_grad *h);
+long cheb_grad_size(const cheb_grad *h);                  /* N = prod(dims); -1: NULL */
+long cheb_grad_work_size(const cheb_grad *h, int nfields); /* doubles cheb_grad_laplacian's `work` must hold (0: it may be NULL); -1 on a bad argument */
+/* All arrays are DEVICE pointers.  A call takes at most 16 input fields (nfields, or nvec * d) and fewer than 2^31 values per
+ * array; no input may overlap an output or the work array (CHEBHIP_ERR_ARG).  Asynchronous on `stream`. */
+int  cheb_grad_grad(cheb_grad *h, int nfields, const double *s_dev, double *out_dev, void *stream);
+int  cheb_grad_tensor(cheb_grad *h, int nvec, const double *u_dev, double *G_dev, void *stream);
+int  cheb_grad_div(cheb_grad *h, int nvec, const double *u_dev, double *out_dev, void *stream);
+int  cheb_grad_curl(cheb_grad *h, int nvec, const double *u_dev, double *out_dev, void *stream);
+int  cheb_grad_strain(cheb_grad *h, int nvec, const double *u_dev, double *out_dev, void *stream);
+int  cheb_grad_laplacian(cheb_grad *h, int nfields, const double *s_dev, double *work_dev, double *out_dev, void *stream);
+/* mask: a nonempty set of CHEB_INV_* bits; out: nvec * popcount(mask) fields; 1 <= nvec <= 16.  One kernel launch. */
+int  cheb_grad_invariants(cheb_grad *h, int nvec, const double *G_dev, unsigned mask, double *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- */
+/* Between the operators' vectors and full-grid fields.  ell_op and stokes_op */
+/* take the reference's vectors: interior nodes only, node-major, the         */
+/* components of a node interleaved, and the Dirichlet values in a compact    */
+/* array of the boundary nodes in BlockIt (row-major) order (the layout of    */
+/* ell_op_set_dirichlet / stokes_op_set_dirichlet).  With m = the number of a */
+/* node among the interior nodes and b = its number among the boundary nodes, */
+/* both row-major, and l its row-major number among all N nodes:              */
+/*   unpack  out[c*N + l] = xi[m*si + oi + c]   (interior node)               */
+/*           out[c*N + l] = xb[b*sb + ob + c]   (boundary node)               */
+/*   pack    the inverse                                                      */
+/* for c < ncomp.  A Stokes state has si = d + 1: velocity oi = 0, ncomp = d  */
+/* with sb = d, ob = 0; pressure oi = d, ncomp = 1 with no boundary source.   */
+/* A NULL source of unpack gives 0 at its nodes: for a pressure these zeros   */
+/* are a placeholder, NOT an extrapolation of the pressure to the boundary.   */
+/* A NULL target of pack is skipped; entries of a target that no (node,       */
+/* component) addresses -- the other interleaved components -- keep their     */
+/* bits.  Values are moved, never computed: every bit arrives.                */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_layout cheb_layout;
+/* 1 <= d <= 10; 3 <= dims[k] <= 1024; fewer than 2^31 nodes.  The handle owns one int per node on the device. */
+int  cheb_layout_create(int d, const int *dims, cheb_layout **out);
+int  cheb_layout_destroy(cheb_layout *h);
+long cheb_layout_size(const cheb_layout *h, int which);   /* 0: nodes N, 1: interior nodes I, 2: boundary nodes N - I; -1 on a bad argument */
+/* The handle's table on the HOST, N ints: map[l] >= 0 is m, map[l] < 0 is -1 - b.  Needs no device. */
+int  cheb_layout_map_host(int d, const int *dims, int *map);
+/* xi: I * si doubles, xb: (N - I) * sb doubles, out / fields: ncomp * N doubles, all on the DEVICE; 1 <= ncomp, 0 <= oi, oi + ncomp <= si
+ * and 0 <= ob, ob + ncomp <= sb for the arrays that are given; the field side must not overlap the vector side.  Asynchronous. */
+int  cheb_layout_unpack(cheb_layout *h, int ncomp, const double *xi_dev, long si, long oi, const double *xb_dev, long sb, long ob,
+                        double *out_dev, void *stream);
+int  cheb_layout_pack(cheb_layout *h, int ncomp, const double *fields_dev, double *xi_dev, long si, long oi, double *xb_dev, long sb, long ob,
+                      void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Operator level: the scalar elliptic MatShell (elliptic.C:78-86,250-293).   */
 /* Vectors at this boundary are the reference's GLOBAL vectors: interior      */
 /* nodes only, row-major (SetupBC, elliptic.C:372-434).  All work vectors     */

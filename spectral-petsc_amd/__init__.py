@@ -73,6 +73,9 @@ ABI_SYMBOLS = [
     "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
     "cheb_reduce_weights_host", "cheb_reduce_create", "cheb_reduce_destroy", "cheb_reduce_set_weights", "cheb_reduce_size",
     "cheb_reduce_slices", "cheb_reduce_apply",
+    "cheb_grad_create", "cheb_grad_destroy", "cheb_grad_size", "cheb_grad_work_size", "cheb_grad_grad", "cheb_grad_tensor",
+    "cheb_grad_div", "cheb_grad_curl", "cheb_grad_strain", "cheb_grad_laplacian", "cheb_grad_invariants",
+    "cheb_layout_create", "cheb_layout_destroy", "cheb_layout_size", "cheb_layout_map_host", "cheb_layout_unpack", "cheb_layout_pack",
 ]
 
 
@@ -288,6 +291,23 @@ def lib():
         L.cheb_reduce_size.restype = C.c_long
         L.cheb_reduce_slices.argtypes = [vp]
         L.cheb_reduce_apply.argtypes = [vp, vp, vp, vp, vp]
+        L.cheb_grad_create.argtypes = [C.c_int, ip, dp, C.POINTER(vp)]
+        L.cheb_grad_destroy.argtypes = [vp]
+        L.cheb_grad_size.argtypes = [vp]
+        L.cheb_grad_size.restype = C.c_long
+        L.cheb_grad_work_size.argtypes = [vp, C.c_int]
+        L.cheb_grad_work_size.restype = C.c_long
+        for f in (L.cheb_grad_grad, L.cheb_grad_tensor, L.cheb_grad_div, L.cheb_grad_curl, L.cheb_grad_strain):
+            f.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.cheb_grad_laplacian.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.cheb_grad_invariants.argtypes = [vp, C.c_int, vp, C.c_uint, vp, vp]
+        L.cheb_layout_create.argtypes = [C.c_int, ip, C.POINTER(vp)]
+        L.cheb_layout_destroy.argtypes = [vp]
+        L.cheb_layout_size.argtypes = [vp, C.c_int]
+        L.cheb_layout_size.restype = C.c_long
+        L.cheb_layout_map_host.argtypes = [C.c_int, ip, ip]
+        L.cheb_layout_unpack.argtypes = [vp, C.c_int, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp, vp]
+        L.cheb_layout_pack.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp]
         _lib = L
     return _lib
 
@@ -845,6 +865,157 @@ class ChebReduce(_Handle):
         _chk(lib().cheb_reduce_apply(self._h, _dev_ptr(u, self.size(0)), None if v is None else _dev_ptr(v, self.size(0)),
                                      _dev_ptr(out, self.size(1)), _stream()))
         return out
+
+
+INVARIANTS = {"div": 1, "vort2": 2, "strain2": 4, "gamma": 8, "q": 16, "norm2": 32}
+
+
+def _inv_mask(which):
+    """(mask, number of fields) of a tuple of names of INVARIANTS (one name is taken as a tuple of one)."""
+    which = (which,) if isinstance(which, str) else tuple(which)
+    mask = 0
+    for w in which:
+        if w not in INVARIANTS:
+            raise ValueError("invariant %r: expected one of %s" % (w, sorted(INVARIANTS)))
+        mask |= INVARIANTS[w]
+    if not mask:
+        raise ValueError("no invariant selected")
+    return mask, bin(mask).count("1")
+
+
+class ChebGrad(_Handle):
+    """Vector calculus of stacked full-grid fields on the CGL grid `dims` (cheb_grad_*; field-major, row-major over all nodes, as
+    ChebModal): grad, tensor, div, curl, strain, laplacian as signed derivative sweeps added in a fixed order, and the pointwise
+    invariants of a gradient tensor.  scale[k] multiplies the derivative along direction k (2 / L_k for a box of length L_k).  A
+    vector field is d consecutive fields; the number of fields (vectors) of a call is taken from numel() // N.  out=None allocates
+    the output.  The outputs come back with the layouts of include/chebhip.h, shaped (fields, *dims).  Asynchronous on torch's
+    current stream; the same input gives the same bits."""
+    _destroy = "cheb_grad_destroy"
+
+    def __init__(self, dims, scale=None):
+        import numpy as np
+        self.dims = tuple(int(d) for d in dims)
+        self.d = len(self.dims)
+        sc = None
+        if scale is not None:
+            sc = np.ascontiguousarray(scale, dtype=np.float64)
+            if sc.shape != (self.d,):
+                raise ValueError("scale: expected %d values, got shape %r" % (self.d, sc.shape))
+        self.scale = None if sc is None else tuple(float(v) for v in sc)
+        h = C.c_void_p()
+        _chk(lib().cheb_grad_create(self.d, _ints(self.dims), None if sc is None else _np_dp(sc), C.byref(h)))
+        self._h = h
+        self.N = lib().cheb_grad_size(h)
+
+    def _count(self, t, per, what):
+        n = t.numel()
+        if n == 0 or n % (self.N * per):
+            raise ValueError("%s: %d values are no multiple of %d" % (what, n, self.N * per))
+        return n // (self.N * per)
+
+    def _run(self, fn, x, per_in, per_out, out, what):
+        import torch
+        n = self._count(x, per_in, what)
+        if out is None:
+            out = torch.empty((n * per_out,) + self.dims, dtype=torch.float64, device=x.device)
+        _chk(fn(self._h, n, _dev_ptr(x, n * per_in * self.N), _dev_ptr(out, n * per_out * self.N), _stream()))
+        return out
+
+    def grad(self, s, out=None):
+        """out[f * d + k] = scale_k d_k s[f]."""
+        return self._run(lib().cheb_grad_grad, s, 1, self.d, out, "grad")
+
+    def tensor(self, u, out=None):
+        """G[v][c][k] = scale_k d_k u[v][c]: the gradient of a vector field, d * d fields per vector."""
+        return self._run(lib().cheb_grad_tensor, u, self.d, self.d * self.d, out, "tensor")
+
+    def div(self, u, out=None):
+        return self._run(lib().cheb_grad_div, u, self.d, 1, out, "div")
+
+    def curl(self, u, out=None):
+        """d = 3: three fields per vector; d = 2: the one field d_0 u_1 - d_1 u_0."""
+        return self._run(lib().cheb_grad_curl, u, self.d, 3 if self.d == 3 else 1, out, "curl")
+
+    def strain(self, u, out=None):
+        """Per vector the d (d + 1) / 2 fields (0,0), (0,1), .., (d-1,d-1) of the symmetrised gradient."""
+        return self._run(lib().cheb_grad_strain, u, self.d, self.d * (self.d + 1) // 2, out, "strain")
+
+    def work_size(self, nfields):
+        """Doubles laplacian's `work` must hold for nfields fields (0: none needed)."""
+        return lib().cheb_grad_work_size(self._h, int(nfields))
+
+    def laplacian(self, s, out=None, work=None):
+        """out[f] = sum_k scale_k^2 d_k^2 s[f]; `work` (work_size(nfields) doubles) is allocated if needed and not given."""
+        import torch
+        n = self._count(s, 1, "laplacian")
+        if out is None:
+            out = torch.empty((n,) + self.dims, dtype=torch.float64, device=s.device)
+        ws = self.work_size(n) if n <= 16 else 0
+        if ws and work is None:
+            work = torch.empty(ws, dtype=torch.float64, device=s.device)
+        _chk(lib().cheb_grad_laplacian(self._h, n, _dev_ptr(s, n * self.N), None if not ws else _dev_ptr(work, ws),
+                                       _dev_ptr(out, n * self.N), _stream()))
+        return out
+
+    def invariants_from(self, G, which, out=None):
+        """The invariants named in `which` (names of INVARIANTS) of the tensor G[v][c][k], per vector in the order of INVARIANTS'
+        bits: a device tensor of shape (vectors * len(which), *dims)."""
+        import torch
+        mask, nsel = _inv_mask(which)
+        nv = self._count(G, self.d * self.d, "invariants")
+        if out is None:
+            out = torch.empty((nv * nsel,) + self.dims, dtype=torch.float64, device=G.device)
+        _chk(lib().cheb_grad_invariants(self._h, nv, _dev_ptr(G, nv * self.d * self.d * self.N), mask,
+                                        _dev_ptr(out, nv * nsel * self.N), _stream()))
+        return out
+
+    def invariants(self, u, which, out=None):
+        """invariants_from(tensor(u), which): G is a torch allocation of this call."""
+        return self.invariants_from(self.tensor(u), which, out)
+
+
+def layout_map(dims):
+    """ChebLayout's node table on the host (cheb_layout_map_host): per row-major node its number among the interior nodes, or
+    -1 - (its number among the boundary nodes); an int32 numpy array of shape dims.  Needs no device."""
+    import numpy as np
+    dims = tuple(int(d) for d in dims)
+    m = np.empty(dims if all(n > 0 for n in dims) else (0,), dtype=np.int32)
+    _chk(lib().cheb_layout_map_host(len(dims), _ints(dims), m.ctypes.data_as(C.POINTER(C.c_int)) if m.size else None))
+    return m
+
+
+class ChebLayout(_Handle):
+    """Between the operators' vectors (interior nodes, node-major, components interleaved; Dirichlet values in a compact array of
+    the boundary nodes) and full-grid, field-major fields (cheb_layout_*).  unpack / pack take the interior array with its stride
+    and offset (xi, si, oi) and the boundary array likewise (xb, sb, ob); either may be None.  Values are moved, never computed.
+    Asynchronous on torch's current stream."""
+    _destroy = "cheb_layout_destroy"
+
+    def __init__(self, dims):
+        self.dims = tuple(int(d) for d in dims)
+        h = C.c_void_p()
+        _chk(lib().cheb_layout_create(len(self.dims), _ints(self.dims), C.byref(h)))
+        self._h = h
+        self.N, self.I, self.B = (lib().cheb_layout_size(h, w) for w in range(3))
+
+    def unpack(self, ncomp, xi=None, si=1, oi=0, xb=None, sb=1, ob=0, out=None):
+        """out[c] = component c as a full-grid field, shape (ncomp, *dims); a missing source gives 0 at its nodes."""
+        import torch
+        ncomp = int(ncomp)
+        if out is None:
+            dev = xi.device if xi is not None else xb.device if xb is not None else torch.device("cuda", torch.cuda.current_device())
+            out = torch.empty((max(ncomp, 0),) + self.dims, dtype=torch.float64, device=dev)
+        _chk(lib().cheb_layout_unpack(self._h, ncomp, None if xi is None else _dev_ptr(xi, self.I * int(si)), int(si), int(oi),
+                                      None if xb is None else _dev_ptr(xb, self.B * int(sb)), int(sb), int(ob),
+                                      _dev_ptr(out, ncomp * self.N) if ncomp > 0 else out.data_ptr(), _stream()))
+        return out
+
+    def pack(self, ncomp, fields, xi=None, si=1, oi=0, xb=None, sb=1, ob=0):
+        """The inverse of unpack: writes the addressed entries of xi and xb, leaves every other entry alone."""
+        ncomp = int(ncomp)
+        _chk(lib().cheb_layout_pack(self._h, ncomp, _dev_ptr(fields, ncomp * self.N) if ncomp > 0 else fields.data_ptr(),
+                                    None if xi is None else _dev_ptr(xi, self.I * int(si)), int(si), int(oi),
+                                    None if xb is None else _dev_ptr(xb, self.B * int(sb)), int(sb), int(ob), _stream()))
 
 
 def helmholtz_line(P):

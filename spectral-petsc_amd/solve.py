@@ -460,3 +460,58 @@ def face_flux(sp, dims, u_full, axis, side, integrate=True):
     finally:
         red.destroy()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# From a solver state to the full-grid toolbox (ChebLayout) and the vector calculus of the result (ChebGrad), all on the device
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+_layout_cache = {}
+
+
+def _layout(sp, dims, device):
+    """The ChebLayout of a grid, built once per (dims, device)."""
+    key = (tuple(int(n) for n in dims), str(device))
+    if key not in _layout_cache:
+        _layout_cache[key] = sp.ChebLayout(key[0])
+    return _layout_cache[key]
+
+
+def stokes_fields(sp, op, x, dirichlet):
+    """The Stokes state x ([v_0 .. v_{d-1}, p] per interior node, a device tensor of op.global_size values) as full-grid fields: a
+    (d + 1, *dims) device tensor whose first d fields are the velocity with its Dirichlet values (`dirichlet`: the compact array
+    of stokes_op_set_dirichlet, d values per boundary node; a host array is uploaded) and whose last field is the pressure with
+    ZERO on the boundary -- a placeholder, not an extrapolation.  Two ChebLayout.unpack launches, nothing through the host."""
+    d = op.d
+    lay = _layout(sp, op.dims, x.device)
+    out = torch.empty((d + 1,) + tuple(op.dims), dtype=torch.float64, device=x.device)
+    xb = _dev_values(dirichlet, x).reshape(-1).contiguous()
+    xv = x.reshape(-1)
+    lay.unpack(d, xv, d + 1, 0, xb, d, 0, out=out[:d])
+    lay.unpack(1, xv, d + 1, d, None, 1, 0, out=out[d:])
+    return out
+
+
+def elliptic_field(sp, op, x, dirichlet):
+    """The elliptic state x (interior nodes, a device tensor of op.global_size values) with its compact Dirichlet values
+    (ell_op_set_dirichlet order; a host array is uploaded) as one full-grid field: a (*dims) device tensor."""
+    lay = _layout(sp, op.dims, x.device)
+    out = torch.empty((1,) + tuple(op.dims), dtype=torch.float64, device=x.device)
+    lay.unpack(1, x.reshape(-1), 1, 0, _dev_values(dirichlet, x).reshape(-1).contiguous(), 1, 0, out=out)
+    return out[0]
+
+
+def strain_invariant(sp, dims, vel_full, scale=None):
+    """gamma = 1/2 S:S (stokes.C:711-717) of the full-grid velocity vel_full (d fields, all nodes of the CGL grid dims), the number
+    the power-law viscosity is a function of: a (*dims) device tensor.  One ChebGrad.tensor and one invariants launch; scale[k]
+    multiplies the derivative along direction k."""
+    dims = tuple(int(n) for n in dims)
+    g = sp.ChebGrad(dims, scale)
+    try:
+        if vel_full.numel() != g.N * len(dims):
+            raise ValueError("vel_full: expected %d fields of %d values" % (len(dims), g.N))
+        out = g.invariants(vel_full.reshape(-1), ("gamma",))
+        torch.cuda.current_stream().synchronize()       # (the handle's matrices are freed below)
+    finally:
+        g.destroy()
+    return out[0]
