@@ -776,6 +776,55 @@ int  cheb_helmholtz_singular(const cheb_helmholtz *h);        /* 1: the zero mod
  * Dirichlet: its matrices, bit for bit); different ends: modes by ascending lam.  Neumann at both ends: lam = 0 exactly. */
 int  cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam,
                                  double *Q /* 2 x M */, double *L /* M x 2 */, double *Binv /* 2 x 2 */);
+/* The same solve on a box: scale[k] = s_k = 2 / L_k > 0 and finite (d HOST values; NULL: all 1, the handle of _create_bc with the
+ * same bits), (sigma - sum_k s_k^2 d_k^2) u = f with alpha u + beta s_k du/dnu = g on the faces of direction k: beta multiplies
+ * the physical outward normal derivative.  The line of direction k is the line of the ends (alpha, beta s_k) with lam and L times
+ * s_k^2; directions share a line only if extent, ends and scale agree.  singular as before: sigma = 0 and alpha = 0 on
+ * every face.  Solved with cheb_helmholtz_solve / _solve_bc. */
+int  cheb_helmholtz_create_box(int d, const int *dims, const double *bc, const double *scale, double sigma, int nfields, cheb_helmholtz **out);
+/* cheb_helmholtz_line_bc_host for a direction of scale s (s = 1: its bits) */
+int  cheb_helmholtz_line_box_host(int P, const double *bc4, double s, double *S, double *Sinv, double *lam,
+                                  double *Q /* 2 x M */, double *L /* M x 2 */, double *Binv /* 2 x 2 */);
+
+/* ------------------------------------------------------------------------- */
+/* Projection onto discretely divergence-free fields on a box.   */
+/* A velocity is d stacked full-grid fields u[v][k] (the layout of            */
+/* cheb_grad_div), s_k = scale[k], d_k the derivative sweep of direction k    */
+/* (index 0 is x = +1: the outward normal derivative is +s_k d_k at index 0,  */
+/* -s_k d_k at index n_k - 1).  Every face (k, end) is a WALL (the normal     */
+/* velocity of the result is prescribed) or OPEN (phi = 0, the normal         */
+/* velocity is free).  phi, a full-grid field, solves the collocation problem */
+/*   interior nodes:  sum_k s_k^2 (D D)_k phi = sum_k s_k d_k u_k             */
+/*   boundary node b, k the HIGHEST direction in which b is an end node:      */
+/*     wall:  +- s_k d_k phi = +- u_k - flux_b      open:  phi = 0            */
+/* (flux: the prescribed outward normal velocity, compact boundary layout of  */
+/* cheb_helmholtz_solve_bc) and the result is  out_k = u_k - s_k d_k phi  at  */
+/* every node.  With an open face div(out) = 0 at the interior nodes to       */
+/* rounding; with walls only the problem is singular, the solver drops the    */
+/* constant-like mode and div(out) equals ONE constant c(u) at the interior   */
+/* nodes (the part of the right-hand side along the dropped mode: spectrally  */
+/* small for resolved fields, O(1) for noise).  The normal component of out   */
+/* equals flux at every wall node for the direction that supplies the node's  */
+/* condition; an edge or corner node meets the condition of its highest end   */
+/* direction only, its normal components in lower directions are not          */
+/* controlled.  P(P u) = P u to rounding; the gradient of a nodal field maps  */
+/* to 0 at every node.                                                        */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_project cheb_project;
+enum { CHEB_FACE_WALL = 0, CHEB_FACE_OPEN = 1 };
+/* 1 <= d <= 10; 3 <= dims[k] <= 258; faces: 2 d ints, faces[2 k + end] (end 0 = index 0), NULL = walls everywhere; scale as
+ * cheb_helmholtz_create_box; nvec vectors per call, nvec * d <= 16, fewer than 2^31 values per array.  The handle owns a cheb_grad,
+ * a box Helmholtz handle (sigma = 0, nvec fields), two node tables and the solver's f and g: apply allocates nothing. */
+int  cheb_project_create(int d, const int *dims, const int *faces, const double *scale, int nvec, cheb_project **out);
+int  cheb_project_destroy(cheb_project *h);
+long cheb_project_size(const cheb_project *h, int which);  /* 0: nodes N, 1: interior nodes G, 2: boundary nodes N - G; -1 on a bad argument */
+int  cheb_project_singular(const cheb_project *h);         /* 1: walls everywhere, the constant-like mode is dropped; -1: NULL */
+/* face[b] = 2 k + end of the face whose condition boundary node b takes, N - G HOST ints in row-major boundary order.  No device. */
+int  cheb_project_faces_host(int d, const int *dims, int *face);
+/* DEVICE arrays: u, out nvec * d * N; phi nvec * N (required: the potential comes back in it); flux nvec * (N - G) or NULL (0).
+ * out may BE u (in place); any other overlap of two arrays is CHEBHIP_ERR_ARG.  Divergence into phi, one launch for f and g, the
+ * direct solve, one accumulating sweep per component of out.  Asynchronous on `stream`; the same input gives the same bits. */
+int  cheb_project_apply(cheb_project *h, const double *u_dev, const double *flux_dev, double *phi_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
 /* The block preconditioners of the Stokes saddle-point system:  */

@@ -76,6 +76,9 @@ ABI_SYMBOLS = [
     "cheb_grad_create", "cheb_grad_destroy", "cheb_grad_size", "cheb_grad_work_size", "cheb_grad_grad", "cheb_grad_tensor",
     "cheb_grad_div", "cheb_grad_curl", "cheb_grad_strain", "cheb_grad_laplacian", "cheb_grad_invariants",
     "cheb_layout_create", "cheb_layout_destroy", "cheb_layout_size", "cheb_layout_map_host", "cheb_layout_unpack", "cheb_layout_pack",
+    "cheb_helmholtz_create_box", "cheb_helmholtz_line_box_host",
+    "cheb_project_create", "cheb_project_destroy", "cheb_project_size", "cheb_project_singular", "cheb_project_faces_host",
+    "cheb_project_apply",
 ]
 
 
@@ -308,6 +311,15 @@ def lib():
         L.cheb_layout_map_host.argtypes = [C.c_int, ip, ip]
         L.cheb_layout_unpack.argtypes = [vp, C.c_int, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp, vp]
         L.cheb_layout_pack.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp]
+        L.cheb_helmholtz_create_box.argtypes = [C.c_int, ip, dp, dp, C.c_double, C.c_int, C.POINTER(vp)]
+        L.cheb_helmholtz_line_box_host.argtypes = [C.c_int, dp, C.c_double, dp, dp, dp, dp, dp, dp]
+        L.cheb_project_create.argtypes = [C.c_int, ip, ip, dp, C.c_int, C.POINTER(vp)]
+        L.cheb_project_destroy.argtypes = [vp]
+        L.cheb_project_size.argtypes = [vp, C.c_int]
+        L.cheb_project_size.restype = C.c_long
+        L.cheb_project_singular.argtypes = [vp]
+        L.cheb_project_faces_host.argtypes = [C.c_int, ip, ip]
+        L.cheb_project_apply.argtypes = [vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1076,6 +1088,30 @@ def helmholtz_line_bc(P, bc):
     return S, Si, lam, Q, L, Bi
 
 
+def helmholtz_line_box(P, bc, s):
+    """helmholtz_line_bc for a direction of scale s = 2 / length (cheb_helmholtz_line_box_host): the line of the ends
+    (alpha, beta s) with lam and L times s^2, so that A~ = -s^2 ((DD)_II + (DD)_IB Q) and the ends carry
+    alpha u + beta s du/dnu = g.  s = 1 gives helmholtz_line_bc's bits.  Needs no device."""
+    import numpy as np
+    M = max(int(P) - 2, 0)
+    b4 = np.array(_bc_ends(bc), dtype=np.float64)
+    S, Si, lam, Q, L, Bi = np.empty((M, M)), np.empty((M, M)), np.empty(M), np.empty((2, M)), np.empty((M, 2)), np.empty((2, 2))
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+    _chk(lib().cheb_helmholtz_line_box_host(int(P), ptr(b4), float(s), ptr(S), ptr(Si), ptr(lam), ptr(Q), ptr(L), ptr(Bi)))
+    return S, Si, lam, Q, L, Bi
+
+
+def _scale_array(scale, d):
+    """(numpy array or None, tuple or None) of a per-direction scale."""
+    import numpy as np
+    if scale is None:
+        return None, None
+    sc = np.ascontiguousarray(scale, dtype=np.float64)
+    if sc.shape != (d,):
+        raise ValueError("scale: expected %d values, got shape %r" % (d, sc.shape))
+    return sc, tuple(float(v) for v in sc)
+
+
 class HelmholtzSolver(_Handle):
     """u = (sigma I + A)^-1 f with A the EllipticOp operator at eta == 1 (zero Dirichlet values) by fast diagonalisation
     (cheb_helmholtz_*): `nfields` stacked interior fields of the grid `dims` per call; `size` values.  Usable as the M of
@@ -1084,22 +1120,32 @@ class HelmholtzSolver(_Handle):
     bc (None: Dirichlet on every face, today's solver): one entry per direction, either one spec for both ends or a pair
     (spec at index 0, spec at index n-1); a spec is "dirichlet", "neumann" or (alpha, beta) for alpha u + beta du/dnu = g,
     du/dnu outward.  Such a solver also has solve_full (full-grid output from interior f and boundary data g), full_size,
-    boundary_size and singular (sigma = 0 with Neumann everywhere: the constant-like zero mode is dropped)."""
+    boundary_size and singular (sigma = 0 with Neumann everywhere: the constant-like zero mode is dropped).
+
+    scale (needs bc; None: the cube, today's handle): scale[k] = 2 / L_k of a box; the solver inverts sigma - sum_k scale_k^2 d_k^2
+    and beta multiplies the physical normal derivative, alpha u + beta scale_k du/dnu = g (cheb_helmholtz_create_box)."""
     _destroy = "cheb_helmholtz_destroy"
 
-    def __init__(self, dims, sigma=0.0, nfields=1, bc=None):
+    def __init__(self, dims, sigma=0.0, nfields=1, bc=None, scale=None):
         self.dims = tuple(int(d) for d in dims)
         self.sigma = float(sigma)
         self.nfields = int(nfields)
         self.bc = None
+        if scale is not None and bc is None:
+            raise ValueError("scale needs bc: the box solve is a boundary-condition handle")
+        sc, self.scale = _scale_array(scale, len(self.dims))
         h = C.c_void_p()
         if bc is None:
             _chk(lib().cheb_helmholtz_create(len(self.dims), _ints(self.dims), self.sigma, self.nfields, C.byref(h)))
         else:
             b = bc_array(bc, len(self.dims))
             self.bc = tuple(tuple(b[4 * k:4 * k + 4]) for k in range(len(self.dims)))
-            _chk(lib().cheb_helmholtz_create_bc(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), self.sigma,
-                                                self.nfields, C.byref(h)))
+            if sc is None:
+                _chk(lib().cheb_helmholtz_create_bc(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), self.sigma,
+                                                    self.nfields, C.byref(h)))
+            else:
+                _chk(lib().cheb_helmholtz_create_box(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), _np_dp(sc), self.sigma,
+                                                     self.nfields, C.byref(h)))
             self.full_size = lib().cheb_helmholtz_full_size(h)
             self.boundary_size = lib().cheb_helmholtz_boundary_size(h)
             self.singular = bool(lib().cheb_helmholtz_singular(h))
@@ -1127,6 +1173,76 @@ class HelmholtzSolver(_Handle):
                 raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), n))
         _chk(lib().cheb_helmholtz_solve_bc(self._h, f.data_ptr(), None if g is None else g.data_ptr(), u.data_ptr(), _stream()))
         return u
+
+
+FACES = {"wall": 0, "open": 1}           # CHEB_FACE_*
+
+
+def _face_codes(bc, d):
+    """The 2 d ints of cheb_project_create from one entry per direction: "wall", "open" or a pair (index 0, index n - 1)."""
+    if bc is None:
+        return None
+    if isinstance(bc, str) or len(bc) != d:
+        raise ValueError("bc needs one entry per direction (%d)" % d)
+    out = []
+    for entry in bc:
+        pair = (entry, entry) if isinstance(entry, str) else tuple(entry) if isinstance(entry, (tuple, list)) else ()
+        if len(pair) != 2 or any(not isinstance(e, str) or e.lower() not in FACES for e in pair):
+            raise ValueError("a direction's faces are 'wall', 'open' or a pair of them, got %r" % (entry,))
+        out += [FACES[e.lower()] for e in pair]
+    return out
+
+
+def project_faces(dims):
+    """Per compact boundary node (row-major boundary order) 2 k + end of the face whose condition the node takes: the highest
+    direction k in which it is an end node, end 0 = index 0 (cheb_project_faces_host).  An int32 numpy array; needs no device."""
+    import numpy as np
+    dims = tuple(int(d) for d in dims)
+    nb = int(np.prod(dims)) - int(np.prod([n - 2 for n in dims])) if all(n >= 3 for n in dims) else 0
+    f = np.empty(max(nb, 0), dtype=np.int32)
+    _chk(lib().cheb_project_faces_host(len(dims), _ints(dims), f.ctypes.data_as(C.POINTER(C.c_int)) if f.size else None))
+    return f
+
+
+class ChebProject(_Handle):
+    """Projection of velocity fields onto discretely divergence-free ones on the box of `dims` and `scale` (scale[k] = 2 / L_k;
+    cheb_project_*): out_k = u_k - scale_k d_k phi, phi from one direct solve.  bc: per direction "wall" (the normal
+    velocity of the result is `flux`, default 0), "open" (phi = 0, an outflow face) or a pair for the two ends; None: walls.  A
+    velocity is d stacked full-grid fields (ChebGrad.div's layout), `nvec` of them per call, nvec * d <= 16.
+
+    With an open face div(out) = 0 at the interior nodes to rounding.  With walls only (`singular`) the solver drops the
+    constant-like mode and div(out) is one constant c(u) there: small for resolved fields, O(1) for noise.  An edge or corner node
+    meets the wall condition of its highest end direction only.  Asynchronous on torch's current stream; the same input gives the
+    same bits."""
+    _destroy = "cheb_project_destroy"
+
+    def __init__(self, dims, nvec=1, bc=None, scale=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.d = len(self.dims)
+        self.nvec = int(nvec)
+        faces = _face_codes(bc, self.d)
+        self.faces = None if faces is None else tuple(faces)
+        sc, self.scale = _scale_array(scale, self.d)
+        h = C.c_void_p()
+        _chk(lib().cheb_project_create(self.d, _ints(self.dims), None if faces is None else _ints(faces),
+                                       None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
+        self._h = h
+        self.size, self.interior_size, self.boundary_size = (lib().cheb_project_size(h, w) for w in range(3))
+        self.singular = bool(lib().cheb_project_singular(h))
+
+    def project(self, u, out=None, phi=None, flux=None):
+        """u: (nvec * d, *dims); flux: nvec * boundary_size prescribed outward normal velocities at the boundary nodes (compact,
+        row-major) or None; phi: nvec * size values, receives the potential (allocated if None); out (allocated if None) may be u.
+        Returns out."""
+        import torch
+        nu = self.nvec * self.d * self.size
+        if out is None:
+            out = torch.empty((self.nvec * self.d,) + self.dims, dtype=torch.float64, device=u.device)
+        if phi is None:
+            phi = torch.empty((self.nvec,) + self.dims, dtype=torch.float64, device=u.device)
+        _chk(lib().cheb_project_apply(self._h, _dev_ptr(u, nu), None if flux is None else _dev_ptr(flux, self.nvec * self.boundary_size),
+                                      _dev_ptr(phi, self.nvec * self.size), _dev_ptr(out, nu), _stream()))
+        return out
 
 
 class Lap1dPlan(_Handle):

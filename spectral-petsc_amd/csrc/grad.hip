@@ -8,7 +8,8 @@
 // a round write different arrays and read only inputs (which may overlap no output): they are independent, and go to
 // sweep_launch_multi in groups of at most 9 -- one launch where the 16-byte kernels take the group (plain stores, one matrix size
 // class, 16-byte aligned fields), one launch per job otherwise.  Rounds follow each other on the stream, so an accumulate always finds
-// its array's earlier terms.  Nothing depends on timing: the same call gives the same bits.
+// its array's earlier terms.  Nothing depends on timing: the same call gives the same bits.  A first term may name an array `acc` of
+// its own (cheb_grad_axpy_grad, the projection's out_k = u_k - s_k D_k phi): it is then added to acc instead of stored.
 //
 // Invariants.  k_grad_invariants reads the tensor G[v][c][k] (what cheb_grad_tensor writes) once and writes the selected fields; the
 // diagonal entries are loaded only if a selected field needs them, the off-diagonal ones likewise.  d <= 3 keeps the d^2 entries of
@@ -110,7 +111,7 @@ void launch_invariants(int d, long N, int nv, unsigned mask, int nsel, const dou
 }
 
 // one term of one output array: out (+)= alpha * M_k in, M = D or D D
-struct Term { const DiffMat *m; int k; const double *in; double alpha; };
+struct Term { const DiffMat *m; int k; const double *in; double alpha; const double *acc = nullptr; };
 
 }  // namespace
 
@@ -144,7 +145,9 @@ int run_rounds(const cheb_grad *h, const std::vector<std::vector<Term>> &terms, 
     int n = 0;
     for (size_t o = 0; o < terms.size(); o++) {
       if (r >= terms[o].size()) continue;
-      m[n] = terms[o][r].m; sp[n] = h->job(terms[o][r], outs[o], r > 0); n++;
+      m[n] = terms[o][r].m; sp[n] = h->job(terms[o][r], outs[o], r > 0);
+      if (r == 0 && terms[o][0].acc) { sp[n].out_mode = OUT_ACC; sp[n].acc = terms[o][0].acc; }
+      n++;
       if (n == GROUP) { HIP_TRY(sweep_launch_multi(n, m, sp, st)); n = 0; }
     }
     if (n) HIP_TRY(sweep_launch_multi(n, m, sp, st));
@@ -245,6 +248,22 @@ extern "C" int cheb_grad_div(cheb_grad *h, int nvec, const double *u_dev, double
     outs[v] = out_dev + (size_t)v * N;
     for (int k = 0; k < d; k++) terms[v].push_back(Term{&h->D.at(h->n[k]), k, u_dev + (size_t)(v * d + k) * N, h->scale[k]});
   }
+  return run_rounds(h, terms, outs, (hipStream_t)stream);
+}
+
+// out[v * d + k] = u[v * d + k] + alpha s_k d_k s[v]: one accumulating sweep per output (csrc/ops.h; project.hip).  out may be u,
+// s may overlap neither; the caller has checked the arrays.
+int cheb_grad_axpy_grad(cheb_grad *h, int nvec, double alpha, const double *s_dev, const double *u_dev, double *out_dev, void *stream) {
+  int rc;
+  if (nvec < 1) return chebhip_fail(CHEBHIP_ERR_ARG, "axpy_grad: %d vectors", nvec);
+  if ((rc = check_call(h, h ? nvec * h->d : nvec, "axpy_grad"))) return rc;
+  const int d = h->d; const long N = h->N;
+  std::vector<std::vector<Term>> terms; std::vector<double *> outs;
+  for (int v = 0; v < nvec; v++)
+    for (int k = 0; k < d; k++) {
+      terms.push_back({Term{&h->D.at(h->n[k]), k, s_dev + (size_t)v * N, alpha * h->scale[k], u_dev + (size_t)(v * d + k) * N}});
+      outs.push_back(out_dev + (size_t)(v * d + k) * N);
+    }
   return run_rounds(h, terms, outs, (hipStream_t)stream);
 }
 

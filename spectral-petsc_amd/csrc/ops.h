@@ -29,6 +29,8 @@ int ell_op_fd_view(ell_op *op, chebhip::FdView *v);          // chebhip.hip (all
 int ell_op_fd_view_any(ell_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view_any(stokes_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view(stokes_op *op, chebhip::FdView *v);    // stokes.hip
+// grad.hip: out[v * d + k] = u[v * d + k] + alpha s_k d_k s[v], one accumulating sweep each; out may be u (project.hip)
+int cheb_grad_axpy_grad(cheb_grad *h, int nvec, double alpha, const double *s_dev, const double *u_dev, double *out_dev, void *stream);
 int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip: sets chebhip_last_error(), returns code
 
 // A failed HIP call ends the calling function: `cleanup` runs, the error text is the call as written plus HIP's reason.

@@ -30,6 +30,7 @@
 #include <array>
 #include <map>
 #include <new>
+#include <tuple>
 #include <vector>
 
 using namespace chebhip;
@@ -279,9 +280,24 @@ __global__ __launch_bounds__(256, 3) void k_fdm_zsolve16(const FzParams p) {
 // parity: the modes use the parity layout (raw transforms, OUT_MUL and k_fdm_zsolve16 usable); a line whose two ends differ has
 // ascending modes and runs the two-launch transforms only.  bcm (boundary-condition lines): Q (2 x M), L^T (2 x M), B_BB^-1 (2 x 2)
 struct LineMats { DiffMat Fcs, Fca, Bcs, Bca, Fraw, Braw; double *lam = nullptr; double *bcm = nullptr; bool ok = false, parity = true; };
-// lines are shared by the directions of equal extent AND equal end conditions (alpha_first, beta_first, alpha_last, beta_last)
-typedef std::pair<int, std::array<double, 4>> LineKey;
+// lines are shared by the directions of equal extent, equal end conditions (alpha_first, beta_first, alpha_last, beta_last) AND
+// equal scale (cheb_helmholtz_create_box; 1 everywhere else)
+typedef std::tuple<int, std::array<double, 4>, double> LineKey;
 static const std::array<double, 4> BC_DIRICHLET = {1.0, 0.0, 1.0, 0.0};
+
+// The line of a direction of scale s = 2 / length (cheb_helmholtz_create_box): the operator is -s^2 (D D) and the end condition
+// alpha u + beta s du/dnu = g, so the line is spec_line_bc's for the ends (alpha, beta s) with lam and L times s^2 (in long double:
+// the caller rounds once); S, S^-1, Q and B_BB^-1 are that line's own.  s = 1 is spec_line_bc itself, bit for bit.
+int spec_line_box(int P, const double *bc4, double s, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam,
+                  std::vector<long double> &Q, std::vector<long double> &L, std::vector<long double> &Binv, bool &parity) {
+  const double e4[4] = {bc4[0], bc4[1] * s, bc4[2], bc4[3] * s};
+  const int rc = spec_line_bc(P, e4, S, Sinv, lam, Q, L, Binv, parity);
+  if (rc || s == 1.0) return rc;
+  const long double s2 = (long double)s * (long double)s;
+  for (auto &v : lam) v *= s2;
+  for (auto &v : L) v *= s2;
+  return 0;
+}
 
 }  // namespace
 
@@ -332,9 +348,10 @@ static void fdpc_free(chebhip_fdpc *pc) {
 
 // kind: LINE_FD (the finite-difference matrix) or LINE_SPECTRAL (sigma + the collocation operator at eta == 1); bare: a spectral
 // handle without an operator (v0.ixL / eta unused): only the buffers of the plain solve are allocated
-// bc (spectral only; may be null = Dirichlet everywhere): 4 d end conditions, spec_line_bc
+// bc (spectral only; may be null = Dirichlet everywhere): 4 d end conditions, spec_line_bc; scale (with bc only; may be null = 1
+// everywhere): d scales, spec_line_box
 static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc **out, int gP0 = 0, int kind = LINE_FD, double sigma = 0.0,
-                       bool bare = false, const double *bc = nullptr) {
+                       bool bare = false, const double *bc = nullptr, const double *scale = nullptr) {
   *out = nullptr;
   FdView v = v0;
   std::vector<int> gdims(v0.dims, v0.dims + (v0.d >= 1 && v0.d <= MAXD ? v0.d : 0));
@@ -362,13 +379,14 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     HIP_TRY_OR(hipMemcpy(pc->xs[k], x.data(), P * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
     std::array<double, 4> bk = BC_DIRICHLET;
     if (bc) for (int e = 0; e < 4; e++) bk[e] = bc[4 * k + e];
-    const LineKey key(P, bk);
+    const double sk = bc && scale ? scale[k] : 1.0;
+    const LineKey key(P, bk, sk);
     if (pc->lines.count(key)) { pc->ln[k] = &pc->lines[key]; continue; }
     LineMats lm;
     std::vector<long double> S, Si, lam, part, Qb, Lb, Bi;
     if (bc) {
       bool par = true;
-      const int rc = spec_line_bc(P, bk.data(), S, Si, lam, Qb, Lb, Bi, par);
+      const int rc = spec_line_box(P, bk.data(), sk, S, Si, lam, Qb, Lb, Bi, par);
       if (rc) {
         fdpc_free(pc);
         if (rc == SPEC_BC_COND) return chebhip_fail(CHEBHIP_ERR_ARG, "bc of dimension %d: (alpha, beta) must be finite, >= 0 and not both 0", k);
@@ -1005,13 +1023,17 @@ extern "C" int cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *
 }
 
 // ---- C ABI: the Helmholtz solve with Dirichlet, Neumann or Robin ends --------------------------------------------
-extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc, double sigma, int nfields, cheb_helmholtz **out) {
+// scale (NULL: 1 everywhere): the box [-1/s_0, 1/s_0] x ..: (sigma - sum_k s_k^2 d_k^2) u = f, alpha u + beta s_k du/dnu = g
+extern "C" int cheb_helmholtz_create_box(int d, const int *dims, const double *bc, const double *scale, double sigma, int nfields,
+                                         cheb_helmholtz **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
   if (!bc) return chebhip_fail(CHEBHIP_ERR_ARG, "bc is NULL");
   int rc = check_sigma(sigma); if (rc) return rc;
   if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  for (int k = 0; scale && k < d; k++)
+    if (!std::isfinite(scale[k]) || !(scale[k] > 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] = %g must be finite and > 0", k, scale[k]);
   for (int k = 0; k < d; k++)
     for (int e = 0; e < 2; e++) {
       const double a = bc[4 * k + 2 * e], b = bc[4 * k + 2 * e + 1];
@@ -1029,7 +1051,7 @@ extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc
   FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
   cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
-  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc);
+  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc, scale);
   if (rc) { delete h; return rc; }
   h->n = G * nfields; h->nf = nfields; h->bc = true;
   h->geo.d = d; h->geo.N = (int)N; h->geo.G = (int)G; h->geo.NB = (int)(N - G);
@@ -1051,6 +1073,10 @@ extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc
   }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc, double sigma, int nfields, cheb_helmholtz **out) {
+  return cheb_helmholtz_create_box(d, dims, bc, nullptr, sigma, nfields, out);
 }
 
 #define BC_LAUNCH(KERNEL, grid, ...)                                                                          \
@@ -1110,13 +1136,15 @@ extern "C" long cheb_helmholtz_full_size(const cheb_helmholtz *h) { return h ? (
 extern "C" long cheb_helmholtz_boundary_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * (h->pc->N - h->pc->G) : -1; }
 extern "C" int cheb_helmholtz_singular(const cheb_helmholtz *h) { return h ? h->singular : -1; }
 
-extern "C" int cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam, double *Q, double *L, double *Binv) {
+extern "C" int cheb_helmholtz_line_box_host(int P, const double *bc4, double scale, double *S, double *Sinv, double *lam, double *Q, double *L,
+                                            double *Binv) {
   if (P < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "P = %d: a line needs interior nodes (P >= 3)", P);
   if (P > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "P = %d: at most 258 points per line", P);
   if (!bc4 || !S || !Sinv || !lam || !Q || !L || !Binv) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!std::isfinite(scale) || !(scale > 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale = %g must be finite and > 0", scale);
   std::vector<long double> s, si, l, q, lf, bi;
   bool parity = true;
-  const int rc = spec_line_bc(P, bc4, s, si, l, q, lf, bi, parity);
+  const int rc = spec_line_box(P, bc4, scale, s, si, l, q, lf, bi, parity);
   if (rc == SPEC_BC_COND) return chebhip_fail(CHEBHIP_ERR_ARG, "bc = (%g, %g, %g, %g): each (alpha, beta) must be finite, >= 0 and not both 0", bc4[0], bc4[1], bc4[2], bc4[3]);
   if (rc == SPEC_BC_SINGULAR) return chebhip_fail(CHEBHIP_ERR_ARG, "bc: the end rows are singular");
   if (rc) return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point spectral line operator with bc failed", P);
@@ -1126,4 +1154,8 @@ extern "C" int cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, 
   for (int i = 0; i < 2 * M; i++) { Q[i] = (double)q[i]; L[i] = (double)lf[i]; }
   for (int i = 0; i < 4; i++) Binv[i] = (double)bi[i];
   return 0;
+}
+
+extern "C" int cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam, double *Q, double *L, double *Binv) {
+  return cheb_helmholtz_line_box_host(P, bc4, 1.0, S, Sinv, lam, Q, L, Binv);
 }

@@ -1,0 +1,178 @@
+// project.hip -- the projection of stacked full-grid velocity fields onto discretely divergence-free ones on a box
+// (cheb_project_*, include/chebhip.h): out_k = u_k - s_k d_k phi with phi the solution of the collocation problem
+//     sum_k s_k^2 (D D)_k phi = sum_k s_k d_k u_k  at the interior nodes,
+//     +- s_k d_k phi = +- u_k - flux  at the nodes of a wall,   phi = 0  at the nodes of an open face,
+// a boundary node taking the condition of the highest direction in which it is an end node (the edge rule of DESIGN 10c).
+//
+// A call is four steps on one stream, none of them a new sweep or solver kernel: the divergence (cheb_grad_div, into phi as
+// scratch), k_project_rhs (the one kernel of this file: the solver's interior right-hand side f = -div u and its compact boundary
+// data g from the divergence, u and the flux), cheb_helmholtz_solve_bc of a box handle (sigma = 0; (0, 1) ends at walls, (1, 0) at
+// open faces), and one accumulating sweep per output component (cheb_grad_axpy_grad: out_k = u_k + (-s_k) D_k phi).
+//
+// k_project_rhs: grid-stride over the nodes, one node per lane, the vectors along the grid's second dimension.  The handle's node table (ChebLayout's: m >= 0 the
+// number among the interior nodes, -1 - b on the boundary) sends a node's value to f or g; the face table gives a boundary node's
+// (direction, end) as 2 k + end.  Values are moved and negated, a flux is one subtraction; the field side is read coalesced.  No
+// LDS, no atomics, no scratch.
+#include "../../include/chebhip.h"
+#include "sweep.h"
+#include "ops.h"
+#include <cmath>
+#include <new>
+#include <vector>
+
+using namespace chebhip;
+
+namespace {
+
+constexpr int MD = 10;
+
+// blockIdx.y: the vector.  openf: bit 2 k + end set = that face is open (g = 0)
+__global__ __launch_bounds__(256) void k_project_rhs(long N, long G, long NB, int d, unsigned openf, const int *__restrict__ map,
+                                                     const unsigned char *__restrict__ face, const double *__restrict__ div,
+                                                     const double *__restrict__ u, const double *__restrict__ flux, double *__restrict__ f,
+                                                     double *__restrict__ g) {
+  const long v = blockIdx.y;
+  GS_LOOP(l, N) {
+    const int m = map[l];
+    if (m >= 0) { f[v * G + m] = -div[v * N + l]; continue; }
+    const long b = -1 - (long)m;
+    const int fc = face[b];
+    double val = 0.0;
+    if (!((openf >> fc) & 1u)) {
+      const double un = u[(size_t)(v * d + (fc >> 1)) * N + l];
+      val = (fc & 1) ? -un : un;
+      if (flux) val -= flux[v * NB + b];
+    }
+    g[v * NB + b] = val;
+  }
+}
+
+int check_grid(int d, const int *dims, long *N_out, long *G_out) {
+  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  long N = 1, G = 1;
+  for (int k = 0; k < d; k++) {
+    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d but must be >= 3: a line needs an interior node", k, dims[k]);
+    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: the direct solve supports at most 258 points per line", k, dims[k]);
+    N *= dims[k]; G *= dims[k] - 2;
+    if (N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 nodes or more");
+  }
+  *N_out = N; *G_out = G;
+  return 0;
+}
+
+// one node walk for both tables (either may be null): map[l] as cheb_layout_map_host, face[b] = 2 k + end of the highest end direction
+void walk(int d, const int *dims, int *map, int *face) {
+  BoxGrid box;
+  box.set_box(d, dims, 0, dims[0]);
+  int g = 0, b = 0;
+  box.for_each_node([&](long l, const int *ind, bool bdy) {
+    if (!bdy) { if (map) map[l] = g; g++; return; }
+    if (face) {
+      int k = d - 1;
+      while (ind[k] != 0 && ind[k] != dims[k] - 1) k--;
+      face[b] = 2 * k + (ind[k] != 0);
+    }
+    if (map) map[l] = -1 - b;
+    b++;
+  });
+}
+
+}  // namespace
+
+struct cheb_project {
+  int d = 0, nvec = 0;
+  long N = 0, G = 0;
+  unsigned open = 0;                 // bit 2 k + end
+  cheb_grad *grad = nullptr;
+  cheb_helmholtz *hz = nullptr;
+  int *map = nullptr;                // device [N]
+  unsigned char *face = nullptr;     // device [N - G]
+  double *f = nullptr, *g = nullptr; // device [nvec * G], [nvec * (N - G)]
+};
+
+extern "C" int cheb_project_destroy(cheb_project *h) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (h->grad) cheb_grad_destroy(h->grad);
+  if (h->hz) cheb_helmholtz_destroy(h->hz);
+  if (h->map) (void)hipFree(h->map);
+  if (h->face) (void)hipFree(h->face);
+  if (h->f) (void)hipFree(h->f);
+  if (h->g) (void)hipFree(h->g);
+  delete h;
+  return 0;
+}
+
+extern "C" int cheb_project_faces_host(int d, const int *dims, int *face) {
+  int rc; long N, G;
+  if ((rc = check_grid(d, dims, &N, &G))) return rc;
+  if (!face) return chebhip_fail(CHEBHIP_ERR_ARG, "face is NULL");
+  walk(d, dims, nullptr, face);
+  return 0;
+}
+
+extern "C" int cheb_project_create(int d, const int *dims, const int *faces, const double *scale, int nvec, cheb_project **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  int rc; long N, G;
+  if ((rc = check_grid(d, dims, &N, &G))) return rc;
+  if (nvec < 1 || (long)nvec * d > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nvec = %d: nvec * d must be in 1..16", nvec);
+  if ((long)nvec * d * N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
+  unsigned open = 0;
+  double bc[4 * MD];
+  for (int k = 0; k < d; k++) {
+    if (scale && (!std::isfinite(scale[k]) || !(scale[k] > 0.0))) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] = %g must be finite and > 0", k, scale[k]);
+    for (int e = 0; e < 2; e++) {
+      const int kind = faces ? faces[2 * k + e] : CHEB_FACE_WALL;
+      if (kind != CHEB_FACE_WALL && kind != CHEB_FACE_OPEN) return chebhip_fail(CHEBHIP_ERR_ARG, "faces[%d] = %d: CHEB_FACE_WALL or CHEB_FACE_OPEN", 2 * k + e, kind);
+      if (kind == CHEB_FACE_OPEN) open |= 1u << (2 * k + e);
+      bc[4 * k + 2 * e] = kind == CHEB_FACE_OPEN ? 1.0 : 0.0;         // open: phi = 0; wall: s_k dphi/dnu = g
+      bc[4 * k + 2 * e + 1] = kind == CHEB_FACE_OPEN ? 0.0 : 1.0;
+    }
+  }
+  if ((rc = require_device())) return rc;
+  cheb_project *h = new (std::nothrow) cheb_project;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  h->d = d; h->nvec = nvec; h->N = N; h->G = G; h->open = open;
+  if ((rc = cheb_grad_create(d, dims, scale, &h->grad)) || (rc = cheb_helmholtz_create_box(d, dims, bc, scale, 0.0, nvec, &h->hz))) {
+    cheb_project_destroy(h);
+    return rc;
+  }
+  const long NB = N - G;
+  std::vector<int> map((size_t)N), face((size_t)NB);
+  walk(d, dims, map.data(), face.data());
+  std::vector<unsigned char> fc(face.begin(), face.end());
+  HIP_TRY_MEM_OR(hipMalloc((void **)&h->map, (size_t)N * sizeof(int)), cheb_project_destroy(h));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&h->face, (size_t)NB), cheb_project_destroy(h));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&h->f, (size_t)nvec * G * sizeof(double)), cheb_project_destroy(h));
+  HIP_TRY_MEM_OR(hipMalloc((void **)&h->g, (size_t)nvec * NB * sizeof(double)), cheb_project_destroy(h));
+  HIP_TRY_OR(hipMemcpy(h->map, map.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice), cheb_project_destroy(h));
+  HIP_TRY_OR(hipMemcpy(h->face, fc.data(), (size_t)NB, hipMemcpyHostToDevice), cheb_project_destroy(h));
+  *out = h;
+  return 0;
+}
+
+extern "C" long cheb_project_size(const cheb_project *h, int which) {
+  if (!h || which < 0 || which > 2) return -1;
+  return which == 0 ? h->N : which == 1 ? h->G : h->N - h->G;
+}
+
+extern "C" int cheb_project_singular(const cheb_project *h) { return h ? cheb_helmholtz_singular(h->hz) : -1; }
+
+extern "C" int cheb_project_apply(cheb_project *h, const double *u_dev, const double *flux_dev, double *phi_dev, double *out_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "project: NULL handle");
+  if (!u_dev || !phi_dev || !out_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "project: NULL array");
+  const long N = h->N, G = h->G, NB = N - G, nu = (long)h->nvec * h->d * N, np = (long)h->nvec * N, nb = (long)h->nvec * NB;
+  if (out_dev != u_dev && overlap(out_dev, nu, u_dev, nu)) return chebhip_fail(CHEBHIP_ERR_ARG, "project: out is u or does not overlap it");
+  if (overlap(phi_dev, np, u_dev, nu) || overlap(phi_dev, np, out_dev, nu)) return chebhip_fail(CHEBHIP_ERR_ARG, "project: phi must not overlap u or out");
+  if (flux_dev && (overlap(flux_dev, nb, u_dev, nu) || overlap(flux_dev, nb, out_dev, nu) || overlap(flux_dev, nb, phi_dev, np)))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "project: flux must not overlap u, out or phi");
+  int rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = cheb_grad_div(h->grad, h->nvec, u_dev, phi_dev, stream))) return rc;
+  hipLaunchKernelGGL(k_project_rhs, dim3(grid1d(N, 256, 4096), (unsigned)h->nvec), dim3(256), 0, st, N, G, NB, h->d, h->open, h->map, h->face, phi_dev, u_dev,
+                     flux_dev, h->f, h->g);
+  sweep_note_launch();
+  HIP_TRY(hipGetLastError());
+  if ((rc = cheb_helmholtz_solve_bc(h->hz, h->f, h->g, phi_dev, stream))) return rc;
+  return cheb_grad_axpy_grad(h->grad, h->nvec, -1.0, phi_dev, u_dev, out_dev, stream);
+}

@@ -78,15 +78,18 @@ def poisson_solve(sp, op, b, x, sigma=0.0, solver=None):
     return x
 
 
-def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None):
+def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     """sigma u - Laplace u = f with alpha u + beta du/dnu = g on every face (sp.HelmholtzSolver's `bc`), solved directly.
     f_full: full-grid device tensor (its boundary entries are ignored); g: the compact boundary values in row-major node order
     (the ell_op_set_dirichlet layout) or None for zero data.  solver: a caller's HelmholtzSolver(dims, sigma, bc=bc) to use and
-    keep (its nfields stacked fields); None: one is made and destroyed here.  Returns the full-grid u (a new tensor)."""
+    keep (its nfields stacked fields); None: one is made and destroyed here.  scale (None: the cube): the box solve of
+    HelmholtzSolver(scale=...), sigma u - sum_k scale_k^2 d_k^2 u = f.  Returns the full-grid u (a new tensor)."""
     dims = tuple(int(d) for d in dims)
     own = solver is None
     if own:
-        solver = sp.HelmholtzSolver(dims, sigma, bc=bc)
+        solver = sp.HelmholtzSolver(dims, sigma, bc=bc, scale=scale)
+    elif solver.scale != (None if scale is None else tuple(float(v) for v in scale)):
+        raise ValueError("solver: a HelmholtzSolver with the same scale")
     elif solver.dims != dims or solver.sigma != float(sigma) or solver.bc is None or solver.bc != tuple(tuple(sp.bc_array(bc, len(dims))[4 * k:4 * k + 4]) for k in range(len(dims))):
         raise ValueError("solver: a HelmholtzSolver of the grid with sigma = %g and the same bc" % sigma)
     try:
@@ -100,6 +103,25 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None):
         if own:
             solver.destroy()
     return u
+
+
+def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
+    """(out, phi) of sp.ChebProject(dims, nvec, bc, scale).project(u, flux=flux) with a handle made and destroyed here: u holds
+    nvec * d full-grid fields, out its divergence-free projection (new tensors)."""
+    dims = tuple(int(d) for d in dims)
+    N = 1
+    for n in dims:
+        N *= n
+    per = N * len(dims)
+    if u.numel() == 0 or u.numel() % per:
+        raise ValueError("u has %d elements, no multiple of %d" % (u.numel(), per))
+    h = sp.ChebProject(dims, u.numel() // per, bc, scale)
+    try:
+        phi = torch.empty((h.nvec,) + dims, dtype=torch.float64, device=u.device)
+        out = h.project(u, phi=phi, flux=flux)
+    finally:
+        h.destroy()
+    return out, phi
 
 
 def continuation_schedule(exponent, regularization, cont0=0, cont=1):
