@@ -827,6 +827,55 @@ int  cheb_project_faces_host(int d, const int *dims, int *face);
 int  cheb_project_apply(cheb_project *h, const double *u_dev, const double *flux_dev, double *phi_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Functions of the Helmholtz operator.  B = sigma - sum_k s_k^2  */
+/* d_k^2 with the faces of cheb_helmholtz_create_box is diagonal in the        */
+/* solver's line eigenvectors S = S_0 x .. x S_{d-1}; one call computes, for   */
+/* every output field o,                                                       */
+/*   y_o = S [ sum_{terms t with out = o} c_t f_t(s) .* (S^-1 x_{i_t}) ]       */
+/* with s = ((sigma + l_0[i_0]) + l_1[i_1]) + ... the eigenvalue sum of a mode */
+/* (the association of the solver's weights) and the terms of an output added  */
+/* in table order into a sum that starts at 0: the same input gives the same   */
+/* bits.  An output without a term is 0.  The kinds, z = -tau s:               */
+/*   ONE   1                                                                   */
+/*   INV   1 / s               (s == 0: 0, the dropped mode of a singular box) */
+/*   RES   1 / (par + tau s)   (a zero denominator: 0)                         */
+/*   EXP   e^z                                                                 */
+/*   PHI1..PHI3  phi_k(z), phi_0 = e^z, phi_{k+1}(z) = (phi_k(z) - 1/k!) / z   */
+/*         (z == 0: 1/k!)                                                      */
+/*   POW   s^par               (s == 0: 0, or 1 for par == 0; s < 0: NaN)      */
+/* EXP and PHI* need a finite tau >= 0, RES finite par and tau, POW a finite   */
+/* par; what a kind does not read is ignored.                                  */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_opfun cheb_opfun;
+enum { CHEB_OPFUN_ONE = 0, CHEB_OPFUN_INV, CHEB_OPFUN_RES, CHEB_OPFUN_EXP, CHEB_OPFUN_PHI1, CHEB_OPFUN_PHI2, CHEB_OPFUN_PHI3, CHEB_OPFUN_POW };
+typedef struct { int out, in, kind; double coef, tau, par; } cheb_opfun_term;
+/* d, dims, bc, scale, sigma as cheb_helmholtz_create_box with the same limits, except that bc may be NULL (Dirichlet on every
+ * face: the lines of cheb_helmholtz_create; scale then has to be NULL too).  nin input and nout output fields per call, 1..16
+ * each: stacked interior fields of G = prod(dims - 2) values.  The handle owns its lines and scratch; a new handle has no term. */
+int  cheb_opfun_create(int d, const int *dims, const double *bc, const double *scale, double sigma, int nin, int nout, cheb_opfun **out);
+int  cheb_opfun_destroy(cheb_opfun *h);
+/* Replaces the term table (0..32 terms, HOST array).  Host work only: no device call, no allocation; the table travels with each
+ * apply as a kernel argument, so a call queued earlier keeps the table it was issued with. */
+int  cheb_opfun_set_terms(cheb_opfun *h, int nterms, const cheb_opfun_term *terms);
+/* set_terms' checks for a handle of nin inputs and nout outputs, without one: 0 or CHEBHIP_ERR_ARG.  Needs no device. */
+int  cheb_opfun_check_terms(int nin, int nout, int nterms, const cheb_opfun_term *terms);
+/* x: nin * G, y: nout * G DEVICE values.  d forward line transforms of nin fields, one launch of the mixing kernel, d backward
+ * line transforms of nout fields.  y may BE x when nin == nout; any other overlap is CHEBHIP_ERR_ARG.  Asynchronous on `stream`,
+ * allocates nothing. */
+int  cheb_opfun_apply(cheb_opfun *h, const double *x_dev, double *y_dev, void *stream);
+/* Handles made with bc: the same, each output written as a full-grid field (nout * N values) whose boundary values are those of
+ * the homogeneous conditions, u_B = Q u_I (the extension of cheb_helmholtz_solve_bc with g = NULL).  yfull may not overlap x. */
+int  cheb_opfun_apply_full(cheb_opfun *h, const double *x_dev, double *yfull_dev, void *stream);
+long cheb_opfun_size(const cheb_opfun *h, int which);      /* 0: nin * G, 1: nout * G, 2: nout * N; -1 on a bad argument */
+int  cheb_opfun_singular(const cheb_opfun *h);             /* 1: sigma = 0 and alpha = 0 on every face (a mode with s == 0); -1: NULL */
+/* f(s) of one kind for HOST doubles: z and f in long double, rounded once (phi_k by a series without cancellation for
+ * |z| <= 1).  Needs no device. */
+int  cheb_opfun_weight_host(int kind, double tau, double par, double s, double *w);
+int  cheb_opfun_weights_host(int kind, double tau, double par, long n, const double *s, double *w);   /* the same for n HOST values */
+/* w[i] = f(s[i]) for n DEVICE values by the mixing kernel's own device functions: the weights of a spectrum. */
+int  cheb_opfun_eval(int kind, double tau, double par, const double *s_dev, long n, double *w_dev, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* The block preconditioners of the Stokes saddle-point system:  */
 /* StokesPCApply0..3 (stokes.C:1714-1817) with the inner solves KSPVelocity,    */
 /* KSPSchur and KSPSchurVelocity (stokes.C:328-341) on device vectors.          */

@@ -79,7 +79,14 @@ ABI_SYMBOLS = [
     "cheb_helmholtz_create_box", "cheb_helmholtz_line_box_host",
     "cheb_project_create", "cheb_project_destroy", "cheb_project_size", "cheb_project_singular", "cheb_project_faces_host",
     "cheb_project_apply",
+    "cheb_opfun_create", "cheb_opfun_destroy", "cheb_opfun_set_terms", "cheb_opfun_apply", "cheb_opfun_apply_full", "cheb_opfun_size",
+    "cheb_opfun_singular", "cheb_opfun_check_terms", "cheb_opfun_weight_host", "cheb_opfun_weights_host", "cheb_opfun_eval",
 ]
+
+
+class OpFunTerm(C.Structure):
+    """cheb_opfun_term"""
+    _fields_ = [("out", C.c_int), ("inp", C.c_int), ("kind", C.c_int), ("coef", C.c_double), ("tau", C.c_double), ("par", C.c_double)]
 
 
 class ChebhipError(RuntimeError):
@@ -320,6 +327,18 @@ def lib():
         L.cheb_project_singular.argtypes = [vp]
         L.cheb_project_faces_host.argtypes = [C.c_int, ip, ip]
         L.cheb_project_apply.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.cheb_opfun_create.argtypes = [C.c_int, ip, dp, dp, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
+        L.cheb_opfun_destroy.argtypes = [vp]
+        L.cheb_opfun_set_terms.argtypes = [vp, C.c_int, C.POINTER(OpFunTerm)]
+        L.cheb_opfun_check_terms.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(OpFunTerm)]
+        L.cheb_opfun_apply.argtypes = [vp, vp, vp, vp]
+        L.cheb_opfun_apply_full.argtypes = [vp, vp, vp, vp]
+        L.cheb_opfun_size.argtypes = [vp, C.c_int]
+        L.cheb_opfun_size.restype = C.c_long
+        L.cheb_opfun_singular.argtypes = [vp]
+        L.cheb_opfun_weight_host.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, dp]
+        L.cheb_opfun_weights_host.argtypes = [C.c_int, C.c_double, C.c_double, C.c_long, dp, dp]
+        L.cheb_opfun_eval.argtypes = [C.c_int, C.c_double, C.c_double, vp, C.c_long, vp, vp]
         _lib = L
     return _lib
 
@@ -1173,6 +1192,130 @@ class HelmholtzSolver(_Handle):
                 raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), n))
         _chk(lib().cheb_helmholtz_solve_bc(self._h, f.data_ptr(), None if g is None else g.data_ptr(), u.data_ptr(), _stream()))
         return u
+
+
+OPFUN_KINDS = {"one": 0, "inv": 1, "res": 2, "exp": 3, "phi1": 4, "phi2": 5, "phi3": 6, "pow": 7}           # CHEB_OPFUN_*
+
+
+def _opfun_kind(kind):
+    if isinstance(kind, str):
+        if kind.lower() not in OPFUN_KINDS:
+            raise ValueError("unknown kind %r: one of %s" % (kind, ", ".join(OPFUN_KINDS)))
+        return OPFUN_KINDS[kind.lower()]
+    return int(kind)
+
+
+def _opfun_terms(terms):
+    """(tuples, ctypes array) of a list of (out, in, kind, coef, tau, par)."""
+    terms = [tuple(t) for t in terms]
+    if any(len(t) != 6 for t in terms):
+        raise ValueError("a term is (out, in, kind, coef, tau, par)")
+    arr = (OpFunTerm * max(len(terms), 1))()
+    for e, (o, i, kind, c, ta, pa) in zip(arr, terms):
+        e.out, e.inp, e.kind, e.coef, e.tau, e.par = int(o), int(i), _opfun_kind(kind), float(c), float(ta), float(pa)
+    return terms, arr
+
+
+def opfun_check_terms(nin, nout, terms):
+    """ChebOpFun.set_terms' checks for a handle of nin inputs and nout outputs, without one (cheb_opfun_check_terms): raises
+    ChebhipError as set_terms would.  Needs no device."""
+    terms, arr = _opfun_terms(terms)
+    _chk(lib().cheb_opfun_check_terms(int(nin), int(nout), len(terms), arr))
+
+
+def opfun_weight(kind, tau, par, s):
+    """f(s) of one kind of ChebOpFun for host values (cheb_opfun_weights_host): z = -tau s and f in long double, rounded once.
+    s: a number or a numpy array; the result has its shape.  Needs no device."""
+    import numpy as np
+    a = np.ascontiguousarray(s, dtype=np.float64)
+    w = np.empty_like(a)
+    ptr = lambda v: v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None
+    _chk(lib().cheb_opfun_weights_host(_opfun_kind(kind), float(tau), float(par), a.size, ptr(a), ptr(w)))
+    return w if np.ndim(s) else float(w.reshape(-1)[0])
+
+
+def opfun_eval(kind, tau, par, s_dev, out=None):
+    """The same on the device, by the device functions ChebOpFun's kernel runs (cheb_opfun_eval): s_dev a contiguous float64 device
+    tensor; returns a tensor of its shape.  Asynchronous on torch's current stream."""
+    import torch
+    if out is None:
+        out = torch.empty_like(s_dev)
+    n = s_dev.numel()
+    _chk(lib().cheb_opfun_eval(_opfun_kind(kind), float(tau), float(par), _dev_ptr(s_dev, n) if n else None, n,
+                               _dev_ptr(out, n) if n else None, _stream()))
+    return out
+
+
+class ChebOpFun(_Handle):
+    """Functions of the Helmholtz operator B = sigma - sum_k scale_k^2 d_k^2 of HelmholtzSolver (same dims, bc, scale, sigma;
+    cheb_opfun_*): one call maps `nin` stacked interior fields to `nout`,
+        y_o = sum_{terms (o, i, kind, coef, tau, par)} coef f_kind(B) x_i,
+    by the solver's line transforms around ONE pointwise kernel in mode space, whatever the number of terms (at most 32).  Kinds,
+    with s an eigenvalue of B: "one" 1, "inv" 1/s, "res" 1/(par + tau s), "exp" e^(-tau s), "phi1".."phi3" phi_k(-tau s) (the
+    functions of exponential integrators), "pow" s^par.  A mode with s == 0 (`singular`: sigma = 0, Neumann everywhere) gets 0 from
+    inv and pow, 1/k! from phi_k, 1 from exp.  Terms of an output are added in table order; the same input gives the same bits."""
+    _destroy = "cheb_opfun_destroy"
+
+    def __init__(self, dims, nin=1, nout=None, sigma=0.0, bc=None, scale=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.nin = int(nin)
+        self.nout = self.nin if nout is None else int(nout)
+        self.sigma = float(sigma)
+        d = len(self.dims)
+        if scale is not None and bc is None:
+            raise ValueError("scale needs bc: the box is a boundary-condition handle")
+        sc, self.scale = _scale_array(scale, d)
+        b = None if bc is None else bc_array(bc, d)
+        self.bc = None if b is None else tuple(tuple(b[4 * k:4 * k + 4]) for k in range(d))
+        h = C.c_void_p()
+        _chk(lib().cheb_opfun_create(d, _ints(self.dims), None if b is None else (C.c_double * len(b))(*b),
+                                     None if sc is None else _np_dp(sc), self.sigma, self.nin, self.nout, C.byref(h)))
+        self._h = h
+        self.size, self.out_size, self.full_size = (lib().cheb_opfun_size(h, w) for w in range(3))
+        self.singular = bool(lib().cheb_opfun_singular(h))
+        self.terms = ()
+
+    def set_terms(self, terms, tau=0.0, par=0.0, coef=1.0):
+        """terms: tuples (out, in, kind, coef, tau, par), or one kind name: that function on every field (nin == nout) with the
+        keyword tau / par / coef.  Host work only; an apply queued earlier keeps the table it was issued with."""
+        if isinstance(terms, str):
+            if self.nin != self.nout:
+                raise ValueError("the shorthand needs nin == nout")
+            terms = [(f, f, terms, coef, tau, par) for f in range(self.nin)]
+        terms, arr = _opfun_terms(terms)
+        _chk(lib().cheb_opfun_set_terms(self._h, len(terms), arr))
+        self.terms = tuple(terms)
+
+    def _check(self, name, t, n):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 device tensor" % name)
+        if t.numel() != n:
+            raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), n))
+
+    def apply(self, x, out=None):
+        """x: `size` = nin * G values; out (allocated if None): `out_size` = nout * G values, may be x when nin == nout.
+        Asynchronous on torch's current stream."""
+        import torch
+        self._check("x", x, self.size)
+        if out is None:
+            out = torch.empty(self.out_size, dtype=torch.float64, device=x.device)
+        self._check("out", out, self.out_size)
+        _chk(lib().cheb_opfun_apply(self._h, x.data_ptr(), out.data_ptr(), _stream()))
+        return out
+
+    def apply_full(self, x, out=None):
+        """With bc: the same, each output as a full-grid field (`full_size` = nout * N values) whose boundary values are those of
+        the homogeneous conditions (u_B = Q u_I)."""
+        import torch
+        if self.bc is None:
+            raise ValueError("apply_full needs a handle made with bc")
+        self._check("x", x, self.size)
+        if out is None:
+            out = torch.empty(self.full_size, dtype=torch.float64, device=x.device)
+        self._check("out", out, self.full_size)
+        _chk(lib().cheb_opfun_apply_full(self._h, x.data_ptr(), out.data_ptr(), _stream()))
+        return out
 
 
 FACES = {"wall": 0, "open": 1}           # CHEB_FACE_*

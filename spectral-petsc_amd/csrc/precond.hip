@@ -24,6 +24,7 @@
 // Such a handle has no stencil: ell_pc_create_spectral gives z = (sigma I + A)^-1 (r / eta), cheb_helmholtz_* the bare solve.
 #include "../../include/chebhip.h"
 #include "ops.h"
+#include "opfun.h"
 #include "sweep.h"
 #include "timers.h"
 #include <cmath>
@@ -508,11 +509,13 @@ static int fdpc_update(chebhip_fdpc *pc, hipStream_t st) {
 // asked line_in_mul_ok first
 static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool backward, const double *x, double *y, hipStream_t st,
                             const double *mul = nullptr, bool *fused = nullptr, const double *in_mul = nullptr);
+// nf (0: the handle's): the stacked fields of this call, at most the handle's (cheb_opfun: its inputs forward, its outputs backward)
 static int line_transform(chebhip_fdpc *pc, int k, bool backward, const double *x, double *y, hipStream_t st, const double *mul = nullptr, bool *fused = nullptr,
-                          const double *in_mul = nullptr) {
+                          const double *in_mul = nullptr, int nf = 0) {
   if (fused) *fused = false;
-  if (pc->slab && k == 0) return pc->dim0(pc->dim0_ctx, backward ? 1 : 0, pc->nf, x, y, (void *)st);      // collective: every rank of the slab partition
-  return line_transform_g(*pc->ln[k], pc->ncols_g[k] * (unsigned)pc->nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul);
+  if (nf == 0) nf = pc->nf;
+  if (pc->slab && k == 0) return pc->dim0(pc->dim0_ctx, backward ? 1 : 0, nf, x, y, (void *)st);      // collective: every rank of the slab partition
+  return line_transform_g(*pc->ln[k], pc->ncols_g[k] * (unsigned)nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul);
 }
 static SweepParams line_in_mul_params(unsigned ncols, unsigned inner, const double *x, double *y, const double *in_mul) {
   SweepParams sm = {};
@@ -1081,7 +1084,7 @@ extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc
 
 #define BC_LAUNCH(KERNEL, grid, ...)                                                                          \
   do {                                                                                                       \
-    switch (h->geo.d) {                                                                                      \
+    switch (geo.d) {                                                                                         \
       case 1: hipLaunchKernelGGL(KERNEL<1>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
       case 2: hipLaunchKernelGGL(KERNEL<2>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
       case 3: hipLaunchKernelGGL(KERNEL<3>, grid, dim3(256), 0, st, __VA_ARGS__); break;                     \
@@ -1092,6 +1095,31 @@ extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc
 static bool overlaps(const double *a, long na, const double *b, long nb) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
   return pa < pb + (uintptr_t)nb * sizeof(double) && pb < pa + (uintptr_t)na * sizeof(double);
+}
+
+// u (nf full grids) from the interior fields z and the boundary data g (null: zero data, u_B = Q u_I): end values direction by
+// direction, the lines of direction k read the edges direction k - 1 has written
+static int bc_extend(const cheb_helmholtz *h, int nf, const double *z, const double *g_dev, double *u_dev, hipStream_t st) {
+  const BcGeo &geo = h->geo;
+  const int d = geo.d;
+  BcMats bm;
+  for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
+  long before = 1;                             // prod_{m < k} P_m
+  for (int k = 0; k < d; k++) {
+    const double *src = k == 0 ? z : nullptr;
+    if (k < d - 1) {
+      long nl = before;
+      for (int m = k + 1; m < d; m++) nl *= geo.P[m] - 2;
+      BC_LAUNCH(k_bc_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), geo, k, bm.m[k], h->dir[k][0], h->dir[k][1], (int)nl, src,
+                g_dev, u_dev);
+    } else {
+      BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), geo, bm.m[k], h->dir[k][0], h->dir[k][1], (int)before,
+                src, g_dev, u_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    before *= geo.P[k];
+  }
+  return 0;
 }
 
 extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, const double *g_dev, double *u_dev, void *stream) {
@@ -1107,30 +1135,14 @@ extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, c
   for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
   const double *rhs = f_dev;
   if (g_dev) {                                 // (g = NULL: zero data, nothing to lift)
-    BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), h->geo, bm, f_dev, g_dev, h->t);
+    const BcGeo &geo = h->geo;
+    BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), geo, bm, f_dev, g_dev, h->t);
     HIP_TRY(hipGetLastError());
     rhs = h->t;
   }
   int rc = fdm_solve(h->pc, rhs, h->z, st); if (rc) return rc;
-  // end values direction by direction: the lines of direction k read the edges direction k - 1 has written
-  long before = 1;                             // prod_{m < k} P_m
-  for (int k = 0; k < d; k++) {
-    const double *src = k == 0 ? h->z : nullptr;
-    if (k < d - 1) {
-      long nl = before;
-      for (int m = k + 1; m < d; m++) nl *= h->geo.P[m] - 2;
-      BC_LAUNCH(k_bc_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), h->geo, k, bm.m[k], h->dir[k][0], h->dir[k][1], (int)nl, src,
-                g_dev, u_dev);
-    } else {
-      BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), h->geo, bm.m[k], h->dir[k][0], h->dir[k][1], (int)before,
-                src, g_dev, u_dev);
-    }
-    HIP_TRY(hipGetLastError());
-    before *= h->geo.P[k];
-  }
-  return 0;
+  return bc_extend(h, nf, h->z, g_dev, u_dev, st);
 }
-#undef BC_LAUNCH
 
 extern "C" long cheb_helmholtz_full_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * h->pc->N : -1; }
 extern "C" long cheb_helmholtz_boundary_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * (h->pc->N - h->pc->G) : -1; }
@@ -1159,3 +1171,100 @@ extern "C" int cheb_helmholtz_line_box_host(int P, const double *bc4, double sca
 extern "C" int cheb_helmholtz_line_bc_host(int P, const double *bc4, double *S, double *Sinv, double *lam, double *Q, double *L, double *Binv) {
   return cheb_helmholtz_line_box_host(P, bc4, 1.0, S, Sinv, lam, Q, L, Binv);
 }
+
+// ---- C ABI: functions of the Helmholtz operator (cheb_opfun_*) -------------------------------------------------------
+// The handle is a solver handle of max(nin, nout) fields, of which it uses the lines, the eigenvalues (lam0: sigma + l_0), the two
+// transform buffers and, for apply_full, the interior buffer and the extension kernels; the solver's weight array and lift buffer
+// are given back at create.  The pointwise step is opfun.hip's kernel, with the table as its argument.
+struct cheb_opfun {
+  cheb_helmholtz *hz = nullptr;
+  int nin = 1, nout = 1;
+  bool bc = false;
+  long G = 0, N = 0;
+  OpfunTable tb = {};
+};
+
+extern "C" int cheb_opfun_destroy(cheb_opfun *h) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (h->hz) cheb_helmholtz_destroy(h->hz);
+  delete h;
+  return 0;
+}
+
+extern "C" int cheb_opfun_create(int d, const int *dims, const double *bc, const double *scale, double sigma, int nin, int nout, cheb_opfun **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (nin < 1 || nin > OPFUN_MAX_FIELDS) return chebhip_fail(CHEBHIP_ERR_ARG, "nin = %d must be in 1..16", nin);
+  if (nout < 1 || nout > OPFUN_MAX_FIELDS) return chebhip_fail(CHEBHIP_ERR_ARG, "nout = %d must be in 1..16", nout);
+  if (!bc && scale) return chebhip_fail(CHEBHIP_ERR_ARG, "scale needs bc: the box is a boundary-condition handle");
+  cheb_opfun *h = new (std::nothrow) cheb_opfun;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
+  const int nf = nin > nout ? nin : nout;
+  int rc = bc ? cheb_helmholtz_create_box(d, dims, bc, scale, sigma, nf, &h->hz) : cheb_helmholtz_create(d, dims, sigma, nf, &h->hz);
+  if (rc) { delete h; return rc; }
+  h->nin = nin; h->nout = nout; h->bc = bc != nullptr;
+  chebhip_fdpc *pc = h->hz->pc;
+  h->G = pc->G; h->N = pc->N;
+  if (pc->W) { (void)hipFree(pc->W); pc->W = nullptr; }
+  if (h->hz->t) { (void)hipFree(h->hz->t); h->hz->t = nullptr; }
+  (void)opfun_build_table(nin, nout, 0, nullptr, &h->tb);
+  *out = h;
+  return 0;
+}
+
+extern "C" int cheb_opfun_set_terms(cheb_opfun *h, int nterms, const cheb_opfun_term *terms) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  OpfunTable tb;
+  int rc = opfun_build_table(h->nin, h->nout, nterms, terms, &tb); if (rc) return rc;      // (a refused table leaves the old one in place)
+  h->tb = tb;
+  return 0;
+}
+
+extern "C" long cheb_opfun_size(const cheb_opfun *h, int which) {
+  if (!h || which < 0 || which > 2) return -1;
+  return which == 0 ? h->nin * h->G : which == 1 ? h->nout * h->G : h->nout * h->N;
+}
+
+extern "C" int cheb_opfun_singular(const cheb_opfun *h) { return h ? h->hz->singular : -1; }
+
+// y (nout interior fields: the caller's array or the solver's z, never t0 / t1) from x; d transforms, the mixing launch, d transforms
+static int opfun_run(cheb_opfun *h, const double *x, double *y, hipStream_t st) {
+  chebhip_fdpc *pc = h->hz->pc;
+  const int d = pc->geo.d;
+  const double *src = x;
+  double *a = pc->t0, *b = pc->t1;
+  int rc;
+  for (int k = 0; k < d; k++) {
+    if ((rc = line_transform(pc, k, false, src, a, st, nullptr, nullptr, nullptr, h->nin))) return rc;
+    src = a; std::swap(a, b);
+  }
+  int M[MAXD]; const double *lam[MAXD];
+  for (int k = 0; k < d; k++) { M[k] = pc->geo.dims[k] - 2; lam[k] = k == 0 ? pc->lam0 : pc->ln[k]->lam; }
+  if ((rc = opfun_mix_launch(h->tb, d, M, pc->G, lam, src, a, st))) return rc;
+  src = a; std::swap(a, b);
+  for (int k = d - 1; k >= 0; k--) {
+    double *dst = k == 0 ? y : a;
+    if ((rc = line_transform(pc, k, true, src, dst, st, nullptr, nullptr, nullptr, h->nout))) return rc;
+    src = dst; std::swap(a, b);
+  }
+  return 0;
+}
+
+extern "C" int cheb_opfun_apply(cheb_opfun *h, const double *x_dev, double *y_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: NULL handle");
+  if (!x_dev || !y_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: NULL array");
+  // the first forward transform reads x into scratch and the last backward one writes y: y == x is safe
+  if (!(x_dev == y_dev && h->nin == h->nout) && overlaps(x_dev, h->nin * h->G, y_dev, h->nout * h->G))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: y is x (nin == nout) or does not overlap it");
+  return opfun_run(h, x_dev, y_dev, (hipStream_t)stream);
+}
+
+extern "C" int cheb_opfun_apply_full(cheb_opfun *h, const double *x_dev, double *yfull_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: NULL handle");
+  if (!h->bc) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_opfun_apply_full: a handle made with bc");
+  if (!x_dev || !yfull_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: NULL array");
+  if (overlaps(x_dev, h->nin * h->G, yfull_dev, h->nout * h->N)) return chebhip_fail(CHEBHIP_ERR_ARG, "opfun: yfull may not overlap x");
+  int rc = opfun_run(h, x_dev, h->hz->z, (hipStream_t)stream); if (rc) return rc;
+  return bc_extend(h->hz, h->nout, h->hz->z, nullptr, yfull_dev, (hipStream_t)stream);
+}
+#undef BC_LAUNCH

@@ -124,6 +124,51 @@ def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
     return out, phi
 
 
+def diffuse(sp, dims, u_full, t, bc, g=None, f=None, kappa=1.0, scale=None):
+    """The exact solution at time t of u_t = kappa sum_k scale_k^2 d_k^2 u + f from the full-grid field u_full, with the steady
+    conditions alpha u + beta du/dnu = g of `bc` (sp.HelmholtzSolver's) on the faces: u_s + extend(e^(-t kappa A) (u_0 - u_s)_I),
+    u_s the steady solution (one HelmholtzSolver.solve_full; 0 without f and g), the exponential one sp.ChebOpFun.apply_full.
+    f: full-grid device tensor (boundary entries ignored) or None; g: compact boundary values or None.  u_full is expected to
+    meet the conditions; its boundary entries are not read.  Neumann on every face is singular: only f = None, g = None is
+    handled there.  No time stepping: any t >= 0 in one call.  Returns a new (*dims) tensor."""
+    dims = tuple(int(n) for n in dims)
+    t, kappa = float(t), float(kappa)
+    if not (t >= 0.0 and kappa > 0.0):
+        raise ValueError("diffuse: t >= 0 and kappa > 0")
+    fun = sp.ChebOpFun(dims, 1, 1, 0.0, bc=bc, scale=scale)
+    solver = None
+    try:
+        if u_full.numel() != fun.full_size:
+            raise ValueError("u_full has %d elements, expected %d" % (u_full.numel(), fun.full_size))
+        steady = f is not None or g is not None
+        if steady and fun.singular:
+            raise ValueError("diffuse: Neumann conditions on every face have no steady state for general f and g; pass f = None, g = None")
+        v = u_full.reshape((1,) + dims)
+        us = None
+        if steady:
+            solver = sp.HelmholtzSolver(dims, 0.0, bc=bc, scale=scale)
+            rhs = torch.zeros(fun.size, dtype=torch.float64, device=u_full.device)
+            if f is not None:
+                if f.numel() != fun.full_size:
+                    raise ValueError("f has %d elements, expected %d" % (f.numel(), fun.full_size))
+                _layout(sp, dims, u_full.device).pack(1, (f.reshape((1,) + dims) / kappa).contiguous(), xi=rhs)
+            us = torch.empty((1,) + dims, dtype=torch.float64, device=u_full.device)
+            solver.solve_full(rhs, g, us.reshape(-1))
+            v = v - us
+        vi = torch.empty(fun.size, dtype=torch.float64, device=u_full.device)
+        _layout(sp, dims, u_full.device).pack(1, v.contiguous(), xi=vi)
+        fun.set_terms("exp", tau=t * kappa)
+        out = fun.apply_full(vi).reshape((1,) + dims)
+        if us is not None:
+            out += us
+        torch.cuda.current_stream().synchronize()       # (the handles' buffers are freed below)
+    finally:
+        fun.destroy()
+        if solver is not None:
+            solver.destroy()
+    return out[0]
+
+
 def continuation_schedule(exponent, regularization, cont0=0, cont=1):
     """The (exponent, regularization) pairs of the Newton continuation loop, stokes.C:217-221:
     exponent_i = 1 + (i/cont)^0.8 (exponent - 1), regularization_i = exp(log(regularization) i/cont)."""
