@@ -199,6 +199,25 @@ int  cheb_points_rows(cheb_points *h, int k, const double *x_dev, long m, double
  * Per chunk: the rows, direction 0 as one line product on the FP64 matrix cores, one contraction per (field, point).
  * npts = 0 is a no-op; out must not overlap u. */
 int  cheb_points_eval(cheb_points *h, const double *u_dev, const double *xi_dev, long npts, double *out_dev, void *stream);
+/* The transpose of cheb_points_eval: out[f][i0 .. i(d-1)] = sum_p s[f][p] l_{i0}(xi[p][0]) .. l_{i(d-1)}(xi[p][d-1]) -- point forces,
+ * point sources, the transpose of an observation operator.  s is nfields x npts (the layout eval writes), xi npts x d (the layout
+ * eval reads), out `nfields` stacked full-grid fields.  Points run in passes of cheb_points_spread_pass: the rows of all
+ * directions into the handle's work memory, then one product on the FP64 matrix cores whose contracted index is the point and
+ * whose second operand, ((s l_1) l_2 ..) l_{d-1}, is formed on chip.  The first pass stores (or adds, CHEB_SPREAD_ACCUMULATE: out +=
+ * ..), later passes add; no atomics, and the order of the additions depends on (dims, nfields, npts, pass size) alone: results
+ * repeat bit for bit.  CHEB_SPREAD_DELTA divides the result at node i by the Clenshaw-Curtis weights w_{i0} .. w_{i(d-1)} (by
+ * multiplying with the inverses of cheb_modal_weights_host's values, long double, rounded once; built and uploaded by the first
+ * such call, which therefore allocates and synchronises once): cheb_modal_integrate(out, phi) then equals sum_p s_p phi(x_p) for
+ * every polynomial phi of the grid -- a point source of strength s.  Otherwise the call allocates nothing and does not
+ * synchronise the host.  A point on a node has a unit row: spreading one such point stores s at that node bit for bit and zeros
+ * elsewhere.  A NaN or infinite coordinate makes every field's output NaN (the rows are shared), a NaN strength s[f][p] field f's
+ * only; |x| > 1 extrapolates as in eval.  npts = 0 zero-fills out, or leaves it alone with CHEB_SPREAD_ACCUMULATE; out must not
+ * overlap s or xi. */
+enum { CHEB_SPREAD_ACCUMULATE = 1, CHEB_SPREAD_DELTA = 2 };
+int  cheb_points_spread(cheb_points *h, const double *s_dev, const double *xi_dev, long npts, double *out_dev, int flags, void *stream);
+/* points per pass of cheb_points_spread: as many as the handle's work memory holds rows for, whole chunks of 16, at most the
+ * option points_spread_pass where that is set; -1: NULL */
+long cheb_points_spread_pass(const cheb_points *h);
 /* Tensor grids of arbitrary coordinates: direction k takes m[k] coordinates (HOST counts), the DEVICE array `coords` holds them
  * direction after direction (sum of m[k] values); out is nfields x m[0] x .. x m[d-1], field-major and row-major.  One line
  * product per direction, shrinking directions first.  A plane cut is m[k] = 1, a line cut has d - 1 of them.
@@ -971,6 +990,8 @@ int stokes_saddle_iterations(const stokes_saddle *s, int which);
  *                            (read per call; A/B: the two agree to rounding, 4e-16 observed)
  *   krylov_exact_norm     1: chebhip_fgmres runs its Gram-Schmidt step as three launches with an explicit norm pass (rounds 1-4) instead of
  *                            two launches with one reduction and the stored vectors' exact norms carried beside the basis (read per solve; A/B)
+ *   points_spread_pass    cheb_points_spread: at most this many points per pass; 0 (default) = as many as the handle's work memory holds
+ *                            rows for (read per call; tests reach the multi-pass path at small counts with it)
  *   no_rocblas            deprecated alias (rounds 1-3) of vendor_gemm with the inverted meaning; still accepted */
 int chebhip_set_option(const char *name, int value);
 int chebhip_get_option(const char *name, int *value);

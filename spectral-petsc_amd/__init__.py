@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "cheb_modal_set_filter", "cheb_modal_filter", "cheb_modal_spectrum", "cheb_modal_integrate",
     "cheb_modal_matrix_host", "cheb_modal_weights_host", "cheb_modal_filter_matrix_host",
     "cheb_points_create", "cheb_points_destroy", "cheb_points_chunk", "cheb_points_rows", "cheb_points_eval",
+    "cheb_points_spread", "cheb_points_spread_pass",
     "cheb_points_grid_reserve", "cheb_points_eval_grid", "cheb_nodes_host", "cheb_points_matrix_host",
     "cheb_dealias_fine_size", "cheb_dealias_matrix_host", "cheb_dealias_create", "cheb_dealias_destroy", "cheb_dealias_fine_dims",
     "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
@@ -278,6 +279,9 @@ def lib():
         L.cheb_points_chunk.restype = C.c_long
         L.cheb_points_rows.argtypes = [vp, C.c_int, vp, C.c_long, vp, vp]
         L.cheb_points_eval.argtypes = [vp, vp, vp, C.c_long, vp, vp]
+        L.cheb_points_spread.argtypes = [vp, vp, vp, C.c_long, vp, C.c_int, vp]
+        L.cheb_points_spread_pass.argtypes = [vp]
+        L.cheb_points_spread_pass.restype = C.c_long
         L.cheb_points_grid_reserve.argtypes = [vp, ip]
         L.cheb_points_eval_grid.argtypes = [vp, vp, vp, ip, vp, vp]
         L.cheb_nodes_host.argtypes = [C.c_int, dp]
@@ -658,7 +662,8 @@ def interp_matrix(n, x):
 class ChebPoints(_Handle):
     """Values of `nfields` stacked full-grid fields on the CGL grid `dims` (field-major, row-major over all nodes, as ChebModal) at
     arbitrary points of [-1, 1]^d (cheb_points_*): scattered points (eval) and tensor grids of arbitrary coordinates (eval_grid:
-    plane and line cuts, plotting grids).  Coordinates are device tensors; |x| > 1 extrapolates, a NaN coordinate gives NaN at that
+    plane and line cuts, plotting grids), and the transpose of the scattered evaluation (spread: point forces and sources on the
+    grid).  Coordinates are device tensors; |x| > 1 extrapolates, a NaN coordinate gives NaN at that
     point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream."""
     _destroy = "cheb_points_destroy"
 
@@ -706,6 +711,32 @@ class ChebPoints(_Handle):
             _chk(lib().cheb_points_eval(self._h, _dev_ptr(u, self.size()), _dev_ptr(pts, npts * d), npts,
                                         _dev_ptr(out, self.nfields * npts), _stream()))
         return out
+
+    def spread(self, s, pts, out=None, accumulate=False, delta=False):
+        """The transpose of eval: out[f][i] = sum_p s[f][p] prod_k l_{i_k}(pts[p][k]) on the full grid (cheb_points_spread).  s is an
+        (nfields, npts) device tensor (npts values for one field), pts (npts, d), out size() values: nfields stacked fields, written,
+        or added to with accumulate=True.  delta=True divides by the Clenshaw-Curtis weights of the nodes, so that
+        ChebModal.integrate(out, phi) is sum_p s_p phi(x_p): a point source of strength s.  Results repeat bit for bit; a NaN
+        coordinate makes every field NaN, a NaN strength its own field only."""
+        import torch
+        d = len(self.dims)
+        if pts.dim() != 2 or pts.shape[1] != d:
+            raise ValueError("pts: expected shape (npts, %d), got %r" % (d, tuple(pts.shape)))
+        npts = pts.shape[0]
+        if s.numel() != self.nfields * npts:
+            raise ValueError("s: expected %d x %d values, got %d" % (self.nfields, npts, s.numel()))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the array to add to (out)")
+            out = torch.empty(self.size(), dtype=torch.float64, device=pts.device)
+        flags = (1 if accumulate else 0) | (2 if delta else 0)                     # CHEB_SPREAD_ACCUMULATE, CHEB_SPREAD_DELTA
+        _chk(lib().cheb_points_spread(self._h, _dev_ptr(s, self.nfields * npts) if npts else None,
+                                      _dev_ptr(pts, npts * d) if npts else None, npts, _dev_ptr(out, self.size()), flags, _stream()))
+        return out
+
+    def spread_pass(self):
+        """Points per pass of spread (cheb_points_spread_pass; the option points_spread_pass lowers it)."""
+        return lib().cheb_points_spread_pass(self._h)
 
     def reserve_grid(self, m_max):
         """Allocates eval_grid's buffers for every grid of at most m_max[k] coordinates in direction k (synchronous)."""

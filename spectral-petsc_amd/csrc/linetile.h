@@ -1,5 +1,6 @@
 // linetile.h -- the workgroup tile of the batched line product on the FP64 matrix cores: what cheb_resample_kernel (linegemm.hip:
-// one line image) and cheb_pair_kernel (dealias.hip: two images side by side) share on the device.  Only those two units include it.
+// one line image), cheb_pair_kernel (dealias.hip: two images side by side) and k_points_spread (points.hip: the image formed on
+// chip, the contracted index a scattered point) share on the device.  Only those three units include it.
 //
 // In a direction of K -> M points the tensor is (O outer, K, Q inner) and every one of the L = O Q lines (o, q) -- element k at
 // o K Q + k Q + q -- is multiplied by a dense M x K matrix R.  A workgroup computes BM output points x 64 lines; R and the line

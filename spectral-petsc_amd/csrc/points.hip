@@ -19,9 +19,23 @@
 //      directions' rows: the last direction's row in LDS, 16-byte loads where a block row starts on a 16-byte boundary, no
 //      atomics, a fixed order of additions.
 // Tensor grids take the same rows and one line product per direction (line_chain), shrinking directions first, as resample.hip does.
+//
+// cheb_points_spread is the transpose of the scattered evaluation: one number per (field, point) goes onto the grid,
+//   g[f][i_0 .. i_{d-1}] = sum_p s[f][p] l_0,p[i_0] l_1,p[i_1] .. l_{d-1},p[i_{d-1}]
+// in passes of cheb_points_spread_pass points, two launches a pass: k_points_rows into the handle's work memory, then
+// k_points_spread, a product on the FP64 matrix cores with the workgroup tile of linetile.h whose contracted index is the point:
+//   matrix operand  R[i_0][p] = rows_0[p][i_0]: the rows of direction 0 as k_points_rows stores them, read along i_0;
+//   image operand   X[p][line] = ((s[f][p] l_1,p[i_1]) l_2,p[i_2] ..) l_{d-1},p[i_{d-1}], line = (f, i_1 .. i_{d-1}): formed in
+//                   registers by the threads that fill the LDS chunk, in exactly this association; d = 1: X[p][f] = s[f][p].
+// A workgroup owns BM points of direction 0 x 64 lines and walks the pass in LDS chunks of RS_KC points; slots past the last point
+// are zeros in both operands, written by a select and never read from memory (a stale NaN row times 0 would be NaN).  The epilogue stores, or adds
+// to what `out` holds (later passes, CHEB_SPREAD_ACCUMULATE), after multiplying by the inverse Clenshaw-Curtis weights
+// (v iw_0[i_0]) (iw_1[i_1] (.. iw_{d-1}[i_{d-1}])) under CHEB_SPREAD_DELTA.  No atomics: every element of `out` belongs to one lane,
+// and the order of its additions depends on (dims, nfields, npts, pass size) alone.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "linetile.h"
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -151,6 +165,155 @@ __global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const do
   }
 }
 
+// LDS layout of k_points_spread's matrix chunk: Rt[k][point], the way the rows arrive (contiguous in the point of direction 0);
+// the pitch keeps the 4 k a wave reads at once 128 B apart, as RS_XP does for the image
+__device__ __forceinline__ int lds_rt(int k, int point, int bm) { return k * (bm + 16) + point; }
+
+struct SpreadArgs {
+  const double *rows;                // direction k's rows of this pass at rows + P off[k]
+  const double *s;                   // s[f][p] of this pass at s[f npts + p]
+  const double *iw;                  // inverse quadrature weights, direction k at off[k]; null: no scaling
+  double *out;
+  size_t npts;
+  unsigned P, cnt, L, Q;             // row capacity of the pass, its points, lines nf Q, Q = n_1 .. n_{d-1}
+  int accumulate;
+};
+
+// out[f][i_0][q] (+)= sum over the pass's points of rows_0[p][i_0] X[p][(f, q)]: workgroup (line tile, point tile), 4 waves as
+// 2 x 2 of BM/2 points x 32 lines.  DC: d known at compile time (1 .. 3), 0: any d up to MD.
+template <int DC, int BM>
+__global__ __launch_bounds__(256) void k_points_spread(const PtGeo g, const SpreadArgs a) {
+  __shared__ double sR[RS_KC * (BM + 16)];
+  __shared__ double sX[RS_KC * RS_XP];
+  constexpr int MT = BM / 32;                    // m-tiles of 16 points per wave
+  constexpr int XN = RS_KC * RS_BN / 256;        // image elements a thread forms per chunk
+  constexpr int RN = BM * RS_KC / 256;           // matrix elements a thread loads per chunk
+  constexpr int DM = DC ? DC : MD;
+  const int d = DC ? DC : g.d;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kq = lane >> 4, l16 = lane & 15;
+  const int pw = (w >> 1) * (BM / 2), lw = (w & 1) * 32;     // this wave's first point / line within the tile
+  const unsigned M = (unsigned)g.n[0], Q = a.Q, L = a.L, cnt = a.cnt;
+  const unsigned l0 = blockIdx.x * RS_BN, i0 = blockIdx.y * BM;
+
+  // the weight of a line under CHEB_SPREAD_DELTA: iw_1[i_1] (.. iw_{d-1}[i_{d-1}]), built from the last direction down
+  auto line_weight = [&](unsigned line) -> double {
+    unsigned q = line % Q;
+    double wq = 1.0;
+#pragma unroll
+    for (int k = DM - 1; k >= 1; k--)
+      if (k < d) {
+        const unsigned nk = (unsigned)g.n[k], i = k > 1 ? q % nk : q;
+        q /= nk;
+        wq = k == d - 1 ? a.iw[g.off[k] + i] : a.iw[g.off[k] + i] * wq;
+      }
+    return wq;
+  };
+
+  // a thread forms the image of one line at XN points of a chunk, and loads RN matrix elements, the same places in every chunk
+  const unsigned xline = l0 + (unsigned)(tid & (RS_BN - 1));
+  const bool xl = xline < L;
+  const int xk = tid / RS_BN;                    // + 4 e
+  unsigned ro[DM];                               // direction k's entry of the line at point p: rows[ro[k] + p n_k]
+  size_t sb = 0;
+  {
+    const unsigned line = xl ? xline : 0u;
+    unsigned q = line % Q;
+    sb = (size_t)(line / Q) * a.npts;
+#pragma unroll
+    for (int k = DM - 1; k >= 1; k--) {
+      ro[k] = 0;
+      if (k < d) {
+        const unsigned nk = (unsigned)g.n[k], i = k > 1 ? q % nk : q;
+        q /= nk;
+        ro[k] = a.P * g.off[k] + i;
+      }
+    }
+  }
+  // Loads carry no branch: an index past the pass's last point (or the grid's last node, or the last line) is clamped to it and
+  // the value dropped by a select where the LDS slot is written, so the loads of the next chunk stay in flight during the products
+  // and a padding slot is an exact zero whatever its clamped source holds.  d <= 3 keeps the factors and multiplies at the store.
+  constexpr int XF = DC ? DC : 1;                // values kept per image element: s and the entries of directions 1 .. DC - 1
+  double xv[XN][XF], rv[RN];
+  auto load = [&](unsigned k0) {
+#pragma unroll
+    for (int e = 0; e < XN; e++) {
+      const unsigned p = min(k0 + (unsigned)(xk + (256 / RS_BN) * e), cnt - 1);
+      xv[e][0] = a.s[sb + p];
+#pragma unroll
+      for (int k = 1; k < DM; k++)
+        if (k < d) {
+          const double l = a.rows[ro[k] + p * (unsigned)g.n[k]];
+          if (DC) xv[e][k < XF ? k : 0] = l; else xv[e][0] = xv[e][0] * l;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < RN; e++) {
+      const int t = tid + 256 * e;
+      rv[e] = a.rows[min(k0 + (unsigned)(t / BM), cnt - 1) * M + min(i0 + (unsigned)(t % BM), M - 1)];
+    }
+  };
+
+  v4d acc[MT][2];
+#pragma unroll
+  for (int u = 0; u < MT; u++)
+#pragma unroll
+    for (int t = 0; t < 2; t++) acc[u][t] = (v4d){0.0, 0.0, 0.0, 0.0};
+
+  load(0);
+  for (unsigned k0 = 0; k0 < cnt; k0 += RS_KC) {
+    __syncthreads();                             // (the previous chunk has been read)
+#pragma unroll
+    for (int e = 0; e < XN; e++) {
+      const int kk = xk + (256 / RS_BN) * e;
+      double x = xv[e][0];
+#pragma unroll
+      for (int k = 1; k < XF; k++) x = x * xv[e][k];
+      sX[lds_x(kk, tid & (RS_BN - 1))] = (xl && k0 + (unsigned)kk < cnt) ? x : 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < RN; e++) {
+      const int t = tid + 256 * e;
+      sR[lds_rt(t / BM, t % BM, BM)] = (i0 + (unsigned)(t % BM) < M && k0 + (unsigned)(t / BM) < cnt) ? rv[e] : 0.0;
+    }
+    __syncthreads();
+    load(k0 + RS_KC);                            // next chunk in flight during the products (clamped past the end)
+#pragma unroll
+    for (int ks = 0; ks < RS_KC / 4; ks++) {
+      double ra[MT], xb[2];
+#pragma unroll
+      for (int u = 0; u < MT; u++) ra[u] = sR[lds_rt(4 * ks + kq, pw + 16 * u + l16, BM)];
+#pragma unroll
+      for (int t = 0; t < 2; t++) xb[t] = sX[lds_x(4 * ks + kq, lw + 16 * t + l16)];
+#pragma unroll
+      for (int u = 0; u < MT; u++)
+#pragma unroll
+        for (int t = 0; t < 2; t++) acc[u][t] = line_mfma<false>(ra[u], xb[t], acc[u][t]);
+    }
+  }
+
+  // C/D element r of a lane: point (lane >> 4) + 4 r, line lane & 15
+#pragma unroll
+  for (int t = 0; t < 2; t++) {
+    const unsigned line = l0 + lw + 16 * t + l16;
+    if (line >= L) continue;
+    const unsigned f = line / Q, ob = f * M * Q + (line - f * Q);
+    double wl = 1.0;
+    if (a.iw && d > 1) wl = line_weight(line);
+#pragma unroll
+    for (int u = 0; u < MT; u++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const unsigned i = i0 + pw + 16 * u + 4 * r + kq;
+        if (i >= M) continue;
+        double v = acc[u][t][r];
+        if (a.iw) { v = v * a.iw[i]; if (d > 1) v = v * wl; }
+        double *o = a.out + ((size_t)ob + (size_t)i * Q);
+        *o = a.accumulate ? *o + v : v;
+      }
+  }
+}
+
 int rows_lg(int n) {                 // log2 of the power of two >= n, at most 6
   int lg = 0;
   while (lg < 6 && (1 << lg) < n) lg++;
@@ -180,6 +343,7 @@ struct cheb_points {
   std::map<int, double *> nodes;             // device node table per distinct extent
   double *rows = nullptr;                    // C x n_k rows of every direction, direction k at C geo.off[k]
   double *W = nullptr;                       // nf x C x B: direction 0's output
+  double *iw = nullptr;                      // spread's CHEB_SPREAD_DELTA: 1 / Clenshaw-Curtis weight, direction k at geo.off[k]; made at first use
   // tensor grids (cheb_points_grid_reserve)
   int mmax[MD] = {0};
   size_t goff[MD] = {0};                     // direction k's rows in grows
@@ -219,6 +383,7 @@ extern "C" int cheb_points_destroy(cheb_points *h) {
   for (auto &t : h->nodes) if (t.second) (void)hipFree(t.second);
   if (h->rows) (void)hipFree(h->rows);
   if (h->W) (void)hipFree(h->W);
+  if (h->iw) (void)hipFree(h->iw);
   free_grid(h);
   delete h;
   return 0;
@@ -328,6 +493,81 @@ extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *x
     sweep_note_launch();
     e = hipGetLastError();
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval contraction launch: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+namespace {
+// spread keeps the rows of a pass in the larger of the handle's two work arrays: direction k at P off[k]
+struct SpreadPass { double *buf; long P; };
+SpreadPass spread_pass(const cheb_points *h) {
+  const PtGeo &g = h->geo;
+  const long S = (long)g.off[h->d - 1] + g.n[h->d - 1], inW = (long)h->C * h->nf * (long)g.B / S;
+  SpreadPass sp = inW > (long)h->C ? SpreadPass{h->W, inW} : SpreadPass{h->rows, (long)h->C};
+  if (sp.P >= RS_KC) sp.P -= sp.P % RS_KC;       // whole LDS chunks
+  const long cap = opt(OPT_POINTS_SPREAD_PASS);
+  if (cap > 0 && cap < sp.P) sp.P = cap;
+  return sp;
+}
+
+int spread_weights(cheb_points *h) {             // the inverse quadrature weights, uploaded once
+  if (h->iw) return 0;
+  const PtGeo &g = h->geo;
+  std::vector<double> w, iw;
+  for (int k = 0; k < h->d; k++) {
+    w.resize(g.n[k]);
+    modal_weights_host(g.n[k], w.data());
+    for (double v : w) iw.push_back((double)(1.0L / (long double)v));
+  }
+  return device_array(&h->iw, iw.size(), iw.data(), "inverse quadrature weights");
+}
+
+template <int BM>
+void spread_launch(int d, const PtGeo &g, const SpreadArgs &a, hipStream_t st) {
+  const dim3 grid((a.L + RS_BN - 1) / RS_BN, ((unsigned)g.n[0] + BM - 1) / BM);
+#define POINTS_SPREAD(DC) hipLaunchKernelGGL((k_points_spread<DC, BM>), grid, dim3(256), 0, st, g, a)
+  switch (d) { case 1: POINTS_SPREAD(1); break; case 2: POINTS_SPREAD(2); break; case 3: POINTS_SPREAD(3); break; default: POINTS_SPREAD(0); }
+#undef POINTS_SPREAD
+}
+}  // namespace
+
+extern "C" long cheb_points_spread_pass(const cheb_points *h) { return h ? spread_pass(h).P : -1; }
+
+extern "C" int cheb_points_spread(cheb_points *h, const double *s, const double *xi, long npts, double *out, int flags, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
+  if (flags & ~(CHEB_SPREAD_ACCUMULATE | CHEB_SPREAD_DELTA)) return chebhip_fail(CHEBHIP_ERR_ARG, "spread: unknown flags %d", flags);
+  hipStream_t st = (hipStream_t)stream;
+  const bool accumulate = flags & CHEB_SPREAD_ACCUMULATE;
+  if (npts == 0 && accumulate) return 0;
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (npts == 0) {
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)h->total * sizeof(double), st));
+    return 0;
+  }
+  if (!s || !xi) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  const int d = h->d;
+  if (overlap(out, h->total, s, h->nf * npts) || overlap(out, h->total, xi, npts * d))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "spread: the output must not overlap the strengths or the coordinates");
+  int rc;
+  if ((flags & CHEB_SPREAD_DELTA) && (rc = spread_weights(h))) return rc;
+  const PtGeo &g = h->geo;
+  const SpreadPass sp = spread_pass(h);
+  for (long p0 = 0; p0 < npts; p0 += sp.P) {
+    const unsigned cnt = (unsigned)std::min(sp.P, npts - p0);
+    RowsJob job{};
+    job.nd = d;
+    for (int k = 0; k < d; k++) {
+      job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
+      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = sp.buf + (size_t)sp.P * g.off[k];
+    }
+    if ((rc = launch_rows(job, st, "spread"))) return rc;
+    const SpreadArgs a{sp.buf, s + p0, (flags & CHEB_SPREAD_DELTA) ? h->iw : nullptr, out, (size_t)npts,
+                       (unsigned)sp.P, cnt, (unsigned)h->nf * g.B, g.B, (accumulate || p0 > 0) ? 1 : 0};
+    if (g.n[0] > 64) spread_launch<128>(d, g, a, st); else spread_launch<64>(d, g, a, st);
+    sweep_note_launch();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "spread launch: %s", hipGetErrorString(e));
   }
   return 0;
 }

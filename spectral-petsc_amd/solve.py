@@ -444,6 +444,29 @@ def resolution(dims, u_full):
     return out[0] if nf == 1 else out
 
 
+def point_sources(sp, dims, pts, strengths, out=None):
+    """Discrete point sources on the CGL grid dims: the full-grid field g with integral(g phi) = sum_p strengths[p] phi(pts[p]) for
+    every polynomial phi of the grid (ChebPoints.spread with delta=True; one handle made and destroyed: for a one-off call).  pts is
+    an (npts, d) device tensor, strengths npts values (one field) or (nfields, npts); returns a device tensor of shape
+    (nfields,) + dims: a new one, or `out`, which must be contiguous, hold nfields prod(dims) values and is overwritten."""
+    dims = tuple(int(n) for n in dims)
+    if pts.dim() != 2 or pts.shape[1] != len(dims):
+        raise ValueError("pts: expected shape (npts, %d), got %r" % (len(dims), tuple(pts.shape)))
+    npts = pts.shape[0]
+    if strengths.dim() not in (1, 2) or strengths.shape[-1] != npts:
+        raise ValueError("strengths: expected shape (%d,) or (nfields, %d), got %r" % (npts, npts, tuple(strengths.shape)))
+    nf = strengths.shape[0] if strengths.dim() == 2 else 1
+    if out is not None and not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    h = sp.ChebPoints(dims, nf)
+    try:
+        g = h.spread(strengths.reshape(nf, npts).contiguous(), pts.contiguous(), out=None if out is None else out.view(-1), delta=True)
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        h.destroy()
+    return g.view((nf,) + dims)
+
+
 def sample_plane(sp, dims, u_full, axis, coord, m=None):
     """The plane x_axis = coord of the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields if it
     holds a multiple of prod(dims) values): one ChebPoints.eval_grid with a single coordinate along `axis`.  The other directions
