@@ -860,3 +860,313 @@ int orc_fd_matrix(int d, const int *dims, const double *eta, const double *deta,
   return 0;
 }
 
+
+/* ========================================================================= */
+/* Long-double truths of the callbacks with a componentwise weight            */
+/* ("Per-element bar: callbacks").  Dense products with D from the */
+/* closed formula (sine arguments folded into [0, pi/2]); every result is     */
+/* rounded once to double.  The weight W is the same evaluation with every    */
+/* factor replaced by its absolute value and every line product by the        */
+/* symmetrised weight  x -> 1/2 (|M| + |M| flip) (|x| + flip |x|).            */
+/* ========================================================================= */
+typedef long double ld;
+
+static ld sin_half_l(long k, long n) {           /* sin(k pi / 2n), |k| <= 2n, argument folded into [0, pi/2] */
+  const int sg = k < 0 ? -1 : 1;
+  long a = k < 0 ? -k : k;
+  if (a > n) a = 2 * n - a;
+  return sg * sinl(PI_L * (ld)a / (ld)(2 * n));
+}
+
+/* D_ij = (c_i / c_j) (-1)^(i+j) / (x_i - x_j), x_i - x_j = -2 sin((i+j) pi/2n) sin((i-j) pi/2n);
+ * D_ii = -x_i / (2 sin^2(i pi/n)); D_00 = (2 n^2 + 1) / 6 = -D_nn. */
+static ld *truth_D(int P) {
+  const int n = P - 1;
+  ld *D = (ld *)malloc(sizeof(ld) * (size_t)P * P);
+  for (int i = 0; i < P; i++)
+    for (int j = 0; j < P; j++) {
+      if (i == j) continue;
+      const ld ci = (i == 0 || i == n) ? 2.0L : 1.0L, cj = (j == 0 || j == n) ? 2.0L : 1.0L;
+      const ld dx = -2.0L * sin_half_l(i + j, n) * sin_half_l(i - j, n);
+      D[(size_t)i * P + j] = (ci / cj) * (((i + j) & 1) ? -1.0L : 1.0L) / dx;
+    }
+  for (int i = 1; i < n; i++) {
+    const ld s = sin_half_l(2 * i, n);
+    D[(size_t)i * P + i] = -sin_half_l(n - 2 * i, n) / (2.0L * s * s);
+  }
+  D[0] = (2.0L * n * n + 1.0L) / 6.0L;
+  D[(size_t)n * P + n] = -D[0];
+  return D;
+}
+
+/* A = 1/2 (|D| + |D| flip), double, from D rounded once to double (tests/linewise.py bound) */
+static double *truth_A(int P, const ld *D) {
+  double *A = (double *)malloc(sizeof(double) * (size_t)P * P);
+  for (int i = 0; i < P; i++)
+    for (int j = 0; j < P; j++)
+      A[(size_t)i * P + j] = 0.5 * (fabs((double)D[(size_t)i * P + j]) + fabs((double)D[(size_t)i * P + P - 1 - j]));
+  return A;
+}
+
+/* Lagrange weights of the interior nodes x_1 .. x_{n-1} at x_0 = 1 (w0) and x_n = -1 (w1):
+ * l_j(1) = (-1)^(j+1) 2 cos^2(j pi / 2n), l_j(-1) = (-1)^(n-j+1) 2 sin^2(j pi / 2n)  (roots of U_{n-1}).  w[0] = w[n] = 0. */
+static void truth_wext(int P, ld *w0, ld *w1) {
+  const int n = P - 1;
+  for (int j = 0; j < P; j++) w0[j] = w1[j] = 0.0L;
+  for (int j = 1; j < n; j++) {
+    const ld c = sin_half_l(n - j, n), s = sin_half_l(j, n);
+    w0[j] = ((j & 1) ? 1.0L : -1.0L) * 2.0L * c * c;
+    w1[j] = (((n - j) & 1) ? 1.0L : -1.0L) * 2.0L * s * s;
+  }
+}
+
+/* out (op)= M applied along the middle index of in[outer][P][inner]; a line is buffered, so in == out is allowed.
+ * acc: 0 store, +1 add, -1 subtract.  symw: the buffered line becomes x + flip x first (the weight; M is then A). */
+#define ORC_DEF_LINES(NAME, T)                                                                          \
+  static void NAME(long outer, int P, long inner, const T *M, const T *in, T *out, int acc, int symw, int nt) { \
+    if (nt < 1) nt = 1;                                                                                 \
+    _Pragma("omp parallel num_threads(nt)")                                                             \
+    {                                                                                                   \
+      T *buf = (T *)malloc(sizeof(T) * 2 * (size_t)P), *res = buf + P;                                  \
+      _Pragma("omp for schedule(static)")                                                               \
+      for (long l = 0; l < outer * inner; l++) {                                                        \
+        const long off = (l / inner) * P * inner + (l % inner);                                         \
+        int nz = 0;                                                                                     \
+        for (int c = 0; c < P; c++) { buf[c] = in[off + c * inner]; nz |= (buf[c] != 0); }              \
+        if (!nz) {                              /* a line of zeros (impulse inputs): the product is 0 */ \
+          if (acc == 0) for (int r = 0; r < P; r++) out[off + r * inner] = 0;                           \
+          continue;                                                                                     \
+        }                                                                                               \
+        if (symw) for (int c = 0; 2 * c <= P - 1; c++) { const T s = buf[c] + buf[P - 1 - c]; buf[c] = s; buf[P - 1 - c] = s; } \
+        for (int r = 0; r < P; r++) {                                                                   \
+          const T *m = M + (size_t)r * P;                                                               \
+          T a = 0;                                                                                      \
+          for (int c = 0; c < P; c++) a += m[c] * buf[c];                                               \
+          res[r] = a;                                                                                   \
+        }                                                                                               \
+        for (int r = 0; r < P; r++) {                                                                   \
+          T *o = out + off + r * inner;                                                                 \
+          *o = acc == 0 ? res[r] : (acc > 0 ? *o + res[r] : *o - res[r]);                               \
+        }                                                                                               \
+      }                                                                                                 \
+      free(buf);                                                                                        \
+    }                                                                                                   \
+  }
+ORC_DEF_LINES(lines_l, ld)
+ORC_DEF_LINES(lines_w, double)
+
+typedef struct { int d; int P[3]; long outer[3], inner[3]; long N; ld *D[3]; double *A[3]; } tgrid;
+static void tgrid_init(tgrid *g, int d, const int *dims) {
+  g->d = d; g->N = orc_local_size(d, dims);
+  for (int k = 0; k < d; k++) {
+    g->P[k] = dims[k]; g->outer[k] = 1; g->inner[k] = 1;
+    for (int r = 0; r < k; r++) g->outer[k] *= dims[r];
+    for (int r = k + 1; r < d; r++) g->inner[k] *= dims[r];
+    g->D[k] = NULL;
+    for (int r = 0; r < k; r++) if (dims[r] == dims[k]) { g->D[k] = g->D[r]; g->A[k] = g->A[r]; }
+    if (!g->D[k]) { g->D[k] = truth_D(dims[k]); g->A[k] = truth_A(dims[k], g->D[k]); }
+  }
+}
+static void tgrid_free(tgrid *g) {
+  for (int k = 0; k < g->d; k++) {
+    int own = 1;
+    for (int r = 0; r < k; r++) if (g->D[r] == g->D[k]) own = 0;
+    if (own) { free(g->D[k]); free(g->A[k]); }
+  }
+}
+
+static int orc_stokes_truth_core(int d, const int *dims, int fn, const orc_rheology *rh,
+                                 const double *eta_i, const double *deta_i, const double *S0_i,
+                                 const double *dirichlet, const double *force, const double *xG,
+                                 double *y, double *W, double *eta_o, double *deta_o, double *strain_o,
+                                 double *wstrain_o, double *wgamma_o, int nt) {
+  if (d < 2 || d > 3) return 6;
+  for (int k = 0; k < d; k++) if (dims[k] < 3) return 3;
+  if (nt < 1) nt = 1;
+  tgrid g; tgrid_init(&g, d, dims);
+  const long N = g.N, nd = N * d;
+  int *ixL = build_ixL(d, dims, N);
+  ld *xl = (ld *)malloc(sizeof(ld) * (size_t)nd), *G = (ld *)malloc(sizeof(ld) * (size_t)nd * d);
+  ld *yv = (ld *)malloc(sizeof(ld) * (size_t)nd), *pl = (ld *)calloc((size_t)N, sizeof(ld)), *tp = (ld *)malloc(sizeof(ld) * (size_t)N);
+  ld *yp = (ld *)malloc(sizeof(ld) * (size_t)N);
+  double *ax = (double *)malloc(sizeof(double) * (size_t)nd), *WG = (double *)malloc(sizeof(double) * (size_t)nd * d);
+  double *wv = (double *)malloc(sizeof(double) * (size_t)nd), *apl = (double *)calloc((size_t)N, sizeof(double));
+  double *wt = (double *)malloc(sizeof(double) * (size_t)N), *wp = (double *)malloc(sizeof(double) * (size_t)N);
+  /* local vectors: velocity (interior from xG, boundary from dirichlet or 0), pressure (interior) */
+  { long dd = 0;
+    for (long l = 0; l < N; l++)
+      for (int k = 0; k < d; k++) {
+        double v;
+        if (ixL[l] >= 0) v = xG[(long)ixL[l] * (d + 1) + k];
+        else { v = dirichlet ? dirichlet[dd] : 0.0; dd++; }
+        xl[l * d + k] = v; ax[l * d + k] = fabs(v);
+      }
+    for (long l = 0; l < N; l++) if (ixL[l] >= 0) { pl[l] = xG[(long)ixL[l] * (d + 1) + d]; apl[l] = fabs((double)pl[l]); } }
+  /* p_ext: the two end values of every line whose other indices are interior, from the Lagrange weights of its interior nodes */
+  for (int k = 0; k < d; k++) {
+    const int P = g.P[k]; const long inner = g.inner[k];
+    ld *w0 = (ld *)malloc(sizeof(ld) * 2 * (size_t)P), *w1 = w0 + P;
+    truth_wext(P, w0, w1);
+    for (long l = 0; l < g.outer[k] * inner; l++) {
+      const long off = (l / inner) * P * inner + (l % inner);
+      if (ixL[off + inner] < 0) continue;                    /* the line's second node is interior <=> its other indices are */
+      ld e0 = 0, e1 = 0; double a0 = 0, a1 = 0;
+      for (int j = 1; j < P - 1; j++) {
+        const ld v = pl[off + j * inner];
+        e0 += w0[j] * v; e1 += w1[j] * v;
+        a0 += fabs((double)w0[j]) * fabs((double)v); a1 += fabs((double)w1[j]) * fabs((double)v);
+      }
+      pl[off] = e0; pl[off + (long)(P - 1) * inner] = e1; apl[off] = a0; apl[off + (long)(P - 1) * inner] = a1;
+    }
+    free(w0);
+  }
+  /* G_j = D_j u (component k at G[j*nd + i*d + k]) and its weight */
+  for (int j = 0; j < d; j++) {
+    lines_l(g.outer[j], g.P[j], g.inner[j] * d, g.D[j], xl, G + (long)j * nd, 0, 0, nt);
+    lines_w(g.outer[j], g.P[j], g.inner[j] * d, g.A[j], ax, WG + (long)j * nd, 0, 1, nt);
+  }
+  const ld pw = (rh && rh->kind == 1) ? (1.0L - (ld)rh->exponent) / (2.0L * (ld)rh->exponent) : 0.0L;
+#ifdef _OPENMP
+#pragma omp parallel for num_threads(nt) schedule(static)
+#endif
+  for (long i = 0; i < N; i++) {
+    ld s[3][3], S0[3][3], tr = 0, e, de; double ws[3][3], wtr = 0;
+    for (int k = 0; k < d; k++) { tr += G[(long)k * nd + i * d + k]; wtr += WG[(long)k * nd + i * d + k]; }
+    yp[i] = tr; wp[i] = wtr;
+    for (int j = 0; j < d; j++)
+      for (int k = 0; k < d; k++) {
+        s[j][k] = 0.5L * (G[(long)j * nd + i * d + k] + G[(long)k * nd + i * d + j]);
+        ws[j][k] = 0.5 * (WG[(long)j * nd + i * d + k] + WG[(long)k * nd + i * d + j]);
+      }
+    if (fn) {
+      ld gam = 0;
+      for (int j = 0; j < d; j++) for (int k = 0; k < d; k++) { gam += 0.5L * (s[j][k] * s[j][k]); S0[j][k] = s[j][k]; }
+      if (rh && rh->kind == 1) {
+        const ld q = (ld)rh->regularization + gam / (ld)rh->gamma0;
+        e = (ld)rh->hardness * powl(q, pw);
+        de = fabs(rh->exponent) > 1.0e-5 ? (ld)rh->hardness * pw / (ld)rh->gamma0 * powl(q, pw - 1.0L) : 0.0L;
+      } else { e = 1.0L; de = 0.0L; }
+    } else {
+      e = eta_i ? (ld)eta_i[i] : 1.0L; de = deta_i ? (ld)deta_i[i] : 0.0L;
+      for (int j = 0; j < d; j++) for (int k = 0; k < d; k++) S0[j][k] = S0_i ? (ld)S0_i[(long)j * nd + i * d + k] : 0.0L;
+    }
+    ld z = 0; double wz = 0, wgam = 0;
+    for (int j = 0; j < d; j++) for (int k = 0; k < d; k++) {
+      z += s[j][k] * S0[j][k]; wz += fabs((double)S0[j][k]) * ws[j][k]; wgam += fabs((double)s[j][k]) * ws[j][k];
+    }
+    for (int j = 0; j < d; j++)
+      for (int k = 0; k < d; k++) {
+        const long a = (long)j * nd + i * d + k;
+        G[a] = fn ? e * s[j][k] : e * s[j][k] + de * S0[j][k] * z;   /* the residual's stress is eta s; its weight is the linearised one */
+        WG[a] = fabs((double)e) * ws[j][k] + fabs((double)de) * fabs((double)S0[j][k]) * wz;
+        if (strain_o) strain_o[a] = (double)s[j][k];
+        if (wstrain_o) wstrain_o[a] = ws[j][k];
+      }
+    if (eta_o) eta_o[i] = (double)e;
+    if (deta_o) deta_o[i] = (double)de;
+    if (wgamma_o) wgamma_o[i] = wgam;
+  }
+  /* velocity rows: -sum_j D_j tau_j. + D_k p_ext */
+  for (int j = 0; j < d; j++) {
+    lines_l(g.outer[j], g.P[j], g.inner[j] * d, g.D[j], G + (long)j * nd, yv, j == 0 ? 0 : 1, 0, nt);
+    lines_w(g.outer[j], g.P[j], g.inner[j] * d, g.A[j], WG + (long)j * nd, wv, j == 0 ? 0 : 1, 1, nt);
+  }
+  for (long a = 0; a < nd; a++) yv[a] = -yv[a];
+  for (int k = 0; k < d; k++) {
+    lines_l(g.outer[k], g.P[k], g.inner[k], g.D[k], pl, tp, 0, 0, nt);
+    lines_w(g.outer[k], g.P[k], g.inner[k], g.A[k], apl, wt, 0, 1, nt);
+    for (long i = 0; i < N; i++) { yv[i * d + k] += tp[i]; wv[i * d + k] += wt[i]; }
+  }
+  for (long l = 0; l < N; l++) {
+    if (ixL[l] < 0) continue;
+    const long r = (long)ixL[l] * (d + 1);
+    for (int k = 0; k <= d; k++) {
+      ld v = k < d ? yv[l * d + k] : yp[l]; double w = k < d ? wv[l * d + k] : wp[l];
+      if (force) { v -= (ld)force[r + k]; w += fabs(force[r + k]); }
+      y[r + k] = (double)v; W[r + k] = w;
+    }
+  }
+  free(xl); free(G); free(yv); free(pl); free(tp); free(yp); free(ax); free(WG); free(wv); free(apl); free(wt); free(wp); free(ixL);
+  tgrid_free(&g);
+  return 0;
+}
+
+int orc_stokes_truth(int d, const int *dims, const double *eta, const double *deta, const double *strain,
+                     const double *dirichlet, const double *force, const double *xG, double *y, double *W, int nthreads) {
+  return orc_stokes_truth_core(d, dims, 0, NULL, eta, deta, strain, dirichlet, force, xG, y, W, NULL, NULL, NULL, NULL, NULL, nthreads);
+}
+
+int orc_stokes_function_truth(int d, const int *dims, const orc_rheology *rh, const double *dirichlet, const double *force,
+                              const double *xG, double *y, double *W, double *eta, double *deta, double *strain,
+                              double *wstrain, double *wgamma, int nthreads) {
+  return orc_stokes_truth_core(d, dims, 1, rh, NULL, NULL, NULL, dirichlet, force, xG, y, W, eta, deta, strain, wstrain, wgamma, nthreads);
+}
+
+static int orc_elliptic_truth_core(int d, const int *dims, int fn, double gamma, double exponent,
+                                   const double *eta_i, const double *deta_i, const double *g0_i,
+                                   const double *dirichlet, const double *b, const double *U,
+                                   double *V, double *W, double *eta_o, double *deta_o, double *gradu_o, double *wgrad_o, int nt) {
+  if (d < 1 || d > 3) return 4;
+  for (int k = 0; k < d; k++) if (dims[k] < 3) return 3;
+  if (nt < 1) nt = 1;
+  tgrid g; tgrid_init(&g, d, dims);
+  const long N = g.N;
+  int *ixL = build_ixL(d, dims, N);
+  ld *ul = (ld *)malloc(sizeof(ld) * (size_t)N), *gr = (ld *)malloc(sizeof(ld) * (size_t)N * d), *v = (ld *)malloc(sizeof(ld) * (size_t)N);
+  double *au = (double *)malloc(sizeof(double) * (size_t)N), *wg = (double *)malloc(sizeof(double) * (size_t)N * d), *wv = (double *)malloc(sizeof(double) * (size_t)N);
+  { long dd = 0;
+    for (long l = 0; l < N; l++) {
+      double t;
+      if (ixL[l] >= 0) t = U[ixL[l]]; else { t = dirichlet ? dirichlet[dd] : 0.0; dd++; }
+      ul[l] = t; au[l] = fabs(t);
+    } }
+  for (int k = 0; k < d; k++) {
+    lines_l(g.outer[k], g.P[k], g.inner[k], g.D[k], ul, gr + (long)k * N, 0, 0, nt);
+    lines_w(g.outer[k], g.P[k], g.inner[k], g.A[k], au, wg + (long)k * N, 0, 1, nt);
+  }
+#ifdef _OPENMP
+#pragma omp parallel for num_threads(nt) schedule(static)
+#endif
+  for (long i = 0; i < N; i++) {
+    ld e, de;
+    if (fn) {
+      if (exponent == 2.0) { e = 1.0L + (ld)gamma * ul[i] * ul[i]; de = 2.0L * (ld)gamma * ul[i]; }
+      else { e = 1.0L + (ld)gamma * powl(ul[i], (ld)exponent); de = (ld)exponent * (ld)gamma * powl(ul[i], (ld)exponent - 1.0L); }
+    } else { e = eta_i ? (ld)eta_i[i] : 1.0L; de = deta_i ? (ld)deta_i[i] : 0.0L; }
+    for (int k = 0; k < d; k++) {
+      const long a = (long)k * N + i;
+      const ld gk = gr[a]; const double wk = wg[a];
+      const ld g0 = fn ? gk : (g0_i ? (ld)g0_i[a] : 0.0L);
+      if (gradu_o) gradu_o[a] = (double)gk;
+      if (wgrad_o) wgrad_o[a] = wk;
+      gr[a] = fn ? e * gk : e * gk + de * ul[i] * g0;        /* the residual's flux is eta grad u; its weight is the linearised one */
+      wg[a] = fabs((double)e) * wk + fabs((double)de) * au[i] * fabs((double)g0);
+    }
+    if (eta_o) eta_o[i] = (double)e;
+    if (deta_o) deta_o[i] = (double)de;
+  }
+  for (int k = 0; k < d; k++) {
+    lines_l(g.outer[k], g.P[k], g.inner[k], g.D[k], gr + (long)k * N, v, k == 0 ? 0 : 1, 0, nt);
+    lines_w(g.outer[k], g.P[k], g.inner[k], g.A[k], wg + (long)k * N, wv, k == 0 ? 0 : 1, 1, nt);
+  }
+  for (long l = 0; l < N; l++) {
+    if (ixL[l] < 0) continue;
+    ld t = -v[l]; double w = wv[l];
+    if (b) { t -= (ld)b[ixL[l]]; w += fabs(b[ixL[l]]); }
+    V[ixL[l]] = (double)t; W[ixL[l]] = w;
+  }
+  free(ul); free(gr); free(v); free(au); free(wg); free(wv); free(ixL);
+  tgrid_free(&g);
+  return 0;
+}
+
+int orc_elliptic_truth(int d, const int *dims, const double *eta, const double *deta, const double *gradu0,
+                       const double *U, double *V, double *W, int nthreads) {
+  return orc_elliptic_truth_core(d, dims, 0, 0.0, 2.0, eta, deta, gradu0, NULL, NULL, U, V, W, NULL, NULL, NULL, NULL, nthreads);
+}
+
+int orc_elliptic_function_truth(int d, const int *dims, double gamma, double exponent, const double *dirichlet,
+                                const double *U, const double *b, double *rhs, double *W,
+                                double *eta, double *deta, double *gradu, double *wgrad, int nthreads) {
+  return orc_elliptic_truth_core(d, dims, 1, gamma, exponent, NULL, NULL, NULL, dirichlet, b, U, rhs, W, eta, deta, gradu, wgrad, nthreads);
+}

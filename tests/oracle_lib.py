@@ -299,3 +299,80 @@ def stokes_exact(dims, exact):
     if err:
         raise ValueError("orc_stokes_exact error %d" % err)
     return U, U2, dvals
+
+
+# ---------------------------------------------------------------------------------------------
+# Long-double truths of the callbacks with their componentwise weights ("Per-element bar: callbacks")
+# ---------------------------------------------------------------------------------------------
+def _bind_truth():
+    L = _bind_stokes()
+    if getattr(L, "_truth_bound", False):
+        return L
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    L.orc_stokes_truth.argtypes = [C.c_int, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    L.orc_stokes_function_truth.argtypes = [C.c_int, ip, C.POINTER(Rheology), dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    L.orc_elliptic_truth.argtypes = [C.c_int, ip, dp, dp, dp, dp, dp, dp, C.c_int]
+    L.orc_elliptic_function_truth.argtypes = [C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    L._truth_bound = True
+    return L
+
+
+def _flat(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel()
+
+
+def stokes_truth(dims, xG, eta=None, deta=None, strain=None, dirichlet=None, force=None, nthreads=1):
+    """(truth, W) of the linearised Stokes operator on the full global vector: both of global size."""
+    xG = _flat(xG)
+    y, W = np.empty_like(xG), np.empty_like(xG)
+    err = _bind_truth().orc_stokes_truth(len(dims), _ip(dims), _dp(_flat(eta)), _dp(_flat(deta)), _dp(_flat(strain)),
+                                         _dp(_flat(dirichlet)), _dp(_flat(force)), _dp(xG), _dp(y), _dp(W), nthreads)
+    if err:
+        raise ValueError("orc_stokes_truth error %d" % err)
+    return y, W
+
+
+def stokes_function_truth(dims, xG, dirichlet=None, force=None, rheology=(0, 1.0, 1.0, 1.0, 1.0), nthreads=1):
+    """StokesFunction in long double: dict with y, W (global size), eta, deta (N), strain, wstrain (d, N * d), wgamma (N)."""
+    d = len(dims)
+    N = sizes(dims)[0]
+    xG = _flat(xG)
+    r = {"y": np.empty_like(xG), "W": np.empty_like(xG), "eta": np.empty(N), "deta": np.empty(N), "strain": np.empty(d * N * d),
+         "wstrain": np.empty(d * N * d), "wgamma": np.empty(N)}
+    rh = Rheology(*rheology)
+    err = _bind_truth().orc_stokes_function_truth(d, _ip(dims), C.byref(rh), _dp(_flat(dirichlet)), _dp(_flat(force)), _dp(xG),
+                                                  _dp(r["y"]), _dp(r["W"]), _dp(r["eta"]), _dp(r["deta"]), _dp(r["strain"]),
+                                                  _dp(r["wstrain"]), _dp(r["wgamma"]), nthreads)
+    if err:
+        raise ValueError("orc_stokes_function_truth error %d" % err)
+    r["strain"] = r["strain"].reshape(d, N * d)
+    r["wstrain"] = r["wstrain"].reshape(d, N * d)
+    return r
+
+
+def elliptic_truth(dims, U, eta=None, deta=None, gradu0=None, nthreads=1):
+    """(truth, W) of MatMult_Elliptic on the interior vector."""
+    U = _flat(U)
+    V, W = np.empty_like(U), np.empty_like(U)
+    err = _bind_truth().orc_elliptic_truth(len(dims), _ip(dims), _dp(_flat(eta)), _dp(_flat(deta)), _dp(_flat(gradu0)), _dp(U),
+                                           _dp(V), _dp(W), nthreads)
+    if err:
+        raise ValueError("orc_elliptic_truth error %d" % err)
+    return V, W
+
+
+def elliptic_function_truth(dims, U, b=None, dirichlet=None, gamma=0.0, exponent=2.0, nthreads=1):
+    """FormFunction in long double: dict with rhs, W (interior size), eta, deta (N), gradu, wgrad (d, N)."""
+    d = len(dims)
+    N = sizes(dims)[0]
+    U = _flat(U)
+    r = {"rhs": np.empty_like(U), "W": np.empty_like(U), "eta": np.empty(N), "deta": np.empty(N), "gradu": np.empty(d * N),
+         "wgrad": np.empty(d * N)}
+    err = _bind_truth().orc_elliptic_function_truth(d, _ip(dims), gamma, exponent, _dp(_flat(dirichlet)), _dp(U), _dp(_flat(b)),
+                                                    _dp(r["rhs"]), _dp(r["W"]), _dp(r["eta"]), _dp(r["deta"]), _dp(r["gradu"]),
+                                                    _dp(r["wgrad"]), nthreads)
+    if err:
+        raise ValueError("orc_elliptic_function_truth error %d" % err)
+    r["gradu"] = r["gradu"].reshape(d, N)
+    r["wgrad"] = r["wgrad"].reshape(d, N)
+    return r
