@@ -322,6 +322,77 @@ int  cheb_reduce_slices(const cheb_reduce *h);             /* partial sums per o
 int  cheb_reduce_apply(cheb_reduce *h, const double *u_dev, const double *v_dev, double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Field statistics (no counterpart in the reference): what is asked of a     */
+/* field after every step and is no weighted sum -- extrema and where they    */
+/* are, the NaN count, weighted moments; volume-weighted histograms and       */
+/* conditional sums; the advective stability number.  Fields use the          */
+/* full-grid, field-major layout of cheb_modal_*.  The weight of a node is    */
+/* W_i = prod_k w_k[i_k]; every direction starts with the Clenshaw-Curtis     */
+/* weights (cheb_modal_weights_host), so a mass is a volume of [-1, 1]^d:     */
+/* all ones turns masses into node counts, CC L_k / 2 gives physical volume.  */
+/* No atomics: the order of every addition and the launch geometry depend on  */
+/* (dims, nfields, nbins, mode) alone, so results repeat bit for bit, on any  */
+/* stream; a field's results read only that field's values (a NaN or Inf in   */
+/* field f leaves every other field's output as it was).  With U = 2^-53, T   */
+/* values per field and the weights as uploaded:                              */
+/*   |M_p - exact|  <= (T + d + p + 4) U sum_i |W_i| |u_i - c|^p              */
+/*   |mass - exact| <= (T_b + d + 3) U sum_{i in slot} |W_i c_i|, T_b = the   */
+/*                     count of the slot; exactly +0.0 for T_b = 0            */
+/*   cfl: within (d + 2) U relative of the exact sum at the reported node,    */
+/*        which no other node's exact sum exceeds by more than that           */
+/* and counts, slots, min, max, indices and the NaN count are exact.          */
+/* ------------------------------------------------------------------------- */
+typedef struct cheb_stats cheb_stats;
+enum { CHEB_STATS_UNIFORM = 0, CHEB_STATS_EDGES = 1 };
+
+/* h[j] = the smaller of the distances from node j of n CGL nodes to its neighbours (the one distance there is at j = 0 and n - 1),
+ * and r[j] = s / h[j]: long double (the gap between two nodes as a product of two sines, their arguments reduced in integers),
+ * rounded once.  2 <= n <= 1024; a NaN s is CHEBHIP_ERR_ARG.  They need no device. */
+int  cheb_stats_spacing_host(int n, double *h);
+int  cheb_stats_rate_host(int n, double s, double *r);
+/* The checks of cheb_stats_create and of nbins, without a handle: 0 or the error cheb_stats_create / cheb_stats_histogram would
+ * return.  1 <= d <= 10 (CHEBHIP_ERR_ARG otherwise); 2 <= dims[k] <= 1024; 1 <= nfields <= 16; 1 <= nbins <= max_bins <= 1024;
+ * fewer than 2^31 input values.  Needs no device. */
+int  cheb_stats_check(int d, const int *dims, int nfields, int max_bins, int nbins);
+/* The handle owns the weight vectors, the rates of cfl, the partial results of the workgroups and those of the histogram for
+ * max_bins bins: the compute calls below allocate nothing and do not synchronise the host (but see cheb_stats_cfl).  The
+ * partial results and the rates are one set per handle, so a handle is used from ONE stream at a time: a call on another stream
+ * must be ordered after the handle's earlier calls by the caller (an event or a synchronise), as for any buffer they share. */
+int  cheb_stats_create(int d, const int *dims, int nfields, int max_bins, cheb_stats **out);
+int  cheb_stats_destroy(cheb_stats *h);
+/* The weights of direction k: dims[k] HOST values, NULL restores the default.  Synchronous, like cheb_reduce_set_weights. */
+int  cheb_stats_set_weights(cheb_stats *h, int k, const double *w_host);
+/* 0: input values nfields * prod(dims); 1: values of a summary, 9 * nfields; 2: max_bins; 3, 4: workgroups per field of summary /
+ * cfl and of histogram (how many partial results the folds add); -1 on a bad argument */
+long cheb_stats_size(const cheb_stats *h, int which);
+/* out[f][0..8], DEVICE; center_dev: nfields DEVICE values c_f, or NULL for 0.
+ *   0, 1   min and max over the values that are not NaN, with the bits of the element found; +-Inf count as values, -0.0 and
+ *          +0.0 compare equal
+ *   2, 3   the flat index inside the field of the first element that attains min / max, as a double
+ *   4      the number of NaN values.  All NaN: min = +Inf, max = -Inf, both indices -1
+ *   5..8   M_p = sum_i W_i (u_i - c_f)^p, p = 1..4, the power by repeated multiplication.  A NaN or Inf propagates into M_p. */
+int  cheb_stats_summary(cheb_stats *h, const double *u_dev, const double *center_dev, double *out_dev, void *stream);
+/* out[f][2][nbins + 3], DEVICE; slot 0 underflow, 1..nbins the bins, nbins + 1 overflow, nbins + 2 NaN.  Row 0: the mass
+ * sum_{i in slot} W_i, or sum W_i c_i with cond_dev (a second set of fields in the same layout; NULL: none): the numerator of a
+ * conditional mean.  Row 1: the number of values in the slot.  An empty slot has mass +0.0.  1 <= nbins <= max_bins.
+ *   CHEB_STATS_UNIFORM  spec_dev = (lo_f, hi_f) per field, DEVICE (e.g. slots 0, 1 of a summary).  inv = nbins / (hi - lo), one
+ *                       IEEE division; u < lo: underflow; t = (u - lo) * inv, one subtraction and one multiplication; t >= nbins
+ *                       (or a t that is NaN because hi - lo overflowed): overflow; otherwise bin floor(t).  hi <= lo or a bound
+ *                       that is not finite sends every value that is not NaN to overflow.
+ *   CHEB_STATS_EDGES    spec_dev = nbins + 1 non-decreasing edges per field, DEVICE.  u < e_0: underflow; u >= e_nbins: overflow;
+ *                       otherwise the last b with e_b <= u (so that u < e_{b+1}), found by comparisons only.
+ * A NaN value goes to the NaN slot in both modes. */
+int  cheb_stats_histogram(cheb_stats *h, const double *u_dev, const double *cond_dev, int mode, int nbins, const double *spec_dev,
+                          double *out_dev, void *stream);
+/* vel_dev: d fields, whatever nfields is; scale_host: d finite HOST values s_k = 2 / L_k as in cheb_grad_create, or
+ * NULL for ones.  out[0] = max_i sum_k |vel_k(i)| r_k[i_k], k ascending, r_k = cheb_stats_rate_host(dims[k], s_k); out[1] = the
+ * first flat index that attains it.  A NaN in any component at any node makes out[0] NaN and out[1] the first such node.
+ * The handle keeps r of the last scale on the device: a call with another scale forms r again and copies it (sum of dims values,
+ * from pageable memory, which the runtime stages before the call returns) ahead of the kernel on `stream`; a call with the same
+ * scale copies nothing and relies on the one-stream-at-a-time rule above for its order after that copy. */
+int  cheb_stats_cfl(cheb_stats *h, const double *vel_dev, const double *scale_host, double *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Vector calculus of full-grid fields (no counterpart in the reference,      */
 /* whose operators differentiate inside their callbacks only).  Fields use    */
 /* the full-grid, field-major layout of cheb_modal_*: field f of an array at  */

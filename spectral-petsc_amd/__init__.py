@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
     "cheb_reduce_weights_host", "cheb_reduce_create", "cheb_reduce_destroy", "cheb_reduce_set_weights", "cheb_reduce_size",
     "cheb_reduce_slices", "cheb_reduce_apply",
+    "cheb_stats_spacing_host", "cheb_stats_rate_host", "cheb_stats_check", "cheb_stats_create", "cheb_stats_destroy",
+    "cheb_stats_set_weights", "cheb_stats_size", "cheb_stats_summary", "cheb_stats_histogram", "cheb_stats_cfl",
     "cheb_grad_create", "cheb_grad_destroy", "cheb_grad_size", "cheb_grad_work_size", "cheb_grad_grad", "cheb_grad_tensor",
     "cheb_grad_div", "cheb_grad_curl", "cheb_grad_strain", "cheb_grad_laplacian", "cheb_grad_invariants",
     "cheb_layout_create", "cheb_layout_destroy", "cheb_layout_size", "cheb_layout_map_host", "cheb_layout_unpack", "cheb_layout_pack",
@@ -305,6 +307,17 @@ def lib():
         L.cheb_reduce_size.restype = C.c_long
         L.cheb_reduce_slices.argtypes = [vp]
         L.cheb_reduce_apply.argtypes = [vp, vp, vp, vp, vp]
+        L.cheb_stats_spacing_host.argtypes = [C.c_int, dp]
+        L.cheb_stats_rate_host.argtypes = [C.c_int, C.c_double, dp]
+        L.cheb_stats_check.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int]
+        L.cheb_stats_create.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.POINTER(vp)]
+        L.cheb_stats_destroy.argtypes = [vp]
+        L.cheb_stats_set_weights.argtypes = [vp, C.c_int, dp]
+        L.cheb_stats_size.argtypes = [vp, C.c_int]
+        L.cheb_stats_size.restype = C.c_long
+        L.cheb_stats_summary.argtypes = [vp, vp, vp, vp, vp]
+        L.cheb_stats_histogram.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.cheb_stats_cfl.argtypes = [vp, vp, dp, vp, vp]
         L.cheb_grad_create.argtypes = [C.c_int, ip, dp, C.POINTER(vp)]
         L.cheb_grad_destroy.argtypes = [vp]
         L.cheb_grad_size.argtypes = [vp]
@@ -926,6 +939,150 @@ class ChebReduce(_Handle):
             out = torch.empty((self.nfields,) + self.out_dims, dtype=torch.float64, device=u.device)
         _chk(lib().cheb_reduce_apply(self._h, _dev_ptr(u, self.size(0)), None if v is None else _dev_ptr(v, self.size(0)),
                                      _dev_ptr(out, self.size(1)), _stream()))
+        return out
+
+
+def stats_spacing(n):
+    """h[j] = the smaller of the distances from node j of n CGL nodes to its neighbours, one-sided at the two ends
+    (cheb_stats_spacing_host): long double, rounded once.  Needs no device."""
+    import numpy as np
+    h = np.empty(max(int(n), 0))
+    _chk(lib().cheb_stats_spacing_host(int(n), h.ctypes.data_as(C.POINTER(C.c_double)) if h.size else None))
+    return h
+
+
+def stats_rate(n, s=1.0):
+    """r[j] = s / h[j] (cheb_stats_rate_host), the quotient in long double rounded once: what ChebStats.cfl multiplies the
+    speeds along a direction of n points with.  Needs no device."""
+    import numpy as np
+    r = np.empty(max(int(n), 0))
+    _chk(lib().cheb_stats_rate_host(int(n), float(s), r.ctypes.data_as(C.POINTER(C.c_double)) if r.size else None))
+    return r
+
+
+def _stack2(a, b):
+    import torch
+    return torch.stack((a, b), dim=1).contiguous()
+
+
+def stats_edges(edges, nfields, bins):
+    """The host edge array of ChebStats.histogram as an (nfields, bins + 1) array: one row is repeated for every field.  Edges
+    that are NaN or decrease are a ChebhipError of code CHEBHIP_ERR_ARG.  Needs no device."""
+    import numpy as np
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim == 1:
+        e = np.broadcast_to(e, (int(nfields), e.shape[0]))
+    if e.shape != (int(nfields), int(bins) + 1):
+        raise ChebhipError(4, "edges: expected %d + 1 values (per field), got shape %r" % (int(bins), np.shape(edges)))
+    if np.isnan(e).any() or (e[:, 1:] < e[:, :-1]).any():
+        raise ChebhipError(4, "edges: the values must not decrease")
+    return np.ascontiguousarray(e)
+
+
+class ChebStats(_Handle):
+    """Statistics of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_stats_*; field-major, row-major over all
+    nodes, as ChebModal): summary (min, max, where, NaN count, weighted moments), histogram (volume-weighted, optionally of a
+    second field per bin) and cfl.  The weight of a node is prod_k w_k[i_k], Clenshaw-Curtis unless `weights` maps a direction to
+    dims[k] values.  Everything is asynchronous on torch's current stream, adds in a fixed order (the same input gives the same
+    bits) and uses no atomics."""
+    _destroy = "cheb_stats_destroy"
+    SUMMARY = ("min", "max", "argmin", "argmax", "nan", "m1", "m2", "m3", "m4")
+
+    def __init__(self, dims, nfields=1, max_bins=256, weights=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        self.max_bins = int(max_bins)
+        h = C.c_void_p()
+        _chk(lib().cheb_stats_create(len(self.dims), _ints(self.dims), self.nfields, self.max_bins, C.byref(h)))
+        self._h = h
+        for k, w in (weights or {}).items():
+            self.set_weights(k, w)
+
+    def size(self, which=0):
+        """0: values of the input, 1: of a summary, 2: max_bins, 3 / 4: workgroups per field of summary, cfl / of histogram."""
+        return lib().cheb_stats_size(self._h, int(which))
+
+    def set_weights(self, k, w):
+        """The weights of direction k: dims[k] host values; None restores the Clenshaw-Curtis weights.  Synchronous."""
+        import numpy as np
+        k = int(k)
+        if not 0 <= k < len(self.dims):
+            raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(self.dims) - 1))
+        if w is None:
+            _chk(lib().cheb_stats_set_weights(self._h, k, None))
+            return
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.dims[k],):
+            raise ValueError("weights of direction %d: expected %d values, got shape %r" % (k, self.dims[k], w.shape))
+        _chk(lib().cheb_stats_set_weights(self._h, k, _np_dp(w)))
+
+    def summary(self, u, center=None, out=None):
+        """A device tensor (nfields, 9): the columns of ChebStats.SUMMARY.  `center`: a device tensor of nfields values the
+        moments are taken about (e.g. a mean from an earlier summary, without a sync), or None for 0."""
+        import torch
+        if out is None:
+            out = torch.empty((self.nfields, 9), dtype=torch.float64, device=u.device)
+        _chk(lib().cheb_stats_summary(self._h, _dev_ptr(u, self.size(0)), None if center is None else _dev_ptr(center, self.nfields),
+                                      _dev_ptr(out, 9 * self.nfields), _stream()))
+        return out
+
+    @staticmethod
+    def auto_range(summary):
+        """(lo, hi) per field from a summary, on the device: lo = min and hi = max + 2^-40 (max - min + |max| + |min|), so that
+        the maximum falls into the last bin, not into overflow (t < bins by a margin far above the roundings of t).  A field
+        that is zero everywhere, or has no value that is not NaN, gets hi <= lo: everything in overflow."""
+        lo, hi = summary[:, 0], summary[:, 1]
+        return _stack2(lo, hi + 2.0 ** -40 * ((hi - lo) + hi.abs() + lo.abs()))
+
+    def histogram(self, u, bins, range=None, edges=None, cond=None, out=None):
+        """A device tensor (nfields, 2, bins + 3): row 0 the mass of a slot (with `cond`: the sum of W cond over it), row 1 its
+        number of values; slot 0 underflow, 1..bins the bins, bins + 1 overflow, bins + 2 NaN.  `edges` (bins + 1 values, or
+        that per field; host values or a device tensor) selects the bins by comparisons; otherwise the bins are uniform over
+        `range`: (lo, hi), an (nfields, 2) array or device tensor, or None for auto_range of a summary of u (taken on the
+        device, no sync)."""
+        import numpy as np
+        import torch
+        bins = int(bins)
+        if edges is not None:
+            if range is not None:
+                raise ValueError("histogram: give range or edges, not both")
+            mode = 1
+            spec = edges if isinstance(edges, torch.Tensor) else torch.from_numpy(stats_edges(edges, self.nfields, bins)).to(u.device)
+            nspec = self.nfields * (bins + 1)
+        else:
+            mode = 0
+            nspec = 2 * self.nfields
+            if range is None:
+                spec = self.auto_range(self.summary(u))
+            elif isinstance(range, torch.Tensor):
+                spec = range
+            else:
+                r = np.asarray(range, dtype=np.float64)
+                if r.shape not in ((2,), (self.nfields, 2)):
+                    raise ValueError("range: expected (lo, hi) or that per field, got shape %r" % (r.shape,))
+                spec = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(r, (self.nfields, 2)))).to(u.device)
+        if out is None:
+            out = torch.empty((self.nfields, 2, bins + 3), dtype=torch.float64, device=u.device)
+        _chk(lib().cheb_stats_histogram(self._h, _dev_ptr(u, self.size(0)), None if cond is None else _dev_ptr(cond, self.size(0)),
+                                        mode, bins, _dev_ptr(spec, nspec), _dev_ptr(out, self.nfields * 2 * (bins + 3)), _stream()))
+        return out
+
+    def cfl(self, vel, scale=None, out=None):
+        """A device tensor (2,): max_i sum_k |vel_k(i)| s_k / h_k(i_k) of the len(dims) fields of vel (whatever nfields is), and
+        the flat index of the first node that attains it; NaN and the first such node if a component is NaN anywhere.
+        scale: len(dims) values 2 / L_k, or None for ones."""
+        import numpy as np
+        import torch
+        d = len(self.dims)
+        if out is None:
+            out = torch.empty(2, dtype=torch.float64, device=vel.device)
+        sc = None
+        if scale is not None:
+            sc = np.ascontiguousarray(scale, dtype=np.float64)
+            if sc.shape != (d,):
+                raise ValueError("scale: expected %d values, got shape %r" % (d, sc.shape))
+        _chk(lib().cheb_stats_cfl(self._h, _dev_ptr(vel, d * (self.size(0) // self.nfields)), None if sc is None else _np_dp(sc),
+                                  _dev_ptr(out, 2), _stream()))
         return out
 
 

@@ -976,6 +976,34 @@ void points_nodes_host(int n, double *x) {
   for (int j = 0; j < n; j++) x[j] = (double)cos_jk(j, 1, n - 1);
 }
 
+// Node spacings (cheb_stats_*, stats.hip).  The gap between the nodes j and j + 1 of n = N + 1 points is
+//   x_j - x_{j+1} = cos(pi j / N) - cos(pi (j + 1) / N) = 2 sin(pi (2j + 1) / 2N) sin(pi / 2N),
+// a product, so nothing cancels next to the walls, where the gaps are of the order N^-2.  2j + 1 is folded into 1 .. N in integers
+// (sin(pi - t) = sin t): both arguments lie in (0, pi/2].  h_j = the smaller of the gaps on either side of node j, the one gap
+// there is at j = 0 and j = N.  The gaps are symmetric, gap_j = gap_{N-1-j}, exactly.
+static long double stats_gap(long j, long N) {
+  long m = 2 * j + 1;
+  if (m > N) m = 2 * N - m;
+  return 2.0L * sinl(PI_L * (long double)m / (2.0L * (long double)N)) * sinl(PI_L / (2.0L * (long double)N));
+}
+
+static long double stats_spacing_ld(int j, int n) {
+  const long N = n - 1;
+  if (j == 0) return stats_gap(0, N);
+  if (j == N) return stats_gap(N - 1, N);
+  const long double a = stats_gap(j - 1, N), b = stats_gap(j, N);
+  return a < b ? a : b;
+}
+
+void stats_spacing_host(int n, double *h) {
+  for (int j = 0; j < n; j++) h[j] = (double)stats_spacing_ld(j, n);
+}
+
+// r_j = s / h_j: the quotient in long double, rounded once
+void stats_rate_host(int n, double s, double *r) {
+  for (int j = 0; j < n; j++) r[j] = (double)((long double)s / stats_spacing_ld(j, n));
+}
+
 // Row of a coordinate x: l_j = (w_j / (x - x_j)) / sum_k w_k / (x - x_k), w_j = (-1)^j, halved at both ends, in the nearest-node
 // form: s = the node nearest to x (the lowest index on a tie), d_j = x - x_j, r_s = 1, r_j = (w_j / w_s) (d_s / d_j) otherwise
 // (|d_s / d_j| <= 1: nothing overflows), l = r / sum r, the sum in ascending j.  w_j / w_s is +-1/2, +-1 or +-2, so an entry

@@ -134,6 +134,10 @@ void points_matrix_host(int n, int m, const double *x, double *R);
 // or the coordinate x (POINT, DPOINT).  0, or 1: unknown kind, 2: j is no index of the line.
 enum { REDUCE_W_INTEGRAL = 0, REDUCE_W_MEAN, REDUCE_W_NODE, REDUCE_W_DNODE, REDUCE_W_POINT, REDUCE_W_DPOINT };
 int reduce_weights_host(int n, int kind, double arg, double *w);
+// Host side of the field statistics (stats.hip; the extent is checked there): h_j = the smaller of the distances from node j of n
+// CGL nodes to its neighbours (one-sided at the two ends), and r_j = s / h_j; long double, rounded once.
+void stats_spacing_host(int n, double *h);
+void stats_rate_host(int n, double s, double *r);
 
 // Launches one sweep.  jfast selects the line-contiguous tiling.
 hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream);

@@ -605,3 +605,53 @@ def strain_invariant(sp, dims, vel_full, scale=None):
     finally:
         g.destroy()
     return out[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Field statistics (ChebStats)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def pdf(sp, dims, u_full, bins, range=None):
+    """The volume-weighted probability density of the full-grid field u_full (layout as profile): (centres, density), device
+    tensors of shape (nfields, bins), the density normalised to integrate to 1 over the mass that fell inside the range (all
+    zeros if none did).  range: (lo, hi) for every field, or None for ChebStats.auto_range of each field's
+    summary, taken on the device.  A node counts with its Clenshaw-Curtis volume, not once: the CGL grid packs its
+    nodes against the walls, and an unweighted histogram of the node values is the PDF of the grid."""
+    dims, nf = _stacked(dims, u_full)
+    bins = int(bins)
+    st = sp.ChebStats(dims, nf, max_bins=bins)
+    try:
+        u = u_full.reshape(-1)
+        if range is None:
+            lohi = st.auto_range(st.summary(u))
+        else:
+            lo, hi = (float(x) for x in range)
+            lohi = torch.tensor([[lo, hi]] * nf, dtype=torch.float64, device=u.device)
+        h = st.histogram(u, bins, range=lohi)
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        st.destroy()
+    mass = h[:, 0, 1:bins + 1]
+    width = ((lohi[:, 1] - lohi[:, 0]) / bins).unsqueeze(1)
+    k = torch.arange(bins, dtype=torch.float64, device=u.device).unsqueeze(0)
+    centres = lohi[:, :1] + (k + 0.5) * width
+    total = mass.sum(dim=1, keepdim=True)
+    density = torch.where(total > 0, mass / (total * width), torch.zeros_like(mass))
+    return centres, density
+
+
+def cfl_dt(sp, dims, vel_full, cfl=0.5, scale=None):
+    """The advective time-step limit of the full-grid velocity vel_full (d fields, all nodes of the CGL grid dims):
+    dt = cfl / max_i sum_k |vel_k(i)| s_k / h_k(i_k), h_k the local node spacing, s_k = scale[k] = 2 / L_k (ChebStats.cfl).
+    Returns (dt, index of the limiting node) as Python numbers (one sync); dt is NaN if the velocity holds a NaN -- no step
+    must be chosen from a field that has blown up -- and inf for a velocity that is zero everywhere."""
+    dims = tuple(int(n) for n in dims)
+    st = sp.ChebStats(dims, 1, max_bins=1)              # (one bin: the histogram's buffers of this handle are a few KB)
+    try:
+        out = st.cfl(vel_full.reshape(-1), scale).cpu()
+    finally:
+        st.destroy()
+    m, idx = float(out[0]), int(out[1])
+    if m != m:
+        return float("nan"), idx
+    return (float(cfl) / m if m > 0 else float("inf")), idx
