@@ -1063,6 +1063,8 @@ int stokes_saddle_iterations(const stokes_saddle *s, int which);
  *                            two launches with one reduction and the stored vectors' exact norms carried beside the basis (read per solve; A/B)
  *   points_spread_pass    cheb_points_spread: at most this many points per pass; 0 (default) = as many as the handle's work memory holds
  *                            rows for (read per call; tests reach the multi-pass path at small counts with it)
+ *   sweep_alpha_multiply  1: the long-line STORE sweep with alpha = -1 on a symmetric line operator multiplies by alpha as every other launch
+ *                            does, instead of carrying the sign in its recombination (read per launch; A/B, the same values)
  *   no_rocblas            deprecated alias (rounds 1-3) of vendor_gemm with the inverted meaning; still accepted */
 int chebhip_set_option(const char *name, int value);
 int chebhip_get_option(const char *name, int *value);

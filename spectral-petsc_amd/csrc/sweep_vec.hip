@@ -386,7 +386,8 @@ __global__ __launch_bounds__(512, 4) void cheb_sweep_vec_kernel(const SweepParam
 //     loads return 0, out-of-range stores are dropped; a masked lane gets offset 0x80000000);
 //   * loads are not masked at all: lanes outside the tile read other points of the SAME line (or zeros past
 //     the end of the array), which only meet zero entries of the matrix or feed columns that are never stored;
-//   * the lane exchange that makes 16-byte pieces is one DPP broadcast + one select per dword;
+//   * the lane exchange that makes 16-byte pieces is ONE instruction per dword, a select whose source carries the DPP broadcast
+//     (tile.h xpair; the raw transforms keep one broadcast + one select per dword);
 //   * the centro-symmetry sign rides in the scalar factor of the mirror row.
 // What each stream costs (input loads, accumulator loads, stores, MFMA chains compiled out one at a time): DESIGN 4.2b,
 // profiles/r02_v4_ablation.txt.  Cache policies on the result stores (sc1, nt) all lose: DESIGN_history.md, "write-through result stores".
@@ -402,7 +403,10 @@ constexpr int V4_FRAG_AHEAD = 2;
 // GATH: the rows of every line come from up to GATHER_MAX different arrays (sweep.h GatherSrc; the pencil of a slab partition read from the
 // ranks' slabs in place, over xGMI for the remote ones): 64-bit global loads from per-thread row bases instead of the buffer loads --
 // COLFAST, plain input, STORE only.  A thread's loader slots are the same rows for every tile, so their bases are found once.
-template <int KS, bool JFAST, int MODE, int RAW = 0, int INM = 0, int GATH = 0>
+// SG: the STORE launch with alpha = -1 on a centro-symmetric matrix (the constant-coefficient matvec's first direction): the sign rides in
+// the source modifiers of the recombination, hi = (-ce) - co, lo = co - ce, and the results are stored without a multiply (the same
+// values: a sign change is exact; an exact cancellation gives +0 where the multiply gave -0).  Chosen on the host (launch_v4).
+template <int KS, bool JFAST, int MODE, int RAW = 0, int INM = 0, int GATH = 0, int SG = 0>
 __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, const u32 BID, const u32 NBLK, const GatherSrc *gs = nullptr) {
   static_assert(!GATH || (!JFAST && MODE == 0 && RAW == 0 && INM == 0), "the gather loader exists for strided lines, plain input, STORE");
   constexpr bool PUSH = GATH == 2;                     // GATH = 2: the results are stored into the row owners' arrays as well (sweep.h GatherSrc::push)
@@ -415,6 +419,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   static_assert(INM == 0 || (RAW == 1 && MODE == 0), "IN_MUL exists for the raw forward transform with a plain store only");
   static_assert(RAW == 0 || MODE != 1, "the raw modes (sweep.h) are STORE / MUL only");
   static_assert(!MUL || RAW == 1, "OUT_MUL exists for the raw forward transform only");
+  static_assert(SG == 0 || (MODE == 0 && RAW == 0 && INM == 0 && GATH == 0), "the sign-only store exists for the plain STORE launch");
   using G = TileGeom<KS, JFAST>;
   // offsets beyond every buffer (the launcher keeps them < 1 GiB): a per-lane constant may carry INVALID, the scalar
   // part of an offset T_INVALID, and their sum must not wrap back into range
@@ -578,7 +583,8 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       } else if (!JFAST) {
         e = xj + xm;
         o = xj - xm;                                   // the middle point of an odd line is its own mirror: o = 0
-        if (oddP) { const bool mid = 2 * (ld_b + (chunk * G::CH + s) * G::QSTEP) == nn; if (mid) e = xj; }
+        // (a scalar branch: as a select hipcc pays four v_cndmask per slot on every line length, 16 per tile and wave)
+        if (oddP) { asm volatile("" ::: "memory"); const bool mid = 2 * (ld_b + (chunk * G::CH + s) * G::QSTEP) == nn; if (mid) e = xj; }
       } else {
         e = d2{xj.x + xm.y, xj.y + xm.x};
         o = d2{xj.x - xm.y, xj.y - xm.x};
@@ -700,27 +706,37 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       if (RAW == 1) { hi[r] = ce[r]; lo[r] = co[r]; }  // the halves as they are: row i <- (ME e)_i, row n-i <- (MO o)_i
+      else if (SG) { hi[r] = -ce[r] - co[r]; lo[r] = co[r] - ce[r]; }   // alpha = alpha_lo = -1 as source modifiers
       else { hi[r] = ce[r] + co[r]; lo[r] = ce[r] - co[r]; }
     }
 #pragma unroll
     for (int rp = 0; rp < 2; rp++) {
       // even lane: row 2rp of its own column and of the odd neighbour's; odd lane: row 2rp+1 of the even neighbour's and its own
       const double ha = hi[2 * rp], hb = hi[2 * rp + 1], la = lo[2 * rp], lb = lo[2 * rp + 1];
-      // the broadcasts run with EVERY lane active (a DPP read of a lane that EXEC has switched off returns 0), the
-      // selects come after
-      const double hbe = bc_even(hb), hao = bc_odd(ha), lbe = bc_even(lb), lao = bc_odd(la);
-      d2 vh = d2{odd ? hbe : ha, odd ? hb : hao};                         // ascending columns / points
-      d2 vl;
-      if (!JFAST) vl = d2{odd ? lbe : la, odd ? lb : lao};
-      else vl = d2{odd ? lb : lao, odd ? lbe : la};                       // mirrors of (ie, ie+1) are (n-ie, n-ie-1): descending
+      d2 vh, vl;
+      if (RAW == 1) {
+        // (the values are MFMA results: the broadcasts stay with hipcc, which knows the wait between an MFMA and a DPP read.)
+        // the broadcasts run with EVERY lane active (a DPP read of a lane that EXEC has switched off returns 0), the
+        // selects come after
+        const double hbe = bc_even(hb), hao = bc_odd(ha), lbe = bc_even(lb), lao = bc_odd(la);
+        vh = d2{odd ? hbe : ha, odd ? hb : hao};                          // ascending columns / points
+        if (!JFAST) vl = d2{odd ? lbe : la, odd ? lb : lao};
+        else vl = d2{odd ? lb : lao, odd ? lbe : la};                     // mirrors of (ie, ie+1) are (n-ie, n-ie-1): descending
+      } else {
+        // the same exchange as ONE select per dword whose source carries the broadcast (tile.h xpair)
+        double hx, hy, lx, ly;
+        xpair(ha, hb, hx, hy); xpair(la, lb, lx, ly);
+        vh = d2{hx, hy};
+        if (!JFAST) vl = d2{lx, ly}; else vl = d2{ly, lx};
+      }
       if (MUL) { vh = acc_hi[rp] * (alpha * vh); vl = acc_lo[rp] * (alpha_lo * vl); }
       else if (ACC2) {
         const d2 (&bh)[2] = (&acc_hi == &accX_hi) ? acc2X_hi : acc2Y_hi; const d2 (&bl)[2] = (&acc_hi == &accX_hi) ? acc2X_lo : acc2Y_lo;
         vh = (acc_hi[rp] + bh[rp]) + alpha * vh; vl = (acc_lo[rp] + bl[rp]) + alpha_lo * vl;
       }
       else if (ACC) { vh = acc_hi[rp] + alpha * vh; vl = acc_lo[rp] + alpha_lo * vl; }
-      else { vh = alpha * vh; vl = alpha_lo * vl; }
-      if (JFAST && (H & 1)) { if (fold[rp]) vh = d2{vh.x, vl.y}; }       // (y_ie, y_{n-ie}): adjacent when H is odd
+      else if (!SG) { vh = alpha * vh; vl = alpha_lo * vl; }
+      if (JFAST) { if (fold[rp]) vh = d2{vh.x, vl.y}; }                  // (y_ie, y_{n-ie}): adjacent when H is odd (fold[] is false on every lane otherwise)
       if constexpr (PUSH) {
         // row i of this output line belongs to the rank that owns plane i: the 16 bytes go into ITS result array, where the row
         // sits as in the array the line was read from -- remote stores inside the same launch as the remote loads (the two
@@ -805,10 +821,10 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
 #endif
 }
 
-template <int KS, bool JFAST, int MODE, int RAW = 0, int INM = 0>
+template <int KS, bool JFAST, int MODE, int RAW = 0, int INM = 0, int SG = 0>
 __global__ __launch_bounds__(512) void cheb_sweep_vec4_kernel(const SweepParams p) {
   __shared__ double smem[TileGeom<KS, JFAST>::LDS_DOUBLES];
-  vec4_body<KS, JFAST, MODE, RAW, INM>(p, smem, blockIdx.x, gridDim.x);
+  vec4_body<KS, JFAST, MODE, RAW, INM, 0, SG>(p, smem, blockIdx.x, gridDim.x);
 }
 
 template <int KS, bool PUSH>
@@ -874,6 +890,8 @@ static hipError_t launch_v4(const SweepParams &p, unsigned grid, hipStream_t str
   else if (p.out_mode == OUT_ACC) hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 1>), dim3(grid), dim3(512), 0, stream, p);
   else if (p.raw == 1) hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0, 1>), dim3(grid), dim3(512), 0, stream, p);
   else if (p.raw == 2) hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0, 2>), dim3(grid), dim3(512), 0, stream, p);
+  // alpha = -1 on a centro-symmetric matrix (alpha_lo = alpha): the signs ride in the recombination, no multiply (vec4_body, SG)
+  else if (p.alpha == -1.0 && p.sym && !opt(OPT_SWEEP_ALPHA_MULTIPLY)) hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0, 0, 0, 1>), dim3(grid), dim3(512), 0, stream, p);
   else hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0>), dim3(grid), dim3(512), 0, stream, p);
   sweep_note_launch();
   return hipGetLastError();

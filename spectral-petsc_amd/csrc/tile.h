@@ -129,6 +129,29 @@ __device__ __forceinline__ double bc_odd(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// The exchange fused with its select: ONE v_cndmask_b32 per dword whose first source carries the DPP quad_perm (the VOP2 DPP form,
+// which hipcc does not form from update_dpp + select).  Of the values a, b of a lane (rows 2 rp, 2 rp + 1 of its column)
+//   x = the even lane's a in the even lane, the even lane's b in the odd lane   (= odd ? bc_even(b) : a)
+//   y = the odd lane's a in the even lane, the odd lane's b in the odd lane     (= odd ? b : bc_odd(a)).
+// The VOP2 form reads its mask from VCC: the two lane-parity masks arrive as scalar constants (PAIR_EVEN / PAIR_ODD) and are moved there.
+// The rule of bc_even / bc_odd holds: every lane is active while the DPP source is read.  s_mov + s_nop 1 cover the two wait
+// states between a VALU write of a register and a DPP read of it, which hipcc does not count across an asm statement -- and for
+// that reason a and b must be results of ordinary vector instructions, never of an MFMA (its longer wait is not covered).
+constexpr unsigned long long PAIR_EVEN = 0x5555555555555555ull, PAIR_ODD = 0xAAAAAAAAAAAAAAAAull;
+__device__ __forceinline__ void xpair(double a, double b, double &x, double &y) {
+  const int al = __double2loint(a), ah = __double2hiint(a), bl = __double2loint(b), bh = __double2hiint(b);
+  int xl, xh, yl, yh;
+  asm("s_mov_b64 vcc, %8\n\t"
+      "s_nop 1\n\t"
+      "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_mov_b64 vcc, %9\n\t"
+      "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf"
+      : "=&v"(xl), "=&v"(xh), "=&v"(yl), "=&v"(yh) : "v"(al), "v"(ah), "v"(bl), "v"(bh), "s"(PAIR_EVEN), "s"(PAIR_ODD) : "vcc");
+  x = __hiloint2double(xh, xl); y = __hiloint2double(yh, yl);
+}
+
 // raw buffer accesses: 32-bit byte offset, the hardware range check is the mask (out-of-range loads return 0, stores are dropped)
 __device__ __forceinline__ d2 ld16(__amdgpu_buffer_rsrc_t r, u32 off) { return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); }
 __device__ __forceinline__ void st16(__amdgpu_buffer_rsrc_t r, u32 off, d2 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)off, 0, 0); }
