@@ -229,6 +229,40 @@ int  cheb_points_eval_grid(cheb_points *h, const double *u_dev, const double *co
  * long double on the DOUBLE node table, rounded once. */
 int  cheb_nodes_host(int n, double *x);
 int  cheb_points_matrix_host(int n, int m, const double *x_host, double *R);
+/* First derivatives at points.  The derivative of the interpolant is another row per direction: with c_j = w_j / w_s,
+ * q_j = c_j / d_j and r_j = q_j d_s (j != s), R = 1 + sum r_j, Q2 = sum q_k / d_k, T = sum q_k (x_s - x_k) / d_k (sums over k != s),
+ *   l'_j(x) = (q_j / R) ((1 + d_s^2 Q2) / R - d_s / d_j)  (j != s),    l'_s(x) = -T / R^2,
+ * the exact derivative of the rational function the value rows evaluate on the rounded nodes.  Nothing divides by d_s: a point on
+ * a node gets l'_j = q_j, l'_s = -sum q_k, a row of the differentiation matrix, by the same instructions.  A NaN or infinite
+ * coordinate gives a row of NaN, |x| > 1 extrapolates.  cheb_points_drows: R[i][j] = l'_j(x[i]) of direction k, m x dims[k] DEVICE
+ * values (k_points_drows: the lane groups, reductions and order of k_points_rows); cheb_points_dmatrix_host is its host twin, long
+ * double on the DOUBLE node table, rounded once. */
+int  cheb_points_drows(cheb_points *h, int k, const double *x_dev, long m, double *R_dev, void *stream);
+int  cheb_points_dmatrix_host(int n, int m, const double *x_host, double *R);
+/* cheb_points_eval, cheb_points_spread and cheb_points_eval_grid with the rows of the directions flagged in `deriv` exchanged for
+ * their derivative rows: d HOST ints, each 0 or 1 (anything else: CHEBHIP_ERR_ARG), so (1, 0, 0) is d/dx_0 and (1, 1, 0) the mixed
+ * derivative; pure second derivatives are not offered.  The line products, contractions, chunks and passes are those of the plain
+ * calls; NULL or all zeros runs the plain call's launches and gives its bits.  With CHEB_SPREAD_DELTA cheb_modal_integrate(out,
+ * phi) is sum_p s_p d^alpha phi(x_p): a force dipole, the transpose of a gradient observation.  Derivatives are with respect to
+ * the reference coordinates; a box of length L_k takes the factor 2 / L_k per flagged direction. */
+int  cheb_points_eval_deriv(cheb_points *h, const double *u_dev, const double *xi_dev, long npts, const int *deriv, double *out_dev,
+                            void *stream);
+int  cheb_points_spread_deriv(cheb_points *h, const double *s_dev, const double *xi_dev, long npts, const int *deriv, double *out_dev,
+                              int flags, void *stream);
+int  cheb_points_eval_grid_deriv(cheb_points *h, const double *u_dev, const double *coords_dev, const int *m, const int *deriv,
+                                 double *out_dev, void *stream);
+/* The gradient in one call: out[f][c][p] = s_c d u_f / d x_c (xi[p]), c = 0 .. d-1, out nfields x d x npts; with
+ * CHEB_POINTS_GRAD_VALUE out is nfields x (d + 1) x npts and component c = d holds the value, so a derivative's index does not
+ * depend on the flag.  scale: d finite HOST values s_k = 2 / L_k as in cheb_grad_create, NULL = ones; one multiplication at the
+ * store.  Per chunk of cheb_points_chunk / 2 points (the handle's work memory as created): k_points_drows writes both row sets,
+ * ONE direction-0 line product over the stacked value and derivative rows gives every point a value block and a derivative
+ * block, and k_points_contract_grad walks the value block once for the value and every direction >= 1 and the derivative block
+ * once for direction 0, a workgroup per (field, point) and block.  d = 1: the line product's two outputs are the result.  Where the
+ * work memory holds a single point, a point takes one pass of the eval pipeline per component.  No atomics, results repeat bit for
+ * bit; the call allocates nothing and does not synchronise the host.  npts = 0 is a no-op; out must not overlap u. */
+enum { CHEB_POINTS_GRAD_VALUE = 1 };
+int  cheb_points_eval_grad(cheb_points *h, const double *u_dev, const double *xi_dev, long npts, const double *scale_host, int flags,
+                           double *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- */
 /* Dealiased products and advection terms (no counterpart in the reference):  */

@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "cheb_points_create", "cheb_points_destroy", "cheb_points_chunk", "cheb_points_rows", "cheb_points_eval",
     "cheb_points_spread", "cheb_points_spread_pass",
     "cheb_points_grid_reserve", "cheb_points_eval_grid", "cheb_nodes_host", "cheb_points_matrix_host",
+    "cheb_points_drows", "cheb_points_dmatrix_host", "cheb_points_eval_deriv", "cheb_points_spread_deriv",
+    "cheb_points_eval_grid_deriv", "cheb_points_eval_grad",
     "cheb_dealias_fine_size", "cheb_dealias_matrix_host", "cheb_dealias_create", "cheb_dealias_destroy", "cheb_dealias_fine_dims",
     "cheb_dealias_size", "cheb_dealias_work_bytes", "cheb_dealias_multiply", "cheb_dealias_reserve_advect", "cheb_dealias_advect",
     "cheb_reduce_weights_host", "cheb_reduce_create", "cheb_reduce_destroy", "cheb_reduce_set_weights", "cheb_reduce_size",
@@ -288,6 +290,12 @@ def lib():
         L.cheb_points_eval_grid.argtypes = [vp, vp, vp, ip, vp, vp]
         L.cheb_nodes_host.argtypes = [C.c_int, dp]
         L.cheb_points_matrix_host.argtypes = [C.c_int, C.c_int, dp, dp]
+        L.cheb_points_drows.argtypes = [vp, C.c_int, vp, C.c_long, vp, vp]
+        L.cheb_points_dmatrix_host.argtypes = [C.c_int, C.c_int, dp, dp]
+        L.cheb_points_eval_deriv.argtypes = [vp, vp, vp, C.c_long, ip, vp, vp]
+        L.cheb_points_spread_deriv.argtypes = [vp, vp, vp, C.c_long, ip, vp, C.c_int, vp]
+        L.cheb_points_eval_grid_deriv.argtypes = [vp, vp, vp, ip, ip, vp, vp]
+        L.cheb_points_eval_grad.argtypes = [vp, vp, vp, C.c_long, dp, C.c_int, vp, vp]
         L.cheb_dealias_fine_size.argtypes = [C.c_int]
         L.cheb_dealias_matrix_host.argtypes = [C.c_int, C.c_int, C.c_int, dp]
         L.cheb_dealias_create.argtypes = [C.c_int, ip, ip, C.c_int, C.POINTER(vp)]
@@ -672,12 +680,26 @@ def interp_matrix(n, x):
     return R
 
 
+def deriv_matrix(n, x):
+    """The rows l'_j(x_i) of the derivative of the barycentric interpolant on the n CGL nodes (cheb_points_dmatrix_host) as an
+    (len(x), n) numpy array: long double on the double node table, rounded once.  A coordinate on a node gives that node's row of
+    the differentiation matrix, a NaN or infinite one a row of NaN, |x| > 1 extrapolates.  Needs no device."""
+    import numpy as np
+    xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    R = np.empty((xs.size, max(int(n), 0)))
+    _chk(lib().cheb_points_dmatrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
+    return R
+
+
 class ChebPoints(_Handle):
     """Values of `nfields` stacked full-grid fields on the CGL grid `dims` (field-major, row-major over all nodes, as ChebModal) at
     arbitrary points of [-1, 1]^d (cheb_points_*): scattered points (eval) and tensor grids of arbitrary coordinates (eval_grid:
     plane and line cuts, plotting grids), and the transpose of the scattered evaluation (spread: point forces and sources on the
     grid).  Coordinates are device tensors; |x| > 1 extrapolates, a NaN coordinate gives NaN at that
-    point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream."""
+    point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream.
+    First derivatives with respect to the reference coordinates: deriv=(0 or 1 per direction) on eval, spread and eval_grid takes
+    the flagged directions' derivative rows (drows) in place of their value rows; eval_grad gives every first derivative of every
+    field in one call."""
     _destroy = "cheb_points_destroy"
 
     def __init__(self, dims, nfields=1):
@@ -711,8 +733,52 @@ class ChebPoints(_Handle):
             _chk(lib().cheb_points_rows(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
         return out
 
-    def eval(self, u, pts, out=None):
-        """out[f][p] = the value of field f at the point pts[p]: pts is an (npts, d) device tensor, out (nfields, npts)."""
+    def _deriv(self, deriv):
+        """deriv as the C array of d ints (None: NULL, the plain call); values other than 0 and 1 are refused by the library."""
+        if deriv is None:
+            return None
+        deriv = tuple(int(v) for v in deriv)
+        if len(deriv) != len(self.dims):
+            raise ValueError("deriv: expected %d flags, got %d" % (len(self.dims), len(deriv)))
+        return _ints(deriv)
+
+    def drows(self, k, x, out=None):
+        """The rows l'_j(x_i) of the interpolant's derivative in direction k for the device coordinates x (cheb_points_drows): a
+        (len(x), dims[k]) device tensor."""
+        import torch
+        if not 0 <= int(k) < len(self.dims):
+            raise ChebhipError(2, "direction %d out of range 0..%d" % (int(k), len(self.dims) - 1))
+        m, n = x.numel(), self.dims[int(k)]
+        if out is None:
+            out = torch.empty((m, n), dtype=torch.float64, device=x.device)
+        if m:
+            _chk(lib().cheb_points_drows(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
+        return out
+
+    def eval_grad(self, u, pts, out=None, value=False, scale=None):
+        """out[f][c][p] = scale[c] d u_f / d x_c at pts[p], c < d, in one call (cheb_points_eval_grad): an (nfields, d, npts) device
+        tensor; value=True appends the value as component d: (nfields, d + 1, npts).  scale: d finite factors 2 / L_k, None = ones."""
+        import numpy as np
+        import torch
+        d = len(self.dims)
+        if pts.dim() != 2 or pts.shape[1] != d:
+            raise ValueError("pts: expected shape (npts, %d), got %r" % (d, tuple(pts.shape)))
+        npts, nc = pts.shape[0], d + (1 if value else 0)
+        if out is None:
+            out = torch.empty((self.nfields, nc, npts), dtype=torch.float64, device=u.device)
+        sc = None
+        if scale is not None:
+            sc = np.ascontiguousarray(scale, dtype=np.float64).ravel()
+            if sc.size != d:
+                raise ValueError("scale: expected %d factors, got %d" % (d, sc.size))
+        _chk(lib().cheb_points_eval_grad(self._h, _dev_ptr(u, self.size()) if npts else None, _dev_ptr(pts, npts * d) if npts else None,
+                                         npts, None if sc is None else _np_dp(sc), 1 if value else 0,   # CHEB_POINTS_GRAD_VALUE
+                                         _dev_ptr(out, self.nfields * nc * npts) if npts else None, _stream()))
+        return out
+
+    def eval(self, u, pts, out=None, deriv=None):
+        """out[f][p] = the value of field f at the point pts[p]: pts is an (npts, d) device tensor, out (nfields, npts).  deriv: d
+        flags, 0 or 1: the derivative along the flagged directions instead (cheb_points_eval_deriv); None is the plain call."""
         import torch
         d = len(self.dims)
         if pts.dim() != 2 or pts.shape[1] != d:
@@ -720,17 +786,22 @@ class ChebPoints(_Handle):
         npts = pts.shape[0]
         if out is None:
             out = torch.empty((self.nfields, npts), dtype=torch.float64, device=u.device)
-        if npts:
+        dv = self._deriv(deriv)
+        if dv is not None:
+            _chk(lib().cheb_points_eval_deriv(self._h, _dev_ptr(u, self.size()) if npts else None, _dev_ptr(pts, npts * d) if npts else None,
+                                              npts, dv, _dev_ptr(out, self.nfields * npts) if npts else None, _stream()))
+        elif npts:
             _chk(lib().cheb_points_eval(self._h, _dev_ptr(u, self.size()), _dev_ptr(pts, npts * d), npts,
                                         _dev_ptr(out, self.nfields * npts), _stream()))
         return out
 
-    def spread(self, s, pts, out=None, accumulate=False, delta=False):
+    def spread(self, s, pts, out=None, accumulate=False, delta=False, deriv=None):
         """The transpose of eval: out[f][i] = sum_p s[f][p] prod_k l_{i_k}(pts[p][k]) on the full grid (cheb_points_spread).  s is an
         (nfields, npts) device tensor (npts values for one field), pts (npts, d), out size() values: nfields stacked fields, written,
         or added to with accumulate=True.  delta=True divides by the Clenshaw-Curtis weights of the nodes, so that
         ChebModal.integrate(out, phi) is sum_p s_p phi(x_p): a point source of strength s.  Results repeat bit for bit; a NaN
-        coordinate makes every field NaN, a NaN strength its own field only."""
+        coordinate makes every field NaN, a NaN strength its own field only.  deriv: d flags, 0 or 1: the flagged directions take
+        their derivative rows, the transpose of eval(deriv=...) (cheb_points_spread_deriv) -- a force dipole; None is the plain call."""
         import torch
         d = len(self.dims)
         if pts.dim() != 2 or pts.shape[1] != d:
@@ -743,8 +814,12 @@ class ChebPoints(_Handle):
                 raise ValueError("accumulate=True needs the array to add to (out)")
             out = torch.empty(self.size(), dtype=torch.float64, device=pts.device)
         flags = (1 if accumulate else 0) | (2 if delta else 0)                     # CHEB_SPREAD_ACCUMULATE, CHEB_SPREAD_DELTA
-        _chk(lib().cheb_points_spread(self._h, _dev_ptr(s, self.nfields * npts) if npts else None,
-                                      _dev_ptr(pts, npts * d) if npts else None, npts, _dev_ptr(out, self.size()), flags, _stream()))
+        dv = self._deriv(deriv)
+        sp_, xp_ = (_dev_ptr(s, self.nfields * npts), _dev_ptr(pts, npts * d)) if npts else (None, None)
+        if dv is not None:
+            _chk(lib().cheb_points_spread_deriv(self._h, sp_, xp_, npts, dv, _dev_ptr(out, self.size()), flags, _stream()))
+        else:
+            _chk(lib().cheb_points_spread(self._h, sp_, xp_, npts, _dev_ptr(out, self.size()), flags, _stream()))
         return out
 
     def spread_pass(self):
@@ -759,10 +834,11 @@ class ChebPoints(_Handle):
         _chk(lib().cheb_points_grid_reserve(self._h, _ints(m_max)))
         self._reserved = m_max
 
-    def eval_grid(self, u, coords, out=None):
+    def eval_grid(self, u, coords, out=None, deriv=None):
         """The fields on the tensor grid coords[0] x .. x coords[d-1] (one 1-d device tensor of coordinates per direction): a device
         tensor of shape (nfields, len(coords[0]), .., len(coords[d-1])).  Without an earlier reserve_grid the buffers are
-        reserved for this grid's size; a grid larger than the reserved one is refused."""
+        reserved for this grid's size; a grid larger than the reserved one is refused.  deriv: d flags, 0 or 1: the derivative along
+        the flagged directions instead (cheb_points_eval_grid_deriv); None is the plain call."""
         import torch
         if len(coords) != len(self.dims):
             raise ValueError("coords: expected %d coordinate arrays" % len(self.dims))
@@ -775,8 +851,12 @@ class ChebPoints(_Handle):
         if out is None:
             out = torch.empty((self.nfields,) + m, dtype=torch.float64, device=u.device)
         xs = torch.cat([c.reshape(-1) for c in coords]) if len(coords) > 1 else coords[0].reshape(-1).contiguous()
-        _chk(lib().cheb_points_eval_grid(self._h, _dev_ptr(u, self.size()), _dev_ptr(xs, sum(m)) if sum(m) else None, _ints(m),
-                                         _dev_ptr(out, nout) if nout else None, _stream()))
+        dv = self._deriv(deriv)
+        args = (self._h, _dev_ptr(u, self.size()), _dev_ptr(xs, sum(m)) if sum(m) else None, _ints(m))
+        if dv is not None:
+            _chk(lib().cheb_points_eval_grid_deriv(*args, dv, _dev_ptr(out, nout) if nout else None, _stream()))
+        else:
+            _chk(lib().cheb_points_eval_grid(*args, _dev_ptr(out, nout) if nout else None, _stream()))
         return out
 
 

@@ -1044,6 +1044,42 @@ void points_matrix_host(int n, int m, const double *x, double *R) {
   }
 }
 
+// Rows of the interpolant's derivative, l'_j(x) = d l_j / dx (cheb_points_dmatrix_host; the device twin is k_points_drows).  With
+// c_j = w_j / w_s, q_j = c_j / d_j, r_j = q_j d_s (j != s), R = 1 + sum r_j, Q2 = sum q_k / d_k, T = sum q_k (x_s - x_k) / d_k, the
+// sums over k != s in ascending k:
+//   l'_j = (q_j / R) ((1 + d_s^2 Q2) / R - d_s / d_j)   (j != s),     l'_s = -T / R^2
+// the exact derivative of the rational function points_row_ld evaluates.  Nothing divides by d_s; d_s == 0 gives l'_j = q_j,
+// l'_s = -sum q_k, a row of the differentiation matrix on the double nodes.  Long double on the DOUBLE node table, rounded once;
+// a NaN or infinite coordinate: a row of NaN.
+void points_dmatrix_host(int n, int m, const double *x, double *R) {
+  const int N = n - 1;
+  std::vector<double> xn(n);
+  points_nodes_host(n, xn.data());
+  std::vector<long double> q(n);
+  for (int t = 0; t < m; t++) {
+    double *row = R + (size_t)t * n;
+    if (!std::isfinite(x[t])) { for (int j = 0; j < n; j++) row[j] = std::numeric_limits<double>::quiet_NaN(); continue; }
+    const long double xt = x[t];
+    int s = 0;
+    long double best = fabsl(xt - (long double)xn[0]);
+    for (int j = 1; j < n; j++) { const long double a = fabsl(xt - (long double)xn[j]); if (a < best) { best = a; s = j; } }
+    const long double xs = xn[s], ds = xt - xs, hs = (s == 0 || s == N) ? 0.5L : 1.0L;
+    long double Rs = 0.0L, Q2 = 0.0L, T = 0.0L;
+    for (int j = 0; j < n; j++) {
+      if (j == s) continue;
+      const long double hj = (j == 0 || j == N) ? 0.5L : 1.0L, dj = xt - (long double)xn[j];
+      q[j] = (((j - s) & 1) ? -hj : hj) / hs / dj;
+      Rs += q[j] * ds;
+      Q2 += q[j] / dj;
+      T += q[j] * (xs - (long double)xn[j]) / dj;
+    }
+    Rs = 1.0L + Rs;
+    const long double g0 = (1.0L + ds * ds * Q2) / Rs;
+    for (int j = 0; j < n; j++)
+      row[j] = j == s ? (double)(-T / (Rs * Rs)) : (double)(q[j] / Rs * (g0 - ds / (xt - (long double)xn[j])));
+  }
+}
+
 // Weight vectors of the partial contractions (cheb_reduce_*, reduce.hip): what one contracted direction of n points is summed
 // against.  INTEGRAL: modal_weights_host; MEAN: half of it (the interval has length 2; the halving is exact); NODE j: the unit
 // vector e_j; DNODE j: row j of D_n; POINT x: the row of points_matrix_host; DPOINT x: r(x)^T D_n, r the long double row on the

@@ -32,6 +32,12 @@
 // to what `out` holds (later passes, CHEB_SPREAD_ACCUMULATE), after multiplying by the inverse Clenshaw-Curtis weights
 // (v iw_0[i_0]) (iw_1[i_1] (.. iw_{d-1}[i_{d-1}])) under CHEB_SPREAD_DELTA.  No atomics: every element of `out` belongs to one lane,
 // and the order of its additions depends on (dims, nfields, npts, pass size) alone.
+//
+// First derivatives are another row per direction (k_points_drows: the derivative of the same rational function, by a formula that
+// never divides by d_s).  cheb_points_eval_deriv / _spread_deriv / _eval_grid_deriv run the pipelines above with the flagged
+// directions' rows exchanged; without a flagged direction they launch k_points_rows and give the plain calls' bits.
+// cheb_points_eval_grad takes every first derivative of a chunk of C / 2 points from ONE direction-0 line product over the stacked
+// value and derivative rows, [field][2 cnt][i_1 .. i_{d-1}], and one launch of k_points_contract_grad over the blocks it writes.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
@@ -103,6 +109,79 @@ __global__ __launch_bounds__(256) void k_points_rows(const RowsJob g) {
     out[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : entry(j) / sum;
 }
 
+// one launch of k_points_drows: the job of k_points_rows, and per direction what to write: 1 the value rows into r.R, 2 the
+// derivative rows into D, 3 both
+struct DRowsJob {
+  RowsJob r;
+  int what[MD];
+  double *D[MD];
+};
+
+// k_points_rows and the rows of the interpolant's derivative, l'_j(x) = d l_j / dx.  With c_j = w_j / w_s, q_j = c_j / d_j (j != s),
+// R = 1 + sum r_j (the value rows' normalising sum), Q2 = sum q_k / d_k and T = sum q_k ((x_s - x_k) / d_k), all sums over k != s:
+//   l'_j = (q_j / R) ((1 + d_s^2 Q2) / R - d_s / d_j)   (j != s),     l'_s = -T / R^2
+// Nothing divides by d_s; d_s == 0 gives R = 1, (x_s - x_k) / d_k = 1 exactly and the row l'_j = q_j, l'_s = -sum q_k of the
+// differentiation matrix by the same instructions.  The same lane groups, nearest-node reduction and butterflies as k_points_rows;
+// the value rows are formed by the same expressions in the same order.
+__global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
+  const int k = blockIdx.y, n = g.r.n[k], N = n - 1, lg = g.r.lg[k], what = g.what[k];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
+  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
+  const bool ok = row < g.r.m[k];
+  const double *__restrict__ xn = g.r.nodes[k];
+  const double x = ok ? g.r.x[k][(size_t)row * (size_t)g.r.stride[k]] : 0.0;
+
+  // the nearest node, the lowest index on a tie
+  double best = INFINITY;
+  int s = 0x7fffffff;
+  for (int j = l; j < n; j += G) { const double a = fabs(x - xn[j]); if (a < best) { best = a; s = j; } }
+  for (int mm = 1; mm < G; mm <<= 1) {
+    const double ob = __shfl_xor(best, mm);
+    const int os = __shfl_xor(s, mm);
+    if (ob < best || (ob == best && os < s)) { best = ob; s = os; }
+  }
+  const bool fin = fabs(x) < INFINITY;                     // (false for a NaN as well)
+  if (!fin) s = 0;
+  const double xs = xn[s], ds = x - xs, ihs = (s == 0 || s == N) ? 2.0 : 1.0;
+  auto coef = [&](int j) -> double {                       // w_j / w_s
+    const double hj = (j == 0 || j == N) ? 0.5 : 1.0;
+    return (((j - s) & 1) ? -hj : hj) * ihs;
+  };
+  auto entry = [&](int j) -> double {
+    if (j == s) return 1.0;
+    return coef(j) * (ds / (x - xn[j]));
+  };
+  double sum = 0.0;
+  for (int j = l; j < n; j += G) sum += entry(j);
+  for (int mm = 1; mm < G; mm <<= 1) sum += __shfl_xor(sum, mm);
+  double q2 = 0.0, t = 0.0;
+  if (what & 2) {
+    for (int j = l; j < n; j += G)
+      if (j != s) {
+        const double dj = x - xn[j], q = coef(j) / dj;
+        q2 += q / dj;
+        t += q * ((xs - xn[j]) / dj);
+      }
+    for (int mm = 1; mm < G; mm <<= 1) { q2 += __shfl_xor(q2, mm); t += __shfl_xor(t, mm); }
+  }
+  if (!ok) return;
+  if (what & 1) {
+    double *__restrict__ out = g.r.R[k] + (size_t)row * (size_t)n;
+    for (int j = l; j < n; j += G)
+      out[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : entry(j) / sum;
+  }
+  if (what & 2) {
+    double *__restrict__ out = g.D[k] + (size_t)row * (size_t)n;
+    const double g0 = (1.0 + ds * ds * q2) / sum, ls = -t / (sum * sum);
+    for (int j = l; j < n; j += G) {
+      double v = ls;
+      if (j != s) { const double dj = x - xn[j]; v = (coef(j) / dj) / sum * (g0 - ds / dj); }
+      out[j] = fin ? v : __builtin_nan("");
+    }
+  }
+}
+
 // the pair (j, j + 1) of a row; the second value is 0 past the end of the row
 __device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
   if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
@@ -163,6 +242,106 @@ __global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const do
     for (int q = 1; q < nw; q++) s += red[q];
     out[(size_t)f * npts + p] = s;
   }
+}
+
+struct GradArgs {
+  const double *rows;                // direction k's value rows at rows + P off[k], its derivative rows H n_k values further
+  unsigned P, H;
+  const double *V, *D;               // direction 0's value and derivative blocks, (f, p) at ((f bs) + p) B; D null: none
+  unsigned bs;                       // blocks per field
+  double *out;                       // component c of (f, p) at out[(f nc + c) npts + p]
+  size_t npts;
+  int nc;                            // components per field
+  unsigned mask;                     // sums to store: bit k < d the derivative along k, bit d the value sum of V
+  int vdst;                          // the component the value sum of V goes to
+  double scale[MD + 1];              // per component, multiplied at the store
+};
+
+// The gradient of k_points_contract's sum: workgroup (p, f, 0) walks the value block V once, forming per block row
+// s = sum_j l_{d-1}[j] v and s' = sum_j l'_{d-1}[j] v; the value takes w s, the last direction's derivative w s', a middle direction's
+// w_k s with w the product of the middle directions' value entries and w_k the same product with direction k's derivative entry.
+// Workgroup (p, f, 1) walks the derivative block D once for direction 0's derivative, w sum_j l_{d-1}[j] v: the value sum of that
+// block (two workgroups a point: at 256^3 a chunk of 64 points is 64 MiB of blocks, which 64 workgroups read at half the rate
+// 128 do).  The pair loads, the lanes' and the waves' order are k_points_contract's.  With bit d alone in the mask and D null this
+// is k_points_contract with a scale and a component stride.
+template <int DC>
+__global__ __launch_bounds__(256) void k_points_contract_grad(const PtGeo g, const GradArgs a) {
+  constexpr int NA = (DC ? DC : MD) + 1;
+  __shared__ double swl[1024], swd[1024];
+  __shared__ double red[4][NA];
+  const int d = DC ? DC : g.d;
+  const unsigned n = (unsigned)g.n[d - 1];
+  const unsigned p = blockIdx.x, f = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
+  const bool second = blockIdx.z != 0;
+  const unsigned mask = second ? (a.mask & 1u) << d : a.D ? a.mask & ~1u : a.mask;
+  const int vdst = second ? 0 : a.vdst;
+  const bool derivs = (mask & ((1u << d) - 2u)) != 0;      // any of directions 1 .. d - 1
+  const double *rl = a.rows + (size_t)a.P * g.off[d - 1] + (size_t)p * n;
+  for (unsigned j = tid; j < n; j += blockDim.x) { swl[j] = rl[j]; swd[j] = derivs ? rl[(size_t)a.H * n + j] : 0.0; }
+  __syncthreads();
+  const unsigned lpr = 1u << g.lg, rpw = 64u >> g.lg, grp = (unsigned)lane >> g.lg, l = (unsigned)lane & (lpr - 1);
+  const double *bv = (second ? a.D : a.V) + ((size_t)f * a.bs + p) * g.B;
+  double acc[NA];
+#pragma unroll
+  for (int c = 0; c < NA; c++) acc[c] = 0.0;
+  for (unsigned r = (unsigned)wv * rpw + grp; r < g.rpb; r += (unsigned)nw * rpw) {
+    double wr = 1.0, wk[NA];                               // wk[m]: the weight with direction m's derivative entry, 1 <= m <= d - 2
+    if (DC == 3) {
+      wr = a.rows[(size_t)a.P * g.off[1] + (size_t)p * g.n[1] + r];
+      wk[1] = derivs ? a.rows[(size_t)a.P * g.off[1] + (size_t)(a.H + p) * g.n[1] + r] : 0.0;
+    }
+    if (DC == 0) {
+      unsigned q = r;
+#pragma unroll
+      for (int m = 1; m < MD; m++) wk[m] = 1.0;
+      for (int m = d - 2; m >= 1; m--) {
+        const unsigned nm = (unsigned)g.n[m], i = m > 1 ? q % nm : q;
+        q /= nm;
+        const size_t e = (size_t)a.P * g.off[m] + (size_t)p * nm + i;
+        const double lv = a.rows[e], ld = derivs ? a.rows[e + (size_t)a.H * nm] : 0.0;
+        wr *= lv;
+#pragma unroll
+        for (int c = 1; c < MD - 1; c++)
+          if (c < d - 1) wk[c] *= c == m ? ld : lv;
+      }
+    }
+    const double *pr = bv + (size_t)r * n;
+    const bool al = ((size_t)pr & 15) == 0;
+    double s = 0.0, sd = 0.0;
+    for (unsigned j = 2 * l; j < n; j += 2 * lpr) {
+      const d2 v = load_pair(pr, al, j, n);
+      s += swl[j] * v.x + (j + 1 < n ? swl[j + 1] : 0.0) * v.y;
+      sd += swd[j] * v.x + (j + 1 < n ? swd[j + 1] : 0.0) * v.y;
+    }
+    acc[NA - 1] += wr * s;                                 // the block's value sum; acc[c], 1 <= c < d: the derivative along c
+#pragma unroll
+    for (int c = 1; c < NA - 1; c++)
+      if (c < d) acc[c] += c == d - 1 ? wr * sd : wk[c] * s;
+  }
+#pragma unroll
+  for (int c = 0; c < NA; c++) {
+    const double s = wave_sum(acc[c]);
+    if (lane == 0) red[wv][c] = s;
+  }
+  __syncthreads();
+  if (tid <= d && ((mask >> tid) & 1u)) {
+    const int slot = tid == d ? NA - 1 : tid, c = tid == d ? vdst : tid;
+    double s = red[0][slot];
+    for (int q = 1; q < nw; q++) s += red[q][slot];
+    a.out[((size_t)f * a.nc + c) * a.npts + p] = s * a.scale[c];
+  }
+}
+
+// d = 1: the line product's two outputs are the result; W[f][p] the values, W[f][cnt + p] the derivatives of a chunk
+__global__ __launch_bounds__(256) void k_points_grad1(const double *__restrict__ W, unsigned cnt, unsigned nf, int value, double s0,
+                                                      double *__restrict__ out, size_t npts) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= cnt * nf) return;
+  const unsigned f = i / cnt, p = i - f * cnt;
+  const int nc = value ? 2 : 1;
+  out[((size_t)f * nc) * npts + p] = W[(size_t)f * 2 * cnt + cnt + p] * s0;
+  if (value) out[((size_t)f * nc + 1) * npts + p] = W[(size_t)f * 2 * cnt + p];
 }
 
 // LDS layout of k_points_spread's matrix chunk: Rt[k][point], the way the rows arrive (contiguous in the point of direction 0);
@@ -333,6 +512,38 @@ int launch_rows(const RowsJob &job, hipStream_t st, const char *what) {
   return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s rows launch: %s", what, hipGetErrorString(e));
 }
 
+int launch_drows(const DRowsJob &job, hipStream_t st, const char *what) {
+  unsigned gx = 0;
+  for (int k = 0; k < job.r.nd; k++) {
+    const unsigned rpb = 4u * (64u >> job.r.lg[k]);
+    gx = std::max(gx, (job.r.m[k] + rpb - 1) / rpb);
+  }
+  if (gx == 0) return 0;
+  hipLaunchKernelGGL(k_points_drows, dim3(gx, (unsigned)job.r.nd), dim3(256), 0, st, job);
+  sweep_note_launch();
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s derivative rows launch: %s", what, hipGetErrorString(e));
+}
+
+// The rows of one chunk, pass or grid.  Without a derivative direction this is today's k_points_rows launch; otherwise
+// k_points_drows writes a flagged direction's derivative rows where its value rows would go.
+int launch_rows_deriv(const RowsJob &job, const int *deriv, hipStream_t st, const char *what) {
+  bool any = false;
+  for (int k = 0; deriv && k < job.nd; k++) any = any || deriv[k];
+  if (!any) return launch_rows(job, st, what);
+  DRowsJob dj{};
+  dj.r = job;
+  for (int k = 0; k < job.nd; k++) { dj.what[k] = deriv[k] ? 2 : 1; dj.D[k] = job.R[k]; }
+  return launch_drows(dj, st, what);
+}
+
+// a multi-index of first derivatives: d host ints, each 0 or 1; NULL = all zero
+int check_deriv(int d, const int *deriv, const char *what) {
+  for (int k = 0; deriv && k < d; k++)
+    if (deriv[k] != 0 && deriv[k] != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: deriv[%d] = %d must be 0 or 1", what, k, deriv[k]);
+  return 0;
+}
+
 }  // namespace
 
 struct cheb_points {
@@ -453,7 +664,31 @@ extern "C" int cheb_points_rows(cheb_points *h, int k, const double *x, long m, 
   return launch_rows(job, (hipStream_t)stream, "points");
 }
 
-extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *xi, long npts, double *out, void *stream) {
+extern "C" int cheb_points_drows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
+  if (m < 0 || m >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %ld must be in 0..2^31-1", m);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  DRowsJob job{};
+  const int n = h->geo.n[k];
+  job.r.nd = 1; job.r.n[0] = n; job.r.lg[0] = rows_lg(n); job.r.m[0] = (unsigned)m; job.r.stride[0] = 1;
+  job.r.x[0] = x; job.r.nodes[0] = h->nodes[n]; job.what[0] = 2; job.D[0] = R;
+  return launch_drows(job, (hipStream_t)stream, "points");
+}
+
+extern "C" int cheb_points_dmatrix_host(int n, int m, const double *x, double *R) {
+  int rc;
+  if ((rc = check_extent(n))) return rc;
+  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  points_dmatrix_host(n, m, x, R);
+  return 0;
+}
+
+namespace {
+int eval_run(cheb_points *h, const double *u, const double *xi, long npts, const int *deriv, double *out, void *stream) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
   if (npts == 0) return 0;
@@ -472,7 +707,7 @@ extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *x
       job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
       job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->rows + (size_t)C * g.off[k];
     }
-    if ((rc = launch_rows(job, st, "eval"))) return rc;
+    if ((rc = launch_rows_deriv(job, deriv, st, "eval"))) return rc;
     // d == 1: the line product's [field][point] is the result where it is one chunk or one field
     const bool direct = d == 1 && (h->nf == 1 || cnt == npts);
     ResampleDir p{h->rows, u, direct ? out + p0 : h->W, (unsigned)h->nf, (unsigned)g.n[0], cnt, g.B, (unsigned)h->nf * g.B};
@@ -493,6 +728,106 @@ extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *x
     sweep_note_launch();
     e = hipGetLastError();
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval contraction launch: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int cheb_points_eval(cheb_points *h, const double *u, const double *xi, long npts, double *out, void *stream) {
+  return eval_run(h, u, xi, npts, nullptr, out, stream);
+}
+
+extern "C" int cheb_points_eval_deriv(cheb_points *h, const double *u, const double *xi, long npts, const int *deriv, double *out,
+                                      void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  int rc;
+  if ((rc = check_deriv(h->d, deriv, "eval_deriv"))) return rc;
+  return eval_run(h, u, xi, npts, deriv, out, stream);
+}
+
+namespace {
+void grad_contract_launch(int d, dim3 grid, dim3 block, hipStream_t st, const PtGeo &g, const GradArgs &a) {
+#define POINTS_GRAD(DC) hipLaunchKernelGGL(k_points_contract_grad<DC>, grid, block, 0, st, g, a)
+  switch (d) { case 2: POINTS_GRAD(2); break; case 3: POINTS_GRAD(3); break; default: POINTS_GRAD(0); }
+#undef POINTS_GRAD
+  sweep_note_launch();
+}
+}  // namespace
+
+extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const double *xi, long npts, const double *scale, int flags,
+                                     double *out, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
+  if (flags & ~CHEB_POINTS_GRAD_VALUE) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grad: unknown flags %d", flags);
+  const int d = h->d, value = (flags & CHEB_POINTS_GRAD_VALUE) ? 1 : 0, nc = d + value;
+  for (int k = 0; scale && k < d; k++)
+    if (!std::isfinite(scale[k])) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grad: scale[%d] is not finite", k);
+  if (npts == 0) return 0;
+  if (!u || !xi || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (overlap(u, h->total, out, (long)h->nf * nc * npts)) return chebhip_fail(CHEBHIP_ERR_ARG, "eval_grad: fields and output must not overlap");
+  hipStream_t st = (hipStream_t)stream;
+  const PtGeo &g = h->geo;
+  const long C = h->C, H = C / 2;                          // a gradient chunk: half an eval chunk, two row sets and two blocks a point
+  const unsigned nf = (unsigned)h->nf;
+  int rc;
+  GradArgs a{};
+  a.rows = h->rows; a.out = out; a.npts = (size_t)npts; a.nc = nc;
+  for (int k = 0; k <= MD; k++) a.scale[k] = (scale && k < d) ? scale[k] : 1.0;
+  const dim3 block(g.B <= 1024 ? 64 : 256);
+
+  if (H == 0) {
+    // The work memory holds one point's value rows and one block (a first direction of two nodes under fields of 32 MiB or
+    // more): a point takes one pass of the eval pipeline per component, the rows of direction c exchanged for its derivative
+    // rows, and the contraction stores the value sum as component c.
+    a.P = 1; a.H = 0; a.V = h->W; a.D = nullptr; a.bs = 1; a.mask = 1u << d;
+    for (long p = 0; p < npts; p++)
+      for (int c = 0; c < nc; c++) {
+        DRowsJob job{};
+        job.r.nd = d;
+        for (int k = 0; k < d; k++) {
+          job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = 1; job.r.stride[k] = d;
+          job.r.x[k] = xi + (size_t)p * d + k; job.r.nodes[k] = h->nodes[g.n[k]];
+          job.r.R[k] = job.D[k] = h->rows + g.off[k]; job.what[k] = k == c ? 2 : 1;
+        }
+        if ((rc = launch_drows(job, st, "eval_grad"))) return rc;
+        ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 1u, g.B, nf * g.B};
+        hipError_t e = resample_launch(lp, st);
+        if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
+        a.out = out + p; a.vdst = c;
+        grad_contract_launch(d, dim3(1, nf), block, st, g, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
+      }
+    return 0;
+  }
+
+  a.P = (unsigned)(2 * H); a.H = (unsigned)H; a.mask = ((1u << d) - 1u) | (value ? 1u << d : 0u); a.vdst = d;
+  for (long p0 = 0; p0 < npts; p0 += H) {
+    const unsigned cnt = (unsigned)std::min(H, npts - p0);
+    // direction 0: cnt value rows, then cnt derivative rows, one matrix of 2 cnt rows; direction k >= 1: its value rows at
+    // rows + 2 H off[k], its derivative rows H n_k values further
+    DRowsJob job{};
+    job.r.nd = d;
+    for (int k = 0; k < d; k++) {
+      job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = cnt; job.r.stride[k] = d;
+      job.r.x[k] = xi + (size_t)p0 * d + k; job.r.nodes[k] = h->nodes[g.n[k]]; job.what[k] = 3;
+      job.r.R[k] = h->rows + (size_t)(2 * H) * g.off[k];
+      job.D[k] = job.r.R[k] + (size_t)(k == 0 ? cnt : H) * g.n[k];
+    }
+    if ((rc = launch_drows(job, st, "eval_grad"))) return rc;
+    ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 2 * cnt, g.B, nf * g.B};
+    hipError_t e = resample_launch(lp, st);
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
+    if (d == 1) {
+      hipLaunchKernelGGL(k_points_grad1, dim3((cnt * nf + 255) / 256), dim3(256), 0, st, h->W, cnt, nf, value, a.scale[0], out + p0,
+                         (size_t)npts);
+      sweep_note_launch();
+    } else {
+      a.V = h->W; a.D = h->W + (size_t)cnt * g.B; a.bs = 2 * cnt; a.out = out + p0;
+      grad_contract_launch(d, dim3(cnt, nf, 2), block, st, g, a);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
   }
   return 0;
 }
@@ -533,7 +868,8 @@ void spread_launch(int d, const PtGeo &g, const SpreadArgs &a, hipStream_t st) {
 
 extern "C" long cheb_points_spread_pass(const cheb_points *h) { return h ? spread_pass(h).P : -1; }
 
-extern "C" int cheb_points_spread(cheb_points *h, const double *s, const double *xi, long npts, double *out, int flags, void *stream) {
+namespace {
+int spread_run(cheb_points *h, const double *s, const double *xi, long npts, const int *deriv, double *out, int flags, void *stream) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (npts < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "npts = %ld is negative", npts);
   if (flags & ~(CHEB_SPREAD_ACCUMULATE | CHEB_SPREAD_DELTA)) return chebhip_fail(CHEBHIP_ERR_ARG, "spread: unknown flags %d", flags);
@@ -561,7 +897,7 @@ extern "C" int cheb_points_spread(cheb_points *h, const double *s, const double 
       job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
       job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = sp.buf + (size_t)sp.P * g.off[k];
     }
-    if ((rc = launch_rows(job, st, "spread"))) return rc;
+    if ((rc = launch_rows_deriv(job, deriv, st, "spread"))) return rc;
     const SpreadArgs a{sp.buf, s + p0, (flags & CHEB_SPREAD_DELTA) ? h->iw : nullptr, out, (size_t)npts,
                        (unsigned)sp.P, cnt, (unsigned)h->nf * g.B, g.B, (accumulate || p0 > 0) ? 1 : 0};
     if (g.n[0] > 64) spread_launch<128>(d, g, a, st); else spread_launch<64>(d, g, a, st);
@@ -570,6 +906,19 @@ extern "C" int cheb_points_spread(cheb_points *h, const double *s, const double 
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "spread launch: %s", hipGetErrorString(e));
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int cheb_points_spread(cheb_points *h, const double *s, const double *xi, long npts, double *out, int flags, void *stream) {
+  return spread_run(h, s, xi, npts, nullptr, out, flags, stream);
+}
+
+extern "C" int cheb_points_spread_deriv(cheb_points *h, const double *s, const double *xi, long npts, const int *deriv, double *out,
+                                        int flags, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  int rc;
+  if ((rc = check_deriv(h->d, deriv, "spread_deriv"))) return rc;
+  return spread_run(h, s, xi, npts, deriv, out, flags, stream);
 }
 
 extern "C" int cheb_points_grid_reserve(cheb_points *h, const int *m_max) {
@@ -594,7 +943,8 @@ extern "C" int cheb_points_grid_reserve(cheb_points *h, const int *m_max) {
   return 0;
 }
 
-extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const double *coords, const int *m, double *out, void *stream) {
+namespace {
+int grid_run(cheb_points *h, const double *u, const double *coords, const int *m, const int *deriv, double *out, void *stream) {
   if (!h || !m) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   const int d = h->d;
   const PtGeo &g = h->geo;
@@ -616,7 +966,7 @@ extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const doub
     job.x[k] = coords + co; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->grows + h->goff[k];
   }
   int rc;
-  if ((rc = launch_rows(job, st, "eval_grid"))) return rc;
+  if ((rc = launch_rows_deriv(job, deriv, st, "eval_grid"))) return rc;
   int order[MD];
   long cur[MD];
   for (int k = 0; k < d; k++) { order[k] = k; cur[k] = g.n[k]; }
@@ -625,4 +975,17 @@ extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const doub
   for (int s = 0; s < d; s++) steps[s] = LineStep{order[s], h->grows + h->goff[order[s]], m[order[s]]};
   hipError_t e = line_chain(d, cur, h->nf, 1, d, steps, u, out, h->gwork, st);
   return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grid launch: %s", hipGetErrorString(e));
+}
+}  // namespace
+
+extern "C" int cheb_points_eval_grid(cheb_points *h, const double *u, const double *coords, const int *m, double *out, void *stream) {
+  return grid_run(h, u, coords, m, nullptr, out, stream);
+}
+
+extern "C" int cheb_points_eval_grid_deriv(cheb_points *h, const double *u, const double *coords, const int *m, const int *deriv,
+                                           double *out, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = check_deriv(h->d, deriv, "eval_grid_deriv"))) return rc;
+  return grid_run(h, u, coords, m, deriv, out, stream);
 }

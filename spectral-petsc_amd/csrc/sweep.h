@@ -129,6 +129,7 @@ void dealias_matrix_host(int n, int m, int which, double *A);
 // once), and the m x n barycentric rows of m coordinates in long double on that double table, rounded once.
 void points_nodes_host(int n, double *x);
 void points_matrix_host(int n, int m, const double *x, double *R);
+void points_dmatrix_host(int n, int m, const double *x, double *R);
 // Host side of the partial contractions (reduce.hip; the extent is checked there): the n weights one contracted direction is
 // summed against, long double rounded once.  The kinds are CHEB_W_* of include/chebhip.h; arg is the node index j (NODE, DNODE)
 // or the coordinate x (POINT, DPOINT).  0, or 1: unknown kind, 2: j is no index of the line.

@@ -467,11 +467,33 @@ def point_sources(sp, dims, pts, strengths, out=None):
     return g.view((nf,) + dims)
 
 
-def sample_plane(sp, dims, u_full, axis, coord, m=None):
+def velocity_gradient(sp, dims, vel_full, pts, scale=None):
+    """The velocity-gradient tensor A[p][i][j] = d u_i / d x_j at the points pts (an (npts, d) device tensor of reference
+    coordinates) of the d stacked full-grid components vel_full (d prod(dims) values, component-major): one ChebPoints.eval_grad.
+    scale: the d factors 2 / L_k of a box (None: the reference cube).  Returns an (npts, d, d) device tensor."""
+    dims = tuple(int(n) for n in dims)
+    d = len(dims)
+    size = d
+    for n in dims:
+        size *= n
+    if vel_full.numel() != size:
+        raise ValueError("vel_full: expected %d stacked components of prod(dims) values, got %d values" % (d, vel_full.numel()))
+    h = sp.ChebPoints(dims, d)
+    try:
+        out = h.eval_grad(vel_full.reshape(-1), pts, scale=scale)
+        torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
+    finally:
+        h.destroy()
+    return out.permute(2, 0, 1).contiguous()
+
+
+def sample_plane(sp, dims, u_full, axis, coord, m=None, deriv=None):
     """The plane x_axis = coord of the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields if it
     holds a multiple of prod(dims) values): one ChebPoints.eval_grid with a single coordinate along `axis`.  The other directions
     keep their CGL nodes (m = None) or take m uniform points from -1 to +1 each.  Returns a device tensor of shape
-    (nfields, points of the other directions ...), the direction `axis` dropped."""
+    (nfields, points of the other directions ...), the direction `axis` dropped.  deriv: one flag (0 or 1) per direction: the
+    derivative along the flagged directions with respect to the reference coordinates instead of the value (a vorticity cut is two
+    such planes)."""
     dims = tuple(int(n) for n in dims)
     axis = int(axis)
     if not 0 <= axis < len(dims):
@@ -493,7 +515,7 @@ def sample_plane(sp, dims, u_full, axis, coord, m=None):
             coords.append(torch.linspace(-1.0, 1.0, int(m), dtype=torch.float64, device=dev))
     pts = sp.ChebPoints(dims, nf)
     try:
-        out = pts.eval_grid(u_full.reshape(-1), coords)
+        out = pts.eval_grid(u_full.reshape(-1), coords, deriv=deriv)
         torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
     finally:
         pts.destroy()
