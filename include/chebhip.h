@@ -844,6 +844,32 @@ int chebhip_fdpc_apply(void *pc, const double *r_dev, double *z_dev, void *strea
 /* The same for a Stokes velocity preconditioner (stokes_pc_create*) on component-major vectors (stokes_op_mult_vv_cm): the fast
  * diagonalisation z = P_1^-1 (r / eta) (sweeps = 0) only. */
 int chebhip_fdpc_apply_cm(void *pc, const double *r_cm_dev, double *z_cm_dev, void *stream);
+/* The steps of the fast-diagonalisation solve (sweeps = 0), one at a time, for tests: the solve itself is a sequence of these
+ * calls.  x, y: nf stacked interior fields (component-major on a Stokes handle), distinct (SCALE alone works in place and takes
+ * y == x).  A step takes exactly the route the solve takes for this handle, direction k, these arrays and the current options; a
+ * mode the solve does not take there is CHEBHIP_ERR_ARG and nothing runs (ZSOLVE on an odd line, on a line outside 66..128
+ * points, on a line whose ends differ or under option "fdm_z_separate"; FORWARD on the direction that divides by eta; ...).
+ * Slab handles: CHEBHIP_ERR_ARG.  Order of a solve: FORWARD_OVER_ETA (a handle with an operator; a Stokes handle's node-major
+ * apply divides while it pulls the components apart and runs FORWARD) or FORWARD along 0, FORWARD along 1 .. d-2, then along d-1
+ * either FORWARD_SCALED, or FORWARD and SCALE, or ZSOLVE (which is also the BACKWARD step of d-1); BACKWARD along the rest, d-1
+ * first. */
+enum { CHEBHIP_FDPC_STEP_FORWARD = 0, CHEBHIP_FDPC_STEP_FORWARD_OVER_ETA = 1, CHEBHIP_FDPC_STEP_FORWARD_SCALED = 2,
+       CHEBHIP_FDPC_STEP_ZSOLVE = 3, CHEBHIP_FDPC_STEP_SCALE = 4, CHEBHIP_FDPC_STEP_BACKWARD = 5 };
+int chebhip_fdpc_step(chebhip_fdpc *pc, int k, int mode, const double *x_dev, double *y_dev, void *stream);
+/* What runs for that step between the handle's own buffers (the arrays of a solve's inner steps), as CHEBHIP_FDPC_ROUTE_* bits;
+ * -1 where chebhip_fdpc_step would refuse.  Launches nothing.
+ *   RAW: one launch of the 16-byte kernels in a raw mode        TWO_LAUNCH: centro-symmetric plus centro-antisymmetric part
+ *   GENERAL: the general sweep kernel (with TWO_LAUNCH)         FUSED_MUL: the pointwise factor rides on the load / store
+ *   ETA_PASS: the separate division by eta runs first           ZSOLVE: k_fdm_zsolve16
+ *   SCALE3 / SCALE_GENERAL: which modal scaling pass            DENSE: one dense line product with S^-1 itself (the forward
+ *   transform where it cannot be one raw launch) */
+enum { CHEBHIP_FDPC_ROUTE_RAW = 1, CHEBHIP_FDPC_ROUTE_TWO_LAUNCH = 2, CHEBHIP_FDPC_ROUTE_GENERAL = 4, CHEBHIP_FDPC_ROUTE_FUSED_MUL = 8,
+       CHEBHIP_FDPC_ROUTE_ETA_PASS = 16, CHEBHIP_FDPC_ROUTE_ZSOLVE = 32, CHEBHIP_FDPC_ROUTE_SCALE3 = 64, CHEBHIP_FDPC_ROUTE_SCALE_GENERAL = 128,
+       CHEBHIP_FDPC_ROUTE_DENSE = 256 };
+int chebhip_fdpc_step_route(chebhip_fdpc *pc, int k, int mode);
+/* S, S^-1 and lam of the three-point line operator of the preconditioner for a line of P points, as cheb_helmholtz_line_host
+ * gives them for the spectral line: the same layout and mode order.  Needs no device. */
+int chebhip_fdpc_line_host(int P, double *S, double *Sinv, double *lam);
 /* The spectral kind of the same handle: z = (sigma I + A)^-1 (r / eta), exact in the constant-coefficient part (A as for
  * cheb_helmholtz).  chebhip_fdpc_update refreshes eta only; sweeps must stay 0 and chebhip_fdpc_mult is refused (no stencil).
  * A slab-mode operator is refused. */
@@ -873,6 +899,8 @@ long cheb_helmholtz_size(const cheb_helmholtz *h);                              
 /* S (nodal <- modal), S^-1 and lam of A_1 for a line of P points into HOST buffers (M = P - 2; S, Sinv M x M row-major, lam M);
  * needs no device.  Modes by parity: position p < ceil(M/2) the p-th even mode, M-1-q the q-th odd one, each by ascending lam. */
 int  cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *lam);          /* M = P - 2, row-major */
+/* The solve's own handle, owned by h (any kind of solver handle): for chebhip_fdpc_step / chebhip_fdpc_step_route only. */
+chebhip_fdpc *cheb_helmholtz_fdpc(cheb_helmholtz *h);
 
 /* The same solve with a condition alpha u + beta du/dnu = g on every face: Dirichlet (1, 0), Neumann (0, 1),  */
 /* Robin otherwise; du/dnu is the outward normal derivative.  An end whose row eliminates it from the collocation of      */
@@ -1038,11 +1066,13 @@ int stokes_saddle_iterations(const stokes_saddle *s, int which);
 /* ------------------------------------------------------------------------- */
 /* Run-time options: named integer switches, process-wide, read where they apply (the library never reads the
  * environment).  Unknown names are an error.  Set them before creating the handles they concern.
- *   general_kernels       1: every sweep runs the general 8-byte kernel (A/B against the 16-byte kernels)
+ *   general_kernels       1: every sweep runs the general 8-byte kernel (A/B against the 16-byte kernels); the preconditioner's
+ *                            forward line transforms then run as dense line products
  *   separate_launches     1: the d sweeps of a Stokes gradient / divergence are d launches instead of one
  *   vendor_gemm           1: plain sweeps of lines of more than 1024 points go to rocBLAS DGEMM (looked up at run time, never linked)
  *                            instead of the library's own FP64-VALU kernel.  Default 0: no vendor GEMM on any default path
- *   no_raw_transforms     1: the preconditioner's line transforms take two launches instead of one
+ *   no_raw_transforms     1: the preconditioner's line transforms run as a dense line product (forward) / two launches (backward)
+ *                            instead of one raw-mode launch
  *   equal_shares          1: multi-job launches give every job min(tiles, CUs) workgroups instead of proportional shares
  *   force_gemm            1: every extent of 4 .. 256 points takes the library-DGEMM route of the longest lines (read at operator create)
  *   stokes_single_stream  1: StokesMatMult / StokesFunction keep the pressure chain on the caller's stream, also on large grids off the

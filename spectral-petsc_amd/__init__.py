@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "chebhip_fgmres_iterations", "chebhip_fgmres_residual", "chebhip_fgmres_reason", "chebhip_fgmres_set_reduce",
     "ell_pc_create", "stokes_pc_create", "chebhip_fdpc_destroy", "chebhip_fdpc_update", "chebhip_fdpc_set_sweeps",
     "chebhip_fdpc_mult", "chebhip_fdpc_apply", "chebhip_fdpc_apply_cm",
+    "chebhip_fdpc_step", "chebhip_fdpc_step_route", "chebhip_fdpc_line_host", "cheb_helmholtz_fdpc",
     "stokes_saddle_create", "stokes_saddle_destroy", "stokes_saddle_set_type", "stokes_saddle_set_inner",
     "stokes_saddle_setup", "stokes_saddle_apply", "stokes_saddle_iterations", "stokes_saddle_set_pc_sweeps", "stokes_saddle_set_schur_jacobi",
     "chebhip_timers_enable", "chebhip_timers_reset", "chebhip_timers_read", "chebhip_stage_name",
@@ -257,6 +258,11 @@ def lib():
         L.cheb_helmholtz_size.argtypes = [vp]
         L.cheb_helmholtz_size.restype = C.c_long
         L.cheb_helmholtz_line_host.argtypes = [C.c_int, dp, dp, dp]
+        L.chebhip_fdpc_line_host.argtypes = [C.c_int, dp, dp, dp]
+        L.chebhip_fdpc_step.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+        L.chebhip_fdpc_step_route.argtypes = [vp, C.c_int, C.c_int]
+        L.cheb_helmholtz_fdpc.argtypes = [vp]
+        L.cheb_helmholtz_fdpc.restype = vp
         L.ell_pc_create_spectral.argtypes = [vp, C.c_double, C.POINTER(vp)]
         L.cheb_helmholtz_create_bc.argtypes = [C.c_int, ip, dp, C.c_double, C.c_int, C.POINTER(vp)]
         L.cheb_helmholtz_solve_bc.argtypes = [vp, vp, vp, vp, vp]
@@ -1328,6 +1334,44 @@ def helmholtz_line(P):
     return S, Si, lam
 
 
+def fdpc_line(P):
+    """(S, Sinv, lam) of the three-point line operator of the finite-difference preconditioner for a line of P points
+    (chebhip_fdpc_line_host): T = S diag(lam) S^-1, M = P - 2, the layout and mode order of helmholtz_line.  Needs no device."""
+    import numpy as np
+    M = max(int(P) - 2, 0)
+    S, Si, lam = np.empty((M, M)), np.empty((M, M)), np.empty(M)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+    _chk(lib().chebhip_fdpc_line_host(int(P), ptr(S), ptr(Si), ptr(lam)))
+    return S, Si, lam
+
+
+# the steps of the fast-diagonalisation solve (CHEBHIP_FDPC_STEP_*) and what runs for them (CHEBHIP_FDPC_ROUTE_*)
+FDPC_STEPS = {"forward": 0, "forward_over_eta": 1, "forward_scaled": 2, "zsolve": 3, "scale": 4, "backward": 5}
+FDPC_ROUTES = {"raw": 1, "two_launch": 2, "general": 4, "fused_mul": 8, "eta_pass": 16, "zsolve": 32, "scale3": 64, "scale_general": 128, "dense": 256}
+
+
+class _FdmSteps:
+    """step / step_route of the handles whose solve is the fast diagonalisation (chebhip_fdpc_step): one step of the solve along
+    direction k on the handle's stacked interior fields (component-major on a Stokes handle), by the very function the solve is made
+    of.  A mode the solve does not take on this handle raises ChebhipError (code 4)."""
+
+    def _fdpc(self):
+        return self._h
+
+    def _nstep(self):
+        return self.n
+
+    def step(self, k, mode, x, y):
+        n = self._nstep()
+        _chk(lib().chebhip_fdpc_step(self._fdpc(), int(k), FDPC_STEPS[mode], _dev_ptr(x, n), _dev_ptr(y, n), _stream()))
+        return y
+
+    def step_route(self, k, mode):
+        """The set of FDPC_ROUTES names of what that step runs between the handle's own buffers; None where step would refuse."""
+        r = lib().chebhip_fdpc_step_route(self._fdpc(), int(k), FDPC_STEPS[mode])
+        return None if r < 0 else frozenset(name for name, bit in FDPC_ROUTES.items() if r & bit)
+
+
 def _bc_spec(spec):
     """(alpha, beta) of one end: "dirichlet", "neumann" or a pair of numbers."""
     if isinstance(spec, str):
@@ -1399,7 +1443,7 @@ def _scale_array(scale, d):
     return sc, tuple(float(v) for v in sc)
 
 
-class HelmholtzSolver(_Handle):
+class HelmholtzSolver(_FdmSteps, _Handle):
     """u = (sigma I + A)^-1 f with A the EllipticOp operator at eta == 1 (zero Dirichlet values) by fast diagonalisation
     (cheb_helmholtz_*): `nfields` stacked interior fields of the grid `dims` per call; `size` values.  Usable as the M of
     Fgmres.solve.
@@ -1438,6 +1482,12 @@ class HelmholtzSolver(_Handle):
             self.singular = bool(lib().cheb_helmholtz_singular(h))
         self._h = h
         self.size = lib().cheb_helmholtz_size(h)
+
+    def _fdpc(self):
+        return lib().cheb_helmholtz_fdpc(self._h)
+
+    def _nstep(self):
+        return self.size
 
     def solve(self, f, u):
         """Asynchronous on torch's current stream; u may be f.  With bc: the interior problem with zero boundary data."""
@@ -1943,7 +1993,7 @@ def timers(enable=None, reset=False):
     return out
 
 
-class FdPc(_Handle):
+class FdPc(_FdmSteps, _Handle):
     """The finite-difference preconditioner of the reference on the device: FormJacobian's matrix P
     (elliptic.C:537-590) for an EllipticOp, MatVVPC (stokes.C:1160-1241) on velocity vectors for a StokesOp.
     `apply` is an approximate solve with P (fast diagonalisation + `sweeps` defect corrections); pass the object as
@@ -1982,7 +2032,7 @@ class FdPc(_Handle):
         return z
 
 
-class SpectralPc(_Handle):
+class SpectralPc(_FdmSteps, _Handle):
     """z = (sigma I + A)^-1 (r / eta) for an EllipticOp (ell_pc_create_spectral): the direct solve of the constant-coefficient
     operator after division by the viscosity.  `update` refreshes eta from the operator's last FormFunction; pass the object as
     the `M` of Fgmres.solve."""

@@ -12,9 +12,9 @@
 // chip: on the tensor grid the constant-coefficient part of P is  sum_k I x .. x T_k x .. x I  with a 1-D
 // three-point operator T_k, which is diagonalised ONCE (diffmat.cpp: fdm_line), so that
 //     P_1^-1 = (S_0 x S_1 x S_2) diag(1 / (l_i + l_j + l_k)) (S_0^-1 x S_1^-1 x S_2^-1)
-// is 2d batched dense line transforms -- the very sweep kernel the operator itself runs on (each transform
-// is applied as its centro-symmetric plus its centro-antisymmetric part, two launches) -- and one pointwise
-// scaling.  For eta == 1 that is the exact inverse of P; for variable coefficients the approximate solve is
+// is 2d batched dense line transforms -- one raw-mode launch of the very sweep kernel the operator itself runs on; where
+// that cannot run, a dense line product with S^-1 forward and the centro-symmetric plus the centro-antisymmetric part of S,
+// two launches, backward (line_transform_g) -- and one pointwise scaling.  For eta == 1 that is the exact inverse of P; for variable coefficients the approximate solve is
 // `sweeps` iterations of GMRES on P z = r with P_1^-1 (1/eta) as its right preconditioner (sweeps = 0: that
 // preconditioner alone) -- a varying, hence flexible, preconditioner for the outer FGMRES, as ILU(2) is not.
 //
@@ -279,8 +279,9 @@ __global__ __launch_bounds__(256, 3) void k_fdm_zsolve16(const FzParams p) {
 }
 
 // parity: the modes use the parity layout (raw transforms, OUT_MUL and k_fdm_zsolve16 usable); a line whose two ends differ has
-// ascending modes and runs the two-launch transforms only.  bcm (boundary-condition lines): Q (2 x M), L^T (2 x M), B_BB^-1 (2 x 2)
-struct LineMats { DiffMat Fcs, Fca, Bcs, Bca, Fraw, Braw; double *lam = nullptr; double *bcm = nullptr; bool ok = false, parity = true; };
+// ascending modes and runs the dense / two-launch transforms only.  bcm (boundary-condition lines): Q (2 x M), L^T (2 x M), B_BB^-1 (2 x 2)
+// Fdense: S^-1 itself (M x M, row-major, rounded once): the forward transform where it cannot be one raw launch (line_transform_g)
+struct LineMats { DiffMat Bcs, Bca, Fraw, Braw; double *lam = nullptr; double *bcm = nullptr; double *Fdense = nullptr; int M = 0; bool ok = false, parity = true; };
 // lines are shared by the directions of equal extent, equal end conditions (alpha_first, beta_first, alpha_last, beta_last) AND
 // equal scale (cheb_helmholtz_create_box; 1 everywhere else)
 typedef std::tuple<int, std::array<double, 4>, double> LineKey;
@@ -336,10 +337,11 @@ static void fdpc_free(chebhip_fdpc *pc) {
   if (pc->inner) chebhip_fgmres_destroy(pc->inner);
   for (auto &kv : pc->lines) {
     if (!kv.second.ok) continue;
-    diffmat_destroy(&kv.second.Fcs); diffmat_destroy(&kv.second.Fca); diffmat_destroy(&kv.second.Bcs); diffmat_destroy(&kv.second.Bca);
+    diffmat_destroy(&kv.second.Bcs); diffmat_destroy(&kv.second.Bca);
     diffmat_destroy(&kv.second.Fraw); diffmat_destroy(&kv.second.Braw);
     if (kv.second.lam) (void)hipFree(kv.second.lam);
     if (kv.second.bcm) (void)hipFree(kv.second.bcm);
+    if (kv.second.Fdense) (void)hipFree(kv.second.Fdense);
   }
   for (int k = 0; k < MAXD; k++) if (pc->xs[k]) (void)hipFree(pc->xs[k]);
   double *all[] = {pc->cf, pc->eta_g, pc->t0, pc->t1, pc->t2, pc->t3, pc->t4, pc->t5, pc->W, pc->Einv, pc->lam0};
@@ -407,8 +409,6 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
       fdpc_free(pc);
       return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point %s line operator failed", P, kind == LINE_SPECTRAL ? "spectral" : "finite-difference");
     }
-    centro_part(M, Si, 1, part); HIP_TRY_OR(diffmat_from_dense(M, part.data(), 1, &lm.Fcs), fdpc_free(pc));
-    centro_part(M, Si, 0, part); HIP_TRY_OR(diffmat_from_dense(M, part.data(), 0, &lm.Fca), fdpc_free(pc));
     centro_part(M, S, 1, part);  HIP_TRY_OR(diffmat_from_dense(M, part.data(), 1, &lm.Bcs), fdpc_free(pc));
     centro_part(M, S, 0, part);  HIP_TRY_OR(diffmat_from_dense(M, part.data(), 0, &lm.Bca), fdpc_free(pc));
     if (lm.parity) {
@@ -430,6 +430,12 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
           O[(size_t)i * Hh + j] = (2 * j == m) ? 0.0L : S[(size_t)i * M + (m - j)];
         }
       HIP_TRY_OR(diffmat_from_blocks(M, E.data(), O.data(), 1, &lm.Braw), fdpc_free(pc));
+    }
+    {
+      std::vector<double> sd((size_t)M * M); for (size_t i = 0; i < sd.size(); i++) sd[i] = (double)Si[i];
+      HIP_TRY_OR(hipMalloc((void **)&lm.Fdense, sd.size() * sizeof(double)), fdpc_free(pc));
+      HIP_TRY_OR(hipMemcpy(lm.Fdense, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
+      lm.M = M;
     }
     std::vector<double> ld(M); for (int i = 0; i < M; i++) ld[i] = (double)lam[i];
     HIP_TRY_OR(hipMalloc((void **)&lm.lam, M * sizeof(double)), fdpc_free(pc));
@@ -502,20 +508,23 @@ static int fdpc_update(chebhip_fdpc *pc, hipStream_t st) {
 }
 
 // y = S^-1 x (forward) or S x (backward) along dimension k of nf stacked interior fields (x != y): one raw-mode launch
-// where the 16-byte kernels can run it, otherwise the centro-symmetric plus the centro-antisymmetric part (two launches)
+// where the 16-byte kernels can run it, otherwise one dense line product (forward) or the centro-symmetric plus the
+// centro-antisymmetric part (backward, two launches)
 // mul (forward transforms only; may be null): the result is multiplied by this array as it is stored (OUT_MUL) where the one-launch
 // form runs, and *fused says whether it was
 // in_mul (forward only; may be null): every input element is multiplied by this array as it is loaded (IN_MUL) -- the caller has
 // asked line_in_mul_ok first
+// route (may be null): the CHEBHIP_FDPC_ROUTE_* bits of the launches chosen; dry: choose only, launch nothing
 static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool backward, const double *x, double *y, hipStream_t st,
-                            const double *mul = nullptr, bool *fused = nullptr, const double *in_mul = nullptr);
+                            const double *mul = nullptr, bool *fused = nullptr, const double *in_mul = nullptr, int *route = nullptr, bool dry = false);
 // nf (0: the handle's): the stacked fields of this call, at most the handle's (cheb_opfun: its inputs forward, its outputs backward)
 static int line_transform(chebhip_fdpc *pc, int k, bool backward, const double *x, double *y, hipStream_t st, const double *mul = nullptr, bool *fused = nullptr,
-                          const double *in_mul = nullptr, int nf = 0) {
+                          const double *in_mul = nullptr, int nf = 0, int *route = nullptr, bool dry = false) {
   if (fused) *fused = false;
+  if (route) *route = 0;
   if (nf == 0) nf = pc->nf;
-  if (pc->slab && k == 0) return pc->dim0(pc->dim0_ctx, backward ? 1 : 0, nf, x, y, (void *)st);      // collective: every rank of the slab partition
-  return line_transform_g(*pc->ln[k], pc->ncols_g[k] * (unsigned)nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul);
+  if (pc->slab && k == 0) return dry ? 0 : pc->dim0(pc->dim0_ctx, backward ? 1 : 0, nf, x, y, (void *)st);      // collective: every rank of the slab partition
+  return line_transform_g(*pc->ln[k], pc->ncols_g[k] * (unsigned)nf, pc->inner_g[k], backward, x, y, st, mul, fused, in_mul, route, dry);
 }
 static SweepParams line_in_mul_params(unsigned ncols, unsigned inner, const double *x, double *y, const double *in_mul) {
   SweepParams sm = {};
@@ -528,111 +537,217 @@ static bool line_in_mul_ok(chebhip_fdpc *pc, int k, const double *x, double *y, 
   return ncols != 0 && pc->ln[k]->parity && sweep_vec_raw_eligible(pc->ln[k]->Fraw, line_in_mul_params(ncols, pc->inner_g[k], x, y, in_mul));
 }
 static int line_transform_g(LineMats &lm, unsigned ncols, unsigned inner, bool backward, const double *x, double *y, hipStream_t st,
-                            const double *mul, bool *fused, const double *in_mul) {
+                            const double *mul, bool *fused, const double *in_mul, int *route, bool dry) {
   if (fused) *fused = false;
+  if (route) *route = 0;
   if (ncols == 0) return 0;
-  if (in_mul && !backward) { HIP_TRY(sweep_launch(lm.Fraw, line_in_mul_params(ncols, inner, x, y, in_mul), st)); return 0; }
+  if (in_mul && !backward) {
+    if (route) *route = CHEBHIP_FDPC_ROUTE_RAW | CHEBHIP_FDPC_ROUTE_FUSED_MUL;
+    if (!dry) HIP_TRY(sweep_launch(lm.Fraw, line_in_mul_params(ncols, inner, x, y, in_mul), st));
+    return 0;
+  }
   SweepParams sp = {};
   sp.ncols = ncols; sp.inner = inner;
   sp.in0 = x; sp.in_mode = IN_PLAIN; sp.out = y; sp.alpha = 1.0;
   sp.out_mode = OUT_STORE;
   if (mul && fused && !backward && lm.parity) {
     SweepParams sm = sp; sm.out_mode = OUT_MUL; sm.acc = mul; sm.raw = 1;
-    if (sweep_vec_raw_eligible(lm.Fraw, sm)) { HIP_TRY(sweep_launch(lm.Fraw, sm, st)); *fused = true; return 0; }
+    if (sweep_vec_raw_eligible(lm.Fraw, sm)) {
+      if (route) *route = CHEBHIP_FDPC_ROUTE_RAW | CHEBHIP_FDPC_ROUTE_FUSED_MUL;
+      if (!dry) HIP_TRY(sweep_launch(lm.Fraw, sm, st));
+      *fused = true; return 0;
+    }
   }
   if (lm.parity && sweep_vec_raw_eligible(backward ? lm.Braw : lm.Fraw, sp)) {       // one launch: the parity split is the transform's own
     sp.raw = backward ? 2 : 1;
-    HIP_TRY(sweep_launch(backward ? lm.Braw : lm.Fraw, sp, st));
+    if (route) *route = CHEBHIP_FDPC_ROUTE_RAW;
+    if (!dry) HIP_TRY(sweep_launch(backward ? lm.Braw : lm.Fraw, sp, st));
     return 0;
   }
-  HIP_TRY(sweep_launch(backward ? lm.Bcs : lm.Fcs, sp, st));
+  // Forward, not as one raw launch: ONE dense line product with S^-1 itself (linegemm.hip: any stride, any alignment).  S^-1 is
+  // neither centro-symmetric nor centro-antisymmetric, so as the sum of its two parts (the form of the backward transform below)
+  // element i carried the roundings of rows i AND m - i of S^-1 -- where |S^-1[m-i][m-j]| >> |S^-1[i][j]| a relative error of
+  // 1e-12 and more (tests/test_gpu_fdm.py); the dense product forms a row from its own entries.  (S in two parts meets the
+  // row-wise bar: its columns, not its rows, are the parity modes.)
+  if (!backward) {
+    if (route) *route = CHEBHIP_FDPC_ROUTE_DENSE;
+    if (dry) return 0;
+    const ResampleDir rp{lm.Fdense, x, y, ncols / inner, (unsigned)lm.M, (unsigned)lm.M, inner, ncols};
+    HIP_TRY(resample_launch(rp, st));
+    return 0;
+  }
+  // (GENERAL: by sweep_launch's own dispatch test)
+  if (route) *route = CHEBHIP_FDPC_ROUTE_TWO_LAUNCH | (sweep_takes_vec(lm.Bcs, sp) ? 0 : CHEBHIP_FDPC_ROUTE_GENERAL);
+  if (dry) return 0;
+  HIP_TRY(sweep_launch(lm.Bcs, sp, st));
   sp.out_mode = OUT_ACC; sp.acc = y;
-  HIP_TRY(sweep_launch(backward ? lm.Bca : lm.Fca, sp, st));
+  HIP_TRY(sweep_launch(lm.Bca, sp, st));
+  return 0;
+}
+
+// What a solve on this handle does that does not depend on the caller's vectors: the order of the forward transforms, the
+// eigenvalue arrays, whether the weight array W is used, whether the last forward transform carries the modal scaling on its
+// store (it runs between the handle's own buffers t0 / t1 whenever d >= 2: decided on them) and whether k_fdm_zsolve16 runs.
+struct FdmPlan { int d; int order[MAXD]; LamPtrs lam; int nl; long lines; bool w_ok, zsolve, last_fused; };
+static FdmPlan fdm_plan(chebhip_fdpc *pc) {
+  FdmPlan pl = {};
+  const int d = pl.d = pc->geo.d;
+  // Forward transforms commute: on slabs in 3-D the first one is a local direction (1) rather than the collective one (0), so that
+  // it can take the division by eta on its load side.  Dimension d-1 stays LAST in every order: it takes the modal scaling on its
+  // store side, and the one-launch z solve below replaces exactly that transform (a 2-D slab therefore keeps the order 0, 1: its
+  // only local direction is the last one, and the division by eta is the separate pass).
+  for (int k = 0; k < d; k++) pl.order[k] = k;
+  if (pc->slab && d >= 3) { pl.order[0] = 1; pl.order[1] = 0; }
+  for (int k = 0; k < MAXD; k++) pl.lam.p[k] = k < d ? pc->ln[k]->lam : nullptr;
+  if (pc->lam0) pl.lam.p[0] = pc->lam0;                   // spectral: sigma + l_0 (every weight path reads dimension 0's array)
+  pl.nl = pc->geo.dims[d - 1] - 2;
+  pl.lines = pc->G / pl.nl;
+  if (pc->slab && d >= 2) pl.lam.p[0] += pc->i0_off;      // the slab's first interior plane is plane i0_off of the global line
+  // The modal scaling rides on the store of the last forward transform (dimension d-1 > 0: local on slabs too) where that
+  // transform is one launch of the 16-byte kernels: it multiplies by W = 1 / (l_i + l_j + l_k), built on first use (the
+  // separate pass divides: the two differ in the last bit).  Option "fdm_passes" = 1 keeps both pointwise passes (A/B).
+  pl.w_ok = pc->W && d >= 2 && d <= 3 && pl.lines > 0 && pl.lines <= 65535 && pc->nf <= 65535 && !opt(OPT_FDM_PASSES);
+  // The last forward transform, the scaling and the first backward transform act on the same contiguous lines: one launch
+  // (k_fdm_zsolve16) where those lines have 66 .. 128 interior points, an even number of them (option "fdm_z_separate" = 1: A/B)
+  {
+    const int M = pc->geo.dims[d - 1] - 2;
+    LineMats &lm = *pc->ln[d - 1];
+    pl.zsolve = pl.w_ok && d >= 2 && lm.parity && !opt(OPT_FDM_Z_SEPARATE) && !opt(OPT_NO_RAW_TRANSFORMS) && !opt(OPT_GENERAL_KERNELS) && (M & 1) == 0 &&
+                lm.Fraw.KS == FZ_KS && lm.Braw.KS == FZ_KS && lm.Braw.sym == 1 && pc->G * pc->nf / M < 0x7fffffffL - FZ_NT;
+  }
+  if (pl.w_ok && !pl.zsolve) {
+    const double *s = (d - 1) & 1 ? pc->t0 : pc->t1; double *t = (d - 1) & 1 ? pc->t1 : pc->t0;      // forward transform q reads what q - 1 wrote
+    (void)line_transform(pc, d - 1, false, s, t, nullptr, pc->W, &pl.last_fused, nullptr, 0, nullptr, true);
+  }
+  return pl;
+}
+// W is filled on first use rather than at create: a slab handle learns its plane offset after create
+static int fdm_weights(chebhip_fdpc *pc, const FdmPlan &pl, hipStream_t st) {
+  if (!pl.w_ok || pc->W_tried) return 0;
+  pc->W_tried = true;
+  const int n1 = pl.d == 3 ? pc->geo.dims[1] - 2 : 1;
+  hipLaunchKernelGGL(k_modal_weights3, dim3((unsigned)((pl.nl + 255) / 256), (unsigned)pl.lines, (unsigned)pc->nf), dim3(256), 0, st, pl.d, n1, pl.nl, pc->G,
+                     pl.lam.p[0], pl.lam.p[1], pl.lam.p[2], pc->W);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ONE step of the solve along direction k, x -> y (CHEBHIP_FDPC_STEP_*; SCALE alone works in place and takes y == x); fdm_solve is
+// a sequence of these calls and chebhip_fdpc_step is one of them on the caller's arrays.  A mode the solve does not take for this
+// handle, this direction, these pointers and the current options is refused (CHEBHIP_ERR_ARG), never replaced by another route.
+// route (may be null): the CHEBHIP_FDPC_ROUTE_* bits of what runs; dry: decide only.
+static int fdm_step(chebhip_fdpc *pc, const FdmPlan &pl, int k, int mode, const double *x, double *y, hipStream_t st, int *route = nullptr, bool dry = false) {
+  const int d = pl.d;
+  if (route) *route = 0;
+  if (k < 0 || k >= d) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: direction %d of %d", k, d);
+  const bool first = k == pl.order[0], lastdir = k == pl.order[d - 1];
+  int rc = 0, rt = 0;
+  switch (mode) {
+    case CHEBHIP_FDPC_STEP_FORWARD_OVER_ETA: {
+      if (pc->bare || !first) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: the division by eta belongs to the first direction of a handle with an operator");
+      if (pl.zsolve && lastdir) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: direction %d runs inside the one-launch z solve", k);
+      const double *src = x, *in_mul = nullptr;
+      // (dry, on a handle that has not been assembled yet: what its first update will leave -- fdpc_eta_inverse fills Einv wherever it was allocated)
+      const bool einv_ok = dry && !pc->assembled ? pc->Einv != nullptr : pc->Einv_ok;
+      if (einv_ok && !opt(OPT_FDM_PASSES) && d >= 2 && line_in_mul_ok(pc, k, x, y, pc->Einv)) in_mul = pc->Einv;
+      else {
+        if (!dry) hipLaunchKernelGGL(k_resid_over_eta, dim3(grid1d(pc->G, 256, 4096), (unsigned)pc->nf), dim3(256), 0, st, pc->G, pc->nf, x, (const double *)nullptr,
+                                     (const double *)pc->eta_g, pc->t3);
+        src = pc->t3; rt = CHEBHIP_FDPC_ROUTE_ETA_PASS;
+      }
+      if (!dry && (rc = fdm_weights(pc, pl, st))) return rc;
+      int r2 = 0;
+      if ((rc = line_transform(pc, k, false, src, y, st, nullptr, nullptr, in_mul, 0, &r2, dry))) return rc;
+      rt |= r2;
+      break;
+    }
+    case CHEBHIP_FDPC_STEP_FORWARD:
+    case CHEBHIP_FDPC_STEP_FORWARD_SCALED: {
+      const bool want = mode == CHEBHIP_FDPC_STEP_FORWARD_SCALED;
+      if (pl.zsolve && lastdir) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: direction %d runs inside the one-launch z solve", k);
+      // (a Stokes handle divides by eta while it pulls the components apart, chebhip_fdpc_apply, and by the first transform on
+      // component-major vectors, chebhip_fdpc_apply_cm: both forms of its first direction are the solve's own)
+      if (!want && first && !pc->bare && !pc->interleaved) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: the first direction of this handle divides by eta (FORWARD_OVER_ETA)");
+      const bool scaled = lastdir && d >= 2 && pl.last_fused;
+      if (want != scaled) return chebhip_fail(CHEBHIP_ERR_ARG, want ? "fdpc step: direction %d does not carry the modal scaling on its store" :
+                                                                      "fdpc step: direction %d carries the modal scaling on its store (FORWARD_SCALED)", k);
+      bool f = false;
+      if (want) {
+        (void)line_transform(pc, k, false, x, y, st, pc->W, &f, nullptr, 0, nullptr, true);
+        if (!f) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: these arrays cannot take the one-launch transform that carries the modal scaling");
+      }
+      if (!dry && (rc = fdm_weights(pc, pl, st))) return rc;
+      if ((rc = line_transform(pc, k, false, x, y, st, want ? pc->W : nullptr, want ? &f : nullptr, nullptr, 0, &rt, dry))) return rc;
+      break;
+    }
+    case CHEBHIP_FDPC_STEP_SCALE: {
+      if (!lastdir || pl.zsolve || (d >= 2 && pl.last_fused)) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: no separate modal scaling pass after direction %d on this handle", k);
+      if (pc->slab && !(d <= 3 && pl.lines <= 65535 && pc->nf <= 65535)) return chebhip_fail(CHEBHIP_ERR_ARG, "slab-mode preconditioner: d <= 3 and at most 65535 lines per slab");
+      const bool three = d <= 3 && pl.lines <= 65535 && pc->nf <= 65535;
+      rt = three ? CHEBHIP_FDPC_ROUTE_SCALE3 : CHEBHIP_FDPC_ROUTE_SCALE_GENERAL;
+      if (dry || pl.lines == 0) break;       // (a slab without interior planes: nothing to scale; it still takes part in the transforms along dimension 0)
+      if (y != x) HIP_TRY(hipMemcpyAsync(y, x, (size_t)pc->G * pc->nf * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (three) {
+        const int n1 = d == 3 ? pc->geo.dims[1] - 2 : 1;
+        hipLaunchKernelGGL(k_modal_scale3, dim3((unsigned)((pl.nl + 255) / 256), (unsigned)pl.lines, (unsigned)pc->nf), dim3(256), 0, st, d, n1, pl.nl, pc->G,
+                           pl.lam.p[0], pl.lam.p[1], pl.lam.p[2], y);
+      } else
+        hipLaunchKernelGGL(k_modal_scale, dim3(grid1d(pc->G * pc->nf, 256, 4096)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, pl.lam, y);
+      break;
+    }
+    case CHEBHIP_FDPC_STEP_ZSOLVE: {
+      if (!lastdir || !pl.zsolve) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: the one-launch z solve does not run on this handle (direction %d)", k);
+      if (((uintptr_t)x | (uintptr_t)y) & 15) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: the one-launch z solve takes 16-byte-aligned arrays (the handle's own)");
+      rt = CHEBHIP_FDPC_ROUTE_ZSOLVE | CHEBHIP_FDPC_ROUTE_RAW | CHEBHIP_FDPC_ROUTE_FUSED_MUL;
+      if (dry) break;
+      if ((rc = fdm_weights(pc, pl, st))) return rc;
+      const int M = pc->geo.dims[d - 1] - 2;
+      LineMats &lm = *pc->ln[d - 1];
+      FzParams fp = {};
+      fp.M = M; fp.H = (M + 1) / 2; fp.ncols = (unsigned)(pc->G * pc->nf / M); fp.ntiles = (fp.ncols + FZ_NT - 1) / FZ_NT;
+      fp.x = x; fp.y = y;
+      fp.d = d; fp.n1 = d == 3 ? pc->geo.dims[1] - 2 : 1; fp.flines = (unsigned)(pc->G / M);
+      fp.l0 = pl.lam.p[0]; fp.l1 = pl.lam.p[1]; fp.lz = pl.lam.p[d - 1];
+      fp.FE = lm.Fraw.fragE; fp.FO = lm.Fraw.fragO; fp.BE = lm.Braw.fragE; fp.BO = lm.Braw.fragO;
+      hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
+      const unsigned grid = fp.ntiles < 3u * (unsigned)ncu ? fp.ntiles : 3u * (unsigned)ncu;       // three workgroups per CU
+      if (grid) hipLaunchKernelGGL(k_fdm_zsolve16, dim3(grid), dim3(256), 0, st, fp);
+      break;
+    }
+    case CHEBHIP_FDPC_STEP_BACKWARD: {
+      if (pl.zsolve && lastdir) return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: direction %d runs inside the one-launch z solve", k);
+      if ((rc = line_transform(pc, k, true, x, y, st, nullptr, nullptr, nullptr, 0, &rt, dry))) return rc;
+      break;
+    }
+    default: return chebhip_fail(CHEBHIP_ERR_ARG, "fdpc step: unknown mode %d", mode);
+  }
+  if (route) *route = rt;
+  if (!dry) HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // z = P_1^-1 r (the constant-coefficient part, exactly), or z = P_1^-1 (r / eta) with over_eta; r is not modified; t0 / t1 (/ t3 with
 // over_eta) are scratch (r, z must be none of them)
 static int fdm_solve(chebhip_fdpc *pc, const double *r, double *z, hipStream_t st, bool over_eta = false) {
-  const int d = pc->geo.d;
+  const FdmPlan pl = fdm_plan(pc);
+  const int d = pl.d;
   const double *src = r;
   double *a = pc->t0, *b = pc->t1;
-  // Forward transforms commute: on slabs in 3-D the first one is a local direction (1) rather than the collective one (0), so that
-  // it can take the division by eta on its load side.  Dimension d-1 stays LAST in every order: it takes the modal scaling on its
-  // store side, and the one-launch z solve below replaces exactly that transform (a 2-D slab therefore keeps the order 0, 1: its
-  // only local direction is the last one, and the division by eta is the separate pass).
-  int order[MAXD];
-  for (int k = 0; k < d; k++) order[k] = k;
-  if (pc->slab && d >= 3) { order[0] = 1; order[1] = 0; }
-  const double *in_mul = nullptr;
-  if (over_eta) {
-    if (pc->Einv_ok && !opt(OPT_FDM_PASSES) && d >= 2 && line_in_mul_ok(pc, order[0], r, a, pc->Einv)) in_mul = pc->Einv;
-    else {
-      hipLaunchKernelGGL(k_resid_over_eta, dim3(grid1d(pc->G, 256, 4096), (unsigned)pc->nf), dim3(256), 0, st, pc->G, pc->nf, r, (const double *)nullptr,
-                         (const double *)pc->eta_g, pc->t3);
-      src = pc->t3;
-    }
-  }
-  LamPtrs lam; for (int k = 0; k < MAXD; k++) lam.p[k] = k < d ? pc->ln[k]->lam : nullptr;
-  if (pc->lam0) lam.p[0] = pc->lam0;                      // spectral: sigma + l_0 (every weight path reads dimension 0's array)
-  const int nl = pc->geo.dims[d - 1] - 2;
-  const long lines = pc->G / nl;
-  if (pc->slab && d >= 2) lam.p[0] += pc->i0_off;         // the slab's first interior plane is plane i0_off of the global line
-  // The modal scaling rides on the store of the last forward transform (dimension d-1 > 0: local on slabs too) where that
-  // transform is one launch of the 16-byte kernels: it multiplies by W = 1 / (l_i + l_j + l_k), built here on first use (the
-  // separate pass divides: the two differ in the last bit).  Option "fdm_passes" = 1 keeps both pointwise passes (A/B).
-  const bool w_ok = pc->W && d >= 2 && d <= 3 && lines > 0 && lines <= 65535 && pc->nf <= 65535 && !opt(OPT_FDM_PASSES);
-  if (w_ok && !pc->W_tried) {           // (filled here rather than at create: a slab handle learns its plane offset after create)
-    pc->W_tried = true;
-    const int n1 = d == 3 ? pc->geo.dims[1] - 2 : 1;
-    hipLaunchKernelGGL(k_modal_weights3, dim3((unsigned)((nl + 255) / 256), (unsigned)lines, (unsigned)pc->nf), dim3(256), 0, st, d, n1, nl, pc->G,
-                       lam.p[0], lam.p[1], lam.p[2], pc->W);
-    HIP_TRY(hipGetLastError());
-  }
-  // The last forward transform, the scaling and the first backward transform act on the same contiguous lines: one launch
-  // (k_fdm_zsolve16) where those lines have 66 .. 128 interior points, an even number of them (option "fdm_z_separate" = 1: A/B)
-  bool zsolve = false;
-  {
-    const int M = pc->geo.dims[d - 1] - 2;
-    LineMats &lm = *pc->ln[d - 1];
-    zsolve = w_ok && d >= 2 && lm.parity && !opt(OPT_FDM_Z_SEPARATE) && !opt(OPT_NO_RAW_TRANSFORMS) && !opt(OPT_GENERAL_KERNELS) && (M & 1) == 0 &&
-             lm.Fraw.KS == FZ_KS && lm.Braw.KS == FZ_KS && lm.Braw.sym == 1 && pc->G * pc->nf / M < 0x7fffffffL - FZ_NT;
-  }
-  bool scaled = false;
-  for (int q = 0; q < (zsolve ? d - 1 : d); q++) {
-    const int k = order[q];
-    const bool last = q == d - 1 && q > 0 && w_ok;
-    int rc = line_transform(pc, k, false, src, a, st, last ? pc->W : nullptr, last ? &scaled : nullptr, q == 0 ? in_mul : nullptr); if (rc) return rc;
+  int rc;
+  for (int q = 0; q < (pl.zsolve ? d - 1 : d); q++) {
+    const int mode = q == 0 && over_eta ? CHEBHIP_FDPC_STEP_FORWARD_OVER_ETA : (q == d - 1 && q > 0 && pl.last_fused ? CHEBHIP_FDPC_STEP_FORWARD_SCALED : CHEBHIP_FDPC_STEP_FORWARD);
+    if ((rc = fdm_step(pc, pl, pl.order[q], mode, src, a, st))) return rc;
     src = a; std::swap(a, b);
   }
-  if (!scaled && !zsolve) {
-    if (lines == 0) { /* a slab without interior planes: nothing to scale (it still takes part in the transforms along dimension 0) */ }
-    else if (d <= 3 && lines <= 65535 && pc->nf <= 65535) {
-      const int n1 = d == 3 ? pc->geo.dims[1] - 2 : 1;
-      hipLaunchKernelGGL(k_modal_scale3, dim3((unsigned)((nl + 255) / 256), (unsigned)lines, (unsigned)pc->nf), dim3(256), 0, st, d, n1, nl, pc->G,
-                         lam.p[0], lam.p[1], lam.p[2], (double *)src);
-    } else if (pc->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "slab-mode preconditioner: d <= 3 and at most 65535 lines per slab");
-    else
-      hipLaunchKernelGGL(k_modal_scale, dim3(grid1d(pc->G * pc->nf, 256, 4096)), dim3(256), 0, st, pc->geo, pc->G, pc->nf, lam, (double *)src);
-  }
-  if (zsolve) {
-    const int M = pc->geo.dims[d - 1] - 2;
-    LineMats &lm = *pc->ln[d - 1];
-    FzParams fp = {};
-    fp.M = M; fp.H = (M + 1) / 2; fp.ncols = (unsigned)(pc->G * pc->nf / M); fp.ntiles = (fp.ncols + FZ_NT - 1) / FZ_NT;
-    fp.x = src; fp.y = (d == 1) ? z : a;
-    fp.d = d; fp.n1 = d == 3 ? pc->geo.dims[1] - 2 : 1; fp.flines = (unsigned)(pc->G / M);
-    fp.l0 = lam.p[0]; fp.l1 = lam.p[1]; fp.lz = lam.p[d - 1];
-    fp.FE = lm.Fraw.fragE; fp.FO = lm.Fraw.fragO; fp.BE = lm.Braw.fragE; fp.BO = lm.Braw.fragO;
-    hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
-    const unsigned grid = fp.ntiles < 3u * (unsigned)ncu ? fp.ntiles : 3u * (unsigned)ncu;       // three workgroups per CU
-    if (grid) hipLaunchKernelGGL(k_fdm_zsolve16, dim3(grid), dim3(256), 0, st, fp);
-    HIP_TRY(hipGetLastError());
+  if (pl.zsolve) {
+    if ((rc = fdm_step(pc, pl, d - 1, CHEBHIP_FDPC_STEP_ZSOLVE, src, a, st))) return rc;
     src = a; std::swap(a, b);
+  } else if (!(d >= 2 && pl.last_fused)) {
+    if ((rc = fdm_step(pc, pl, d - 1, CHEBHIP_FDPC_STEP_SCALE, src, (double *)src, st))) return rc;
   }
-  for (int k = (zsolve ? d - 2 : d - 1); k >= 0; k--) {
+  for (int k = (pl.zsolve ? d - 2 : d - 1); k >= 0; k--) {
     double *dst = (k == 0) ? z : a;
-    int rc = line_transform(pc, k, true, src, dst, st); if (rc) return rc;
+    if ((rc = fdm_step(pc, pl, k, CHEBHIP_FDPC_STEP_BACKWARD, src, dst, st))) return rc;
     src = dst; std::swap(a, b);
   }
   HIP_TRY(hipGetLastError());
@@ -778,6 +893,43 @@ extern "C" int chebhip_fdpc_apply(void *ctx, const double *r, double *z, void *s
   if (r && r == z) return chebhip_fail(CHEBHIP_ERR_ARG, "r and z must be distinct");
   StageTimer tm(CHEBHIP_STAGE_FDPC_APPLY, stream);
   return fdpc_apply(pc, r, z, (hipStream_t)stream);
+}
+
+// One step of the solve on the caller's arrays (nf stacked interior fields, component-major on a Stokes handle): fdm_step above,
+// the very function fdm_solve is made of.  Serial handles only: a slab's dimension 0 is a collective.
+static int fdpc_step_check(chebhip_fdpc *pc) {
+  if (!pc) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (pc->slab) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_step: not on slab handles");
+  if (pc->G == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_step: the handle has no unknowns");
+  return 0;
+}
+extern "C" int chebhip_fdpc_step(chebhip_fdpc *pc, int k, int mode, const double *x_dev, double *y_dev, void *stream) {
+  int rc = fdpc_step_check(pc); if (rc) return rc;
+  if (!x_dev || !y_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL vector");
+  if (x_dev == y_dev && mode != CHEBHIP_FDPC_STEP_SCALE) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_step: x and y must be distinct (SCALE alone works in place)");
+  const double *own[] = {pc->t0, pc->t1, pc->t3};
+  for (const double *p : own) if (p && (x_dev == p || y_dev == p)) return chebhip_fail(CHEBHIP_ERR_ARG, "chebhip_fdpc_step: the handle's own scratch");
+  hipStream_t st = (hipStream_t)stream;
+  if (!pc->assembled && (rc = fdpc_update(pc, st))) return rc;
+  return fdm_step(pc, fdm_plan(pc), k, mode, x_dev, y_dev, st);
+}
+extern "C" int chebhip_fdpc_step_route(chebhip_fdpc *pc, int k, int mode) {
+  if (fdpc_step_check(pc)) return -1;
+  // the arrays of a solve's inner steps: the handle's own, in the order the solve alternates them
+  int route = 0;
+  if (fdm_step(pc, fdm_plan(pc), k, mode, mode == CHEBHIP_FDPC_STEP_SCALE ? pc->t1 : pc->t0, pc->t1, nullptr, &route, true)) return -1;
+  return route;
+}
+extern "C" int chebhip_fdpc_line_host(int P, double *S, double *Sinv, double *lam) {
+  if (P < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "P = %d: a line needs interior nodes (P >= 3)", P);
+  if (P > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "P = %d: at most 258 points per line", P);
+  if (!S || !Sinv || !lam) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  std::vector<long double> s, si, l;
+  if (!fdm_line(P, s, si, l)) return chebhip_fail(CHEBHIP_ERR_ARG, "eigen-decomposition of the %d-point finite-difference line operator failed", P);
+  const int M = P - 2;
+  for (size_t i = 0; i < (size_t)M * M; i++) { S[i] = (double)s[i]; Sinv[i] = (double)si[i]; }
+  for (int i = 0; i < M; i++) lam[i] = (double)l[i];
+  return 0;
 }
 
 // ---- C ABI: the spectral preconditioner and the direct Helmholtz solve ------------------------------------------
@@ -1012,6 +1164,7 @@ extern "C" int cheb_helmholtz_destroy(cheb_helmholtz *h) {
 }
 
 extern "C" long cheb_helmholtz_size(const cheb_helmholtz *h) { return h ? h->n : -1; }
+extern "C" chebhip_fdpc *cheb_helmholtz_fdpc(cheb_helmholtz *h) { return h ? h->pc : nullptr; }
 
 extern "C" int cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *lam) {
   if (P < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "P = %d: a line needs interior nodes (P >= 3)", P);

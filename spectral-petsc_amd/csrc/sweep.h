@@ -196,6 +196,8 @@ hipError_t sweep_xl_launch(const DiffMat &m, SweepParams p, hipStream_t stream);
 
 // 16-byte-access specialisation (sweep_vec.hip); used by sweep_launch when eligible
 bool sweep_vec_eligible(const DiffMat &m, const SweepParams &p);
+// whether sweep_launch runs this sweep on them (its own dispatch test; false: the general kernel or a long-line route)
+bool sweep_takes_vec(const DiffMat &m, const SweepParams &p);
 // ... and may carry p.raw != 0 (the kernel generations that implement the raw modes)
 bool sweep_vec_raw_eligible(const DiffMat &m, const SweepParams &p);
 hipError_t sweep_vec_launch(const DiffMat &m, SweepParams p, hipStream_t stream);

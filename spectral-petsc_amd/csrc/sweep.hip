@@ -467,10 +467,19 @@ static hipError_t launch_long(const SweepParams &p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream) {
-  if (p.in_mode == IN_SUM3) return hipErrorInvalidValue;    // exists in the multi-job launch of short lines only (sweep_vec.hip)
+// the launch parameters with the matrix's own fields filled in
+static SweepParams with_matrix(const DiffMat &m, SweepParams p) {
   p.P = m.P; p.H = m.H; p.fragE = m.fragE; p.fragO = m.fragO; p.fragE2 = m.fragE2; p.fragO2 = m.fragO2; p.zero = m.zero; p.sink = m.sink; p.sym = m.sym;
   p.longDT = m.longDT; p.longD = m.longD;
+  return p;
+}
+// the one test by which sweep_launch sends a sweep of up to 256 points to the 16-byte kernels (false: the general kernel)
+static bool takes_vec(const DiffMat &m, const SweepParams &p) { return !opt(OPT_GENERAL_KERNELS) && sweep_vec_eligible(m, p); }
+bool sweep_takes_vec(const DiffMat &m, const SweepParams &p) { return m.KS != 0 && takes_vec(m, with_matrix(m, p)); }
+
+hipError_t sweep_launch(const DiffMat &m, SweepParams p0, hipStream_t stream) {
+  if (p0.in_mode == IN_SUM3) return hipErrorInvalidValue;    // exists in the multi-job launch of short lines only (sweep_vec.hip)
+  SweepParams p = with_matrix(m, p0);
   if (m.KS == 0) {
     if (!m.longDT || p.out_mode == OUT_MUL || p.out_mode == OUT_ACC2 || p.in_mode == IN_MUL) return hipErrorInvalidValue;
     // lines of 257 .. 1024 points: the library's own matrix-core kernel; option "long_lines_gemm": the rocBLAS route (A/B)
@@ -478,7 +487,7 @@ hipError_t sweep_launch(const DiffMat &m, SweepParams p, hipStream_t stream) {
     return launch_long(p, stream);
   }
   {
-    if (!opt(OPT_GENERAL_KERNELS) && sweep_vec_eligible(m, p)) {
+    if (takes_vec(m, p)) {
       // diagnostic builds: three stamp areas of 256 x 8 x 16 words, used round-robin (one per launch of a 3-D matvec)
       if (chebhip_stamp_buf()) p.in4 = chebhip_stamp_buf() + (size_t)(chebhip_stamp_next() % 3) * (256 * 8 * 16);
       return sweep_vec_launch(m, p, stream);

@@ -135,3 +135,17 @@ def test_argument_errors_of_the_wider_abi(L):
     assert L.chebhip_comm_null_set_shadow(c, 2, None) == 4 and L.chebhip_comm_null_set_shadow(c, 0, None) == 0
     assert L.chebhip_comm_destroy(c) == 0
     assert h.value is None
+
+
+def test_fdpc_step_argument_errors(L):
+    """The step entry points of the fast-diagonalisation solve and the host accessor of its line: argument checks before any device use."""
+    assert L.chebhip_fdpc_line_host(2, None, None, None) == 1                                   # CHEBHIP_ERR_SIZE
+    assert b"interior nodes" in L.chebhip_last_error()
+    assert L.chebhip_fdpc_line_host(259, None, None, None) == 4
+    assert L.chebhip_fdpc_line_host(5, None, None, None) == 4
+    buf = (C.c_double * 9)()
+    lam = (C.c_double * 3)()
+    assert L.chebhip_fdpc_line_host(5, buf, (C.c_double * 9)(), lam) == 0 and all(v > 0 for v in lam)
+    assert L.chebhip_fdpc_step(None, 0, 0, None, None, None) == 4
+    assert L.chebhip_fdpc_step_route(None, 0, 0) == -1
+    assert L.cheb_helmholtz_fdpc(None) is None
