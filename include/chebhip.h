@@ -1136,6 +1136,9 @@ const char *chebhip_option_name(int index);     /* "" past the last option: enum
 
 /* Number of sweep-kernel launches issued by this process so far. */
 long chebhip_launch_count(void);
+/* ... and how many of them ran the 16-byte line kernels (csrc/sweep_vec.hip) rather than the general kernel or a long-line route:
+ * kernel selection is silent, this is how a caller sees it. */
+long chebhip_vec_launch_count(void);
 
 /* Per-stage device timers: when enabled, every entry point listed below brackets its work with a hipEvent pair on
  * the caller's stream (inclusive times: stokes_saddle_apply contains the stokes_op_mult_vv calls of its inner

@@ -28,7 +28,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 # every symbol include/chebhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
-    "chebhip_last_error", "chebhip_version", "chebhip_arch", "chebhip_launch_count",
+    "chebhip_last_error", "chebhip_version", "chebhip_arch", "chebhip_launch_count", "chebhip_vec_launch_count",
     "chebhip_set_option", "chebhip_get_option", "chebhip_option_name",
     "cheb_plan_create", "cheb_apply", "cheb_apply_host", "cheb_plan_destroy", "cheb_plan_size",
     "cheb_plan_create_trimmed", "cheb_apply_lap1d", "cheb_slab_pack", "cheb_slab_unpack_add",
@@ -124,6 +124,7 @@ def lib():
         L.chebhip_last_error.restype = C.c_char_p
         L.chebhip_arch.restype = C.c_char_p
         L.chebhip_launch_count.restype = C.c_long
+        L.chebhip_vec_launch_count.restype = C.c_long
         L.chebhip_set_option.argtypes = [C.c_char_p, C.c_int]
         L.chebhip_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
         L.chebhip_option_name.argtypes = [C.c_int]

@@ -34,6 +34,7 @@ extern "C" const char *chebhip_last_error(void) { return g_err.c_str(); }
 extern "C" int chebhip_version(void) { return 100; }
 extern "C" const char *chebhip_arch(void) { return "gfx950"; }
 extern "C" long chebhip_launch_count(void) { return sweep_launch_count(); }
+extern "C" long chebhip_vec_launch_count(void) { return sweep_vec_launch_count(); }
 
 // ---------------------------------------------------------------------------------------------
 // run-time options (include/chebhip.h; registry in options.cpp): the only switches of the library; the environment is never read

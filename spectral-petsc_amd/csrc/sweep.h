@@ -71,7 +71,7 @@ struct SweepParams {
   // MatShell vectors stay in the reference's dense interior layout.
   unsigned nouter, qmax;
   unsigned in_os, in_rs, acc_os, acc_rs, out_os, out_rs;
-  unsigned in_bytes, acc_bytes, out_bytes;   // set by the launcher: exact sizes for the buffer descriptors of v4
+  unsigned in_len, acc_len, out_len;         // set by the launcher: exact sizes in doubles, what the buffer descriptors of v4 count down from
   // Input made of stacked FIELDS that are not contiguous (cheb_sweep_vec4_kernel only): field f of the input starts
   // in_fskip elements further than the dense stacking would put it, per field (i.e. at f * (field size + in_fskip)).
   // in_fblocks = outer blocks (COLFAST) / lines (JFAST, a multiple of the tile's lines) per field; 0 = dense.
@@ -224,6 +224,7 @@ hipError_t sweep_launch_multi(int n, const DiffMat *const *m, const SweepParams 
 hipError_t sweep_launch_multi_try(int n, const DiffMat *const *m, const SweepParams *p, hipStream_t stream, bool *done);
 
 long sweep_launch_count();
+long sweep_vec_launch_count();    // of them, the launches of the 16-byte kernels (sweep_vec.hip)
 }  // namespace chebhip
 struct cheb_plan;
 struct stokes_op;

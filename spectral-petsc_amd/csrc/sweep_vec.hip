@@ -15,6 +15,7 @@
 // JFAST: stride 1 and even line length; all arrays 16-B aligned.
 #include "sweep.h"
 #include "tile.h"
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -22,6 +23,11 @@ const double *chebhip_stamp_buf();   // chebhip.hip: diagnostic builds (CHEB_STA
 int chebhip_stamp_next();
 
 namespace chebhip {
+
+// launches of the 16-byte kernels of this file (chebhip_vec_launch_count: how a test tells them from the general kernel's)
+static std::atomic<long> g_vec_launches{0};
+long sweep_vec_launch_count() { return g_vec_launches.load(); }
+static void note_vec_launch() { g_vec_launches.fetch_add(1); sweep_note_launch(); }
 
 // one 16-byte piece into an LDS image whose lines may start on 8-byte boundaries
 template <bool ALIGNED16>
@@ -381,9 +387,11 @@ __global__ __launch_bounds__(512, 4) void cheb_sweep_vec_kernel(const SweepParam
 // of a wave is paid in matrix-pipe time, ~6 cycles each, and the flat-address predecessor of this kernel (round 1-2,
 // deleted) issued 300-450 of them per tile and wave next to 128 MFMAs (in-kernel stamps: an epilogue beside the partner
 // wave's chain took 4,400 cycles).  Here
-//   * every global access is a raw BUFFER access: 32-bit byte offset = per-lane constant + one scalar per
-//     tile (one v_add), the hardware range check replaces every `ok ? address : dummy` select (out-of-range
-//     loads return 0, out-of-range stores are dropped; a masked lane gets offset 0x80000000);
+//   * every global access is a raw BUFFER access whose 32-bit byte offset is a per-lane CONSTANT of the launch: what changes
+//     from tile to tile sits in the descriptor, re-based on the scalar unit (tile.h rsrc_at) -- no vector instruction of the loop
+//     forms an address.  The hardware range check replaces every `ok ? address : dummy` select (out-of-range loads return 0,
+//     out-of-range stores are dropped; a masked lane has offset 0x80000000); the one mask that is no array end, the columns
+//     a row's last tile lacks, is a lane mask made from scalars that the stores run under (the epilogue);
 //   * loads are not masked at all: lanes outside the tile read other points of the SAME line (or zeros past
 //     the end of the array), which only meet zero entries of the matrix or feed columns that are never stored;
 //   * the lane exchange that makes 16-byte pieces is ONE instruction per dword, a select whose source carries the DPP broadcast
@@ -421,9 +429,9 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   static_assert(!MUL || RAW == 1, "OUT_MUL exists for the raw forward transform only");
   static_assert(SG == 0 || (MODE == 0 && RAW == 0 && INM == 0 && GATH == 0), "the sign-only store exists for the plain STORE launch");
   using G = TileGeom<KS, JFAST>;
-  // offsets beyond every buffer (the launcher keeps them < 1 GiB): a per-lane constant may carry INVALID, the scalar
-  // part of an offset T_INVALID, and their sum must not wrap back into range
-  constexpr u32 INVALID = 0x80000000u, T_INVALID = 0x40000000u;
+  // a per-lane offset beyond every window: the launcher keeps the offsets of existing elements below 1 GiB, and no descriptor
+  // has more than 2 GiB of records (tile.h rsrc_at)
+  constexpr u32 INVALID = 0x80000000u;
   static_assert(KS >= 16 && G::CH >= 1, "v4 needs two sub-tiles per tile");
 
 #ifdef CHEB_STAMPS
@@ -438,11 +446,13 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   const int nn = p.P - 1, H = p.H;
   const u32 qmax = p.qmax;
 
-  const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc((void *)p.in0, 0, p.in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_in1 = __builtin_amdgcn_make_buffer_rsrc((void *)(INM ? p.in1 : p.in0), 0, INM ? p.in_bytes : 0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_acc = __builtin_amdgcn_make_buffer_rsrc((void *)(ACC ? p.acc : p.in0), 0, ACC ? p.acc_bytes : 0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_acc2 = __builtin_amdgcn_make_buffer_rsrc((void *)(ACC2 ? p.acc2 : p.in0), 0, ACC2 ? p.acc_bytes : 0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc((void *)p.out, 0, p.out_bytes, 0x00020000);
+  // Addressing: every access is a raw buffer access through a descriptor that is RE-BASED per tile on the scalar unit (tile.h
+  // rsrc_at): base = array + origin of the tile (of a loader slot, of a sub-tile) as a 64-bit address, num_records = what is left
+  // of the array from there.  The per-lane offsets are constants of the launch, no vector instruction of the loop forms an
+  // address, and the range check stays the exact mask of the array's end; a tile past the workgroup's last gets num_records = 0.
+
+  // the whole result: gather launches only (see the epilogue)
+  const __amdgpu_buffer_rsrc_t r_whole = __builtin_amdgcn_make_buffer_rsrc((void *)p.out, 0, (GATH == 1) ? p.out_len * 8u : 0u, 0x00020000);
 
   double ae[KS], ao[G::KR > 0 ? G::KR : 1];
   double *aoL = smem + 4 * G::LDS_ELEMS + (w * G::NFL) * 64 + lane;
@@ -455,24 +465,33 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   // line ld_b + s*QSTEP).  Per-lane byte offsets of slot 0 (point / mirror); a slot adds a scalar
   const int ld_a = tid % G::LD_W, ld_b = tid / G::LD_W;
   const int ld_lds0 = JFAST ? ld_b * G::LDJ + 2 * ld_a : ld_b * G::NT + ((2 * ld_a) ^ ((ld_b & 1) << 4));
+  // Slot sg of a lane lies sg * slot doubles behind slot 0 -- further than an instruction's 12-bit immediate reaches -- and has a
+  // descriptor of its own.  COLFAST: the mirror of slot sg is the row nn - ld_b - sg QSTEP, i.e. the row nn - ld_b - (ITEMS - 1) QSTEP
+  // (>= 0: lines of KS k-steps have more than 4 KS points) seen from the origin of slot ITEMS - 1 - sg.
   const u32 in_os8 = p.in_os * 8u, in_rs8 = p.in_rs * 8u;
   const u32 lj = JFAST ? (u32)ld_b * in_os8 + (u32)(2 * ld_a) * 8u : (u32)(2 * ld_a) * 8u + (u32)ld_b * in_rs8;
-  const u32 lm = JFAST ? (u32)ld_b * in_os8 + (u32)(nn - 2 * ld_a - 1) * 8u : (u32)(2 * ld_a) * 8u + (u32)(nn - ld_b) * in_rs8;
-  const u32 slot8 = JFAST ? (u32)G::QSTEP * in_os8 : (u32)G::QSTEP * in_rs8;      // byte step between two slots of a lane
-  // byte offset of a tile's origin in an array of geometry (os8, rs8), or INVALID past the workgroup's last tile
-  auto tile_off = [&](u32 tl, bool valid, u32 os8) -> u32 {
-    if (JFAST) return valid ? tl * G::NT * os8 : T_INVALID;
+  const u32 lm = JFAST ? (u32)ld_b * in_os8 + (u32)(nn - 2 * ld_a - 1) * 8u : (u32)(2 * ld_a) * 8u + (u32)(nn - ld_b - (G::ITEMS - 1) * G::QSTEP) * in_rs8;
+  const u32 slot = JFAST ? (u32)G::QSTEP * p.in_os : (u32)G::QSTEP * p.in_rs;      // doubles between two slots of a lane
+  // The slots of chunk 0 / 1 (one chunk rides under one sub-tile's chain).  COLFAST: the outer pair {0, ITEMS - 1} and the inner pair,
+  // so that a chunk's slots and their mirrors share two descriptors; JFAST and the gather loader (no descriptors): neighbours.
+  static_assert(G::CH == 2 && G::ITEMS == 4, "two chunks of two loader slots");
+  auto slot_of = [](int chunk, int s) -> int { return (JFAST || GATH) ? chunk * G::CH + s : (s == 0 ? chunk : G::ITEMS - 1 - chunk); };
+  // first element of tile tl in an array whose outer blocks (COLFAST) / lines (JFAST) lie os doubles apart (a scalar)
+  auto tile_org = [&](u32 tl, u32 os) -> u32 {
+    if (JFAST) return tl * G::NT * os;
     const u32 o = tl / tpo, q0 = (tl - o * tpo) * G::NT;
-    return valid ? o * os8 + q0 * 8u : T_INVALID;
+    return o * os + q0;
   };
-
   // ... of the INPUT, whose fields may be spaced out (sweep.h: in_fblocks / in_fskip)
-  const u32 fb = p.in_fblocks, fskip8 = p.in_fskip * 8u;
-  auto in_tile_off = [&](u32 tl) -> u32 {
-    u32 off = tile_off(tl, true, in_os8);
-    if (fb) off += __umulhi(JFAST ? tl * G::NT : tl / tpo, p.in_fblocks_inv) * fskip8;
-    return off;
+  const u32 fb = p.in_fblocks;
+  auto in_tile_org = [&](u32 tl) -> u32 {
+    u32 org = tile_org(tl, p.in_os);
+    if (fb) org += __umulhi(JFAST ? tl * G::NT : tl / tpo, p.in_fblocks_inv) * p.in_fskip;
+    return org;
   };
+  // the wave group's sub-tile `sub` lies this many doubles behind the tile's origin in an array of pitch os (a scalar: ng is the wave's)
+  const u32 ngs = (G::NG == 1) ? 0u : (u32)__builtin_amdgcn_readfirstlane(ng);
+  auto sub_org = [&](int sub, u32 os) -> u32 { return (ngs * G::NSUB + (u32)sub) * 16u * (JFAST ? os : 1u); };
 
   // GATH: byte address of (row, first column) in vector 0 of the array that holds the row, and that array's doubles per vector,
   // for the thread's ITEMS loader slots (row ld_b + sg QSTEP) and their mirrors
@@ -542,27 +561,27 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       u32 qq = q0 + 2u * (u32)ld_a; if (qq > qmax - 2u) qq = qmax - 2u;
 #pragma unroll
       for (int s = 0; s < G::CH; s++) {
-        const int sg = chunk * G::CH + s;
+        const int sg = slot_of(chunk, s);
         rj[s] = *(gd2p)(gb_j[sg] + ((unsigned long long)(o + gf0) * glq_j[sg] + qq) * 8ull);
         rm[s] = *(gd2p)(gb_m[sg] + ((unsigned long long)(o + gf0) * glq_m[sg] + qq) * 8ull);
       }
       return;
     }
-    const u32 t0 = in_tile_off(tl);
+    const u32 org = in_tile_org(tl);
     if constexpr (INM != 0) {
       d2 (&ej)[ECH] = (&rj == &rjA) ? ejA : ejB; d2 (&em)[ECH] = (&rj == &rjA) ? emA : emB;
 #pragma unroll
       for (int s = 0; s < G::CH; s++) {
-        const u32 so = (u32)(chunk * G::CH + s) * slot8;
-        ej[s] = ld16(r_in1, lj + (valid ? t0 + so : T_INVALID));
-        em[s] = ld16(r_in1, lm + (valid ? (JFAST ? t0 + so : t0 - so) : T_INVALID));
+        const int sg = slot_of(chunk, s), sm = JFAST ? sg : G::ITEMS - 1 - sg;
+        ej[s] = ld16(rsrc_at(p.in1, p.in_len, org + (u32)sg * slot, valid), lj);
+        em[s] = ld16(rsrc_at(p.in1, p.in_len, org + (u32)sm * slot, valid), lm);
       }
     }
 #pragma unroll
     for (int s = 0; s < G::CH; s++) {
-      const u32 so = (u32)(chunk * G::CH + s) * slot8;                          // scalar
-      rj[s] = ld16(r_in, lj + (valid ? t0 + so : T_INVALID));
-      rm[s] = ld16(r_in, lm + (valid ? (JFAST ? t0 + so : t0 - so) : T_INVALID));
+      const int sg = slot_of(chunk, s), sm = JFAST ? sg : G::ITEMS - 1 - sg;
+      rj[s] = ld16(rsrc_at(p.in0, p.in_len, org + (u32)sg * slot, valid), lj);
+      rm[s] = ld16(rsrc_at(p.in0, p.in_len, org + (u32)sm * slot, valid), lm);
     }
   };
   const bool oddP = (p.P & 1) != 0;                    // a self-paired middle point exists (COLFAST only; JFAST needs even P)
@@ -570,7 +589,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
     double *dE = smem + buf * (2 * G::LDS_ELEMS), *dO = dE + G::LDS_ELEMS;
 #pragma unroll
     for (int s = 0; s < G::CH; s++) {
-      const int idx = ld_lds0 + (chunk * G::CH + s) * G::LDS_QSTEP;
+      const int idx = ld_lds0 + slot_of(chunk, s) * G::LDS_QSTEP;
       d2 e, o;
       d2 xj = rj[s], xm = rm[s];
       if constexpr (INM != 0) {
@@ -584,7 +603,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
         e = xj + xm;
         o = xj - xm;                                   // the middle point of an odd line is its own mirror: o = 0
         // (a scalar branch: as a select hipcc pays four v_cndmask per slot on every line length, 16 per tile and wave)
-        if (oddP) { asm volatile("" ::: "memory"); const bool mid = 2 * (ld_b + (chunk * G::CH + s) * G::QSTEP) == nn; if (mid) e = xj; }
+        if (oddP) { asm volatile("" ::: "memory"); const bool mid = 2 * (ld_b + slot_of(chunk, s) * G::QSTEP) == nn; if (mid) e = xj; }
       } else {
         e = d2{xj.x + xm.y, xj.y + xm.x};
         o = d2{xj.x - xm.y, xj.y - xm.x};
@@ -621,20 +640,19 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       c_lo[rp] = (u32)(4 * r + kq) * (p.acc_os * 8u) + (u32)(ok ? nn - ie - 1 : 0) * 8u;
     }
   }
-  const u32 out_os8 = p.out_os * 8u, acc_os8 = p.acc_os * 8u;
-  const u32 sub8_out = JFAST ? 16u * out_os8 : 16u * 8u, sub8_acc = JFAST ? 16u * acc_os8 : 16u * 8u;   // sub-tile 1 vs 0
-  const u32 ng8_out = (u32)ng * G::NSUB * sub8_out, ng8_acc = (u32)ng * G::NSUB * sub8_acc;
   const double alpha = p.alpha, alpha_lo = (p.sym || RAW == 1) ? p.alpha : -p.alpha;      // mirror row: D: b - a; D D: a - b
 
   auto acc_issue = [&](u32 tl, bool valid, int sub, d2 (&ah)[2], d2 (&al)[2]) {
     if (!ACC) return;
-    const u32 t0 = tile_off(tl, valid, acc_os8) + ng8_acc + (u32)sub * sub8_acc;
+    const u32 org = tile_org(tl, p.acc_os) + sub_org(sub, p.acc_os);
+    const __amdgpu_buffer_rsrc_t r_acc = rsrc_at(p.acc, p.acc_len, org, valid);
 #pragma unroll
-    for (int rp = 0; rp < 2; rp++) { ah[rp] = ld16(r_acc, c_hi[rp] + t0); al[rp] = ld16(r_acc, c_lo[rp] + t0); }
+    for (int rp = 0; rp < 2; rp++) { ah[rp] = ld16(r_acc, c_hi[rp]); al[rp] = ld16(r_acc, c_lo[rp]); }
     if constexpr (ACC2) {
       d2 (&bh)[2] = (&ah == &accX_hi) ? acc2X_hi : acc2Y_hi; d2 (&bl)[2] = (&ah == &accX_hi) ? acc2X_lo : acc2Y_lo;
+      const __amdgpu_buffer_rsrc_t r_acc2 = rsrc_at(p.acc2, p.acc_len, org, valid);
 #pragma unroll
-      for (int rp = 0; rp < 2; rp++) { bh[rp] = ld16(r_acc2, c_hi[rp] + t0); bl[rp] = ld16(r_acc2, c_lo[rp] + t0); }
+      for (int rp = 0; rp < 2; rp++) { bh[rp] = ld16(r_acc2, c_hi[rp]); bl[rp] = ld16(r_acc2, c_lo[rp]); }
     }
   };
 
@@ -696,11 +714,28 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
   };
   // out = (acc +) alpha * (sums) for sub-tile `sub` of tile tl
   auto epilogue = [&](u32 tl, int sub, const v4d &ce, const v4d &co, const d2 (&acc_hi)[2], const d2 (&acc_lo)[2]) {
-    u32 t0 = tile_off(tl, true, out_os8) + ng8_out + (u32)sub * sub8_out;
-    u32 t0v = t0;                                      // per-lane: INVALID where the tile's last column block ends early
-    if (!JFAST) {
-      const u32 o = tl / tpo, q = (tl - o * tpo) * G::NT + (ng * G::NSUB + sub) * 16 + l16e;
-      t0v = (q < qmax) ? t0 : T_INVALID;
+    const __amdgpu_buffer_rsrc_t r_out = (GATH == 1) ? r_whole : rsrc_at(p.out, p.out_len, tile_org(tl, p.out_os) + sub_org(sub, p.out_os), true);
+    // COLFAST: the last tile of a row may end early.  Its missing columns are whole lane pairs of the sub-tile, the same in every
+    // quarter of the wave: the lanes that store come from scalars (all of them in every other tile), and the stores run under that
+    // mask (below)
+    unsigned long long cols = ~0ull;
+    // (the gather launches keep ONE descriptor of the whole result and an offset per access, with the column mask in it: with the
+    // re-based form hipcc's register allocation of their loop runs out of the 256 VGPRs -- profiles/sweep_saddr/loop_counts.txt;
+    // their launcher keeps the result below the 32-bit reach of such offsets)
+    u32 g_t0v = 0;
+    if constexpr (GATH == 1) {
+      const u32 o = tl / tpo, q0 = (tl - o * tpo) * G::NT + sub_org(sub, 1u);
+      g_t0v = (q0 + (u32)l16e < qmax) ? (o * p.out_os + q0) * 8u : 0x40000000u;
+    }
+    if (!JFAST && !GATH) {
+      const u32 o = tl / tpo;
+      const u32 left = qmax - (tl - o * tpo) * G::NT, c0 = sub_org(sub, 1u);         // columns of the row from this tile on; the sub-tile's first
+      u32 c0x = c0;
+      asm("" : "+s"(c0x));                                                           // (scalar max - c0, not a vector saturating difference: tile.h rsrc_at)
+      u32 k = (left > c0x ? left : c0x) - c0;
+      k = k < 16u ? k : 16u;
+      const u32 m16 = (1u << k) - 1u, m32 = m16 | (m16 << 16);
+      cols = (unsigned long long)m32 | ((unsigned long long)m32 << 32);
     }
     double hi[4], lo[4];
 #pragma unroll
@@ -749,9 +784,25 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
         const unsigned long long al = (cv && o_lo[rp] != INVALID) ? pb_lo[rp] + (of * pl_lo[rp] + q) * 8ull : psink;
         *(gd2w)ah = vh;
         *(gd2w)al = vl;
+      } else if (GATH == 1) {
+        st16(r_out, o_hi[rp] + g_t0v, vh);
+        st16(r_out, o_lo[rp] + g_t0v, vl);
+      } else if (JFAST) {
+        st16(r_out, o_hi[rp], vh);
+        st16(r_out, o_lo[rp], vl);
       } else {
-        st16(r_out, o_hi[rp] + t0v, vh);
-        st16(r_out, o_lo[rp] + t0v, vl);
+        // the two stores with the lanes of `cols` only, in straight-line code: EXEC is set and restored by hand (hipcc takes no
+        // clobber of a reserved register: it warns and promises nothing), and the fences keep the schedulers out -- what the stores read has been computed above the first
+        // fence.  Nothing tells the register allocator that the region runs with part of the lanes, so a copy or a reload placed
+        // inside it would be wrong: tests/test_sweep_listing.py compiles this file and holds every such region to the two stores,
+        // s_nop and s_waitcnt.  (The compiler-visible form, a branch on the mask, was not measured: reasoned only, its paths
+        // have different numbers of stores in flight where hipcc places the later waits -- DESIGN_history.md section 16.)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_mov_b64 exec, %0" :: "s"(cols) : "memory");
+        st16(r_out, o_hi[rp], vh);
+        st16(r_out, o_lo[rp], vl);
+        asm volatile("s_mov_b64 exec, -1" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
   };
@@ -766,7 +817,7 @@ __device__ __forceinline__ void vec4_body(const SweepParams &p, double *smem, co
       if constexpr (!ONEBUF) acc_issue(tile, true, 0, accX_hi, accX_lo);
       issue_loads(nx, nx < t_hi, 0, rjA, rmA);
 #pragma unroll
-      for (int q = 0; q < 4; q++) st16(r_out, INVALID, d2{0.0, 0.0});
+      for (int q = 0; q < 4; q++) st16((GATH == 1) ? r_whole : rsrc_at(p.out, p.out_len, 0u, false), INVALID, d2{0.0, 0.0});
       if constexpr (ONEBUF) acc_issue(tile, true, 0, accX_hi, accX_lo);
     }
     lds_barrier();
@@ -893,14 +944,14 @@ static hipError_t launch_v4(const SweepParams &p, unsigned grid, hipStream_t str
   // alpha = -1 on a centro-symmetric matrix (alpha_lo = alpha): the signs ride in the recombination, no multiply (vec4_body, SG)
   else if (p.alpha == -1.0 && p.sym && !opt(OPT_SWEEP_ALPHA_MULTIPLY)) hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0, 0, 0, 1>), dim3(grid), dim3(512), 0, stream, p);
   else hipLaunchKernelGGL((cheb_sweep_vec4_kernel<KS, JFAST, 0>), dim3(grid), dim3(512), 0, stream, p);
-  sweep_note_launch();
+  note_vec_launch();
   return hipGetLastError();
 }
 
 // Geometry defaults, tile count and (KS >= 16) the byte sizes of the buffer descriptors.  Returns 4: cheb_sweep_vec4_kernel
 // runs the launch; 1: cheb_sweep_vec_kernel (lines of at most 64 points, dense geometry); 0: neither (per-array geometry
-// on short lines, or an array of 0.94 GB and more -- the 32-bit buffer offsets of the long-line kernel do not reach;
-// the general kernel of sweep.hip runs those).
+// on short lines, or a tile window of 1 GiB and more / an array of 32 GiB and more -- the 32-bit offsets of the long-line
+// kernel's re-based descriptors do not reach; the general kernel of sweep.hip runs those).
 template <int KS, bool JFAST>
 static int prepare_v(SweepParams &p) {
   constexpr int NT = TileGeom<KS, JFAST>::NT;
@@ -935,12 +986,25 @@ static int prepare_v(SweepParams &p) {
       p.in_fblocks_inv = (unsigned)((0x100000000ull + p.in_fblocks - 1) / p.in_fblocks);
       if ((unsigned long long)(JFAST ? p.ncols + NT : p.nouter) * p.in_fblocks >= 0x100000000ull) return 0;   // exactness of the reciprocal
     }
-    if (!(bi < 0x38000000ull && ba < 0x38000000ull && bo < 0x38000000ull)) return 0;   // < 1 GiB minus slack: see T_INVALID
-    p.in_bytes = (unsigned)bi; p.acc_bytes = (unsigned)ba; p.out_bytes = (unsigned)bo;
+    // The descriptors are re-based per tile (tile.h rsrc_at), so the 32-bit byte offsets span one tile's window only: a lane's
+    // offsets stay below 1 GiB (half of RSRC_MAX_RECORDS, so that no sum with a slot or a masked lane wraps), and the tile
+    // origins, counted in doubles, below 2^32 with the window on top.
+    auto window = [&](unsigned os, unsigned rs) -> unsigned long long {      // bytes, generous: the padded line, all its slots
+      constexpr unsigned long long HP2 = 2ull * TileGeom<KS, JFAST>::HP;
+      return (JFAST ? (unsigned long long)NT * os + HP2 : HP2 * rs + NT) * 8ull;
+    };
+    const unsigned long long wi = window(p.in_os, p.in_rs), wa = window(p.acc_os, p.acc_rs), wo = window(p.out_os, p.out_rs);
+    if (!(wi < 0x40000000ull && wa < 0x40000000ull && wo < 0x40000000ull)) return 0;
+    if (!(bi + wi < 0x800000000ull && ba + wa < 0x800000000ull && bo + wo < 0x800000000ull)) return 0;
+    p.in_len = (unsigned)(bi / 8ull); p.acc_len = (unsigned)(ba / 8ull); p.out_len = (unsigned)(bo / 8ull);
     return 4;
   }
   return custom ? 0 : 1;
 }
+
+// A gather launch addresses its result through ONE descriptor with 32-bit byte offsets (vec4_body's epilogue): the dense
+// result stays below 1 GiB minus slack, as every array of the long-line kernel did before its descriptors were re-based.
+static bool gather_out_ok(const SweepParams &p) { return (unsigned long long)p.out_len * 8ull < 0x38000000ull; }
 
 // Workgroups of a persistent launch per CU.  Lines of at most 64 points (KS <= 8) need 64-70 KiB of LDS and at most 124
 // VGPRs per workgroup: two fit on a CU, and at such sizes (64^3: a few tiles per workgroup) one workgroup's memory round
@@ -964,7 +1028,7 @@ static hipError_t launch_v(const SweepParams &p0, hipStream_t stream) {
     if (p.in_mode == IN_MUL) return hipErrorInvalidValue;
     if (p.out_mode == OUT_STORE) hipLaunchKernelGGL((cheb_sweep_vec_kernel<KS, JFAST, false>), dim3(grid), dim3(512), 0, stream, p);
     else hipLaunchKernelGGL((cheb_sweep_vec_kernel<KS, JFAST, true>), dim3(grid), dim3(512), 0, stream, p);
-    sweep_note_launch();
+    note_vec_launch();
     return hipGetLastError();
   }
 }
@@ -1029,7 +1093,7 @@ hipError_t sweep_vec_launch(const DiffMat &m, SweepParams p, hipStream_t stream)
 template <int KS>
 static hipError_t launch_gather_t(SweepParams p, const GatherSrc &g, hipStream_t stream, bool *done) {
   const int gen = prepare_v<KS, false>(p);
-  if (gen != 4) return hipSuccess;
+  if (gen != 4 || !gather_out_ok(p)) return hipSuccess;
   hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err);
   if (cu_err != hipSuccess) return cu_err;
   const unsigned grid = p.ntiles < (unsigned)ncu ? p.ntiles : (unsigned)ncu;
@@ -1037,7 +1101,7 @@ static hipError_t launch_gather_t(SweepParams p, const GatherSrc &g, hipStream_t
   if (grid == 0) return hipSuccess;
   if (g.push) hipLaunchKernelGGL((cheb_sweep_vec4_gather_kernel<KS, true>), dim3(grid), dim3(512), 0, stream, p, g);
   else hipLaunchKernelGGL((cheb_sweep_vec4_gather_kernel<KS, false>), dim3(grid), dim3(512), 0, stream, p, g);
-  sweep_note_launch();
+  note_vec_launch();
   return hipGetLastError();
 }
 
@@ -1081,7 +1145,7 @@ static hipError_t launch_multi_t(int n, SweepParams *jobs, hipStream_t stream, b
     SweepParams &p = jobs[j];
     const bool jfast = p.inner < 16;
     const int gen = jfast ? prepare_v<KS, true>(p) : prepare_v<KS, false>(p);
-    if (gen == 0) return hipSuccess;                       // not for this launch: done stays false
+    if (gen == 0 || (g && ((gmask >> j) & 1u) && !gather_out_ok(p))) return hipSuccess;   // not for this launch: done stays false
     total += p.ntiles;
   }
   // One workgroup per CU in all, shared out in proportion to the jobs' tiles: every workgroup walks several tiles with
@@ -1156,7 +1220,7 @@ static hipError_t launch_multi_t(int n, SweepParams *jobs, hipStream_t stream, b
     else if (g) hipLaunchKernelGGL((cheb_sweep_multi_gather_kernel<KS, false>), dim3(b), dim3(512), 0, stream, mp, *g, gmask);
     else hipLaunchKernelGGL((cheb_sweep_multi_kernel<KS>), dim3(b), dim3(512), 0, stream, mp);
   }
-  sweep_note_launch();
+  note_vec_launch();
   *done = true;
   return hipGetLastError();
 }

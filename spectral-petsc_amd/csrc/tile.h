@@ -152,6 +152,22 @@ __device__ __forceinline__ void xpair(double a, double b, double &x, double &y) 
   x = __hiloint2double(xh, xl); y = __hiloint2double(yh, yl);
 }
 
+// Descriptor of the window that starts `org` doubles into an array of `len` doubles, formed on the scalar unit: base = a + org as a
+// 64-bit address, num_records = the bytes left of the array from there (none when the window starts behind its end, or when
+// !valid), at most RSRC_MAX_RECORDS.  An access through it at a per-lane byte offset below RSRC_MAX_RECORDS is in range exactly when
+// it lies inside the array; an offset of RSRC_MAX_RECORDS and more is out of range always (the lanes that must not store).
+// org and len are wave-uniform and org + the window < 2^32 doubles (the launchers see to it), so arrays of any size below 32 GiB do.
+// (The subtraction is written as max - org with one operand hidden from the optimiser: as a saturating difference hipcc computes it
+// on the VECTOR unit -- the scalar one has no such instruction -- and the descriptor would sit in vector registers.)
+constexpr u32 RSRC_MAX_RECORDS = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_at(const double *a, u32 len, u32 org, bool valid) {
+  u32 orgx = org;
+  asm("" : "+s"(orgx));
+  u32 rem = (len > orgx ? len : orgx) - org;
+  rem = rem < RSRC_MAX_RECORDS / 8u ? rem : RSRC_MAX_RECORDS / 8u;
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(a + org), 0, valid ? rem * 8u : 0u, 0x00020000);
+}
+
 // raw buffer accesses: 32-bit byte offset, the hardware range check is the mask (out-of-range loads return 0, stores are dropped)
 __device__ __forceinline__ d2 ld16(__amdgpu_buffer_rsrc_t r, u32 off) { return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); }
 __device__ __forceinline__ void st16(__amdgpu_buffer_rsrc_t r, u32 off, d2 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, (int)off, 0, 0); }
