@@ -1062,6 +1062,46 @@ int stokes_saddle_apply(void *s, const double *x_dev, double *y_dev, void *strea
 int stokes_saddle_iterations(const stokes_saddle *s, int which);
 
 /* ------------------------------------------------------------------------- */
+/* Periodic (Fourier) directions.  A periodic direction of n     */
+/* points, 2 <= n <= 256, has the nodes x_j = -1 + 2 j / n (period 2, no      */
+/* duplicated end point) and runs on the same dense line kernels as a CGL     */
+/* line.  basis[k] = 0: CGL (two walls), 1: Fourier.                          */
+/* ------------------------------------------------------------------------- */
+enum { CHEB_BASIS_CGL = 0, CHEB_BASIS_FOURIER = 1 };
+enum { CHEB_FOURIER_COS = 0, CHEB_FOURIER_SIN = 1, CHEB_FOURIER_NYQUIST = 2 };
+/* Host-side matrices; they need no device.  Long double, rounded once; n x n row-major.
+ *   diff_matrix  order 1: D_F = pi D_theta, D_theta[i][j] = 1/2 (-1)^(i-j) cot(pi (i-j) / n) for even n, 1/2 (-1)^(i-j) /
+ *                sin(pi (i-j) / n) for odd n, zero diagonal; order 2: D_F D_F (NOT the textbook second-derivative matrix: for
+ *                even n the two differ at the Nyquist vector (-1)^j, which D_F D_F annihilates)
+ *   modes        position p of the coefficient layout -> wavenumber k[p] and kind[p] (CHEB_FOURIER_*): the parity layout of
+ *                cheb_helmholtz_line_host about the flip j -> n-1-j, which reflects x about c = -1/n.  Even modes at p < ceil(n/2):
+ *                the constant (COS, k = 0) at p = 0 and cos(pi k (x - c)) at p = k; odd modes at n-1-q: for even n the Nyquist
+ *                vector (k = n/2) at q = 0 and sin(pi k (x - c)) at q = k, for odd n sin at q = k - 1; 1 <= k <= floor((n-1)/2)
+ *   modal_matrix which = 1 backward B (column p = mode p with amplitude 1: the constant's coefficient is the mean), 0 forward
+ *                T = B^-1; every column of B and every row of T is even or odd under the flip bit for bit
+ *   line         -scale^2 D_F D_F = S diag(lam) S^-1 in closed form: S = B, Sinv = T, lam = (pi k scale)^2 and exactly 0 for the
+ *                constant and the Nyquist vector */
+int  cheb_fourier_nodes_host(int n, double *x);
+int  cheb_fourier_diff_matrix_host(int n, int order, double *D);
+int  cheb_fourier_modes_host(int n, int *k, int *kind);
+int  cheb_fourier_modal_matrix_host(int n, int which, double *M);
+int  cheb_fourier_line_host(int n, double scale, double *S, double *Sinv, double *lam);
+/* cheb_grad_create with a basis per direction (basis not NULL): a Fourier direction differentiates with D_F, and the Laplacian
+ * with D_F D_F, through the same sweeps.  All-zero basis: the handle and the bits of cheb_grad_create. */
+int  cheb_grad_create_basis(int d, const int *dims, const double *scale, const int *basis, cheb_grad **out);
+/* cheb_modal_create with a basis per direction: forward / backward / filter use T, B and B diag(sigma) T of
+ * cheb_fourier_modal_matrix_host on a Fourier direction (sigma per coefficient POSITION), integrate the weight 2 / n. */
+int  cheb_modal_create_basis(int d, const int *dims, int nfields, const int *basis, cheb_modal **out);
+/* cheb_helmholtz_create_box with a basis per direction.  A Fourier direction k has dims[k] unknowns (2 <= dims[k] <= 256), no faces
+ * and no entries in g; its four bc values are not read (bc may be NULL when every direction is periodic).  The unknown-node arrays
+ * are row-major over M_k = dims[k] (Fourier) or dims[k] - 2 (wall) points per direction, size = nfields * prod M_k; boundary_size =
+ * nfields * (N - G) counts the nodes that are end nodes of some wall direction, in row-major order.  singular: sigma = 0 and every
+ * direction periodic or Neumann / Neumann; the solve then drops every product of zero-eigenvalue modes (the constants and, on a
+ * periodic direction of even extent, the Nyquist vector).  All-zero basis: cheb_helmholtz_create_box itself. */
+int  cheb_helmholtz_create_basis(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nfields,
+                                 cheb_helmholtz **out);
+
+/* ------------------------------------------------------------------------- */
 /* Instrumentation (the reference has none: SURVEY 5.1).                      */
 /* ------------------------------------------------------------------------- */
 /* Run-time options: named integer switches, process-wide, read where they apply (the library never reads the

@@ -83,6 +83,8 @@ ABI_SYMBOLS = [
     "cheb_grad_div", "cheb_grad_curl", "cheb_grad_strain", "cheb_grad_laplacian", "cheb_grad_invariants",
     "cheb_layout_create", "cheb_layout_destroy", "cheb_layout_size", "cheb_layout_map_host", "cheb_layout_unpack", "cheb_layout_pack",
     "cheb_helmholtz_create_box", "cheb_helmholtz_line_box_host",
+    "cheb_fourier_nodes_host", "cheb_fourier_diff_matrix_host", "cheb_fourier_modes_host", "cheb_fourier_modal_matrix_host",
+    "cheb_fourier_line_host", "cheb_grad_create_basis", "cheb_modal_create_basis", "cheb_helmholtz_create_basis",
     "cheb_project_create", "cheb_project_destroy", "cheb_project_size", "cheb_project_singular", "cheb_project_faces_host",
     "cheb_project_apply",
     "cheb_opfun_create", "cheb_opfun_destroy", "cheb_opfun_set_terms", "cheb_opfun_apply", "cheb_opfun_apply_full", "cheb_opfun_size",
@@ -352,6 +354,14 @@ def lib():
         L.cheb_layout_pack.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp]
         L.cheb_helmholtz_create_box.argtypes = [C.c_int, ip, dp, dp, C.c_double, C.c_int, C.POINTER(vp)]
         L.cheb_helmholtz_line_box_host.argtypes = [C.c_int, dp, C.c_double, dp, dp, dp, dp, dp, dp]
+        L.cheb_fourier_nodes_host.argtypes = [C.c_int, dp]
+        L.cheb_fourier_diff_matrix_host.argtypes = [C.c_int, C.c_int, dp]
+        L.cheb_fourier_modes_host.argtypes = [C.c_int, ip, ip]
+        L.cheb_fourier_modal_matrix_host.argtypes = [C.c_int, C.c_int, dp]
+        L.cheb_fourier_line_host.argtypes = [C.c_int, C.c_double, dp, dp, dp]
+        L.cheb_grad_create_basis.argtypes = [C.c_int, ip, dp, ip, C.POINTER(vp)]
+        L.cheb_modal_create_basis.argtypes = [C.c_int, ip, C.c_int, ip, C.POINTER(vp)]
+        L.cheb_helmholtz_create_basis.argtypes = [C.c_int, ip, ip, dp, dp, C.c_double, C.c_int, C.POINTER(vp)]
         L.cheb_project_create.argtypes = [C.c_int, ip, ip, dp, C.c_int, C.POINTER(vp)]
         L.cheb_project_destroy.argtypes = [vp]
         L.cheb_project_size.argtypes = [vp, C.c_int]
@@ -608,14 +618,22 @@ def sharp_filter(n, keep):
 class ChebModal(_Handle):
     """The modal side of `nfields` stacked full-grid fields on the CGL grid `dims` (cheb_modal_*): values <-> Chebyshev
     coefficients, modal filters, per-direction spectra and Clenshaw-Curtis integrals.  Fields are field-major, row-major over all
-    nodes; size() values per array.  Everything is asynchronous on torch's current stream."""
+    nodes; size() values per array.  Everything is asynchronous on torch's current stream.  periodic (None: no direction): one
+    flag per direction; a flagged direction (2 <= dims[k] <= 256) transforms with fourier_modal_matrix, its coefficients laid out
+    as fourier_modes(dims[k]) says, integrates with the weight 2 / dims[k], and takes its filter's sigma per coefficient position
+    (fourier_filter expands a function of the wavenumber); spectrum sums squares per position, the caller folds cos / sin pairs."""
     _destroy = "cheb_modal_destroy"
 
-    def __init__(self, dims, nfields=1):
+    def __init__(self, dims, nfields=1, periodic=None):
         self.dims = tuple(int(d) for d in dims)
         self.nfields = int(nfields)
+        self.periodic = _periodic_flags(periodic, len(self.dims))
         h = C.c_void_p()
-        _chk(lib().cheb_modal_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        if periodic is None:
+            _chk(lib().cheb_modal_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        else:
+            _chk(lib().cheb_modal_create_basis(len(self.dims), _ints(self.dims), self.nfields, _ints([int(p) for p in self.periodic]),
+                                               C.byref(h)))
         self._h = h
 
     def size(self):
@@ -665,6 +683,80 @@ class ChebModal(_Handle):
         _chk(lib().cheb_modal_integrate(self._h, _dev_ptr(u, self.size()), None if v is None else _dev_ptr(v, self.size()),
                                         _dev_ptr(out, self.nfields), _stream()))
         return out
+
+
+def _periodic_flags(periodic, d):
+    if periodic is None:
+        return (False,) * d
+    flags = tuple(bool(p) for p in periodic)
+    if len(flags) != d:
+        raise ValueError("periodic: expected %d flags, got %d" % (d, len(flags)))
+    return flags
+
+
+def fourier_nodes(n):
+    """The n nodes x_j = -1 + 2 j / n of a periodic direction (cheb_fourier_nodes_host): period 2, no duplicated end point;
+    2 <= n <= 256.  Needs no device."""
+    import numpy as np
+    x = np.empty(max(int(n), 0))
+    _chk(lib().cheb_fourier_nodes_host(int(n), _np_dp(x) if x.size else None))
+    return x
+
+
+def fourier_diff_matrix(n, order=1):
+    """D_F (order 1) or D_F D_F (order 2) of a periodic direction of n nodes as an (n, n) numpy array (cheb_fourier_diff_matrix_host):
+    D_F = pi D_theta with D_theta[i][j] = 1/2 (-1)^(i-j) cot(pi (i-j) / n) for even n and 1/2 (-1)^(i-j) / sin(pi (i-j) / n) for
+    odd n, zero diagonal.  The second derivative is the product, formed in long double and rounded once -- not the textbook
+    second-derivative matrix, from which it differs at the Nyquist vector of an even n.  Needs no device."""
+    import numpy as np
+    D = np.empty((max(int(n), 0),) * 2)
+    _chk(lib().cheb_fourier_diff_matrix_host(int(n), int(order), _np_dp(D) if D.size else None))
+    return D
+
+
+FOURIER_KINDS = ("cos", "sin", "nyquist")        # CHEB_FOURIER_*
+
+
+def fourier_modes(n):
+    """The coefficient layout of a periodic direction of n nodes (cheb_fourier_modes_host): a list of (k, kind) per position, kind
+    one of FOURIER_KINDS.  With c = -1 / n, the point the flip j -> n-1-j reflects about: position 0 is the constant (0, "cos"),
+    position k <= floor((n-1)/2) is cos(pi k (x - c)); from the far end, position n-1 is the Nyquist vector (n/2, "nyquist") for
+    even n, followed downwards by sin(pi k (x - c)), k = 1, 2, ...; for odd n the sines start at n-1.  Needs no device."""
+    n = int(n)
+    k, kind = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+    _chk(lib().cheb_fourier_modes_host(n, k, kind))
+    return [(k[p], FOURIER_KINDS[kind[p]]) for p in range(n)]
+
+
+def fourier_modal_matrix(n, which):
+    """The transform matrix of a periodic direction (cheb_fourier_modal_matrix_host) as an (n, n) numpy array: "backward" B, whose
+    column p is mode p of fourier_modes(n) with amplitude 1 (the constant's coefficient is the mean, a cos / sin coefficient the
+    amplitude), or "forward" T = B^-1.  Needs no device."""
+    import numpy as np
+    if which not in MODAL:
+        raise ValueError("transform %r: expected one of %s" % (which, sorted(MODAL)))
+    M = np.empty((max(int(n), 0),) * 2)
+    _chk(lib().cheb_fourier_modal_matrix_host(int(n), MODAL[which], _np_dp(M) if M.size else None))
+    return M
+
+
+def fourier_line(n, scale=1.0):
+    """(S, Sinv, lam) of the line operator -scale^2 D_F D_F on all n nodes of a periodic direction (cheb_fourier_line_host), in
+    closed form: S = fourier_modal_matrix(n, "backward"), Sinv its inverse, lam = (pi k scale)^2 in the layout of fourier_modes(n),
+    exactly 0 for the constant and the Nyquist vector.  Needs no device."""
+    import numpy as np
+    n = int(n)
+    S, Si, lam = np.empty((max(n, 0),) * 2), np.empty((max(n, 0),) * 2), np.empty(max(n, 0))
+    ptr = lambda a: _np_dp(a) if a.size else None
+    _chk(lib().cheb_fourier_line_host(n, float(scale), ptr(S), ptr(Si), ptr(lam)))
+    return S, Si, lam
+
+
+def fourier_filter(n, sigma_of_k):
+    """sigma per coefficient position of a periodic direction from a function of the wavenumber k = 0 .. n // 2 (what
+    ChebModal.set_filter takes there): a cos / sin pair gets one value."""
+    import numpy as np
+    return np.array([float(sigma_of_k(k)) for k, _ in fourier_modes(n)], dtype=np.float64)
 
 
 def cgl_nodes(n):
@@ -1195,13 +1287,16 @@ class ChebGrad(_Handle):
     invariants of a gradient tensor.  scale[k] multiplies the derivative along direction k (2 / L_k for a box of length L_k).  A
     vector field is d consecutive fields; the number of fields (vectors) of a call is taken from numel() // N.  out=None allocates
     the output.  The outputs come back with the layouts of include/chebhip.h, shaped (fields, *dims).  Asynchronous on torch's
-    current stream; the same input gives the same bits."""
+    current stream; the same input gives the same bits.  periodic (None: no direction): one flag per direction; a flagged
+    direction lives on fourier_nodes(dims[k]) (2 <= dims[k] <= 256, period 2 / scale[k]) and is differentiated with
+    fourier_diff_matrix, by the same sweeps (cheb_grad_create_basis)."""
     _destroy = "cheb_grad_destroy"
 
-    def __init__(self, dims, scale=None):
+    def __init__(self, dims, scale=None, periodic=None):
         import numpy as np
         self.dims = tuple(int(d) for d in dims)
         self.d = len(self.dims)
+        self.periodic = _periodic_flags(periodic, self.d)
         sc = None
         if scale is not None:
             sc = np.ascontiguousarray(scale, dtype=np.float64)
@@ -1209,7 +1304,11 @@ class ChebGrad(_Handle):
                 raise ValueError("scale: expected %d values, got shape %r" % (self.d, sc.shape))
         self.scale = None if sc is None else tuple(float(v) for v in sc)
         h = C.c_void_p()
-        _chk(lib().cheb_grad_create(self.d, _ints(self.dims), None if sc is None else _np_dp(sc), C.byref(h)))
+        if periodic is None:
+            _chk(lib().cheb_grad_create(self.d, _ints(self.dims), None if sc is None else _np_dp(sc), C.byref(h)))
+        else:
+            _chk(lib().cheb_grad_create_basis(self.d, _ints(self.dims), None if sc is None else _np_dp(sc),
+                                              _ints([int(p) for p in self.periodic]), C.byref(h)))
         self._h = h
         self.N = lib().cheb_grad_size(h)
 
@@ -1400,6 +1499,30 @@ def _bc_ends(entry):
     raise ValueError("a direction's boundary condition is one spec or a pair of specs, got %r" % (entry,))
 
 
+def _bc_periodic(entry):
+    """True for the entry "periodic", which covers the whole direction; a pair with one periodic end is refused."""
+    if isinstance(entry, str):
+        return entry.lower() == "periodic"
+    try:
+        ends = tuple(entry)
+    except TypeError:
+        return False
+    if any(isinstance(e, str) and e.lower() == "periodic" for e in ends):
+        raise ChebhipError(4, "bc %r: a direction is periodic as a whole, not at one end" % (entry,))
+    return False
+
+
+def bc_split(bc, d):
+    """(periodic, b, ends) of HelmholtzSolver's `bc`: the flag per direction, the 4 d doubles of the create calls (Dirichlet
+    placeholders on a periodic direction, whose entries are not read) and, per direction, the four end values or None where it is
+    periodic.  The one place that parses "periodic": a pair with one periodic end is refused here."""
+    if isinstance(bc, str) or len(bc) != d:
+        raise ValueError("bc needs one entry per direction (%d)" % d)
+    periodic = tuple(_bc_periodic(entry) for entry in bc)
+    b = bc_array(["dirichlet" if p else entry for p, entry in zip(periodic, bc)], d)
+    return periodic, b, tuple(None if periodic[k] else tuple(b[4 * k:4 * k + 4]) for k in range(d))
+
+
 def bc_array(bc, d):
     """The 4 d doubles of cheb_helmholtz_create_bc from a length-d sequence of per-direction entries (HelmholtzSolver's `bc`)."""
     if isinstance(bc, str) or len(bc) != d:
@@ -1455,7 +1578,14 @@ class HelmholtzSolver(_FdmSteps, _Handle):
     boundary_size and singular (sigma = 0 with Neumann everywhere: the constant-like zero mode is dropped).
 
     scale (needs bc; None: the cube, today's handle): scale[k] = 2 / L_k of a box; the solver inverts sigma - sum_k scale_k^2 d_k^2
-    and beta multiplies the physical normal derivative, alpha u + beta scale_k du/dnu = g (cheb_helmholtz_create_box)."""
+    and beta multiplies the physical normal derivative, alpha u + beta scale_k du/dnu = g (cheb_helmholtz_create_box).
+
+    A bc entry "periodic" makes the whole direction periodic (cheb_helmholtz_create_basis): dims[k] unknowns on the
+    nodes fourier_nodes(dims[k]), 2 <= dims[k] <= 256, period 2 / scale[k], no faces and no entries in g.  The arrays of solve are
+    then row-major over dims[k] (periodic) or dims[k] - 2 (wall) unknowns per direction; `periodic` holds the flags.  singular is
+    true for sigma = 0 with every direction periodic or Neumann / Neumann: every product of the directions' zero-eigenvalue modes is
+    dropped -- the constants and, on a periodic direction of even extent, the Nyquist vector (-1)^j.  With every direction periodic
+    boundary_size is 0 and g must be None."""
     _destroy = "cheb_helmholtz_destroy"
 
     def __init__(self, dims, sigma=0.0, nfields=1, bc=None, scale=None):
@@ -1463,6 +1593,7 @@ class HelmholtzSolver(_FdmSteps, _Handle):
         self.sigma = float(sigma)
         self.nfields = int(nfields)
         self.bc = None
+        self.periodic = (False,) * len(self.dims)
         if scale is not None and bc is None:
             raise ValueError("scale needs bc: the box solve is a boundary-condition handle")
         sc, self.scale = _scale_array(scale, len(self.dims))
@@ -1470,9 +1601,12 @@ class HelmholtzSolver(_FdmSteps, _Handle):
         if bc is None:
             _chk(lib().cheb_helmholtz_create(len(self.dims), _ints(self.dims), self.sigma, self.nfields, C.byref(h)))
         else:
-            b = bc_array(bc, len(self.dims))
-            self.bc = tuple(tuple(b[4 * k:4 * k + 4]) for k in range(len(self.dims)))
-            if sc is None:
+            d = len(self.dims)
+            self.periodic, b, self.bc = bc_split(bc, d)
+            if any(self.periodic):
+                _chk(lib().cheb_helmholtz_create_basis(d, _ints(self.dims), _ints([int(p) for p in self.periodic]), (C.c_double * len(b))(*b),
+                                                       None if sc is None else _np_dp(sc), self.sigma, self.nfields, C.byref(h)))
+            elif sc is None:
                 _chk(lib().cheb_helmholtz_create_bc(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), self.sigma,
                                                     self.nfields, C.byref(h)))
             else:
@@ -1505,6 +1639,8 @@ class HelmholtzSolver(_FdmSteps, _Handle):
         for name, t, n in (("f", f, self.size), ("g", g, self.boundary_size), ("u", u, self.full_size)):
             if t is None and name == "g":
                 continue
+            if name == "g" and n == 0:
+                raise ChebhipError(4, "g given, but every direction is periodic: there is no boundary data to lift")
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous float64 device tensor" % name)
             if t.numel() != n:

@@ -1117,6 +1117,107 @@ int reduce_weights_host(int n, int kind, double arg, double *w) {
   return 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Periodic (Fourier) directions.  n nodes x_j = -1 + 2 j / n, j = 0 .. n-1, period 2, no duplicated end point.
+//   D_F = pi D_theta, theta = pi (x + 1):  D_theta[i][j] = 1/2 (-1)^(i-j) cot(pi (i-j) / n)  (n even),
+//                                                          1/2 (-1)^(i-j) / sin(pi (i-j) / n) (n odd),   zero diagonal.
+// D_F is circulant and odd, hence centro-antisymmetric; for even n it annihilates the Nyquist vector (-1)^j.  The second
+// derivative is D_F D_F (long double, rounded once: the convention of diffmat_create_dd, not the textbook D^(2), which differs at
+// the Nyquist mode), centro-symmetric.  Every sine / cosine takes its argument as an integer multiple of pi / n reduced in
+// integers and folded into [0, pi/2], as sin_half above.
+// ---------------------------------------------------------------------------------------------
+// sin(pi m / n), any integer m
+static long double sin_pi(long m, long n) {
+  long r = m % (2 * n);
+  if (r < 0) r += 2 * n;
+  long double sg = 1.0L;
+  if (r >= n) { r -= n; sg = -1.0L; }
+  if (2 * r > n) r = n - r;
+  if (r == 0) return 0.0L;
+  if (2 * r == n) return sg;
+  return sg * sinl(PI_L * (long double)r / (long double)n);
+}
+static long double cos_pi(long m, long n) { return sin_pi(2 * m + n, 2 * n); }
+
+static long double fourier_dentry(int i, int j, int n) {
+  if (i == j) return 0.0L;
+  const long m = i - j;
+  const long double sg = (m & 1) ? -1.0L : 1.0L, s = sin_pi(m, n);
+  return PI_L * 0.5L * sg * ((n & 1) ? 1.0L / s : cos_pi(m, n) / s);
+}
+
+void fourier_nodes_host(int n, double *x) {
+  for (int j = 0; j < n; j++) x[j] = (double)((long double)(2 * j - n) / (long double)n);
+}
+
+void fourier_diff_ld(int n, int order, std::vector<long double> &A) {
+  std::vector<long double> D((size_t)n * n);
+  for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) D[(size_t)i * n + j] = fourier_dentry(i, j, n);
+  if (order == 1) { A.swap(D); return; }
+  A.assign((size_t)n * n, 0.0L);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      long double s = 0.0L;
+      for (int q = 0; q < n; q++) s += D[(size_t)i * n + q] * D[(size_t)q * n + j];
+      A[(size_t)i * n + j] = s;
+    }
+}
+
+// Position -> mode in spec_line's parity layout, the flip j -> n-1-j reflecting about c = -1/n: the even modes at p < ceil(n/2) are
+// the constant (p = 0) and cos(pi k (x - c)) at p = k; the odd ones at n-1-q are, for even n, the Nyquist vector (q = 0) and
+// sin(pi k (x - c)) at q = k, for odd n sin at q = k - 1; 1 <= k <= floor((n-1)/2).  kind: 0 cos (k = 0: the constant), 1 sin,
+// 2 Nyquist (k = n / 2).
+void fourier_modes_host(int n, int *k, int *kind) {
+  const int K = (n - 1) / 2;
+  k[0] = 0; kind[0] = 0;
+  for (int q = 1; q <= K; q++) { k[q] = q; kind[q] = 0; }
+  if (!(n & 1)) { k[n - 1] = n / 2; kind[n - 1] = 2; }
+  for (int q = 1; q <= K; q++) { const int pos = (n & 1) ? n - q : n - 1 - q; k[pos] = q; kind[pos] = 1; }
+}
+
+// B (which = 1: values <- coefficients; column p holds mode p with amplitude 1, so the constant's coefficient is the mean) or its
+// inverse T (which = 0: row p = mode p times 1/n for the constant and the Nyquist vector, 2/n otherwise).  Entries of half a line,
+// mirrored with the mode's sign: every column of B and every row of T carries its parity exactly.
+void fourier_modal_ld(int n, int which, std::vector<long double> &M) {
+  std::vector<int> k(n), kind(n);
+  fourier_modes_host(n, k.data(), kind.data());
+  M.assign((size_t)n * n, 0.0L);
+  const int H = (n + 1) / 2;
+  for (int p = 0; p < n; p++) {
+    const long double sg = kind[p] == 0 ? 1.0L : -1.0L;
+    const long double w = which ? 1.0L : ((kind[p] == 2 || k[p] == 0) ? 1.0L : 2.0L) / (long double)n;
+    for (int j = 0; j < H; j++) {
+      long double v;
+      if (kind[p] == 2) v = (j & 1) ? -1.0L : 1.0L;
+      else if (kind[p] == 0) v = cos_pi((long)k[p] * (2 * j + 1 - n), n);
+      else v = sin_pi((long)k[p] * (2 * j + 1 - n), n);
+      v *= w;
+      const int jm = n - 1 - j;
+      if (which) { M[(size_t)j * n + p] = v; M[(size_t)jm * n + p] = jm == j ? v : sg * v; }
+      else { M[(size_t)p * n + j] = v; M[(size_t)p * n + jm] = jm == j ? v : sg * v; }
+    }
+  }
+}
+
+// The line of the solve: A_1 = -s^2 D_F D_F on all n points = S diag(lam) S^-1 in closed form, S = B and S^-1 = T above,
+// lam = s^2 (pi k)^2; the constant's and the Nyquist vector's eigenvalue is exactly 0.  No eigensolver runs.
+void fourier_line(int n, double s, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam) {
+  std::vector<int> k(n), kind(n);
+  fourier_modes_host(n, k.data(), kind.data());
+  fourier_modal_ld(n, 1, S);
+  fourier_modal_ld(n, 0, Sinv);
+  lam.assign(n, 0.0L);
+  for (int p = 0; p < n; p++)
+    if (kind[p] != 2 && k[p] != 0) { const long double a = PI_L * (long double)k[p] * (long double)s; lam[p] = a * a; }
+}
+
+hipError_t diffmat_create_fourier(int n, int order, DiffMat *out) {
+  if (n < 2 || n > 256) return hipErrorInvalidValue;
+  std::vector<long double> A;
+  fourier_diff_ld(n, order, A);
+  return diffmat_from_dense(n, A.data(), order == 2 ? 1 : 0, out);
+}
+
 void diffmat_destroy(DiffMat *m) {
   if (m->fragE) (void)hipFree(m->fragE);
   if (m->fragO) (void)hipFree(m->fragO);

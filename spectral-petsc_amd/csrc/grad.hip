@@ -19,6 +19,7 @@
 #include "ops.h"
 #include <map>
 #include <new>
+#include <utility>
 #include <vector>
 
 using namespace chebhip;
@@ -121,7 +122,10 @@ struct cheb_grad {
   double scale[MD] = {0};
   unsigned inner[MD] = {0};
   long N = 0;
-  std::map<int, DiffMat> D, DD;      // by extent; DD for 3 <= n <= 256
+  int basis[MD] = {0};                // BASIS_CGL / BASIS_FOURIER per direction (cheb_grad_create_basis)
+  std::map<std::pair<int, int>, DiffMat> D, DD;      // by (extent, basis); DD for 3 <= n <= 256 (Fourier: 2 <= n <= 256)
+  const DiffMat *Dk(int k) const { return &D.at(std::make_pair(n[k], basis[k])); }
+  const DiffMat &DDk(int k) const { return DD.at(std::make_pair(n[k], basis[k])); }
   bool two_sweeps = false;           // some direction has more than 256 points: the Laplacian needs `work`
 
   SweepParams job(const Term &t, double *out, bool acc, int nfields = 1) const {
@@ -178,7 +182,9 @@ extern "C" int cheb_grad_destroy(cheb_grad *h) {
   return 0;
 }
 
-extern "C" int cheb_grad_create(int d, const int *dims, const double *scale, cheb_grad **out) {
+// basis[k]: BASIS_CGL or BASIS_FOURIER (a periodic direction of 2 <= n <= 256 nodes x_j = -1 + 2 j / n: D_F and D_F D_F of diffmat.cpp
+// through diffmat_from_dense); null: CGL everywhere, which is cheb_grad_create
+static int grad_create(int d, const int *dims, const double *scale, const int *basis, cheb_grad **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
@@ -189,6 +195,9 @@ extern "C" int cheb_grad_create(int d, const int *dims, const double *scale, che
     N *= dims[k];
     if (N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
     if (scale && !(scale[k] == scale[k] && scale[k] - scale[k] == 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] is not finite", k);
+    if (basis && basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
+    if (basis && basis[k] == BASIS_FOURIER && dims[k] > 256)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
   }
   if ((rc = require_device())) return rc;
   cheb_grad *h = new (std::nothrow) cheb_grad;
@@ -197,13 +206,27 @@ extern "C" int cheb_grad_create(int d, const int *dims, const double *scale, che
   unsigned in = 1;
   for (int k = d - 1; k >= 0; k--) { h->n[k] = dims[k]; h->scale[k] = scale ? scale[k] : 1.0; h->inner[k] = in; in *= (unsigned)dims[k]; }
   for (int k = 0; k < d; k++) {
-    const int n = dims[k];
+    const int n = dims[k], b = h->basis[k] = basis ? basis[k] : BASIS_CGL;
+    const std::pair<int, int> key(n, b);
     if (n > 256) h->two_sweeps = true;
-    if (!h->D.count(n)) { DiffMat m; HIP_TRY_OR(diffmat_create(n, &m), cheb_grad_destroy(h)); h->D[n] = m; }
-    if (n >= 3 && n <= 256 && !h->DD.count(n)) { DiffMat m; HIP_TRY_OR(diffmat_create_dd(n, &m), cheb_grad_destroy(h)); h->DD[n] = m; }
+    if (b == BASIS_FOURIER) {
+      if (!h->D.count(key)) { DiffMat m; HIP_TRY_OR(diffmat_create_fourier(n, 1, &m), cheb_grad_destroy(h)); h->D[key] = m; }
+      if (!h->DD.count(key)) { DiffMat m; HIP_TRY_OR(diffmat_create_fourier(n, 2, &m), cheb_grad_destroy(h)); h->DD[key] = m; }
+      continue;
+    }
+    if (!h->D.count(key)) { DiffMat m; HIP_TRY_OR(diffmat_create(n, &m), cheb_grad_destroy(h)); h->D[key] = m; }
+    if (n >= 3 && n <= 256 && !h->DD.count(key)) { DiffMat m; HIP_TRY_OR(diffmat_create_dd(n, &m), cheb_grad_destroy(h)); h->DD[key] = m; }
   }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_grad_create(int d, const int *dims, const double *scale, cheb_grad **out) { return grad_create(d, dims, scale, nullptr, out); }
+
+extern "C" int cheb_grad_create_basis(int d, const int *dims, const double *scale, const int *basis, cheb_grad **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return grad_create(d, dims, scale, basis, out);
 }
 
 extern "C" long cheb_grad_size(const cheb_grad *h) { return h ? h->N : -1; }
@@ -222,7 +245,7 @@ extern "C" int cheb_grad_grad(cheb_grad *h, int nfields, const double *s_dev, do
   std::vector<std::vector<Term>> terms; std::vector<double *> outs;
   for (int f = 0; f < nfields; f++)
     for (int k = 0; k < d; k++) {
-      terms.push_back({Term{&h->D.at(h->n[k]), k, s_dev + (size_t)f * N, h->scale[k]}});
+      terms.push_back({Term{h->Dk(k), k, s_dev + (size_t)f * N, h->scale[k]}});
       outs.push_back(out_dev + (size_t)(f * d + k) * N);
     }
   return run_rounds(h, terms, outs, (hipStream_t)stream);
@@ -246,7 +269,7 @@ extern "C" int cheb_grad_div(cheb_grad *h, int nvec, const double *u_dev, double
   std::vector<std::vector<Term>> terms(nvec); std::vector<double *> outs(nvec);
   for (int v = 0; v < nvec; v++) {
     outs[v] = out_dev + (size_t)v * N;
-    for (int k = 0; k < d; k++) terms[v].push_back(Term{&h->D.at(h->n[k]), k, u_dev + (size_t)(v * d + k) * N, h->scale[k]});
+    for (int k = 0; k < d; k++) terms[v].push_back(Term{h->Dk(k), k, u_dev + (size_t)(v * d + k) * N, h->scale[k]});
   }
   return run_rounds(h, terms, outs, (hipStream_t)stream);
 }
@@ -261,7 +284,7 @@ int cheb_grad_axpy_grad(cheb_grad *h, int nvec, double alpha, const double *s_de
   std::vector<std::vector<Term>> terms; std::vector<double *> outs;
   for (int v = 0; v < nvec; v++)
     for (int k = 0; k < d; k++) {
-      terms.push_back({Term{&h->D.at(h->n[k]), k, s_dev + (size_t)v * N, alpha * h->scale[k], u_dev + (size_t)(v * d + k) * N}});
+      terms.push_back({Term{h->Dk(k), k, s_dev + (size_t)v * N, alpha * h->scale[k], u_dev + (size_t)(v * d + k) * N}});
       outs.push_back(out_dev + (size_t)(v * d + k) * N);
     }
   return run_rounds(h, terms, outs, (hipStream_t)stream);
@@ -276,7 +299,7 @@ extern "C" int cheb_grad_curl(cheb_grad *h, int nvec, const double *u_dev, doubl
   const int d = h->d, no = d == 3 ? 3 : 1; const long N = h->N;
   if ((rc = check_arrays(h, "curl", u_dev, (long)nvec * d, out_dev, (long)nvec * no))) return rc;
   std::vector<std::vector<Term>> terms; std::vector<double *> outs;
-  auto term = [&](int v, int k, int c, double sign) { return Term{&h->D.at(h->n[k]), k, u_dev + (size_t)(v * d + c) * N, sign * h->scale[k]}; };
+  auto term = [&](int v, int k, int c, double sign) { return Term{h->Dk(k), k, u_dev + (size_t)(v * d + c) * N, sign * h->scale[k]}; };
   for (int v = 0; v < nvec; v++) {
     if (d == 2) { terms.push_back({term(v, 0, 1, 1.0), term(v, 1, 0, -1.0)}); outs.push_back(out_dev + (size_t)v * N); continue; }
     for (int i = 0; i < 3; i++) {
@@ -301,9 +324,9 @@ extern "C" int cheb_grad_strain(cheb_grad *h, int nvec, const double *u_dev, dou
     const double *u = u_dev + (size_t)v * d * N;
     for (int c = 0; c < d; c++)
       for (int k = c; k < d; k++, o++) {
-        if (k == c) terms.push_back({Term{&h->D.at(h->n[c]), c, u + (size_t)c * N, h->scale[c]}});
-        else terms.push_back({Term{&h->D.at(h->n[k]), k, u + (size_t)c * N, 0.5 * h->scale[k]},
-                              Term{&h->D.at(h->n[c]), c, u + (size_t)k * N, 0.5 * h->scale[c]}});
+        if (k == c) terms.push_back({Term{h->Dk(c), c, u + (size_t)c * N, h->scale[c]}});
+        else terms.push_back({Term{h->Dk(k), k, u + (size_t)c * N, 0.5 * h->scale[k]},
+                              Term{h->Dk(c), c, u + (size_t)k * N, 0.5 * h->scale[c]}});
         outs.push_back(out_dev + (size_t)(v * ns + o) * N);
       }
   }
@@ -329,10 +352,10 @@ extern "C" int cheb_grad_laplacian(cheb_grad *h, int nfields, const double *s_de
     const double a = h->scale[k] * h->scale[k];
     if (n == 2) continue;
     if (n <= 256) {
-      HIP_TRY(sweep_launch(h->DD.at(n), h->job(Term{nullptr, k, s_dev, a}, out_dev, !first, nfields), st));
+      HIP_TRY(sweep_launch(h->DDk(k), h->job(Term{nullptr, k, s_dev, a}, out_dev, !first, nfields), st));
     } else {
-      HIP_TRY(sweep_launch(h->D.at(n), h->job(Term{nullptr, k, s_dev, 1.0}, work_dev, false, nfields), st));
-      HIP_TRY(sweep_launch(h->D.at(n), h->job(Term{nullptr, k, work_dev, a}, out_dev, !first, nfields), st));
+      HIP_TRY(sweep_launch(*h->Dk(k), h->job(Term{nullptr, k, s_dev, 1.0}, work_dev, false, nfields), st));
+      HIP_TRY(sweep_launch(*h->Dk(k), h->job(Term{nullptr, k, work_dev, a}, out_dev, !first, nfields), st));
     }
     first = false;
   }

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <map>
 #include <new>
+#include <utility>
 #include <vector>
 
 using namespace chebhip;
@@ -213,7 +214,8 @@ struct cheb_modal {
   int d = 0, nf = 1;
   long total = 0;                            // nf * prod(dims)
   ModalGeo geo{};
-  std::map<int, double *> mats;              // device: T then B (2 n^2 doubles) per distinct extent
+  int basis[MD] = {0};                       // BASIS_CGL / BASIS_FOURIER per direction (cheb_modal_create_basis)
+  std::map<std::pair<int, int>, double *> mats;   // device: T then B (2 n^2 doubles) per distinct (extent, basis)
   double *F[MD] = {nullptr};                 // device filter matrix of a direction, or null: none set / all ones
   double *w = nullptr;                       // device: the directions' Clenshaw-Curtis weights, concatenated (geo.off)
   double *work[2] = {nullptr, nullptr};      // ping-pong intermediates
@@ -258,7 +260,34 @@ extern "C" int cheb_modal_destroy(cheb_modal *h) {
   return 0;
 }
 
-extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal **out) {
+namespace {
+
+// T (which = 0) / B (which = 1) of a periodic direction, long double rounded once (diffmat.cpp: fourier_modal_ld)
+void fourier_modal_matrix(int n, int which, double *M) {
+  std::vector<long double> A;
+  fourier_modal_ld(n, which, A);
+  for (size_t e = 0; e < A.size(); e++) M[e] = (double)A[e];
+}
+
+// F = B diag(sigma) T of a periodic direction, sigma per coefficient position, the sum in long double, rounded once.  (All ones never
+// comes here: cheb_modal_set_filter drops such a direction from the filter, which is what makes it the identity exactly.)
+void fourier_filter_matrix(int n, const double *sigma, double *F) {
+  std::vector<long double> B, T;
+  fourier_modal_ld(n, 1, B);
+  fourier_modal_ld(n, 0, T);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      long double s = 0.0L;
+      for (int p = 0; p < n; p++) if (sigma[p] != 0.0) s += B[(size_t)i * n + p] * (long double)sigma[p] * T[(size_t)p * n + j];
+      F[(size_t)i * n + j] = (double)s;
+    }
+}
+
+}  // namespace
+
+// basis[k]: BASIS_CGL or BASIS_FOURIER (2 <= n <= 256; the coefficient layout is the parity mode layout of cheb_fourier_modes_host,
+// the quadrature weight 2 / n at every node); null: CGL everywhere, which is cheb_modal_create
+static int modal_create(int d, const int *dims, int nfields, const int *basis, cheb_modal **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
@@ -267,6 +296,9 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   long total = nfields, S = 0;
   for (int k = 0; k < d; k++) {
     if ((rc = check_extent(dims[k]))) return rc;
+    if (basis && basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
+    if (basis && basis[k] == BASIS_FOURIER && dims[k] > 256)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
     total *= dims[k]; S += dims[k];
     if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
   }
@@ -281,7 +313,11 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   g.lg = 0;
   while (g.lg < 6 && (1 << g.lg) < (n + 1) / 2) g.lg++;
   std::vector<double> w(S);
-  for (int k = 0, o = 0; k < d; o += dims[k], k++) { g.n[k] = dims[k]; g.off[k] = o; modal_weights_host(dims[k], w.data() + o); }
+  for (int k = 0, o = 0; k < d; o += dims[k], k++) {
+    g.n[k] = dims[k]; g.off[k] = o; h->basis[k] = basis ? basis[k] : BASIS_CGL;
+    if (h->basis[k] == BASIS_FOURIER) for (int j = 0; j < dims[k]; j++) w[o + j] = (double)(2.0L / (long double)dims[k]);
+    else modal_weights_host(dims[k], w.data() + o);
+  }
 
   // launch geometry of the two reductions, fixed per handle: results do not depend on anything but the shape
   const unsigned rpw = 64u >> g.lg, cr = rpw > SPEC_CR ? rpw : SPEC_CR, sr = 4 * cr, cap_int = 2048u / nfields, cap_spec = 1024u / nfields;
@@ -295,13 +331,14 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   std::vector<double> m;
   for (int k = 0; k < d && !rc; k++) {
     const int nk = dims[k];
-    if (h->mats.count(nk)) continue;
+    const std::pair<int, int> key(nk, h->basis[k]);
+    if (h->mats.count(key)) continue;
     const size_t nn = (size_t)nk * nk;
     m.resize(2 * nn);
-    modal_matrix_host(nk, 0, m.data());
-    modal_matrix_host(nk, 1, m.data() + nn);
+    if (h->basis[k] == BASIS_FOURIER) { fourier_modal_matrix(nk, 0, m.data()); fourier_modal_matrix(nk, 1, m.data() + nn); }
+    else { modal_matrix_host(nk, 0, m.data()); modal_matrix_host(nk, 1, m.data() + nn); }
     double *dev = nullptr;
-    if (!(rc = device_array(&dev, 2 * nn, m.data(), "modal matrices"))) h->mats[nk] = dev;
+    if (!(rc = device_array(&dev, 2 * nn, m.data(), "modal matrices"))) h->mats[key] = dev;
   }
   if (!rc) rc = device_array(&h->w, S, w.data(), "quadrature weights");
   for (int b = 0; b < 2 && b < d - 1 && !rc; b++) rc = device_array(&h->work[b], total, nullptr, "modal work buffer");
@@ -309,6 +346,14 @@ extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal
   if (rc) { cheb_modal_destroy(h); return rc; }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_modal_create(int d, const int *dims, int nfields, cheb_modal **out) { return modal_create(d, dims, nfields, nullptr, out); }
+
+extern "C" int cheb_modal_create_basis(int d, const int *dims, int nfields, const int *basis, cheb_modal **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return modal_create(d, dims, nfields, basis, out);
 }
 
 extern "C" long cheb_modal_size(const cheb_modal *h) { return h ? h->total : -1; }
@@ -339,7 +384,7 @@ int modal_product(cheb_modal *h, const double *const *M, const double *x, double
 int modal_transform(cheb_modal *h, int which, const double *x, double *y, void *stream) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   const double *M[MD];
-  for (int k = 0; k < h->d; k++) M[k] = h->mats[h->geo.n[k]] + (which ? (size_t)h->geo.n[k] * h->geo.n[k] : 0);
+  for (int k = 0; k < h->d; k++) M[k] = h->mats[std::make_pair(h->geo.n[k], h->basis[k])] + (which ? (size_t)h->geo.n[k] * h->geo.n[k] : 0);
   return modal_product(h, M, x, y, stream, which ? "backward" : "forward");
 }
 
@@ -359,7 +404,8 @@ extern "C" int cheb_modal_set_filter(cheb_modal *h, int k, const double *sigma) 
     return 0;
   }
   std::vector<double> F((size_t)n * n);
-  modal_filter_matrix_host(n, sigma, F.data());
+  if (h->basis[k] == BASIS_FOURIER) fourier_filter_matrix(n, sigma, F.data());
+  else modal_filter_matrix_host(n, sigma, F.data());
   hipError_t e = h->F[k] ? hipSuccess : hipMalloc(&h->F[k], F.size() * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(h->F[k], F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice);
   return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_MEMORY, "filter matrix: %s", hipGetErrorString(e));

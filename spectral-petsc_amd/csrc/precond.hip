@@ -284,7 +284,8 @@ __global__ __launch_bounds__(256, 3) void k_fdm_zsolve16(const FzParams p) {
 struct LineMats { DiffMat Bcs, Bca, Fraw, Braw; double *lam = nullptr; double *bcm = nullptr; double *Fdense = nullptr; int M = 0; bool ok = false, parity = true; };
 // lines are shared by the directions of equal extent, equal end conditions (alpha_first, beta_first, alpha_last, beta_last) AND
 // equal scale (cheb_helmholtz_create_box; 1 everywhere else)
-typedef std::tuple<int, std::array<double, 4>, double> LineKey;
+// ... AND equal basis (BASIS_FOURIER: a periodic line of cheb_helmholtz_create_basis, whose end conditions are unused)
+typedef std::tuple<int, std::array<double, 4>, double, int> LineKey;
 static const std::array<double, 4> BC_DIRICHLET = {1.0, 0.0, 1.0, 0.0};
 
 // The line of a direction of scale s = 2 / length (cheb_helmholtz_create_box): the operator is -s^2 (D D) and the end condition
@@ -311,6 +312,8 @@ struct chebhip_fdpc {
   bool bare = false;                           // no operator behind the handle (cheb_helmholtz): no eta, no update
   double *lam0 = nullptr;                      // spectral: sigma + eigenvalues of dimension 0 (a copy: lines[] is shared by directions)
   long N = 0, G = 0;
+  int M[MAXD] = {0};                           // unknowns along direction k: dims[k] - 2, or dims[k] on a periodic direction
+  int basis[MAXD] = {0};                       // BASIS_CGL / BASIS_FOURIER (cheb_helmholtz_create_basis only)
   int nf = 1;                                  // 1: scalar operator; d: Stokes velocity (component-major inside)
   bool interleaved = false;                    // vectors at the ABI are node-major (Stokes)
   std::map<LineKey, LineMats> lines;           // per distinct (extent, end conditions)
@@ -352,15 +355,21 @@ static void fdpc_free(chebhip_fdpc *pc) {
 // kind: LINE_FD (the finite-difference matrix) or LINE_SPECTRAL (sigma + the collocation operator at eta == 1); bare: a spectral
 // handle without an operator (v0.ixL / eta unused): only the buffers of the plain solve are allocated
 // bc (spectral only; may be null = Dirichlet everywhere): 4 d end conditions, spec_line_bc; scale (with bc only; may be null = 1
-// everywhere): d scales, spec_line_box
+// everywhere): d scales, spec_line_box; basis (with bc only; may be null = CGL everywhere): BASIS_FOURIER makes direction k a
+// periodic line of M = dims[k] unknowns (fourier_line: closed form, parity layout, no Q, L or B_BB^-1), v0.G counted accordingly
 static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc **out, int gP0 = 0, int kind = LINE_FD, double sigma = 0.0,
-                       bool bare = false, const double *bc = nullptr, const double *scale = nullptr) {
+                       bool bare = false, const double *bc = nullptr, const double *scale = nullptr, const int *basis = nullptr) {
   *out = nullptr;
   FdView v = v0;
   std::vector<int> gdims(v0.dims, v0.dims + (v0.d >= 1 && v0.d <= MAXD ? v0.d : 0));
   if (gP0 > 0 && !gdims.empty()) { gdims[0] = gP0; v.dims = gdims.data(); }      // slab mode: matrices of the global extent
   if (v.d < 1 || v.d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d out of range", v.d);
   for (int k = 0; k < v.d; k++) {
+    if (basis && basis[k] == BASIS_FOURIER) {
+      if (v.dims[k] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: a periodic direction needs at least 2 points", k, v.dims[k]);
+      if (v.dims[k] > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, v.dims[k]);
+      continue;
+    }
     if (v.dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the preconditioner needs interior nodes", k, v.dims[k]);
     if (v.dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, v.dims[k]);
   }
@@ -369,11 +378,16 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
   pc->geo.d = v.d; pc->N = v.N; pc->G = v.G; pc->nf = nf; pc->interleaved = interleaved;
   pc->kind = kind; pc->bare = bare;
   if (kind == LINE_SPECTRAL) { pc->sweeps = 0; pc->assembled = bare; }
-  for (int k = 0; k < v.d; k++) pc->geo.dims[k] = v.dims[k];
-  { long s = 1; for (int k = v.d - 1; k >= 0; k--) { pc->geo.gs[k] = s; s *= (v.dims[k] - 2); } }
+  for (int k = 0; k < v.d; k++) {
+    pc->geo.dims[k] = v.dims[k];
+    pc->basis[k] = basis ? basis[k] : BASIS_CGL;
+    pc->M[k] = pc->basis[k] == BASIS_FOURIER ? v.dims[k] : v.dims[k] - 2;
+  }
+  { long s = 1; for (int k = v.d - 1; k >= 0; k--) { pc->geo.gs[k] = s; s *= pc->M[k]; } }
   pc->inner_g.resize(v.d); pc->ncols_g.resize(v.d);
   for (int k = 0; k < v.d; k++) {
-    const int P = v.dims[k], M = P - 2;
+    const int P = v.dims[k], M = pc->M[k];
+    const bool fourier = pc->basis[k] == BASIS_FOURIER;
     pc->inner_g[k] = (unsigned)pc->geo.gs[k];
     pc->ncols_g[k] = (unsigned)(v.G / M);                      // (dimension 0 of a slab: unused, its transforms run on pencils)
     std::vector<double> x(P);
@@ -381,13 +395,14 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     HIP_TRY_OR(hipMalloc((void **)&pc->xs[k], P * sizeof(double)), fdpc_free(pc));
     HIP_TRY_OR(hipMemcpy(pc->xs[k], x.data(), P * sizeof(double), hipMemcpyHostToDevice), fdpc_free(pc));
     std::array<double, 4> bk = BC_DIRICHLET;
-    if (bc) for (int e = 0; e < 4; e++) bk[e] = bc[4 * k + e];
+    if (bc && !fourier) for (int e = 0; e < 4; e++) bk[e] = bc[4 * k + e];
     const double sk = bc && scale ? scale[k] : 1.0;
-    const LineKey key(P, bk, sk);
+    const LineKey key(P, bk, sk, pc->basis[k]);
     if (pc->lines.count(key)) { pc->ln[k] = &pc->lines[key]; continue; }
     LineMats lm;
     std::vector<long double> S, Si, lam, part, Qb, Lb, Bi;
-    if (bc) {
+    if (fourier) fourier_line(P, sk, S, Si, lam);
+    else if (bc) {
       bool par = true;
       const int rc = spec_line_box(P, bk.data(), sk, S, Si, lam, Qb, Lb, Bi, par);
       if (rc) {
@@ -445,7 +460,7 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
     pc->ln[k] = &pc->lines[key];
   }
   if (kind == LINE_SPECTRAL) {
-    const int M0 = v.dims[0] - 2;
+    const int M0 = pc->M[0];
     std::vector<double> l0(M0);
     HIP_TRY_OR(hipMemcpy(l0.data(), pc->ln[0]->lam, M0 * sizeof(double), hipMemcpyDeviceToHost), fdpc_free(pc));
     for (int i = 0; i < M0; i++) l0[i] += sigma;
@@ -464,7 +479,7 @@ static int fdpc_create(const FdView &v0, int nf, bool interleaved, chebhip_fdpc 
   // allocated here so that no solve meets a hipMalloc.  A failed allocation only means the separate passes run.
   if (!opt(OPT_FDM_PASSES) && v.G > 0) {
     bool any_long = false;
-    for (int k = 0; k < v.d; k++) any_long = any_long || v.dims[k] - 2 > 64;
+    for (int k = 0; k < v.d; k++) any_long = any_long || pc->M[k] > 64;
     if (v.d >= 2 && v.d <= 3 && hipMalloc((void **)&pc->W, nf * gb) != hipSuccess) { pc->W = nullptr; (void)hipGetLastError(); }
     if (any_long && !bare && hipMalloc((void **)&pc->Einv, nf * gb) != hipSuccess) { pc->Einv = nullptr; (void)hipGetLastError(); }
   }
@@ -477,7 +492,7 @@ static int fdpc_eta_inverse(chebhip_fdpc *pc, hipStream_t st) {
   pc->Einv_ok = false;
   if (opt(OPT_FDM_PASSES) || pc->G == 0) return 0;
   bool any_long = false;
-  for (int k = 0; k < pc->geo.d; k++) any_long = any_long || pc->geo.dims[k] - 2 > 64;
+  for (int k = 0; k < pc->geo.d; k++) any_long = any_long || pc->M[k] > 64;
   if (!any_long) return 0;
   if (!pc->Einv) return 0;              // (allocated at create)
   hipLaunchKernelGGL(k_eta_inverse, dim3(grid1d(pc->G, 256, 4096), (unsigned)pc->nf), dim3(256), 0, st, pc->G, (const double *)pc->eta_g, pc->Einv);
@@ -600,7 +615,7 @@ static FdmPlan fdm_plan(chebhip_fdpc *pc) {
   if (pc->slab && d >= 3) { pl.order[0] = 1; pl.order[1] = 0; }
   for (int k = 0; k < MAXD; k++) pl.lam.p[k] = k < d ? pc->ln[k]->lam : nullptr;
   if (pc->lam0) pl.lam.p[0] = pc->lam0;                   // spectral: sigma + l_0 (every weight path reads dimension 0's array)
-  pl.nl = pc->geo.dims[d - 1] - 2;
+  pl.nl = pc->M[d - 1];
   pl.lines = pc->G / pl.nl;
   if (pc->slab && d >= 2) pl.lam.p[0] += pc->i0_off;      // the slab's first interior plane is plane i0_off of the global line
   // The modal scaling rides on the store of the last forward transform (dimension d-1 > 0: local on slabs too) where that
@@ -610,7 +625,7 @@ static FdmPlan fdm_plan(chebhip_fdpc *pc) {
   // The last forward transform, the scaling and the first backward transform act on the same contiguous lines: one launch
   // (k_fdm_zsolve16) where those lines have 66 .. 128 interior points, an even number of them (option "fdm_z_separate" = 1: A/B)
   {
-    const int M = pc->geo.dims[d - 1] - 2;
+    const int M = pc->M[d - 1];
     LineMats &lm = *pc->ln[d - 1];
     pl.zsolve = pl.w_ok && d >= 2 && lm.parity && !opt(OPT_FDM_Z_SEPARATE) && !opt(OPT_NO_RAW_TRANSFORMS) && !opt(OPT_GENERAL_KERNELS) && (M & 1) == 0 &&
                 lm.Fraw.KS == FZ_KS && lm.Braw.KS == FZ_KS && lm.Braw.sym == 1 && pc->G * pc->nf / M < 0x7fffffffL - FZ_NT;
@@ -625,7 +640,7 @@ static FdmPlan fdm_plan(chebhip_fdpc *pc) {
 static int fdm_weights(chebhip_fdpc *pc, const FdmPlan &pl, hipStream_t st) {
   if (!pl.w_ok || pc->W_tried) return 0;
   pc->W_tried = true;
-  const int n1 = pl.d == 3 ? pc->geo.dims[1] - 2 : 1;
+  const int n1 = pl.d == 3 ? pc->M[1] : 1;
   hipLaunchKernelGGL(k_modal_weights3, dim3((unsigned)((pl.nl + 255) / 256), (unsigned)pl.lines, (unsigned)pc->nf), dim3(256), 0, st, pl.d, n1, pl.nl, pc->G,
                      pl.lam.p[0], pl.lam.p[1], pl.lam.p[2], pc->W);
   HIP_TRY(hipGetLastError());
@@ -688,7 +703,7 @@ static int fdm_step(chebhip_fdpc *pc, const FdmPlan &pl, int k, int mode, const 
       if (dry || pl.lines == 0) break;       // (a slab without interior planes: nothing to scale; it still takes part in the transforms along dimension 0)
       if (y != x) HIP_TRY(hipMemcpyAsync(y, x, (size_t)pc->G * pc->nf * sizeof(double), hipMemcpyDeviceToDevice, st));
       if (three) {
-        const int n1 = d == 3 ? pc->geo.dims[1] - 2 : 1;
+        const int n1 = d == 3 ? pc->M[1] : 1;
         hipLaunchKernelGGL(k_modal_scale3, dim3((unsigned)((pl.nl + 255) / 256), (unsigned)pl.lines, (unsigned)pc->nf), dim3(256), 0, st, d, n1, pl.nl, pc->G,
                            pl.lam.p[0], pl.lam.p[1], pl.lam.p[2], y);
       } else
@@ -701,12 +716,12 @@ static int fdm_step(chebhip_fdpc *pc, const FdmPlan &pl, int k, int mode, const 
       rt = CHEBHIP_FDPC_ROUTE_ZSOLVE | CHEBHIP_FDPC_ROUTE_RAW | CHEBHIP_FDPC_ROUTE_FUSED_MUL;
       if (dry) break;
       if ((rc = fdm_weights(pc, pl, st))) return rc;
-      const int M = pc->geo.dims[d - 1] - 2;
+      const int M = pc->M[d - 1];
       LineMats &lm = *pc->ln[d - 1];
       FzParams fp = {};
       fp.M = M; fp.H = (M + 1) / 2; fp.ncols = (unsigned)(pc->G * pc->nf / M); fp.ntiles = (fp.ncols + FZ_NT - 1) / FZ_NT;
       fp.x = x; fp.y = y;
-      fp.d = d; fp.n1 = d == 3 ? pc->geo.dims[1] - 2 : 1; fp.flines = (unsigned)(pc->G / M);
+      fp.d = d; fp.n1 = d == 3 ? pc->M[1] : 1; fp.flines = (unsigned)(pc->G / M);
       fp.l0 = pl.lam.p[0]; fp.l1 = pl.lam.p[1]; fp.lz = pl.lam.p[d - 1];
       fp.FE = lm.Fraw.fragE; fp.FO = lm.Fraw.fragO; fp.BE = lm.Braw.fragE; fp.BO = lm.Braw.fragO;
       hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
@@ -1107,11 +1122,173 @@ __global__ __launch_bounds__(256) void k_bc_extend_row(BcGeo geo, const double *
   }
 }
 
+// ---- the same with periodic directions (cheb_helmholtz_create_basis) ------------------------------------------------
+// Direction k has M[k] unknowns starting at full-grid index off[k]: (P - 2, 1) between two walls, (P, 0) on a periodic direction, which
+// has no face data and no end values.  The compact boundary layout keeps its rule -- full-grid index minus the unknown nodes before
+// it -- over the nodes that are end nodes of some WALL direction.  These kernels run only on handles with a periodic direction.
+struct PbGeo { int d; int P[MAXD]; int M[MAXD]; int off[MAXD]; int ls[MAXD]; int gs[MAXD]; int N, G, NB; };
+
+// bc_before for PbGeo: a periodic direction m < k counts j[m] whole blocks of unknowns and never ends the walk
+template <int DC>
+__device__ __forceinline__ int pb_before(const PbGeo &g, const int *j, int k, bool last) {
+  int c = 0;
+  bool done = false;
+  for (int m = 0; m < (DC ? DC : MAXD); m++)
+    if (m < k && !done) {
+      if (!g.off[m]) c += j[m] * g.gs[m];
+      else if (j[m] == 0) done = true;
+      else if (j[m] == g.P[m] - 1) { c += g.M[m] * g.gs[m]; done = true; }
+      else c += (j[m] - 1) * g.gs[m];
+    }
+  return last && !done ? c + g.M[k] * g.gs[k] : c;
+}
+
+// t = f + sum over the wall directions k of L_k (g at the two faces of direction k), nf stacked unknown fields (field = blockIdx.y).
+// One wave per line of the last direction, four lines per workgroup: the line's other indices are decoded once, by wave-uniform
+// arithmetic, and the lanes walk the contiguous run -- f, t and the face values of every direction but the last are read and written
+// as consecutive doubles, the last direction's two face values are shared by the line.  The terms are added in k's order, each as
+// L0 g0 + L1 g1: the association of k_bc_lift.
+template <int DC>
+__global__ __launch_bounds__(256) void k_pb_lift(PbGeo geo, BcMats bm, int nlines, const double *__restrict__ f, const double *__restrict__ g,
+                                                 double *__restrict__ t) {
+  const int d = DC ? DC : geo.d;
+  const unsigned line = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (line >= (unsigned)nlines) return;        // (wave-uniform)
+  const int lane = threadIdx.x & 63, fo = blockIdx.y;
+  const double *gf = g + fo * geo.NB;
+  int i[MAXD];
+  unsigned r = line;
+  for (int m = (DC ? DC : MAXD) - 2; m > 0; m--)
+    if (m < d - 1) { const unsigned Mm = (unsigned)geo.M[m]; i[m] = (int)(r % Mm); r /= Mm; }
+  i[0] = (int)r;
+  int base = geo.off[d - 1];                   // full-grid index of the line's first unknown
+  for (int m = 0; m < (DC ? DC : MAXD) - 1; m++) if (m < d - 1) base += (i[m] + geo.off[m]) * geo.ls[m];
+  const int Ml = geo.M[d - 1], row = fo * geo.G + (int)line * Ml;
+  for (int il = lane; il < Ml; il += 64) {
+    double s = f[row + il];
+    int c = 0;                                 // unknown nodes before the first face node: sum_{m < k} i_m gs_m
+    for (int k = 0; k < (DC ? DC : MAXD); k++)
+      if (k < d) {
+        const int ik = k == d - 1 ? il : i[k];
+        if (geo.off[k]) {
+          const int M = geo.M[k];
+          const double *L = bm.m[k] + 2 * M;
+          const int b0 = base + il - (ik + 1) * geo.ls[k] - c;
+          const int b1 = b0 + (geo.P[k] - 1) * geo.ls[k] - M * geo.gs[k];
+          s += L[ik] * gf[b0] + L[M + ik] * gf[b1];
+        }
+        c += ik * geo.gs[k];
+      }
+    t[row + il] = s;
+  }
+}
+
+// End values of the wall direction k < d-1 (k_bc_extend_col's tiling: 64 lines consecutive in the last index per workgroup, four
+// segments per line): the lines whose indices in directions < k are any and in directions > k unknowns.  src (the FIRST wall
+// direction only, where every direction before k is periodic and these lines hold every unknown exactly once): the lines' unknowns are
+// read from the solution in the unknown layout and embedded into u on the way.
+template <int DC>
+__global__ __launch_bounds__(256) void k_pb_extend_col(PbGeo geo, int k, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
+  __shared__ double red[2][BC_SEG][64];
+  const int d = DC ? DC : geo.d;
+  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
+  const unsigned t = blockIdx.x * 64u + lane;
+  const bool ok = t < (unsigned)nlines;
+  const int fo = blockIdx.y;
+  double *uf = u + fo * geo.N;
+  const int M = geo.M[k], ls = geo.ls[k], lend = (geo.P[k] - 1) * ls;
+  int j[MAXD];
+  unsigned r = ok ? t : 0u;
+  int base = 0, ibase = 0;
+  for (int m = (DC ? DC : MAXD) - 1; m >= 0; m--) {
+    if (m >= d || m == k) continue;
+    const unsigned rad = (unsigned)(m < k ? geo.P[m] : geo.M[m]);
+    const int x = (int)(r % rad); r /= rad;
+    j[m] = m < k ? x : x + geo.off[m];
+    base += j[m] * geo.ls[m];
+    ibase += (j[m] - geo.off[m]) * geo.gs[m];  // (read with src only: then off[m] = 0 for every m < k)
+  }
+  const int per = (M + BC_SEG - 1) / BC_SEG, i0 = seg * per, i1 = i0 + per < M ? i0 + per : M;
+  double s0 = 0.0, s1 = 0.0;
+  if (ok) {
+    if (src) {
+      const double *sf = src + fo * geo.G + ibase;
+      const int gk = geo.gs[k];
+#pragma unroll 4
+      for (int i = i0; i < i1; i++) {
+        const double v = sf[i * gk];
+        uf[base + (i + 1) * ls] = v;
+        s0 += bm[i] * v; s1 += bm[M + i] * v;
+      }
+    } else if (!(dir0 && dir1)) {
+#pragma unroll 4
+      for (int i = i0; i < i1; i++) { const double v = uf[base + (i + 1) * ls]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+    }
+  }
+  red[0][seg][lane] = s0; red[1][seg][lane] = s1;
+  __syncthreads();
+  if (seg != 0 || !ok) return;
+  s0 = red[0][0][lane]; s1 = red[1][0][lane];
+  for (int q = 1; q < BC_SEG; q++) { s0 += red[0][q][lane]; s1 += red[1][q][lane]; }
+  double g0 = 0.0, g1 = 0.0;
+  if (g) {
+    const double *gf = g + fo * geo.NB;
+    g0 = gf[base - pb_before<DC>(geo, j, k, false)];
+    g1 = gf[base + lend - pb_before<DC>(geo, j, k, true)];
+  }
+  const double *Bi = bm + 4 * M;
+  uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
+  uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
+}
+
+// The same for a wall in the last direction (contiguous lines, one wave per line).  src: as above, every earlier direction periodic,
+// so line t of u is line t of the solution.
+template <int DC>
+__global__ __launch_bounds__(256) void k_pb_extend_row(PbGeo geo, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
+  const int d = DC ? DC : geo.d, k = d - 1;
+  const unsigned t = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (t >= (unsigned)nlines) return;           // (wave-uniform)
+  const int fo = blockIdx.y;
+  double *uf = u + fo * geo.N;
+  const int M = geo.M[k], lane = threadIdx.x & 63, lend = geo.P[k] - 1;
+  int j[MAXD];
+  unsigned r = t;
+  int base = 0;
+  for (int m = (DC ? DC : MAXD) - 2; m >= 0; m--) {
+    if (m >= k) continue;
+    const int x = (int)(r % (unsigned)geo.P[m]); r /= (unsigned)geo.P[m];
+    j[m] = x; base += x * geo.ls[m];
+  }
+  double s0 = 0.0, s1 = 0.0;
+  if (src) {
+    const double *sf = src + fo * geo.G + (int)t * M;
+    for (int i = lane; i < M; i += 64) { const double v = sf[i]; uf[base + 1 + i] = v; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+  } else if (!(dir0 && dir1)) {
+    for (int i = lane; i < M; i += 64) { const double v = uf[base + 1 + i]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64); }
+  if (lane == 0) {
+    double g0 = 0.0, g1 = 0.0;
+    if (g) {
+      const double *gf = g + fo * geo.NB;
+      g0 = gf[base - pb_before<DC>(geo, j, k, false)];
+      g1 = gf[base + lend - pb_before<DC>(geo, j, k, true)];
+    }
+    const double *Bi = bm + 4 * M;
+    uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
+    uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
+  }
+}
+
 }  // namespace
 
 struct cheb_helmholtz {
   chebhip_fdpc *pc = nullptr;
   long n = 0;                                  // nfields * prod(dims - 2)
+  bool per = false; PbGeo pgeo = {};           // cheb_helmholtz_create_basis with a periodic direction: the k_pb_* kernels run
   // cheb_helmholtz_create_bc only: full-grid geometry, per-direction end flags (beta = 0), the singular flag, two nf * G buffers
   bool bc = false; int singular = 0; int nf = 1;
   BcGeo geo = {};
@@ -1178,45 +1355,121 @@ extern "C" int cheb_helmholtz_line_host(int P, double *S, double *Sinv, double *
   return 0;
 }
 
+// ---- C ABI: host matrices of a periodic direction; they need no device ------------------------------------------------
+static int check_fourier_extent(int n) {
+  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d: a periodic direction needs at least 2 points", n);
+  if (n > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: a periodic direction supports at most 256 points", n);
+  return 0;
+}
+extern "C" int cheb_fourier_nodes_host(int n, double *x) {
+  int rc = check_fourier_extent(n); if (rc) return rc;
+  if (!x) return chebhip_fail(CHEBHIP_ERR_ARG, "x is NULL");
+  fourier_nodes_host(n, x);
+  return 0;
+}
+extern "C" int cheb_fourier_diff_matrix_host(int n, int order, double *D) {
+  int rc = check_fourier_extent(n); if (rc) return rc;
+  if (order != 1 && order != 2) return chebhip_fail(CHEBHIP_ERR_ARG, "order = %d is neither 1 nor 2", order);
+  if (!D) return chebhip_fail(CHEBHIP_ERR_ARG, "D is NULL");
+  std::vector<long double> A;
+  fourier_diff_ld(n, order, A);
+  for (size_t e = 0; e < A.size(); e++) D[e] = (double)A[e];
+  return 0;
+}
+extern "C" int cheb_fourier_line_host(int n, double scale, double *S, double *Sinv, double *lam) {
+  int rc = check_fourier_extent(n); if (rc) return rc;
+  if (!S || !Sinv || !lam) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  if (!std::isfinite(scale) || !(scale > 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale = %g must be finite and > 0", scale);
+  std::vector<long double> s, si, l;
+  fourier_line(n, scale, s, si, l);
+  for (size_t e = 0; e < s.size(); e++) { S[e] = (double)s[e]; Sinv[e] = (double)si[e]; }
+  for (int i = 0; i < n; i++) lam[i] = (double)l[i];
+  return 0;
+}
+extern "C" int cheb_fourier_modal_matrix_host(int n, int which, double *M) {
+  int rc = check_fourier_extent(n); if (rc) return rc;
+  if (which != 0 && which != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d is neither 0 (forward) nor 1 (backward)", which);
+  if (!M) return chebhip_fail(CHEBHIP_ERR_ARG, "M is NULL");
+  std::vector<long double> A;
+  fourier_modal_ld(n, which, A);
+  for (size_t e = 0; e < A.size(); e++) M[e] = (double)A[e];
+  return 0;
+}
+extern "C" int cheb_fourier_modes_host(int n, int *k, int *kind) {
+  int rc = check_fourier_extent(n); if (rc) return rc;
+  if (!k || !kind) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  fourier_modes_host(n, k, kind);
+  return 0;
+}
+
 // ---- C ABI: the Helmholtz solve with Dirichlet, Neumann or Robin ends --------------------------------------------
 // scale (NULL: 1 everywhere): the box [-1/s_0, 1/s_0] x ..: (sigma - sum_k s_k^2 d_k^2) u = f, alpha u + beta s_k du/dnu = g
-extern "C" int cheb_helmholtz_create_box(int d, const int *dims, const double *bc, const double *scale, double sigma, int nfields,
-                                         cheb_helmholtz **out) {
+// basis (cheb_helmholtz_create_basis; NULL: walls everywhere, cheb_helmholtz_create_box itself): basis[k] = 1 makes direction k
+// periodic -- dims[k] unknowns on the nodes -1 + 2 j / dims[k], no faces; its bc entries are not read (bc may be NULL if every
+// direction is periodic)
+static int helmholtz_create(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nfields,
+                            cheb_helmholtz **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
-  if (!bc) return chebhip_fail(CHEBHIP_ERR_ARG, "bc is NULL");
+  bool any_per = false, all_per = basis != nullptr;
+  for (int k = 0; basis && k < d; k++) {
+    if (basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
+    any_per = any_per || basis[k] == BASIS_FOURIER; all_per = all_per && basis[k] == BASIS_FOURIER;
+  }
+  auto fourier = [&](int k) { return basis && basis[k] == BASIS_FOURIER; };
+  if (!bc && !all_per) return chebhip_fail(CHEBHIP_ERR_ARG, "bc is NULL");
   int rc = check_sigma(sigma); if (rc) return rc;
   if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   for (int k = 0; scale && k < d; k++)
     if (!std::isfinite(scale[k]) || !(scale[k] > 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] = %g must be finite and > 0", k, scale[k]);
   for (int k = 0; k < d; k++)
-    for (int e = 0; e < 2; e++) {
+    for (int e = 0; e < 2 && !fourier(k); e++) {
       const double a = bc[4 * k + 2 * e], b = bc[4 * k + 2 * e + 1];
       if (!std::isfinite(a) || !std::isfinite(b) || a < 0.0 || b < 0.0 || (a == 0.0 && b == 0.0))
         return chebhip_fail(CHEBHIP_ERR_ARG, "bc[%d] %s end: (alpha, beta) = (%g, %g) must be finite, >= 0 and not both 0", k, e ? "last" : "first", a, b);
     }
   long N = 1, G = 1;
   for (int k = 0; k < d; k++) {
-    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
-    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
-    G *= dims[k] - 2;
+    if (fourier(k)) {
+      if (dims[k] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: a periodic direction needs at least 2 points", k, dims[k]);
+      if (dims[k] > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
+    } else {
+      if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
+      if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
+    }
+    G *= fourier(k) ? dims[k] : dims[k] - 2;
     N *= dims[k];
     if (N * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 full-grid values");
   }
   FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
   cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
-  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc, scale);
+  std::vector<double> bcd;                     // the end conditions fdpc_create reads: Dirichlet placeholders on periodic directions
+  if (any_per) {
+    bcd.resize((size_t)4 * d);
+    for (int k = 0; k < d; k++) for (int e = 0; e < 4; e++) bcd[(size_t)4 * k + e] = fourier(k) ? BC_DIRICHLET[e] : bc[4 * k + e];
+    bc = bcd.data();
+  }
+  rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc, scale, any_per ? basis : nullptr);
   if (rc) { delete h; return rc; }
-  h->n = G * nfields; h->nf = nfields; h->bc = true;
+  h->n = G * nfields; h->nf = nfields; h->bc = true; h->per = any_per;
   h->geo.d = d; h->geo.N = (int)N; h->geo.G = (int)G; h->geo.NB = (int)(N - G);
+  h->pgeo.d = d; h->pgeo.N = (int)N; h->pgeo.G = (int)G; h->pgeo.NB = (int)(N - G);
   {
     int s = 1, si = 1;
-    for (int k = d - 1; k >= 0; k--) { h->geo.P[k] = dims[k]; h->geo.ls[k] = s; h->geo.gs[k] = si; s *= dims[k]; si *= dims[k] - 2; }
+    for (int k = d - 1; k >= 0; k--) {
+      const int Mk = fourier(k) ? dims[k] : dims[k] - 2;
+      h->geo.P[k] = h->pgeo.P[k] = dims[k]; h->geo.ls[k] = h->pgeo.ls[k] = s; h->geo.gs[k] = h->pgeo.gs[k] = si;
+      h->pgeo.M[k] = Mk; h->pgeo.off[k] = fourier(k) ? 0 : 1;
+      s *= dims[k]; si *= Mk;
+    }
   }
+  // singular: some modal sum is exactly 0 -- sigma = 0 and every direction has a zero eigenvalue (Neumann / Neumann: the constant;
+  // periodic: the constant and, for an even extent, the Nyquist vector).  Every product of such modes is dropped.
   bool neumann = true;
   for (int k = 0; k < d; k++) {
+    if (fourier(k)) { h->dir[k][0] = h->dir[k][1] = 0; continue; }
     h->dir[k][0] = bc[4 * k + 1] == 0.0; h->dir[k][1] = bc[4 * k + 3] == 0.0;
     neumann = neumann && bc[4 * k] == 0.0 && bc[4 * k + 2] == 0.0;
   }
@@ -1229,6 +1482,18 @@ extern "C" int cheb_helmholtz_create_box(int d, const int *dims, const double *b
   }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_helmholtz_create_box(int d, const int *dims, const double *bc, const double *scale, double sigma, int nfields,
+                                         cheb_helmholtz **out) {
+  return helmholtz_create(d, dims, nullptr, bc, scale, sigma, nfields, out);
+}
+
+extern "C" int cheb_helmholtz_create_basis(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nfields,
+                                           cheb_helmholtz **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return helmholtz_create(d, dims, basis, bc, scale, sigma, nfields, out);
 }
 
 extern "C" int cheb_helmholtz_create_bc(int d, const int *dims, const double *bc, double sigma, int nfields, cheb_helmholtz **out) {
@@ -1275,6 +1540,32 @@ static int bc_extend(const cheb_helmholtz *h, int nf, const double *z, const dou
   return 0;
 }
 
+// bc_extend on a handle with a periodic direction: the wall directions in ascending order, the first of them embedding the unknowns;
+// no wall at all: the unknown layout IS the full grid
+static int pb_extend(const cheb_helmholtz *h, int nf, const double *z, const double *g_dev, double *u_dev, hipStream_t st) {
+  const PbGeo &geo = h->pgeo;
+  const int d = geo.d;
+  bool first = true;
+  long before = 1;                             // prod_{m < k} P_m
+  for (int k = 0; k < d; k++) {
+    if (geo.off[k]) {
+      const double *src = first ? z : nullptr, *bm = h->pc->ln[k]->bcm;
+      first = false;
+      if (k < d - 1) {
+        long nl = before;
+        for (int m = k + 1; m < d; m++) nl *= geo.M[m];
+        BC_LAUNCH(k_pb_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), geo, k, bm, h->dir[k][0], h->dir[k][1], (int)nl, src, g_dev, u_dev);
+      } else {
+        BC_LAUNCH(k_pb_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), geo, bm, h->dir[k][0], h->dir[k][1], (int)before, src, g_dev, u_dev);
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    before *= geo.P[k];
+  }
+  if (first) HIP_TRY(hipMemcpyAsync(u_dev, z, (size_t)nf * geo.N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, const double *g_dev, double *u_dev, void *stream) {
   if (!h || !h->pc) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (!h->bc) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_helmholtz_solve_bc: a handle from cheb_helmholtz_create_bc");
@@ -1283,17 +1574,25 @@ extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, c
   const long G = h->geo.G, N = h->geo.N, NB = h->geo.NB;
   if (overlaps(u_dev, nf * N, f_dev, nf * G) || (g_dev && overlaps(u_dev, nf * N, g_dev, nf * NB)))
     return chebhip_fail(CHEBHIP_ERR_ARG, "u may not alias f or g");
+  if (g_dev && NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "g given, but every direction is periodic: there is no boundary data to lift");
   hipStream_t st = (hipStream_t)stream;
   BcMats bm;
   for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
   const double *rhs = f_dev;
-  if (g_dev) {                                 // (g = NULL: zero data, nothing to lift)
+  if (g_dev && h->per) {
+    const PbGeo &geo = h->pgeo;
+    const int nl = geo.G / geo.M[d - 1];
+    BC_LAUNCH(k_pb_lift, dim3((unsigned)((nl + 3) / 4), (unsigned)nf), geo, bm, nl, f_dev, g_dev, h->t);
+    HIP_TRY(hipGetLastError());
+    rhs = h->t;
+  } else if (g_dev) {                          // (g = NULL: zero data, nothing to lift)
     const BcGeo &geo = h->geo;
     BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), geo, bm, f_dev, g_dev, h->t);
     HIP_TRY(hipGetLastError());
     rhs = h->t;
   }
   int rc = fdm_solve(h->pc, rhs, h->z, st); if (rc) return rc;
+  if (h->per) return pb_extend(h, nf, h->z, g_dev, u_dev, st);
   return bc_extend(h, nf, h->z, g_dev, u_dev, st);
 }
 
@@ -1392,7 +1691,7 @@ static int opfun_run(cheb_opfun *h, const double *x, double *y, hipStream_t st) 
     src = a; std::swap(a, b);
   }
   int M[MAXD]; const double *lam[MAXD];
-  for (int k = 0; k < d; k++) { M[k] = pc->geo.dims[k] - 2; lam[k] = k == 0 ? pc->lam0 : pc->ln[k]->lam; }
+  for (int k = 0; k < d; k++) { M[k] = pc->M[k]; lam[k] = k == 0 ? pc->lam0 : pc->ln[k]->lam; }
   if ((rc = opfun_mix_launch(h->tb, d, M, pc->G, lam, src, a, st))) return rc;
   src = a; std::swap(a, b);
   for (int k = d - 1; k >= 0; k--) {

@@ -268,4 +268,16 @@ int spec_line_bc(int P, const double *bc4, std::vector<long double> &S, std::vec
                  std::vector<long double> &Q, std::vector<long double> &L, std::vector<long double> &Binv, bool &parity);
 void centro_part(int M, const std::vector<long double> &A, int part, std::vector<long double> &out);
 
+// Periodic (Fourier) directions (diffmat.cpp): n nodes x_j = -1 + 2 j / n, 2 <= n <= 256 (checked by the callers).
+// The nodes; D_F (order 1) or D_F D_F (order 2) in long double; the position -> (k, kind) map of the parity mode layout (kind 0 cos
+// with k = 0 the constant, 1 sin, 2 Nyquist); the transform matrices B (which = 1) and T = B^-1 (which = 0); the line of the solve
+// -s^2 D_F D_F = S diag(lam) S^-1 (S = B, S^-1 = T); and the DiffMat of D_F / D_F D_F for the sweep kernels.
+enum { BASIS_CGL = 0, BASIS_FOURIER = 1 };
+void fourier_nodes_host(int n, double *x);
+void fourier_diff_ld(int n, int order, std::vector<long double> &A);
+void fourier_modes_host(int n, int *k, int *kind);
+void fourier_modal_ld(int n, int which, std::vector<long double> &M);
+void fourier_line(int n, double s, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam);
+hipError_t diffmat_create_fourier(int n, int order, DiffMat *out);
+
 }  // namespace chebhip

@@ -78,6 +78,19 @@ def poisson_solve(sp, op, b, x, sigma=0.0, solver=None):
     return x
 
 
+def channel_poisson(sp, dims, f, periodic, scale=None):
+    """-sum_k scale_k^2 d_k^2 u = f on a box whose flagged directions are periodic and whose other faces carry u = 0, solved
+    directly for the one-off case (a HelmholtzSolver with bc "periodic" / "dirichlet" made and destroyed here).  f: full-grid
+    device tensor of prod(dims) values, the nodes fourier_nodes(dims[k]) along a periodic direction and cgl_nodes(dims[k]) along a
+    wall one; its wall entries are ignored.  With every direction periodic the problem is singular: the components of f along the
+    dropped modes (HelmholtzSolver's docstring) are ignored and u has none.  Returns the full-grid u (a new tensor)."""
+    dims = tuple(int(d) for d in dims)
+    flags = tuple(bool(p) for p in periodic)
+    if len(flags) != len(dims):
+        raise ValueError("periodic: expected %d flags, got %d" % (len(dims), len(flags)))
+    return helmholtz_bvp(sp, dims, f, None, ["periodic" if p else "dirichlet" for p in flags], 0.0, scale=scale)
+
+
 def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     """sigma u - Laplace u = f with alpha u + beta du/dnu = g on every face (sp.HelmholtzSolver's `bc`), solved directly.
     f_full: full-grid device tensor (its boundary entries are ignored); g: the compact boundary values in row-major node order
@@ -90,12 +103,12 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
         solver = sp.HelmholtzSolver(dims, sigma, bc=bc, scale=scale)
     elif solver.scale != (None if scale is None else tuple(float(v) for v in scale)):
         raise ValueError("solver: a HelmholtzSolver with the same scale")
-    elif solver.dims != dims or solver.sigma != float(sigma) or solver.bc is None or solver.bc != tuple(tuple(sp.bc_array(bc, len(dims))[4 * k:4 * k + 4]) for k in range(len(dims))):
+    elif solver.dims != dims or solver.sigma != float(sigma) or solver.bc is None or solver.bc != sp.bc_split(bc, len(dims))[2]:
         raise ValueError("solver: a HelmholtzSolver of the grid with sigma = %g and the same bc" % sigma)
     try:
         if f_full.numel() != solver.full_size:
             raise ValueError("f_full has %d elements, expected %d" % (f_full.numel(), solver.full_size))
-        inner = tuple(slice(1, -1) for _ in dims)
+        inner = tuple(slice(None) if p else slice(1, -1) for p in solver.periodic)      # a periodic direction has no end nodes
         f = f_full.reshape((solver.nfields,) + dims)[(slice(None),) + inner].contiguous().reshape(-1)
         u = torch.empty_like(f_full).contiguous()
         solver.solve_full(f, g, u)
