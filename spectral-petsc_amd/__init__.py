@@ -1603,15 +1603,9 @@ class HelmholtzSolver(_FdmSteps, _Handle):
         else:
             d = len(self.dims)
             self.periodic, b, self.bc = bc_split(bc, d)
-            if any(self.periodic):
-                _chk(lib().cheb_helmholtz_create_basis(d, _ints(self.dims), _ints([int(p) for p in self.periodic]), (C.c_double * len(b))(*b),
-                                                       None if sc is None else _np_dp(sc), self.sigma, self.nfields, C.byref(h)))
-            elif sc is None:
-                _chk(lib().cheb_helmholtz_create_bc(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), self.sigma,
-                                                    self.nfields, C.byref(h)))
-            else:
-                _chk(lib().cheb_helmholtz_create_box(len(self.dims), _ints(self.dims), (C.c_double * len(b))(*b), _np_dp(sc), self.sigma,
-                                                     self.nfields, C.byref(h)))
+            # (no periodic direction and no scale: cheb_helmholtz_create_bc's handle; no periodic direction: cheb_helmholtz_create_box's)
+            _chk(lib().cheb_helmholtz_create_basis(d, _ints(self.dims), _ints([int(p) for p in self.periodic]), (C.c_double * len(b))(*b),
+                                                   None if sc is None else _np_dp(sc), self.sigma, self.nfields, C.byref(h)))
             self.full_size = lib().cheb_helmholtz_full_size(h)
             self.boundary_size = lib().cheb_helmholtz_boundary_size(h)
             self.singular = bool(lib().cheb_helmholtz_singular(h))

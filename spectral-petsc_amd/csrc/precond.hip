@@ -966,171 +966,19 @@ extern "C" int ell_pc_create_spectral(ell_op *op, double sigma, chebhip_fdpc **o
 // ---- boundary conditions (cheb_helmholtz_create_bc): the lift of the boundary data and the full-grid extension -------------------
 namespace {
 
-// full-grid geometry: extents, row-major strides of the full grid (ls) and of the interior (gs), sizes per field (NB = N - G).
-// 32-bit: a boundary-condition handle has nf N <= 2^31 - 1 (cheb_helmholtz_create_bc), so every index below fits.
-struct BcGeo { int d; int P[MAXD]; int ls[MAXD]; int gs[MAXD]; int N, G, NB; };
+// full-grid geometry: extents, row-major strides of the full grid (ls) and of the unknowns (gs), sizes per field (NB = N - G).
+// Direction k has M[k] unknowns starting at full-grid index off[k]: (P - 2, 1) between two walls, (P, 0) on a periodic direction
+// (cheb_helmholtz_create_basis), which has no face data and no end values.
+// 32-bit: a boundary-condition handle has nf N <= 2^31 - 1 (helmholtz_create), so every index below fits.
+struct BcGeo { int d; int P[MAXD]; int M[MAXD]; int off[MAXD]; int ls[MAXD]; int gs[MAXD]; int N, G, NB; };
 struct BcMats { const double *m[MAXD]; };      // per direction: Q row 0, Q row 1, L column 0, L column 1 (M each), B_BB^-1 (4)
 
-// Position of a boundary node in the compact boundary layout (row-major node order, ell_op_set_dirichlet): its full-grid index
-// minus the number of interior nodes before it.  The node is end `last` of direction k on a line whose indices in directions
-// < k are j[]; the count stops at the first non-interior index (0: no interior node of that subtree comes before; n: all do).
+// Position of a boundary node in the compact boundary layout (row-major order over the nodes that are end nodes of some wall
+// direction, ell_op_set_dirichlet): its full-grid index minus the number of unknown nodes before it.  The node is end `last` of
+// direction k on a line whose indices in directions < k are j[]; the count stops at the first wall end (0: no unknown of that
+// subtree comes before; n: all do); a periodic direction m < k counts j[m] whole blocks of unknowns and never ends the walk.
 template <int DC>
 __device__ __forceinline__ int bc_before(const BcGeo &g, const int *j, int k, bool last) {
-  int c = 0;
-  bool done = false;
-  for (int m = 0; m < (DC ? DC : MAXD); m++)
-    if (m < k && !done) {
-      if (j[m] == 0) done = true;
-      else if (j[m] == g.P[m] - 1) { c += (g.P[m] - 2) * g.gs[m]; done = true; }
-      else c += (j[m] - 1) * g.gs[m];
-    }
-  return last && !done ? c + (g.P[k] - 2) * g.gs[k] : c;
-}
-
-// t = f + sum_k L_k (g at the two faces of direction k) on nf stacked interior fields (field = blockIdx.y).  One thread per
-// interior node, the last index fastest: for k < d-1 consecutive threads read consecutive face values; for k = d-1 a line's
-// threads share its two values.  (DC: d known at compile time, 0: any d up to MAXD.)
-template <int DC>
-__global__ __launch_bounds__(256) void k_bc_lift(BcGeo geo, BcMats bm, const double *__restrict__ f, const double *__restrict__ g,
-                                                 double *__restrict__ t) {
-  const int d = DC ? DC : geo.d;
-  const unsigned q = blockIdx.x * 256u + threadIdx.x;
-  if (q >= (unsigned)geo.G) return;
-  const int fo = blockIdx.y;
-  const double *gf = g + fo * geo.NB;
-  int i[MAXD];
-  unsigned r = q;
-  for (int m = (DC ? DC : MAXD) - 1; m > 0; m--)
-    if (m < d) { const unsigned Mm = (unsigned)(geo.P[m] - 2); i[m] = (int)(r % Mm); r /= Mm; }
-  i[0] = (int)r;
-  int base = 0;
-  for (int m = 0; m < (DC ? DC : MAXD); m++) if (m < d) base += (i[m] + 1) * geo.ls[m];
-  double s = f[fo * geo.G + (int)q];
-  int c = 0;                                   // interior nodes before the first face node: sum_{m < k} i_m gs_m
-  for (int k = 0; k < (DC ? DC : MAXD); k++)
-    if (k < d) {
-      const int M = geo.P[k] - 2;
-      const double *L = bm.m[k] + 2 * M;
-      const int b0 = base - (i[k] + 1) * geo.ls[k] - c;
-      const int b1 = b0 + (geo.P[k] - 1) * geo.ls[k] - M * geo.gs[k];
-      s += L[i[k]] * gf[b0] + L[M + i[k]] * gf[b1];
-      c += i[k] * geo.gs[k];
-    }
-  t[fo * geo.G + (int)q] = s;
-}
-
-// End values of direction k < d-1 on nf stacked full grids (field = blockIdx.y): u_end = Q_k u_line + B_BB^-1 g_line on every
-// line whose indices in directions < k are any and in directions > k interior.  A workgroup takes 64 lines, consecutive in the
-// last index (a wave reads 64 consecutive values at every step), and splits each line into four segments, one per wave (one
-// thread per line would leave a single wave per SIMD at 256^3); the partial sums meet in LDS.  A Dirichlet end (beta = 0) is
-// B_BB^-1 g, a copy for alpha = 1.  src (k = 0 only): the lines' interior values are read from the interior solution and
-// embedded into u on the way.
-constexpr int BC_SEG = 4;
-template <int DC>
-__global__ __launch_bounds__(256) void k_bc_extend_col(BcGeo geo, int k, const double *__restrict__ bm, int dir0, int dir1, int nlines,
-                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
-  __shared__ double red[2][BC_SEG][64];
-  const int d = DC ? DC : geo.d;
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const unsigned t = blockIdx.x * 64u + lane;
-  const bool ok = t < (unsigned)nlines;
-  const int fo = blockIdx.y;
-  double *uf = u + fo * geo.N;
-  const int M = geo.P[k] - 2, ls = geo.ls[k], lend = (geo.P[k] - 1) * ls;
-  int j[MAXD];
-  unsigned r = ok ? t : 0u;
-  int base = 0, ibase = 0;
-  for (int m = (DC ? DC : MAXD) - 1; m >= 0; m--) {
-    if (m >= d || m == k) continue;
-    const unsigned rad = (unsigned)(m < k ? geo.P[m] : geo.P[m] - 2);
-    const int x = (int)(r % rad); r /= rad;
-    j[m] = m < k ? x : x + 1;
-    base += j[m] * geo.ls[m];
-    ibase += (j[m] - 1) * geo.gs[m];
-  }
-  const int per = (M + BC_SEG - 1) / BC_SEG, i0 = seg * per, i1 = i0 + per < M ? i0 + per : M;
-  double s0 = 0.0, s1 = 0.0;
-  if (ok) {
-    if (src) {
-      const double *sf = src + fo * geo.G + ibase;
-      const int gk = geo.gs[k];
-#pragma unroll 4
-      for (int i = i0; i < i1; i++) {
-        const double v = sf[i * gk];
-        uf[base + (i + 1) * ls] = v;
-        s0 += bm[i] * v; s1 += bm[M + i] * v;
-      }
-    } else if (!(dir0 && dir1)) {
-#pragma unroll 4
-      for (int i = i0; i < i1; i++) { const double v = uf[base + (i + 1) * ls]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
-    }
-  }
-  red[0][seg][lane] = s0; red[1][seg][lane] = s1;
-  __syncthreads();
-  if (seg != 0 || !ok) return;
-  s0 = red[0][0][lane]; s1 = red[1][0][lane];
-  for (int q = 1; q < BC_SEG; q++) { s0 += red[0][q][lane]; s1 += red[1][q][lane]; }
-  double g0 = 0.0, g1 = 0.0;
-  if (g) {
-    const double *gf = g + fo * geo.NB;
-    g0 = gf[base - bc_before<DC>(geo, j, k, false)];
-    g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
-  }
-  const double *Bi = bm + 4 * M;
-  uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
-  uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
-}
-
-// The same for the last direction, whose lines are contiguous: one wave per line (four per workgroup) reduces Q_k u_line across its
-// lanes.  src (d = 1 only): embed the interior solution on the way.
-template <int DC>
-__global__ __launch_bounds__(256) void k_bc_extend_row(BcGeo geo, const double *__restrict__ bm, int dir0, int dir1, int nlines,
-                                                       const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
-  const int d = DC ? DC : geo.d, k = d - 1;
-  const unsigned t = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (t >= (unsigned)nlines) return;           // (wave-uniform)
-  const int fo = blockIdx.y;
-  double *uf = u + fo * geo.N;
-  const int M = geo.P[k] - 2, lane = threadIdx.x & 63, lend = geo.P[k] - 1;
-  int j[MAXD];
-  unsigned r = t;
-  int base = 0;
-  for (int m = (DC ? DC : MAXD) - 2; m >= 0; m--) {
-    if (m >= k) continue;
-    const int x = (int)(r % (unsigned)geo.P[m]); r /= (unsigned)geo.P[m];
-    j[m] = x; base += x * geo.ls[m];
-  }
-  double s0 = 0.0, s1 = 0.0;
-  if (src) {
-    const double *sf = src + fo * geo.G;
-    for (int i = lane; i < M; i += 64) { const double v = sf[i]; uf[base + 1 + i] = v; s0 += bm[i] * v; s1 += bm[M + i] * v; }
-  } else if (!(dir0 && dir1)) {
-    for (int i = lane; i < M; i += 64) { const double v = uf[base + 1 + i]; s0 += bm[i] * v; s1 += bm[M + i] * v; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64); }
-  if (lane == 0) {
-    double g0 = 0.0, g1 = 0.0;
-    if (g) {
-      const double *gf = g + fo * geo.NB;
-      g0 = gf[base - bc_before<DC>(geo, j, k, false)];
-      g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
-    }
-    const double *Bi = bm + 4 * M;
-    uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
-    uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
-  }
-}
-
-// ---- the same with periodic directions (cheb_helmholtz_create_basis) ------------------------------------------------
-// Direction k has M[k] unknowns starting at full-grid index off[k]: (P - 2, 1) between two walls, (P, 0) on a periodic direction, which
-// has no face data and no end values.  The compact boundary layout keeps its rule -- full-grid index minus the unknown nodes before
-// it -- over the nodes that are end nodes of some WALL direction.  These kernels run only on handles with a periodic direction.
-struct PbGeo { int d; int P[MAXD]; int M[MAXD]; int off[MAXD]; int ls[MAXD]; int gs[MAXD]; int N, G, NB; };
-
-// bc_before for PbGeo: a periodic direction m < k counts j[m] whole blocks of unknowns and never ends the walk
-template <int DC>
-__device__ __forceinline__ int pb_before(const PbGeo &g, const int *j, int k, bool last) {
   int c = 0;
   bool done = false;
   for (int m = 0; m < (DC ? DC : MAXD); m++)
@@ -1144,51 +992,50 @@ __device__ __forceinline__ int pb_before(const PbGeo &g, const int *j, int k, bo
 }
 
 // t = f + sum over the wall directions k of L_k (g at the two faces of direction k), nf stacked unknown fields (field = blockIdx.y).
-// One wave per line of the last direction, four lines per workgroup: the line's other indices are decoded once, by wave-uniform
-// arithmetic, and the lanes walk the contiguous run -- f, t and the face values of every direction but the last are read and written
-// as consecutive doubles, the last direction's two face values are shared by the line.  The terms are added in k's order, each as
-// L0 g0 + L1 g1: the association of k_bc_lift.
+// One thread per unknown, the last index fastest: for k < d-1 consecutive threads read consecutive face values; for k = d-1 a
+// line's threads share its two values.  The terms are added in k's order, each as L0 g0 + L1 g1.  (DC: d known at compile time,
+// 0: any d up to MAXD.)
 template <int DC>
-__global__ __launch_bounds__(256) void k_pb_lift(PbGeo geo, BcMats bm, int nlines, const double *__restrict__ f, const double *__restrict__ g,
+__global__ __launch_bounds__(256) void k_bc_lift(BcGeo geo, BcMats bm, const double *__restrict__ f, const double *__restrict__ g,
                                                  double *__restrict__ t) {
   const int d = DC ? DC : geo.d;
-  const unsigned line = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (line >= (unsigned)nlines) return;        // (wave-uniform)
-  const int lane = threadIdx.x & 63, fo = blockIdx.y;
+  const unsigned q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= (unsigned)geo.G) return;
+  const int fo = blockIdx.y;
   const double *gf = g + fo * geo.NB;
   int i[MAXD];
-  unsigned r = line;
-  for (int m = (DC ? DC : MAXD) - 2; m > 0; m--)
-    if (m < d - 1) { const unsigned Mm = (unsigned)geo.M[m]; i[m] = (int)(r % Mm); r /= Mm; }
+  unsigned r = q;
+  for (int m = (DC ? DC : MAXD) - 1; m > 0; m--)
+    if (m < d) { const unsigned Mm = (unsigned)geo.M[m]; i[m] = (int)(r % Mm); r /= Mm; }
   i[0] = (int)r;
-  int base = geo.off[d - 1];                   // full-grid index of the line's first unknown
-  for (int m = 0; m < (DC ? DC : MAXD) - 1; m++) if (m < d - 1) base += (i[m] + geo.off[m]) * geo.ls[m];
-  const int Ml = geo.M[d - 1], row = fo * geo.G + (int)line * Ml;
-  for (int il = lane; il < Ml; il += 64) {
-    double s = f[row + il];
-    int c = 0;                                 // unknown nodes before the first face node: sum_{m < k} i_m gs_m
-    for (int k = 0; k < (DC ? DC : MAXD); k++)
-      if (k < d) {
-        const int ik = k == d - 1 ? il : i[k];
-        if (geo.off[k]) {
-          const int M = geo.M[k];
-          const double *L = bm.m[k] + 2 * M;
-          const int b0 = base + il - (ik + 1) * geo.ls[k] - c;
-          const int b1 = b0 + (geo.P[k] - 1) * geo.ls[k] - M * geo.gs[k];
-          s += L[ik] * gf[b0] + L[M + ik] * gf[b1];
-        }
-        c += ik * geo.gs[k];
+  int base = 0;
+  for (int m = 0; m < (DC ? DC : MAXD); m++) if (m < d) base += (i[m] + geo.off[m]) * geo.ls[m];
+  double s = f[fo * geo.G + (int)q];
+  int c = 0;                                   // unknown nodes before the first face node: sum_{m < k} i_m gs_m
+  for (int k = 0; k < (DC ? DC : MAXD); k++)
+    if (k < d) {
+      if (geo.off[k]) {
+        const int M = geo.M[k];
+        const double *L = bm.m[k] + 2 * M;
+        const int b0 = base - (i[k] + 1) * geo.ls[k] - c;
+        const int b1 = b0 + (geo.P[k] - 1) * geo.ls[k] - M * geo.gs[k];
+        s += L[i[k]] * gf[b0] + L[M + i[k]] * gf[b1];
       }
-    t[row + il] = s;
-  }
+      c += i[k] * geo.gs[k];
+    }
+  t[fo * geo.G + (int)q] = s;
 }
 
-// End values of the wall direction k < d-1 (k_bc_extend_col's tiling: 64 lines consecutive in the last index per workgroup, four
-// segments per line): the lines whose indices in directions < k are any and in directions > k unknowns.  src (the FIRST wall
-// direction only, where every direction before k is periodic and these lines hold every unknown exactly once): the lines' unknowns are
-// read from the solution in the unknown layout and embedded into u on the way.
+// End values of the wall direction k < d-1 on nf stacked full grids (field = blockIdx.y): u_end = Q_k u_line + B_BB^-1 g_line on
+// every line whose indices in directions < k are any and in directions > k unknowns.  A workgroup takes 64 lines, consecutive in
+// the last index (a wave reads 64 consecutive values at every step), and splits each line into four segments, one per wave (one
+// thread per line would leave a single wave per SIMD at 256^3); the partial sums meet in LDS.  A Dirichlet end (beta = 0) is
+// B_BB^-1 g, a copy for alpha = 1.  src (the FIRST wall direction only, where every direction before k is periodic and these lines
+// hold every unknown exactly once): the lines' unknowns are read from the solution in the unknown layout and embedded into u on
+// the way.
+constexpr int BC_SEG = 4;
 template <int DC>
-__global__ __launch_bounds__(256) void k_pb_extend_col(PbGeo geo, int k, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+__global__ __launch_bounds__(256) void k_bc_extend_col(BcGeo geo, int k, const double *__restrict__ bm, int dir0, int dir1, int nlines,
                                                        const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
   __shared__ double red[2][BC_SEG][64];
   const int d = DC ? DC : geo.d;
@@ -1234,18 +1081,18 @@ __global__ __launch_bounds__(256) void k_pb_extend_col(PbGeo geo, int k, const d
   double g0 = 0.0, g1 = 0.0;
   if (g) {
     const double *gf = g + fo * geo.NB;
-    g0 = gf[base - pb_before<DC>(geo, j, k, false)];
-    g1 = gf[base + lend - pb_before<DC>(geo, j, k, true)];
+    g0 = gf[base - bc_before<DC>(geo, j, k, false)];
+    g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
   }
   const double *Bi = bm + 4 * M;
   uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
   uf[base + lend] = dir1 ? Bi[3] * g1 : s1 + (Bi[2] * g0 + Bi[3] * g1);
 }
 
-// The same for a wall in the last direction (contiguous lines, one wave per line).  src: as above, every earlier direction periodic,
-// so line t of u is line t of the solution.
+// The same for the last direction, whose lines are contiguous: one wave per line (four per workgroup) reduces Q_k u_line across its
+// lanes.  src (the first wall direction, as above): every earlier direction is periodic, so line t of u is line t of the solution.
 template <int DC>
-__global__ __launch_bounds__(256) void k_pb_extend_row(PbGeo geo, const double *__restrict__ bm, int dir0, int dir1, int nlines,
+__global__ __launch_bounds__(256) void k_bc_extend_row(BcGeo geo, const double *__restrict__ bm, int dir0, int dir1, int nlines,
                                                        const double *__restrict__ src, const double *__restrict__ g, double *__restrict__ u) {
   const int d = DC ? DC : geo.d, k = d - 1;
   const unsigned t = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -1274,8 +1121,8 @@ __global__ __launch_bounds__(256) void k_pb_extend_row(PbGeo geo, const double *
     double g0 = 0.0, g1 = 0.0;
     if (g) {
       const double *gf = g + fo * geo.NB;
-      g0 = gf[base - pb_before<DC>(geo, j, k, false)];
-      g1 = gf[base + lend - pb_before<DC>(geo, j, k, true)];
+      g0 = gf[base - bc_before<DC>(geo, j, k, false)];
+      g1 = gf[base + lend - bc_before<DC>(geo, j, k, true)];
     }
     const double *Bi = bm + 4 * M;
     uf[base] = dir0 ? Bi[0] * g0 : s0 + (Bi[0] * g0 + Bi[1] * g1);
@@ -1287,29 +1134,46 @@ __global__ __launch_bounds__(256) void k_pb_extend_row(PbGeo geo, const double *
 
 struct cheb_helmholtz {
   chebhip_fdpc *pc = nullptr;
-  long n = 0;                                  // nfields * prod(dims - 2)
-  bool per = false; PbGeo pgeo = {};           // cheb_helmholtz_create_basis with a periodic direction: the k_pb_* kernels run
-  // cheb_helmholtz_create_bc only: full-grid geometry, per-direction end flags (beta = 0), the singular flag, two nf * G buffers
-  bool bc = false; int singular = 0; int nf = 1;
+  long n = 0;                                  // nfields * unknowns per field
+  // boundary-condition handles (helmholtz_create) only: full-grid geometry, per-direction end flags (beta = 0), the singular flag,
+  // two nfields * G buffers
+  bool bc = false; int singular = 0;
   BcGeo geo = {};
   int dir[MAXD][2] = {};
   double *t = nullptr, *z = nullptr;
 };
 
-extern "C" int cheb_helmholtz_create(int d, const int *dims, double sigma, int nfields, cheb_helmholtz **out) {
-  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
-  *out = nullptr;
+// The argument checks of every Helmholtz handle, and its sizes: N full-grid values and G unknowns per field.  basis: NULL (walls
+// everywhere) or as in helmholtz_create.  full: the handle addresses full grids with 32-bit indices, so the bound is on their values
+// and not on the unknowns.
+static int helmholtz_sizes(int d, const int *dims, const int *basis, double sigma, int nfields, bool full, long *N_out, long *G_out) {
   if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
   int rc = check_sigma(sigma); if (rc) return rc;
   if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   long N = 1, G = 1;
   for (int k = 0; k < d; k++) {
-    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
-    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
-    G *= dims[k] - 2;
-    if (G * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 unknowns");
-    N *= dims[k];                              // (<= 3^d G: no overflow)
+    const bool fourier = basis && basis[k] == BASIS_FOURIER;
+    if (fourier) {
+      if (dims[k] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: a periodic direction needs at least 2 points", k, dims[k]);
+      if (dims[k] > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
+    } else {
+      if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
+      if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
+    }
+    G *= fourier ? dims[k] : dims[k] - 2;
+    N *= dims[k];                              // (<= 3^d G: no overflow under either bound)
+    if (full && N * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 full-grid values");
+    if (!full && G * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 unknowns");
   }
+  *N_out = N; *G_out = G;
+  return 0;
+}
+
+extern "C" int cheb_helmholtz_create(int d, const int *dims, double sigma, int nfields, cheb_helmholtz **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  long N, G;
+  int rc = helmholtz_sizes(d, dims, nullptr, sigma, nfields, false, &N, &G); if (rc) return rc;
   FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
   cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
@@ -1411,7 +1275,8 @@ static int helmholtz_create(int d, const int *dims, const int *basis, const doub
                             cheb_helmholtz **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  long N, G;
+  int rc = helmholtz_sizes(d, dims, basis, sigma, nfields, true, &N, &G); if (rc) return rc;
   bool any_per = false, all_per = basis != nullptr;
   for (int k = 0; basis && k < d; k++) {
     if (basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
@@ -1419,8 +1284,6 @@ static int helmholtz_create(int d, const int *dims, const int *basis, const doub
   }
   auto fourier = [&](int k) { return basis && basis[k] == BASIS_FOURIER; };
   if (!bc && !all_per) return chebhip_fail(CHEBHIP_ERR_ARG, "bc is NULL");
-  int rc = check_sigma(sigma); if (rc) return rc;
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   for (int k = 0; scale && k < d; k++)
     if (!std::isfinite(scale[k]) || !(scale[k] > 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] = %g must be finite and > 0", k, scale[k]);
   for (int k = 0; k < d; k++)
@@ -1429,19 +1292,6 @@ static int helmholtz_create(int d, const int *dims, const int *basis, const doub
       if (!std::isfinite(a) || !std::isfinite(b) || a < 0.0 || b < 0.0 || (a == 0.0 && b == 0.0))
         return chebhip_fail(CHEBHIP_ERR_ARG, "bc[%d] %s end: (alpha, beta) = (%g, %g) must be finite, >= 0 and not both 0", k, e ? "last" : "first", a, b);
     }
-  long N = 1, G = 1;
-  for (int k = 0; k < d; k++) {
-    if (fourier(k)) {
-      if (dims[k] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: a periodic direction needs at least 2 points", k, dims[k]);
-      if (dims[k] > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
-    } else {
-      if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: the solve needs interior nodes", k, dims[k]);
-      if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: fast diagonalisation supports at most 258 points per line", k, dims[k]);
-    }
-    G *= fourier(k) ? dims[k] : dims[k] - 2;
-    N *= dims[k];
-    if (N * nfields > 0x7fffffffL) return chebhip_fail(CHEBHIP_ERR_DIMS, "more than 2^31 - 1 full-grid values");
-  }
   FdView v; v.d = d; v.dims = dims; v.N = N; v.G = G;
   cheb_helmholtz *h = new (std::nothrow) cheb_helmholtz;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
@@ -1453,17 +1303,13 @@ static int helmholtz_create(int d, const int *dims, const int *basis, const doub
   }
   rc = fdpc_create(v, nfields, false, &h->pc, 0, LINE_SPECTRAL, sigma, true, bc, scale, any_per ? basis : nullptr);
   if (rc) { delete h; return rc; }
-  h->n = G * nfields; h->nf = nfields; h->bc = true; h->per = any_per;
-  h->geo.d = d; h->geo.N = (int)N; h->geo.G = (int)G; h->geo.NB = (int)(N - G);
-  h->pgeo.d = d; h->pgeo.N = (int)N; h->pgeo.G = (int)G; h->pgeo.NB = (int)(N - G);
-  {
-    int s = 1, si = 1;
-    for (int k = d - 1; k >= 0; k--) {
-      const int Mk = fourier(k) ? dims[k] : dims[k] - 2;
-      h->geo.P[k] = h->pgeo.P[k] = dims[k]; h->geo.ls[k] = h->pgeo.ls[k] = s; h->geo.gs[k] = h->pgeo.gs[k] = si;
-      h->pgeo.M[k] = Mk; h->pgeo.off[k] = fourier(k) ? 0 : 1;
-      s *= dims[k]; si *= Mk;
-    }
+  h->n = G * nfields; h->bc = true;
+  BcGeo &geo = h->geo;
+  geo.d = d; geo.N = (int)N; geo.G = (int)G; geo.NB = (int)(N - G);
+  for (int k = d - 1, s = 1, si = 1; k >= 0; k--) {
+    geo.P[k] = dims[k]; geo.off[k] = fourier(k) ? 0 : 1; geo.M[k] = dims[k] - 2 * geo.off[k];
+    geo.ls[k] = s; geo.gs[k] = si;
+    s *= geo.P[k]; si *= geo.M[k];
   }
   // singular: some modal sum is exactly 0 -- sigma = 0 and every direction has a zero eigenvalue (Neumann / Neumann: the constant;
   // periodic: the constant and, for an even extent, the Nyquist vector).  Every product of such modes is dropped.
@@ -1515,35 +1361,11 @@ static bool overlaps(const double *a, long na, const double *b, long nb) {
   return pa < pb + (uintptr_t)nb * sizeof(double) && pb < pa + (uintptr_t)na * sizeof(double);
 }
 
-// u (nf full grids) from the interior fields z and the boundary data g (null: zero data, u_B = Q u_I): end values direction by
-// direction, the lines of direction k read the edges direction k - 1 has written
+// u (nf full grids) from the unknown fields z and the boundary data g (null: zero data, u_B = Q u_I): end values of the wall
+// directions in ascending order, the lines of one reading the edges the one before has written; the first of them embeds the
+// unknowns.  No wall at all: the unknown layout IS the full grid.
 static int bc_extend(const cheb_helmholtz *h, int nf, const double *z, const double *g_dev, double *u_dev, hipStream_t st) {
   const BcGeo &geo = h->geo;
-  const int d = geo.d;
-  BcMats bm;
-  for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
-  long before = 1;                             // prod_{m < k} P_m
-  for (int k = 0; k < d; k++) {
-    const double *src = k == 0 ? z : nullptr;
-    if (k < d - 1) {
-      long nl = before;
-      for (int m = k + 1; m < d; m++) nl *= geo.P[m] - 2;
-      BC_LAUNCH(k_bc_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), geo, k, bm.m[k], h->dir[k][0], h->dir[k][1], (int)nl, src,
-                g_dev, u_dev);
-    } else {
-      BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), geo, bm.m[k], h->dir[k][0], h->dir[k][1], (int)before,
-                src, g_dev, u_dev);
-    }
-    HIP_TRY(hipGetLastError());
-    before *= geo.P[k];
-  }
-  return 0;
-}
-
-// bc_extend on a handle with a periodic direction: the wall directions in ascending order, the first of them embedding the unknowns;
-// no wall at all: the unknown layout IS the full grid
-static int pb_extend(const cheb_helmholtz *h, int nf, const double *z, const double *g_dev, double *u_dev, hipStream_t st) {
-  const PbGeo &geo = h->pgeo;
   const int d = geo.d;
   bool first = true;
   long before = 1;                             // prod_{m < k} P_m
@@ -1554,9 +1376,9 @@ static int pb_extend(const cheb_helmholtz *h, int nf, const double *z, const dou
       if (k < d - 1) {
         long nl = before;
         for (int m = k + 1; m < d; m++) nl *= geo.M[m];
-        BC_LAUNCH(k_pb_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), geo, k, bm, h->dir[k][0], h->dir[k][1], (int)nl, src, g_dev, u_dev);
+        BC_LAUNCH(k_bc_extend_col, dim3((unsigned)((nl + 63) / 64), (unsigned)nf), geo, k, bm, h->dir[k][0], h->dir[k][1], (int)nl, src, g_dev, u_dev);
       } else {
-        BC_LAUNCH(k_pb_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), geo, bm, h->dir[k][0], h->dir[k][1], (int)before, src, g_dev, u_dev);
+        BC_LAUNCH(k_bc_extend_row, dim3((unsigned)((before + 3) / 4), (unsigned)nf), geo, bm, h->dir[k][0], h->dir[k][1], (int)before, src, g_dev, u_dev);
       }
       HIP_TRY(hipGetLastError());
     }
@@ -1570,31 +1392,25 @@ extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, c
   if (!h || !h->pc) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (!h->bc) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_helmholtz_solve_bc: a handle from cheb_helmholtz_create_bc");
   if (!f_dev || !u_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL vector");
-  const int d = h->geo.d, nf = h->nf;
-  const long G = h->geo.G, N = h->geo.N, NB = h->geo.NB;
+  const BcGeo &geo = h->geo;
+  const int nf = h->pc->nf;
+  const long G = geo.G, N = geo.N, NB = geo.NB;
   if (overlaps(u_dev, nf * N, f_dev, nf * G) || (g_dev && overlaps(u_dev, nf * N, g_dev, nf * NB)))
     return chebhip_fail(CHEBHIP_ERR_ARG, "u may not alias f or g");
   if (g_dev && NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "g given, but every direction is periodic: there is no boundary data to lift");
   hipStream_t st = (hipStream_t)stream;
-  BcMats bm;
-  for (int k = 0; k < MAXD; k++) bm.m[k] = k < d ? h->pc->ln[k]->bcm : nullptr;
   const double *rhs = f_dev;
-  if (g_dev && h->per) {
-    const PbGeo &geo = h->pgeo;
-    const int nl = geo.G / geo.M[d - 1];
-    BC_LAUNCH(k_pb_lift, dim3((unsigned)((nl + 3) / 4), (unsigned)nf), geo, bm, nl, f_dev, g_dev, h->t);
-    HIP_TRY(hipGetLastError());
-    rhs = h->t;
-  } else if (g_dev) {                          // (g = NULL: zero data, nothing to lift)
-    const BcGeo &geo = h->geo;
+  if (g_dev) {                                 // (g = NULL: zero data, nothing to lift)
+    BcMats bm;
+    for (int k = 0; k < MAXD; k++) bm.m[k] = k < geo.d ? h->pc->ln[k]->bcm : nullptr;
     BC_LAUNCH(k_bc_lift, dim3((unsigned)((G + 255) / 256), (unsigned)nf), geo, bm, f_dev, g_dev, h->t);
     HIP_TRY(hipGetLastError());
     rhs = h->t;
   }
   int rc = fdm_solve(h->pc, rhs, h->z, st); if (rc) return rc;
-  if (h->per) return pb_extend(h, nf, h->z, g_dev, u_dev, st);
   return bc_extend(h, nf, h->z, g_dev, u_dev, st);
 }
+
 
 extern "C" long cheb_helmholtz_full_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * h->pc->N : -1; }
 extern "C" long cheb_helmholtz_boundary_size(const cheb_helmholtz *h) { return h ? (long)h->pc->nf * (h->pc->N - h->pc->G) : -1; }

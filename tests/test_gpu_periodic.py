@@ -449,6 +449,8 @@ def lifted(c, f, Gf):
 
 
 FULL = [(dims, m, q) for dims, m, q in HGRID if not all(m)]
+# ... and the handles without a periodic direction, which run the same lift and extension kernels
+FULL += [(dims, (0,) * len(dims), len(GRID) + q) for q, dims in enumerate(SHAPES_12 + SHAPES_3 + [(4, 5, 4, 6)])]
 
 
 @pytest.mark.parametrize("dims,mask,q", FULL, ids=ids)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Periodic directions beside walls, device events, warm-up first, both handles in the same process:
   1. a (periodic, wall, periodic) Helmholtz solve -- solve (unknown arrays) and solve_full with boundary data (lift + solve +
-     extension through the k_pb_* kernels) -- against the all-wall Dirichlet handle of the same dims;
+     extension: the k_bc_* kernels every boundary-condition handle runs) -- against the all-wall Dirichlet handle of the same dims;
   2. ChebGrad.laplacian with the same two periodic directions against the all-wall handle.
 Every launch of the periodic handle should be the kernel the all-wall handle launches, on lines two points longer in the periodic
 directions; a kernel-trace run of the same script shows whether it is:
