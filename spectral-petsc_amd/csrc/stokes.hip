@@ -11,6 +11,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "stokes_node.h"
 #include "timers.h"
 #include <cmath>
 #include <cstdarg>
@@ -47,9 +48,47 @@ __global__ void k_st_local(long N, int gs, int go, const int *__restrict__ ixL, 
     if (pL) pL[l] = n >= 0 ? s[go] : 0.0;
   }
 }
-// The same for the full 3-D vector (node stride 4, pressure last, 16-byte aligned): the 32 bytes of a node come as two
-// 16-byte loads, and a thread keeps UN nodes in flight (index loads first, then the node loads, then the stores) -- the
-// one-node version is a chain of two dependent memory round trips per node and ran at 3.7 TB/s at 128^3.
+// Interior indices of the node pair (2t, 2t + 1) of a serial 3-D grid with an even last extent, by arithmetic instead of from the table
+// ixL (4 B/node of every gather and scatter: 1.2 % of the bytes of a 128^3 callback): n(i, j, k) = ((i-1) M1 + (j-1)) M2 + (k-1) for
+// interior nodes (BlockIt order, stokes.C:791-879), -1 on the boundary.  P2 == 0: read the table (slab handles, odd extents, d = 2).
+struct StGrid { unsigned P0, P1, P2; };
+__device__ __forceinline__ int2 st_pair_ix(const int *__restrict__ ixL, long t, const StGrid g) {
+  if (g.P2 == 0) return ((const int2 *)ixL)[t];
+  const unsigned l = (unsigned)(2 * t), q = l / g.P2, k = l - q * g.P2;          // k even: the pair shares its line
+  const unsigned i = q / g.P1, j = q - i * g.P1;
+  if (i == 0 || i == g.P0 - 1 || j == 0 || j == g.P1 - 1) return make_int2(-1, -1);
+  const int base = (int)(((i - 1) * (g.P1 - 2) + (j - 1)) * (g.P2 - 2)) - 1;
+  return make_int2(k == 0 ? -1 : base + (int)k, k + 2 == g.P2 ? -1 : base + (int)k + 1);
+}
+// The interior index of item i of `count`: of node i (int, from the table) or of the node pair (2i, 2i + 1) (PAIR: int2); -1 past the end
+template <bool PAIR>
+__device__ __forceinline__ auto st_ix(const int *ixL, long i, long count, const StGrid g) {
+  if constexpr (PAIR) return i < count ? st_pair_ix(ixL, i, g) : make_int2(-1, -1);
+  else return i < count ? ixL[i] : -1;
+}
+
+// The UN-deep walk of the full scatters k_st_out4 / k_st_out4p: the interior indices of UN items (nodes or node pairs, gridDim * blockDim apart),
+// then load(u, n, i) for all UN, then store(u, n) for all UN -- three separate loops because the one-item form is two dependent memory round
+// trips per item (the index, then what it addresses: 3.7 TB/s at 128^3).  A dead tail item loads as item 0 and has index -1, which masks its
+// stores like a boundary node's.  ST_WALK_GEOM: the kernel reads its own launch geometry (behind a function hipcc does not fold blockDim of a
+// uniform launch into one scalar load).  The other four write the loops out: through st_walk hipcc sinks the gathers' loads into their guarded
+// stores (k_st_local4 / 4p / _cm3p: 110 -> 104, 52 -> 40, 28 -> 26 VGPRs) and gives k_st_out_cm3p other scalar registers (58 -> 56).
+#define ST_WALK_GEOM blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x
+template <int UN, bool PAIR, class LOAD, class STORE>
+__device__ __forceinline__ void st_walk(long count, long first, long T, const int *ixL, const StGrid g, LOAD &&load, STORE &&store) {
+  for (long i0 = first; i0 < count; i0 += UN * T) {
+    decltype(st_ix<PAIR>(ixL, 0L, count, g)) n[UN];
+#pragma unroll
+    for (int u = 0; u < UN; u++) n[u] = st_ix<PAIR>(ixL, i0 + u * T, count, g);
+#pragma unroll
+    for (int u = 0; u < UN; u++) load(u, n[u], (i0 + u * T < count) ? i0 + u * T : 0);
+#pragma unroll
+    for (int u = 0; u < UN; u++) store(u, n[u]);
+  }
+}
+
+// k_st_local for the full 3-D vector (node stride 4, pressure last, 16-byte aligned): the 32 bytes of a node come as two
+// 16-byte loads, and a thread keeps UN nodes in flight (the three loops of st_walk).
 template <int UN>
 __global__ __launch_bounds__(256) void k_st_local4(long N, const int *__restrict__ ixL, const double *__restrict__ src,
                                                    const double *__restrict__ dirloc, double *__restrict__ xL, double *__restrict__ pL) {
@@ -57,7 +96,7 @@ __global__ __launch_bounds__(256) void k_st_local4(long N, const int *__restrict
   for (long l0 = blockIdx.x * (long)blockDim.x + threadIdx.x; l0 < N; l0 += UN * T) {
     int n[UN];
 #pragma unroll
-    for (int u = 0; u < UN; u++) { const long l = l0 + u * T; n[u] = l < N ? ixL[l] : -1; }
+    for (int u = 0; u < UN; u++) n[u] = st_ix<false>(ixL, l0 + u * T, N, StGrid{});
     double2 a[UN], b[UN];
 #pragma unroll
     for (int u = 0; u < UN; u++) {
@@ -77,19 +116,6 @@ __global__ __launch_bounds__(256) void k_st_local4(long N, const int *__restrict
   }
 }
 
-// Interior indices of the node pair (2t, 2t + 1) of a serial 3-D grid with an even last extent, by arithmetic instead of from the table
-// ixL (4 B/node of every gather and scatter: 1.2 % of the bytes of a 128^3 callback): n(i, j, k) = ((i-1) M1 + (j-1)) M2 + (k-1) for
-// interior nodes (BlockIt order, stokes.C:791-879), -1 on the boundary.  P2 == 0: read the table (slab handles, odd extents, d = 2).
-struct StGrid { unsigned P0, P1, P2; };
-__device__ __forceinline__ int2 st_pair_ix(const int *__restrict__ ixL, long t, const StGrid g) {
-  if (g.P2 == 0) return ((const int2 *)ixL)[t];
-  const unsigned l = (unsigned)(2 * t), q = l / g.P2, k = l - q * g.P2;          // k even: the pair shares its line
-  const unsigned i = q / g.P1, j = q - i * g.P1;
-  if (i == 0 || i == g.P0 - 1 || j == 0 || j == g.P1 - 1) return make_int2(-1, -1);
-  const int base = (int)(((i - 1) * (g.P1 - 2) + (j - 1)) * (g.P2 - 2)) - 1;
-  return make_int2(k == 0 ? -1 : base + (int)k, k + 2 == g.P2 ? -1 : base + (int)k + 1);
-}
-
 // ... and on node PAIRS (N even): the two nodes (l, l+1) of a pair are neighbours in every local field, so each field
 // leaves as one 16-byte store per pair instead of two 8-byte ones (a CU's store path moves 8-byte accesses at ~0.6x the
 // rate of 16-byte ones, sweep_vec.hip); UN pairs in flight per thread.
@@ -100,7 +126,7 @@ __global__ __launch_bounds__(256) void k_st_local4p(long N, const int *__restric
   for (long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x; t0 < half; t0 += UN * T) {
     int2 n[UN];
 #pragma unroll
-    for (int u = 0; u < UN; u++) { const long t = t0 + u * T; n[u] = t < half ? st_pair_ix(ixL, t, sg) : make_int2(-1, -1); }
+    for (int u = 0; u < UN; u++) n[u] = st_ix<true>(ixL, t0 + u * T, half, sg);
     double2 a[UN][2], b[UN][2];
 #pragma unroll
     for (int u = 0; u < UN; u++) {
@@ -240,7 +266,7 @@ __global__ void k_st_node_vv(long N, double *__restrict__ V0, double *__restrict
   double *V[3] = {V0, V1, V2};
   const double *S[3] = {S0, S1, S2};
   GS_LOOP(i, N) {
-    double g[D][D], strain[D][D], S0v[D][D], z = 0.0;
+    double g[D][D], S0v[D][D], tau[D][D], tr;
 #pragma unroll
     for (int j = 0; j < D; j++)
 #pragma unroll
@@ -251,58 +277,40 @@ __global__ void k_st_node_vv(long N, double *__restrict__ V0, double *__restrict
     for (int j = 0; j < D; j++)
 #pragma unroll
       for (int k = j; k < D; k++) { S0v[j][k] = DETA ? S[j][k * N + i] : 0.0; S0v[k][j] = S0v[j][k]; }
+    st_node_vv<D, DETA>(g, S0v, eta[i], DETA ? deta[i] : 0.0, tau, tr);
 #pragma unroll
     for (int j = 0; j < D; j++)
 #pragma unroll
-      for (int k = 0; k < D; k++) { strain[j][k] = 0.5 * (g[j][k] + g[k][j]); z += strain[j][k] * S0v[j][k]; }
-    const double e = eta[i], de = DETA ? deta[i] : 0.0;
-#pragma unroll
-    for (int j = 0; j < D; j++)
-#pragma unroll
-      for (int k = 0; k < D; k++) V[j][k * N + i] = DETA ? e * strain[j][k] + de * S0v[j][k] * z : e * strain[j][k];
-    if (div) { double t = g[0][0] + g[1][1]; if (D == 3) t += g[D - 1][D - 1]; div[i] = t; }
+      for (int k = 0; k < D; k++) V[j][k * N + i] = tau[j][k];
+    if (div) div[i] = tr;
   }
 }
 
-// Node loop of StokesFunction, stokes.C:710-725, with the rheology inlined (stokes.C:1920-1944).
+// Node loop of StokesFunction, stokes.C:710-725, with the rheology (stokes.C:1920-1944) on the way.
 template <int D>
 __global__ void k_st_node_fn(long N, double *__restrict__ S0, double *__restrict__ S1, double *__restrict__ S2,
                              double *__restrict__ V0, double *__restrict__ V1, double *__restrict__ V2,
-                             double *__restrict__ eta, double *__restrict__ deta, double *__restrict__ div,
-                             int kind, double hardness, double expo, double eps, double gamma0) {
+                             double *__restrict__ eta, double *__restrict__ deta, double *__restrict__ div, const StRheology rh) {
   double *V[3] = {V0, V1, V2};
   double *S[3] = {S0, S1, S2};
   GS_LOOP(i, N) {
-    double g[D][D], s[D][D], gamma = 0.0;
+    double g[D][D], s[D][D], tau[D][D], e, de, tr;
 #pragma unroll
     for (int j = 0; j < D; j++)
 #pragma unroll
       for (int k = 0; k < D; k++) g[j][k] = S[j][k * N + i];
-#pragma unroll
-    for (int j = 0; j < D; j++)
-#pragma unroll
-      for (int k = 0; k < D; k++) { s[j][k] = 0.5 * (g[j][k] + g[k][j]); gamma += 0.5 * (s[j][k] * s[j][k]); }
-    double e = 1.0, de = 0.0;
-    if (kind == 1) {
-      const double p = (1.0 - expo) / (2.0 * expo);
-      // one pow: q^(p-1) = q^p / q (the second pow was half of this kernel's time at 128^3; the quotient differs from
-      // it by an ulp, far inside the 1e-10 bar)
-      const double q = eps + gamma / gamma0, qp = pow(q, p);
-      e = hardness * qp;
-      de = (fabs(expo) > 1.0e-5) ? hardness * p / gamma0 * (qp / q) : 0.0;
-    }
+    st_node_fn<D>(g, rh, s, tau, e, de, tr);
     eta[i] = e; deta[i] = de;
 #pragma unroll
     for (int j = 0; j < D; j++)
 #pragma unroll
-      for (int k = 0; k < D; k++) { V[j][k * N + i] = e * s[j][k]; S[j][k * N + i] = s[j][k]; }
-    if (div) { double t = g[0][0] + g[1][1]; if (D == 3) t += g[D - 1][D - 1]; div[i] = t; }    // stokes.C:746
+      for (int k = 0; k < D; k++) { V[j][k * N + i] = tau[j][k]; S[j][k * N + i] = s[j][k]; }
+    if (div) div[i] = tr;                                                                       // stokes.C:746
   }
 }
 
 // The two node loops for d = 3 on node PAIRS (N even; every array is an allocation of the handle, 16-byte aligned): each
-// field is read and written 16 bytes at a time.  Same arithmetic per node as k_st_node_vv / k_st_node_fn.
-__device__ __forceinline__ double &comp(double2 &v, int q) { return q ? v.y : v.x; }
+// field is read and written 16 bytes at a time; lane q of a pair goes through the same node law (st_comp(): stokes_node.h).
 // SYM: the stress goes to the 6 slots of T (stokes_op::T) instead of overwriting the 9 gradient fields.
 template <bool DETA, bool SYM>
 __global__ __launch_bounds__(256) void k_st_node_vv_pair(long N, double *__restrict__ V0, double *__restrict__ V1, double *__restrict__ V2,
@@ -324,21 +332,7 @@ __global__ __launch_bounds__(256) void k_st_node_vv_pair(long N, double *__restr
       for (int k = j; k < 3; k++) { s0[j][k] = DETA ? ((const double2 *)(S[j] + k * N))[t] : make_double2(0.0, 0.0); s0[k][j] = s0[j][k]; }
     double2 e = ((const double2 *)eta)[t], de = DETA ? ((const double2 *)deta)[t] : make_double2(0.0, 0.0);
     double2 out[3][3], dv;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      double strain[3][3], z = 0.0;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { strain[j][k] = 0.5 * (comp(g[j][k], q) + comp(g[k][j], q)); z += strain[j][k] * comp(s0[j][k], q); }
-      const double eq = comp(e, q), deq = comp(de, q);
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) comp(out[j][k], q) = DETA ? eq * strain[j][k] + deq * comp(s0[j][k], q) * z : eq * strain[j][k];
-      double tr = comp(g[0][0], q) + comp(g[1][1], q); tr += comp(g[2][2], q);
-      comp(dv, q) = tr;
-    }
+    st_node_vv2<DETA>(g, s0, e, de, out, dv);
 #pragma unroll
     for (int j = 0; j < 3; j++)
 #pragma unroll
@@ -354,7 +348,7 @@ template <bool SYM>
 __global__ __launch_bounds__(256) void k_st_node_fn_pair(long N, double *__restrict__ S0, double *__restrict__ S1, double *__restrict__ S2,
                                                          double *__restrict__ V0, double *__restrict__ V1, double *__restrict__ V2,
                                                          double *__restrict__ eta, double *__restrict__ deta, double *__restrict__ div,
-                                                         int kind, double hardness, double expo, double eps, double gamma0, double *__restrict__ T) {
+                                                         const StRheology rh, double *__restrict__ T) {
   double *V[3] = {V0, V1, V2};
   double *S[3] = {S0, S1, S2};
   const long half = N >> 1;
@@ -364,28 +358,7 @@ __global__ __launch_bounds__(256) void k_st_node_fn_pair(long N, double *__restr
     for (int j = 0; j < 3; j++)
 #pragma unroll
       for (int k = 0; k < 3; k++) g[j][k] = ((const double2 *)(S[j] + k * N))[t];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      double s[3][3], gamma = 0.0;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { s[j][k] = 0.5 * (comp(g[j][k], q) + comp(g[k][j], q)); gamma += 0.5 * (s[j][k] * s[j][k]); }
-      double e = 1.0, de = 0.0;
-      if (kind == 1) {
-        const double p = (1.0 - expo) / (2.0 * expo);
-        const double qq = eps + gamma / gamma0, qp = pow(qq, p);
-        e = hardness * qp;
-        de = (fabs(expo) > 1.0e-5) ? hardness * p / gamma0 * (qp / qq) : 0.0;
-      }
-      comp(e2, q) = e; comp(de2, q) = de;
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { comp(tv[j][k], q) = e * s[j][k]; comp(sv[j][k], q) = s[j][k]; }
-      double tr = comp(g[0][0], q) + comp(g[1][1], q); tr += comp(g[2][2], q);
-      comp(dv, q) = tr;
-    }
+    st_node_fn2(g, rh, sv, tv, e2, de2, dv);
     ((double2 *)eta)[t] = e2; ((double2 *)deta)[t] = de2;
 #pragma unroll
     for (int j = 0; j < 3; j++)
@@ -434,23 +407,26 @@ __global__ void k_st_out(long N, int gs, const int *__restrict__ ixL, const doub
   }
 }
 
+// A node's four values, minus the force, as two 16-byte stores (k_st_out4, both halves of k_st_out4p)
+__device__ __forceinline__ void st_store_node4(double *__restrict__ out, const double *__restrict__ force, int n, double w0, double w1, double w2, double w3) {
+  double2 *o2 = (double2 *)(out + 4L * n);
+  if (force) {
+    const double2 f0 = ((const double2 *)(force + 4L * n))[0], f1 = ((const double2 *)(force + 4L * n))[1];
+    w0 += -1.0 * f0.x; w1 += -1.0 * f0.y; w2 += -1.0 * f1.x; w3 += -1.0 * f1.y;
+  }
+  o2[0] = make_double2(w0, w1); o2[1] = make_double2(w2, w3);
+}
 // The final scatter of StokesMatMult / StokesFunction in 3-D (all terms present, 16-byte aligned output): UN nodes in
-// flight per thread, the node's four values leave as two 16-byte stores.  Same sums in the same order as k_st_out.
+// flight per thread (st_walk), the node's four values leave as two 16-byte stores.  Same sums in the same order as k_st_out.
 template <int UN>
 __global__ __launch_bounds__(256) void k_st_out4(long N, const int *__restrict__ ixL, const double *__restrict__ yL,
                                                  const double *__restrict__ yL1, const double *__restrict__ yL2,
                                                  const double *__restrict__ gp0, const double *__restrict__ gp1, const double *__restrict__ gp2,
                                                  const double *__restrict__ p2, const double *__restrict__ force, double *__restrict__ out,
                                                  const double *__restrict__ G) {                // G (may be null): as in k_st_out
-  const long T = (long)gridDim.x * blockDim.x;
-  for (long l0 = blockIdx.x * (long)blockDim.x + threadIdx.x; l0 < N; l0 += UN * T) {
-    int n[UN];
-#pragma unroll
-    for (int u = 0; u < UN; u++) { const long l = l0 + u * T; n[u] = l < N ? ixL[l] : -1; }
-    double v[UN][4];
-#pragma unroll
-    for (int u = 0; u < UN; u++) {
-      const long l = (l0 + u * T < N) ? l0 + u * T : 0;
+  double v[UN][4];
+  st_walk<UN, false>(N, ST_WALK_GEOM, ixL, StGrid{},
+    [&](int u, int, long l) {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         double t = yL[k * N + l];
@@ -461,18 +437,8 @@ __global__ __launch_bounds__(256) void k_st_out4(long N, const int *__restrict__
       }
       v[u][0] += 1.0 * gp0[l]; v[u][1] += 1.0 * gp1[l]; v[u][2] += 1.0 * gp2[l];
       v[u][3] = p2[l];
-    }
-#pragma unroll
-    for (int u = 0; u < UN; u++) {
-      if (n[u] < 0) continue;
-      double2 *o2 = (double2 *)(out + 4L * n[u]);
-      if (force) {
-        const double2 f0 = ((const double2 *)(force + 4L * n[u]))[0], f1 = ((const double2 *)(force + 4L * n[u]))[1];
-        v[u][0] += -1.0 * f0.x; v[u][1] += -1.0 * f0.y; v[u][2] += -1.0 * f1.x; v[u][3] += -1.0 * f1.y;
-      }
-      o2[0] = make_double2(v[u][0], v[u][1]); o2[1] = make_double2(v[u][2], v[u][3]);
-    }
-  }
+    },
+    [&](int u, int n) { if (n >= 0) st_store_node4(out, force, n, v[u][0], v[u][1], v[u][2], v[u][3]); });
 }
 
 // ... and on node PAIRS (N even): every term array is read 16 bytes at a time.  Same sums in the same order.
@@ -483,16 +449,10 @@ __global__ __launch_bounds__(256) void k_st_out4p(long N, const int *__restrict_
                                                   const double *__restrict__ p2, const double *__restrict__ force, double *__restrict__ out,
                                                   const double *__restrict__ G, const double *__restrict__ p2b, const double *__restrict__ p2c, const StGrid sg) {
   // p2b, p2c (may be null): the pressure rows are (p2 + p2b) + p2c -- the divergence as the sum of its three terms
-  const long T = (long)gridDim.x * blockDim.x, half = N >> 1;
   const double *gp[3] = {gp0, gp1, gp2};
-  for (long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x; t0 < half; t0 += UN * T) {
-    int2 n[UN];
-#pragma unroll
-    for (int u = 0; u < UN; u++) { const long t = t0 + u * T; n[u] = t < half ? st_pair_ix(ixL, t, sg) : make_int2(-1, -1); }
-    double2 v[UN][4];
-#pragma unroll
-    for (int u = 0; u < UN; u++) {
-      const long t = (t0 + u * T < half) ? t0 + u * T : 0;
+  double2 v[UN][4];
+  st_walk<UN, true>(N >> 1, ST_WALK_GEOM, ixL, sg,
+    [&](int u, int2, long t) {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         double2 s = ((const double2 *)(yL + k * N))[t];
@@ -505,23 +465,11 @@ __global__ __launch_bounds__(256) void k_st_out4p(long N, const int *__restrict_
       }
       v[u][3] = ((const double2 *)p2)[t];
       if (p2b) { const double2 b = ((const double2 *)p2b)[t], c = ((const double2 *)p2c)[t]; v[u][3].x = (v[u][3].x + b.x) + c.x; v[u][3].y = (v[u][3].y + b.y) + c.y; }
-    }
-#pragma unroll
-    for (int u = 0; u < UN; u++) {
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int nn = h ? n[u].y : n[u].x;
-        if (nn < 0) continue;
-        double w0 = h ? v[u][0].y : v[u][0].x, w1 = h ? v[u][1].y : v[u][1].x, w2 = h ? v[u][2].y : v[u][2].x, w3 = h ? v[u][3].y : v[u][3].x;
-        double2 *o2 = (double2 *)(out + 4L * nn);
-        if (force) {
-          const double2 f0 = ((const double2 *)(force + 4L * nn))[0], f1 = ((const double2 *)(force + 4L * nn))[1];
-          w0 += -1.0 * f0.x; w1 += -1.0 * f0.y; w2 += -1.0 * f1.x; w3 += -1.0 * f1.y;
-        }
-        o2[0] = make_double2(w0, w1); o2[1] = make_double2(w2, w3);
-      }
-    }
-  }
+    },
+    [&](int u, int2 n) {
+      if (n.x >= 0) st_store_node4(out, force, n.x, v[u][0].x, v[u][1].x, v[u][2].x, v[u][3].x);
+      if (n.y >= 0) st_store_node4(out, force, n.y, v[u][0].y, v[u][1].y, v[u][2].y, v[u][3].y);
+    });
 }
 
 // Gather / scatter of the d = 3 velocity blocks on COMPONENT-MAJOR vectors (component c of interior node n at c I + n), on node
@@ -533,7 +481,7 @@ __global__ __launch_bounds__(256) void k_st_local_cm3p(long N, long I, const int
   for (long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x; t0 < half; t0 += UN * T) {
     int2 n[UN];
 #pragma unroll
-    for (int u = 0; u < UN; u++) { const long t = t0 + u * T; n[u] = t < half ? st_pair_ix(ixL, t, sg) : make_int2(-1, -1); }
+    for (int u = 0; u < UN; u++) n[u] = st_ix<true>(ixL, t0 + u * T, half, sg);
     double2 v[UN][3];
 #pragma unroll
     for (int u = 0; u < UN; u++)
@@ -558,7 +506,7 @@ __global__ __launch_bounds__(256) void k_st_out_cm3p(long N, long I, const int *
   for (long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x; t0 < half; t0 += UN * T) {
     int2 n[UN];
 #pragma unroll
-    for (int u = 0; u < UN; u++) { const long t = t0 + u * T; n[u] = t < half ? st_pair_ix(ixL, t, sg) : make_int2(-1, -1); }
+    for (int u = 0; u < UN; u++) n[u] = st_ix<true>(ixL, t0 + u * T, half, sg);
     double2 v[UN][3];
 #pragma unroll
     for (int u = 0; u < UN; u++) {
@@ -610,7 +558,7 @@ struct ZfParams {
   // StokesFunction (MODE 2): Vx / Vy are strain[0] / strain[1] (gradient in, symmetrised upper triangle out), Sz = strain[2];
   // eta_w / deta_w and the six-slot stress T are written; the rheology of stokes.C:1920-1944
   double *Sz, *eta_w, *deta_w, *T;
-  int kind; double hardness, expo, eps, gamma0;
+  StRheology rh;
   // pL (may be null): the pressure with its face values extrapolated (k_st_pfaces) -- the stress leaves as tau - p I, so that the
   // three divergence sweeps deliver -div tau + grad p and neither the pressure-gradient sweeps nor their term in the scatter exist
   const double *pL;
@@ -742,41 +690,20 @@ __global__ __launch_bounds__(256, 2) void k_st_zfused16(const ZfParams p) {
 #pragma unroll
         for (int k = 0; k < 3; k++) { tz[k][0] = make_double2(0.0, 0.0); tz[k][1] = tz[k][0]; }
         if (live[u] && MODE == 2) {
-          double2 g[3][3][2];
+          double2 g[2][3][3];
           const long off[2] = {a[u], m[u]};
 #pragma unroll
           for (int h = 0; h < 2; h++)
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-              g[0][k][h] = *(const double2 *)(p.Vx + k * N + off[h]);
-              g[1][k][h] = *(const double2 *)(p.Vy + k * N + off[h]);
-              g[2][k][h] = gz[u][k][h];
+              g[h][0][k] = *(const double2 *)(p.Vx + k * N + off[h]);
+              g[h][1][k] = *(const double2 *)(p.Vy + k * N + off[h]);
+              g[h][2][k] = gz[u][k][h];
             }
 #pragma unroll
           for (int h = 0; h < 2; h++) {
             double2 sv[3][3], tv[3][3], e2, de2, dv;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-              double sn[3][3], gamma = 0.0;
-#pragma unroll
-              for (int j = 0; j < 3; j++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) { sn[j][k] = 0.5 * (comp(g[j][k][h], q) + comp(g[k][j][h], q)); gamma += 0.5 * (sn[j][k] * sn[j][k]); }
-              double e = 1.0, de = 0.0;
-              if (p.kind == 1) {
-                const double pw = (1.0 - p.expo) / (2.0 * p.expo);
-                const double qq = p.eps + gamma / p.gamma0, qp = pow(qq, pw);
-                e = p.hardness * qp;
-                de = (fabs(p.expo) > 1.0e-5) ? p.hardness * pw / p.gamma0 * (qp / qq) : 0.0;
-              }
-              comp(e2, q) = e; comp(de2, q) = de;
-#pragma unroll
-              for (int j = 0; j < 3; j++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) { comp(tv[j][k], q) = e * sn[j][k]; comp(sv[j][k], q) = sn[j][k]; }
-              double tr = comp(g[0][0][h], q) + comp(g[1][1][h], q); tr += comp(g[2][2][h], q);
-              comp(dv, q) = tr;
-            }
+            st_node_fn2(g[h], p.rh, sv, tv, e2, de2, dv);
             *(double2 *)(p.eta_w + off[h]) = e2; *(double2 *)(p.deta_w + off[h]) = de2;
             // state: the symmetrised strain in its upper triangle; stress: slot j + k + j k of T for j <= k, but (2,2): tau_zz is used
             // on chip only
@@ -799,42 +726,28 @@ __global__ __launch_bounds__(256, 2) void k_st_zfused16(const ZfParams p) {
           }
         }
         if (live[u] && MODE != 2) {
-          double2 g[3][3][2], s0[3][3][2], e[2], de[2];
+          double2 g[2][3][3], s0[2][3][3], e[2], de[2];
           const long off[2] = {a[u], m[u]};
           const double *S[3] = {p.S0, p.S1, p.S2};
 #pragma unroll
           for (int h = 0; h < 2; h++) {
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-              g[0][k][h] = *(const double2 *)(p.Vx + k * N + off[h]);
-              g[1][k][h] = *(const double2 *)(p.Vy + k * N + off[h]);
-              g[2][k][h] = gz[u][k][h];
+              g[h][0][k] = *(const double2 *)(p.Vx + k * N + off[h]);
+              g[h][1][k] = *(const double2 *)(p.Vy + k * N + off[h]);
+              g[h][2][k] = gz[u][k][h];
             }
 #pragma unroll
             for (int j = 0; j < 3; j++)
 #pragma unroll
-              for (int k = j; k < 3; k++) { s0[j][k][h] = DETA ? *(const double2 *)(S[j] + k * N + off[h]) : make_double2(0.0, 0.0); s0[k][j][h] = s0[j][k][h]; }
+              for (int k = j; k < 3; k++) { s0[h][j][k] = DETA ? *(const double2 *)(S[j] + k * N + off[h]) : make_double2(0.0, 0.0); s0[h][k][j] = s0[h][j][k]; }
             e[h] = *(const double2 *)(p.eta + off[h]);
             de[h] = DETA ? *(const double2 *)(p.deta + off[h]) : make_double2(0.0, 0.0);
           }
 #pragma unroll
           for (int h = 0; h < 2; h++) {
             double2 out[3][3], dv;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-              double strain[3][3], z = 0.0;
-#pragma unroll
-              for (int j = 0; j < 3; j++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) { strain[j][k] = 0.5 * (comp(g[j][k][h], q) + comp(g[k][j][h], q)); z += strain[j][k] * comp(s0[j][k][h], q); }
-              const double eq = comp(e[h], q), deq = comp(de[h], q);
-#pragma unroll
-              for (int j = 0; j < 3; j++)
-#pragma unroll
-                for (int k = 0; k < 3; k++) comp(out[j][k], q) = DETA ? eq * strain[j][k] + deq * comp(s0[j][k][h], q) * z : eq * strain[j][k];
-              double tr = comp(g[0][0][h], q) + comp(g[1][1][h], q); tr += comp(g[2][2][h], q);
-              comp(dv, q) = tr;
-            }
+            st_node_vv2<DETA>(g[h], s0[h], e[h], de[h], out, dv);
             if (FOLD) {                                                // tau - p I
               const double2 pp = *(const double2 *)(sP + sl[u] * ZF_PG + (h ? nn - sj[u] - 1 : sj[u]));
 #pragma unroll
@@ -938,7 +851,7 @@ struct stokes_op : BoxGrid {                                  // d, dims, N, gP0
   stokes_dim0_fn dim0 = nullptr;
   void *dim0_ctx = nullptr;
   bool deta_nonzero = false;                                 // deta == 0 everywhere: the node loop skips S0
-  int rh_kind = 0; double rh_hard = 1.0, rh_expo = 1.0, rh_eps = 1.0, rh_g0 = 1.0;   // stokes.C:403
+  StRheology rh = {0, 1.0, 1.0, 1.0, 1.0};                   // stokes.C:403
 };
 
 // Work arrays of one handle.  (Round 4 tried starting every array at a different multiple of 4352 bytes of its allocation, against
@@ -1135,7 +1048,7 @@ extern "C" long stokes_op_size(const stokes_op *op, int which) {
 extern "C" int stokes_op_set_rheology(stokes_op *op, int kind, double hardness, double exponent, double eps, double gamma0) {
   if (!op) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (kind != 0 && kind != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "rheology %d not implemented (stokes.C:470-480)", kind);
-  op->rh_kind = kind; op->rh_hard = hardness; op->rh_expo = exponent; op->rh_eps = eps; op->rh_g0 = gamma0;
+  op->rh = StRheology{kind, hardness, exponent, eps, gamma0};
   return 0;
 }
 
@@ -1226,21 +1139,43 @@ static void st_out_full(stokes_op *op, const double *force, double *out, hipStre
     return;
   }
   if (!y0) { y0 = op->yL; y1 = op->yLx[1]; y2 = op->yLx[2]; }
-  if (d == 3 && y1 && y2 && st_al16(out) && (!force || st_al16(force))) {
-    if ((op->N & 1) == 0 && st_al16(y0) && st_al16(y1) && st_al16(y2) && (!G || st_al16(G))) {     // (the handle's own arrays: always)
-      // (one pair per thread: twice the waves in flight of the two-pair form for the same loads per CU -- 128^3 StokesMatMult 282.4 ->
-      // 279.2 us, StokesFunction 296.1 -> 292.7 us in one process; four pairs per thread: 286.6 / 294.8)
-      hipLaunchKernelGGL((k_st_out4p<1>), dim3(ugrid(op->N >> 1, 1)), dim3(256), 0, st, op->N, (const int *)op->ixL, y0, y1, y2,
-                         (const double *)(no_gp ? nullptr : op->gp[0]), (const double *)op->gp[1], (const double *)op->gp[2], (const double *)op->p2, force, out, G,
-                         (const double *)nullptr, (const double *)nullptr, st_grid(op));
-    }
-    else
-      hipLaunchKernelGGL((k_st_out4<4>), dim3(ugrid(op->N, 4)), dim3(256), 0, st, op->N, (const int *)op->ixL, y0, y1, y2,
-                         (const double *)op->gp[0], (const double *)op->gp[1], (const double *)op->gp[2], (const double *)op->p2, force, out, G);
+  if (st_out_pairs(op, y0, y1, y2, G, force, out)) {        // (even N: the handle's own arrays are always 16-byte aligned)
+    // (one pair per thread: twice the waves in flight of the two-pair form for the same loads per CU -- 128^3 StokesMatMult 282.4 ->
+    // 279.2 us, StokesFunction 296.1 -> 292.7 us in one process; four pairs per thread: 286.6 / 294.8)
+    hipLaunchKernelGGL((k_st_out4p<1>), dim3(ugrid(op->N >> 1, 1)), dim3(256), 0, st, op->N, (const int *)op->ixL, y0, y1, y2,
+                       (const double *)(no_gp ? nullptr : op->gp[0]), (const double *)op->gp[1], (const double *)op->gp[2], (const double *)op->p2, force, out, G,
+                       (const double *)nullptr, (const double *)nullptr, st_grid(op));
+    return;
+  }
+  if (d == 3 && y1 && y2 && st_al16(out) && (!force || st_al16(force))) {       // odd N, or a term at an 8-byte offset
+    hipLaunchKernelGGL((k_st_out4<4>), dim3(ugrid(op->N, 4)), dim3(256), 0, st, op->N, (const int *)op->ixL, y0, y1, y2,
+                       (const double *)op->gp[0], (const double *)op->gp[1], (const double *)op->gp[2], (const double *)op->p2, force, out, G);
     return;
   }
   ST_D(k_st_out, d + 1, (const int *)op->ixL, y0, y1, y2,
        (const double *)op->gp[0], (const double *)op->gp[1], (const double *)op->gp[2], (const double *)op->p2, d, force, out, G, 1L);
+}
+
+// The node loops of the separate-pass route, one launcher per node law (stokes_node.h): pair kernels for d = 3 with N even, else scalar ones
+static void st_node_vv_launch(stokes_op *op, double *div, hipStream_t st) {
+  const bool nz = op->deta_nonzero;
+  const double *S0 = op->strain[0], *S1 = op->strain[1], *S2 = op->strain[2], *eta = op->eta, *deta = op->deta;
+  auto kp = nz ? k_st_node_vv_pair<true, false> : k_st_node_vv_pair<false, false>;
+  auto ks = op->d == 2 ? (nz ? k_st_node_vv<2, true> : k_st_node_vv<2, false>) : (nz ? k_st_node_vv<3, true> : k_st_node_vv<3, false>);
+  if (op->d == 3 && (op->N & 1) == 0)
+    hipLaunchKernelGGL(kp, dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], S0, S1, S2, eta, deta, div, op->T);
+  else hipLaunchKernelGGL(ks, dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], S0, S1, S2, eta, deta, div);
+}
+static void st_node_fn_launch(stokes_op *op, hipStream_t st) {
+  const int d = op->d;
+  auto kp = op->sym ? k_st_node_fn_pair<true> : k_st_node_fn_pair<false>;
+  if (op->sym || (d == 3 && (op->N & 1) == 0))
+    hipLaunchKernelGGL(kp, dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
+                       op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh, op->T);
+  else ST_D(k_st_node_fn, op->strain[0], op->strain[1], op->strain[2], op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh);
+}
+static void st_state_after_fn(stokes_op *op) {              // what the node loop left: the linear rheology writes eta = 1, eta' = 0 (st_rheology)
+  op->deta_nonzero = (op->rh.kind == 1); op->eta_uniform = (op->rh.kind == 0); op->eta_value = 1.0;
 }
 
 // d independent plain sweeps y[k] = alpha * D_k x[k] (DV: vec, d stacked fields; DP: scalar) as ONE launch where the
@@ -1410,7 +1345,7 @@ __global__ void k_st_symmetrise(long N, double *__restrict__ S0, double *__restr
 #pragma unroll
     for (int j = 0; j < D; j++)
 #pragma unroll
-      for (int k = j + 1; k < D; k++) { const double s = 0.5 * (S[j][k * N + i] + S[k][j * N + i]); S[j][k * N + i] = s; S[k][j * N + i] = s; }
+      for (int k = j + 1; k < D; k++) { const double s = st_sym(S[j][k * N + i], S[k][j * N + i]); S[j][k * N + i] = s; S[k][j * N + i] = s; }
   }
 }
 static int st_sync_strain(stokes_op *op, hipStream_t st) {
@@ -1443,15 +1378,9 @@ static int st_zfused_launch(stokes_op *op, int mode, ZfParams zp, hipStream_t st
   zp.fragE = m.fragE; zp.fragO = m.fragO;
   hipError_t cu_err; const int ncu = sweep_num_cus(&cu_err); HIP_TRY(cu_err);
   const unsigned grid = zp.ntiles < 2u * (unsigned)ncu ? zp.ntiles : 2u * (unsigned)ncu;      // two workgroups per CU
-  if (zp.pL) {
-    if (mode == 2) hipLaunchKernelGGL((k_st_zfused16<2, true>), dim3(grid), dim3(256), 0, st, zp);
-    else if (mode == 1) hipLaunchKernelGGL((k_st_zfused16<1, true>), dim3(grid), dim3(256), 0, st, zp);
-    else hipLaunchKernelGGL((k_st_zfused16<0, true>), dim3(grid), dim3(256), 0, st, zp);
-  } else {
-    if (mode == 2) hipLaunchKernelGGL((k_st_zfused16<2, false>), dim3(grid), dim3(256), 0, st, zp);
-    else if (mode == 1) hipLaunchKernelGGL((k_st_zfused16<1, false>), dim3(grid), dim3(256), 0, st, zp);
-    else hipLaunchKernelGGL((k_st_zfused16<0, false>), dim3(grid), dim3(256), 0, st, zp);
-  }
+  auto k = zp.pL ? (mode == 2 ? k_st_zfused16<2, true> : mode == 1 ? k_st_zfused16<1, true> : k_st_zfused16<0, true>)
+                 : (mode == 2 ? k_st_zfused16<2, false> : mode == 1 ? k_st_zfused16<1, false> : k_st_zfused16<0, false>);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, zp);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1516,18 +1445,9 @@ static int st_viscous_jacobian_zfused(stokes_op *op, double *div, hipStream_t st
   return sweeps_multi(op, true, 0, t, y, -1.0, st, false, false, 2);                                     // yL = -D_x tau_x., yLx[1] = -D_y tau_y.
 }
 static int st_viscous_jacobian(stokes_op *op, double *div, hipStream_t st, bool have_gradient = false) {
-  const int d = op->d;
   if (!have_gradient && st_zfused_ok(op)) return st_viscous_jacobian_zfused(op, div, st);
   if (!have_gradient) { int rc = st_gradient(op, op->V, st); if (rc) return rc; }                                               // :639
-#define NODE_VV(D_, DETA_) hipLaunchKernelGGL((k_st_node_vv<D_, DETA_>), dim3(grid1d(op->N, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
-    (const double *)op->strain[0], (const double *)op->strain[1], (const double *)op->strain[2], (const double *)op->eta, (const double *)op->deta, div)
-#define NODE_VV_PAIR(DETA_, SYM_) hipLaunchKernelGGL((k_st_node_vv_pair<DETA_, SYM_>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->V[0], op->V[1], op->V[2], \
-    (const double *)op->strain[0], (const double *)op->strain[1], (const double *)op->strain[2], (const double *)op->eta, (const double *)op->deta, div, op->T)
-  if (d == 2) { if (op->deta_nonzero) NODE_VV(2, true); else NODE_VV(2, false); }
-  else if ((op->N & 1) == 0) { if (op->deta_nonzero) NODE_VV_PAIR(true, false); else NODE_VV_PAIR(false, false); }
-  else        { if (op->deta_nonzero) NODE_VV(3, true); else NODE_VV(3, false); }
-#undef NODE_VV_PAIR
-#undef NODE_VV
+  st_node_vv_launch(op, div, st);
   return st_div_stress(op, st);
 }
 
@@ -1757,7 +1677,7 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
   chebhip::StageTimer tm(CHEBHIP_STAGE_STOKES_FUNCTION, stream);
   hipStream_t st = (hipStream_t)stream;
   const int d = op->d;
-  if (op->rh_kind == 0 && op->uniform_ok) {
+  if (op->rh.kind == 0 && op->uniform_ok) {
     // Linear rheology (stokes.C:1920-1926: eta = 1, eta' = 0): the residual's viscous part is -1/2 (sum_j D_j D_j v + grad div v)
     // of the velocity WITH its Dirichlet values (sweeps along different directions commute on the full grid), so the node
     // loop and the second set of d^2 sweeps are not needed (st_viscous_uniform); the symmetrised strain it would leave as
@@ -1787,11 +1707,10 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
     ZfParams zp = {};
     zp.xL = op->xL; zp.Vx = op->strain[0]; zp.Vy = op->strain[1]; zp.Sz = op->strain[2];
     zp.eta_w = op->eta; zp.deta_w = op->deta; zp.T = op->T; zp.div = op->p2;
-    zp.kind = op->rh_kind; zp.hardness = op->rh_hard; zp.expo = op->rh_expo; zp.eps = op->rh_eps; zp.gamma0 = op->rh_g0;
+    zp.rh = op->rh;
     zp.pL = fold ? op->pL : nullptr;
     if (!ST_ABL(2) && (rc = st_zfused_launch(op, 2, zp, st))) return rc;
-    op->deta_nonzero = (op->rh_kind == 1);
-    op->eta_uniform = (op->rh_kind == 0); op->eta_value = 1.0;
+    st_state_after_fn(op);
     double *y[3] = {op->yL, op->yLx[1], op->yLx[2]};
     const double *t[3] = {op->T, op->T + op->N, op->T + 2 * op->N};
     if (!ST_ABL(3) && (rc = sweeps_multi(op, true, 0, t, y, -1.0, st, true, false, 2))) return rc;                               // :737-740 (x, y)
@@ -1809,17 +1728,8 @@ extern "C" int stokes_op_function(stokes_op *op, const double *xG, double *yG, v
     { int rc = st_pressure_gradient_forked(op, st); if (rc) return rc; }                                                         // :747
     { int rc = st_gradient(op, op->strain, st); if (rc) return rc; }                                                              // :701
   }
-  if (op->sym)
-    hipLaunchKernelGGL((k_st_node_fn_pair<true>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
-                       op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh_kind, op->rh_hard, op->rh_expo, op->rh_eps, op->rh_g0, op->T);
-  else if (d == 3 && (op->N & 1) == 0)
-    hipLaunchKernelGGL((k_st_node_fn_pair<false>), dim3(grid1d(op->N >> 1, 256, 4096)), dim3(256), 0, st, op->N, op->strain[0], op->strain[1], op->strain[2],
-                       op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2, op->rh_kind, op->rh_hard, op->rh_expo, op->rh_eps, op->rh_g0, op->T);
-  else
-    ST_D(k_st_node_fn, op->strain[0], op->strain[1], op->strain[2], op->V[0], op->V[1], op->V[2], op->eta, op->deta, op->p2,
-         op->rh_kind, op->rh_hard, op->rh_expo, op->rh_eps, op->rh_g0);
-  op->deta_nonzero = (op->rh_kind == 1);
-  op->eta_uniform = (op->rh_kind == 0); op->eta_value = 1.0;                      // linear rheology: eta = 1, eta' = 0 (k_st_node_fn)
+  st_node_fn_launch(op, st);
+  st_state_after_fn(op);
   int rc = st_div_stress(op, st, op->sym); if (rc) return rc;                                                                    // :737-740
   if ((rc = st_join(op, st))) return rc;
   st_out_full(op, op->force, yG, st);                                                                                              // :750-756
