@@ -1101,6 +1101,51 @@ int  cheb_modal_create_basis(int d, const int *dims, int nfields, const int *bas
 int  cheb_helmholtz_create_basis(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nfields,
                                  cheb_helmholtz **out);
 
+/* The toolbox on periodic directions.  The interpolant of n periodic values is I u(x) = sum_j u_j r_j(x),
+ *   r_j(x) = (1/n) [1 + 2 sum_{k=1}^{K} cos pi k (x - x_j)]                             n odd,  K = floor(n/2)
+ *   r_j(x) = (1/n) [1 + 2 sum_{k=1}^{K-1} cos pi k (x - x_j) + cos pi K (x - x_j)]      n even
+ * Every _basis call refuses a NULL basis ("basis is NULL") and any value other than CHEB_BASIS_*; an all-zero basis is the old
+ * create call itself: the same handle, the same bits. */
+/* cheb_dealias_create with a basis per direction.  A Fourier direction of n coarse (2 .. 256) and m >= n fine nodes -1 + 2 i / m uses
+ * R[i][j] = r_j(y_i), G = R D_F (long double product, rounded once) and P[i][j] = (1/m) [1 + 2 sum_{k=1}^{K} cos pi k (x_i - y_j)]: the
+ * fine-grid function's Fourier series cut at |k| <= K, at the coarse nodes (m == n: the identity).  For even n the wavenumber K is
+ * kept with what the coarse grid sees of it: the square of the Nyquist vector (-1)^j, 1 at every node, truncates to 1/2 at every
+ * node.  Default fine size 3 floor(n/2) + 1 (NOT ceil(3n/2): the product reaches wavenumber 2K, which must not fold onto |k| <= K);
+ * dims_fine[k] up to 1024 as before.  Schedule, buffers and launches are those of cheb_dealias_create. */
+int  cheb_dealias_create_basis(int d, const int *dims, const int *dims_fine, const int *basis, int nfields, cheb_dealias **out);
+int  cheb_dealias_fine_size_basis(int n, int basis);       /* the default fine size of one direction; -1 on a bad n or basis */
+/* cheb_dealias_matrix_host for one direction of the given basis (CHEB_BASIS_CGL: that call itself) */
+int  cheb_dealias_matrix_basis_host(int n, int m, int which, int basis, double *A);
+/* cheb_project_create with a basis per direction: cheb_grad_create_basis and cheb_helmholtz_create_basis underneath.  A periodic
+ * direction has 2 <= dims[k] <= 256 and no faces (its two face codes are not read).  The unknowns are the nodes interior in every
+ * WALL direction (cheb_project_size which = 1), the boundary nodes the end nodes of some wall direction (which = 2; the highest such
+ * direction names the face), both in the solver's row-major order.  Every direction periodic: no boundary, flux must be NULL.
+ * div(out): every direction periodic -- zero to rounding at EVERY node (D_F's range holds neither the constant nor the Nyquist
+ * vector, so the right-hand side has no component along a dropped mode); an open face -- zero to rounding at the unknown nodes;
+ * walls only in the wall directions (a channel; singular) -- free along the dropped modes' right eigenvectors: constant along the
+ * wall directions and, per periodic direction, the constant or, for an EVEN extent, the Nyquist vector (-1)^j.  With odd periodic
+ * extents that is one constant, as for all-wall handles; with e even ones 2^e coefficients (small for resolved fields). */
+int  cheb_project_create_basis(int d, const int *dims, const int *basis, const int *faces, const double *scale, int nvec, cheb_project **out);
+int  cheb_project_faces_basis_host(int d, const int *dims, const int *basis, int *face);    /* cheb_project_faces_host on that geometry */
+/* cheb_opfun_create over cheb_helmholtz_create_basis: stacked fields in the solver's unknown layout.  bc may be NULL only when every
+ * direction is periodic.  A mode with s == 0 (sigma = 0, every direction periodic or Neumann / Neumann: every product of constants
+ * and Nyquist vectors) gets what cheb_opfun_term's kinds give s == 0 on any singular handle.  apply_full works on every such handle;
+ * with every direction periodic the unknown layout is the full grid and it equals apply. */
+int  cheb_opfun_create_basis(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nin, int nout,
+                             cheb_opfun **out);
+/* cheb_points_create with a basis per direction.  On a periodic direction (2 <= dims[k] <= 256) the rows are those of I u above, in
+ * the barycentric form r_j ~ (-1)^j cot(pi (x - x_j) / 2) (n even), (-1)^j / sin(pi (x - x_j) / 2) (n odd), built on the device in
+ * the nearest-node form of the CGL rows.  Unlike a CGL direction, which extrapolates outside [-1, 1], ANY finite coordinate is
+ * WRAPPED (x - 2 rint(x / 2), exact); a coordinate that is a node modulo the period gives the exact unit row, NaN or +-Inf a row
+ * of NaN.  The derivative rows are the derivative of the same function (at a node: the row of D_F).  Every call that takes rows
+ * (eval, eval_grid, eval_grad, eval_deriv, spread, spread_deriv) works unchanged; CHEB_SPREAD_DELTA divides by the weight 2 / n of
+ * a periodic direction, so that cheb_modal_integrate (same basis) of the spread field against phi is sum_p s_p phi(x_p) for every
+ * phi of the grid's trigonometric space. */
+int  cheb_points_create_basis(int d, const int *dims, int nfields, const int *basis, cheb_points **out);
+/* m rows r_j(x_i) (deriv = 0) or r_j'(x_i) (deriv = 1) of a periodic direction of n nodes into R (m x n, row-major): the cosine
+ * sums of I u with x wrapped as above, long double, rounded once; HOST arrays, no device.  NaN or +-Inf: a row of NaN. */
+int  cheb_points_fourier_matrix_host(int n, int m, const double *x, int deriv, double *R);
+
 /* ------------------------------------------------------------------------- */
 /* Instrumentation (the reference has none: SURVEY 5.1).                      */
 /* ------------------------------------------------------------------------- */

@@ -89,6 +89,9 @@ ABI_SYMBOLS = [
     "cheb_project_apply",
     "cheb_opfun_create", "cheb_opfun_destroy", "cheb_opfun_set_terms", "cheb_opfun_apply", "cheb_opfun_apply_full", "cheb_opfun_size",
     "cheb_opfun_singular", "cheb_opfun_check_terms", "cheb_opfun_weight_host", "cheb_opfun_weights_host", "cheb_opfun_eval",
+    "cheb_dealias_create_basis", "cheb_dealias_fine_size_basis", "cheb_dealias_matrix_basis_host",
+    "cheb_project_create_basis", "cheb_project_faces_basis_host", "cheb_opfun_create_basis",
+    "cheb_points_create_basis", "cheb_points_fourier_matrix_host",
 ]
 
 
@@ -381,6 +384,14 @@ def lib():
         L.cheb_opfun_weight_host.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, dp]
         L.cheb_opfun_weights_host.argtypes = [C.c_int, C.c_double, C.c_double, C.c_long, dp, dp]
         L.cheb_opfun_eval.argtypes = [C.c_int, C.c_double, C.c_double, vp, C.c_long, vp, vp]
+        L.cheb_dealias_create_basis.argtypes = [C.c_int, ip, ip, ip, C.c_int, C.POINTER(vp)]
+        L.cheb_dealias_fine_size_basis.argtypes = [C.c_int, C.c_int]
+        L.cheb_dealias_matrix_basis_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp]
+        L.cheb_project_create_basis.argtypes = [C.c_int, ip, ip, ip, dp, C.c_int, C.POINTER(vp)]
+        L.cheb_project_faces_basis_host.argtypes = [C.c_int, ip, ip, ip]
+        L.cheb_opfun_create_basis.argtypes = [C.c_int, ip, ip, dp, dp, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
+        L.cheb_points_create_basis.argtypes = [C.c_int, ip, C.c_int, ip, C.POINTER(vp)]
+        L.cheb_points_fourier_matrix_host.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp]
         _lib = L
     return _lib
 
@@ -768,25 +779,35 @@ def cgl_nodes(n):
     return x
 
 
-def interp_matrix(n, x):
+def interp_matrix(n, x, periodic=False):
     """The barycentric rows l_j(x_i) of the coordinates x on the n CGL nodes (cheb_points_matrix_host) as an (len(x), n) numpy
     array: long double on the double node table, rounded once.  A coordinate on a node gives the exact unit row, a NaN or infinite
-    one a row of NaN, |x| > 1 extrapolates.  Needs no device."""
+    one a row of NaN, |x| > 1 extrapolates.  Needs no device.
+    periodic: the rows r_j(x_i) of the trigonometric interpolant on fourier_nodes(n) (cheb_points_fourier_matrix_host), by its cosine
+    sums in long double, rounded once; x is wrapped into the period, never extrapolated."""
     import numpy as np
     xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
     R = np.empty((xs.size, max(int(n), 0)))
-    _chk(lib().cheb_points_matrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
+    if periodic:
+        _chk(lib().cheb_points_fourier_matrix_host(int(n), int(xs.size), _np_dp(xs), 0, _np_dp(R)))
+    else:
+        _chk(lib().cheb_points_matrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
     return R
 
 
-def deriv_matrix(n, x):
+def deriv_matrix(n, x, periodic=False):
     """The rows l'_j(x_i) of the derivative of the barycentric interpolant on the n CGL nodes (cheb_points_dmatrix_host) as an
     (len(x), n) numpy array: long double on the double node table, rounded once.  A coordinate on a node gives that node's row of
-    the differentiation matrix, a NaN or infinite one a row of NaN, |x| > 1 extrapolates.  Needs no device."""
+    the differentiation matrix, a NaN or infinite one a row of NaN, |x| > 1 extrapolates.  Needs no device.
+    periodic: the rows r_j'(x_i) of the trigonometric interpolant's derivative (cheb_points_fourier_matrix_host, deriv = 1); at a
+    node, that node's row of fourier_diff_matrix(n)."""
     import numpy as np
     xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
     R = np.empty((xs.size, max(int(n), 0)))
-    _chk(lib().cheb_points_dmatrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
+    if periodic:
+        _chk(lib().cheb_points_fourier_matrix_host(int(n), int(xs.size), _np_dp(xs), 1, _np_dp(R)))
+    else:
+        _chk(lib().cheb_points_dmatrix_host(int(n), int(xs.size), _np_dp(xs), _np_dp(R)))
     return R
 
 
@@ -798,14 +819,26 @@ class ChebPoints(_Handle):
     point only, a point on a node returns the field's bits.  Everything but reserve_grid is asynchronous on torch's current stream.
     First derivatives with respect to the reference coordinates: deriv=(0 or 1 per direction) on eval, spread and eval_grid takes
     the flagged directions' derivative rows (drows) in place of their value rows; eval_grad gives every first derivative of every
-    field in one call."""
+    field in one call.
+
+    periodic (None: no direction): one flag per direction (cheb_points_create_basis).  A flagged direction holds a
+    periodic function on fourier_nodes(dims[k]), 2 <= dims[k] <= 256, and is evaluated by its trigonometric interpolant.  There a
+    coordinate is WRAPPED into the period, whatever its size -- it is never extrapolated, unlike a CGL direction; a coordinate that
+    is a node modulo the period returns the field's bits, NaN or +-Inf poison their point only.  Derivatives are with respect to the
+    reference coordinate (period 2).  spread(delta=True) divides by the weight 2 / n of a periodic direction's nodes, so that
+    ChebModal(dims, periodic=...).integrate(out, phi) is sum_p s_p phi(x_p) for every phi the grid holds."""
     _destroy = "cheb_points_destroy"
 
-    def __init__(self, dims, nfields=1):
+    def __init__(self, dims, nfields=1, periodic=None):
         self.dims = tuple(int(d) for d in dims)
         self.nfields = int(nfields)
+        self.periodic = _periodic_flags(periodic, len(self.dims))
         h = C.c_void_p()
-        _chk(lib().cheb_points_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        if periodic is None:
+            _chk(lib().cheb_points_create(len(self.dims), _ints(self.dims), self.nfields, C.byref(h)))
+        else:
+            _chk(lib().cheb_points_create_basis(len(self.dims), _ints(self.dims), self.nfields, _ints([int(p) for p in self.periodic]),
+                                                C.byref(h)))
         self._h = h
         self._reserved = None
 
@@ -962,25 +995,33 @@ class ChebPoints(_Handle):
 DEALIAS = {"R": 0, "P": 1, "G": 2}
 
 
-def dealias_size(n):
-    """The 3/2 rule's fine size ceil(3n/2) of a direction of n points (cheb_dealias_fine_size)."""
-    m = lib().cheb_dealias_fine_size(int(n))
+def dealias_size(n, periodic=False):
+    """The 3/2 rule's fine size of a direction of n points: ceil(3n/2) on a CGL direction (cheb_dealias_fine_size),
+    3 floor(n/2) + 1 on a periodic one (cheb_dealias_fine_size_basis): a product reaches wavenumber 2K, K = floor(n/2), which must not
+    fold onto |k| <= K."""
+    m = lib().cheb_dealias_fine_size_basis(int(n), 1) if periodic else lib().cheb_dealias_fine_size(int(n))
     if m < 0:
         raise ChebhipError(4, lib().chebhip_last_error().decode())
     return m
 
 
-def dealias_matrix(n, which, m=None):
+def dealias_matrix(n, which, m=None, periodic=False):
     """One direction's dealiasing matrix (cheb_dealias_matrix_host) for n coarse and m fine points (default dealias_size(n)):
     "R" (m, n) interpolation to the fine nodes, "P" (n, m) = B_n T_m[0:n, :] back to the coarse nodes keeping n modes, "G" (m, n)
-    = R D; needs no device."""
+    = R D; needs no device.  periodic (cheb_dealias_matrix_basis_host): the nodes are fourier_nodes(n) and fourier_nodes(m), R is
+    the trigonometric interpolant, G = R D_F, and P cuts the fine grid's Fourier series at |k| <= floor(n/2) (for even n the Nyquist
+    wavenumber stays, as the coarse grid sees it: the square of (-1)^j comes back as 1/2)."""
     import numpy as np
     if which not in DEALIAS:
         raise ValueError("matrix %r: expected one of %s" % (which, sorted(DEALIAS)))
     n = int(n)
-    m = dealias_size(n) if m is None else int(m)
+    m = dealias_size(n, periodic) if m is None else int(m)
     A = np.empty((max(n, 0), max(m, 0)) if which == "P" else (max(m, 0), max(n, 0)))
-    _chk(lib().cheb_dealias_matrix_host(n, m, DEALIAS[which], A.ctypes.data_as(C.POINTER(C.c_double)) if A.size else None))
+    ptr = A.ctypes.data_as(C.POINTER(C.c_double)) if A.size else None
+    if periodic:
+        _chk(lib().cheb_dealias_matrix_basis_host(n, m, DEALIAS[which], 1, ptr))
+    else:
+        _chk(lib().cheb_dealias_matrix_host(n, m, DEALIAS[which], ptr))
     return A
 
 
@@ -989,16 +1030,26 @@ class ChebDealias(_Handle):
     all nodes, as ChebModal): multiply(u, v) = the truncation to degree dims[k] - 1 per direction of the polynomial product u v,
     advect(vel, c) = that of sum_k vel[k] d_k c.  `fine` is the padded grid (default: the 3/2 rule, dealias_size per direction;
     fine[k] == dims[k] leaves direction k unpadded).  Asynchronous on torch's current stream; advect reserves its work memory on
-    first use (synchronous)."""
+    first use (synchronous).
+
+    periodic (None: no direction): one flag per direction (cheb_dealias_create_basis).  A flagged direction holds a
+    periodic function on fourier_nodes(dims[k]), 2 <= dims[k] <= 256; the product is cut at the wavenumbers |k| <= floor(n/2) the
+    grid holds (dealias_matrix(..., periodic=True)), the derivative of advect is D_F, and the default fine size is
+    3 floor(n/2) + 1.  advect differentiates in reference coordinates (period 2), as it does on a CGL direction: it has no scale."""
     _destroy = "cheb_dealias_destroy"
 
-    def __init__(self, dims, nfields=1, fine=None):
+    def __init__(self, dims, nfields=1, fine=None, periodic=None):
         self.dims = tuple(int(d) for d in dims)
         self.nfields = int(nfields)
+        self.periodic = _periodic_flags(periodic, len(self.dims))
         if fine is not None and len(fine) != len(self.dims):
             raise ValueError("fine: expected %d sizes" % len(self.dims))
         h = C.c_void_p()
-        _chk(lib().cheb_dealias_create(len(self.dims), _ints(self.dims), None if fine is None else _ints(fine), self.nfields, C.byref(h)))
+        if periodic is None:
+            _chk(lib().cheb_dealias_create(len(self.dims), _ints(self.dims), None if fine is None else _ints(fine), self.nfields, C.byref(h)))
+        else:
+            _chk(lib().cheb_dealias_create_basis(len(self.dims), _ints(self.dims), None if fine is None else _ints(fine),
+                                                 _ints([int(p) for p in self.periodic]), self.nfields, C.byref(h)))
         self._h = h
         m = (C.c_int * len(self.dims))()
         _chk(lib().cheb_dealias_fine_dims(self._h, m))
@@ -1702,7 +1753,14 @@ class ChebOpFun(_Handle):
     by the solver's line transforms around ONE pointwise kernel in mode space, whatever the number of terms (at most 32).  Kinds,
     with s an eigenvalue of B: "one" 1, "inv" 1/s, "res" 1/(par + tau s), "exp" e^(-tau s), "phi1".."phi3" phi_k(-tau s) (the
     functions of exponential integrators), "pow" s^par.  A mode with s == 0 (`singular`: sigma = 0, Neumann everywhere) gets 0 from
-    inv and pow, 1/k! from phi_k, 1 from exp.  Terms of an output are added in table order; the same input gives the same bits."""
+    inv and pow, 1/k! from phi_k, 1 from exp.  Terms of an output are added in table order; the same input gives the same bits.
+
+    A bc entry "periodic" makes the whole direction periodic, as for HelmholtzSolver (cheb_opfun_create_basis): the
+    fields are then in the solver's unknown layout, dims[k] (periodic) or dims[k] - 2 (wall) values per direction; `periodic` holds
+    the flags.  The rule for s == 0 is the one above, unchanged: `singular` is sigma = 0 with every direction periodic or Neumann /
+    Neumann, and EVERY product of the directions' zero-eigenvalue modes -- the constants and, on a periodic direction of even
+    extent, the Nyquist vector (-1)^j -- has s == 0 exactly.  apply_full works on every handle made with bc; with every direction
+    periodic the unknown layout is the full grid and it equals apply."""
     _destroy = "cheb_opfun_destroy"
 
     def __init__(self, dims, nin=1, nout=None, sigma=0.0, bc=None, scale=None):
@@ -1714,11 +1772,17 @@ class ChebOpFun(_Handle):
         if scale is not None and bc is None:
             raise ValueError("scale needs bc: the box is a boundary-condition handle")
         sc, self.scale = _scale_array(scale, d)
-        b = None if bc is None else bc_array(bc, d)
-        self.bc = None if b is None else tuple(tuple(b[4 * k:4 * k + 4]) for k in range(d))
+        self.periodic, b, ends = (False,) * d, None, None
+        if bc is not None:
+            self.periodic, b, ends = bc_split(bc, d)
+        self.bc = ends                           # per direction the four end values, None where it is periodic
         h = C.c_void_p()
-        _chk(lib().cheb_opfun_create(d, _ints(self.dims), None if b is None else (C.c_double * len(b))(*b),
-                                     None if sc is None else _np_dp(sc), self.sigma, self.nin, self.nout, C.byref(h)))
+        if any(self.periodic):
+            _chk(lib().cheb_opfun_create_basis(d, _ints(self.dims), _ints([int(p) for p in self.periodic]), (C.c_double * len(b))(*b),
+                                               None if sc is None else _np_dp(sc), self.sigma, self.nin, self.nout, C.byref(h)))
+        else:
+            _chk(lib().cheb_opfun_create(d, _ints(self.dims), None if b is None else (C.c_double * len(b))(*b),
+                                         None if sc is None else _np_dp(sc), self.sigma, self.nin, self.nout, C.byref(h)))
         self._h = h
         self.size, self.out_size, self.full_size = (lib().cheb_opfun_size(h, w) for w in range(3))
         self.singular = bool(lib().cheb_opfun_singular(h))
@@ -1771,13 +1835,17 @@ FACES = {"wall": 0, "open": 1}           # CHEB_FACE_*
 
 
 def _face_codes(bc, d):
-    """The 2 d ints of cheb_project_create from one entry per direction: "wall", "open" or a pair (index 0, index n - 1)."""
+    """The 2 d ints of cheb_project_create from one entry per direction: "wall", "open" or a pair (index 0, index n - 1).  A
+    direction that is "periodic" (_bc_periodic: as a whole) has no faces; its two codes are "wall" placeholders that are not read."""
     if bc is None:
         return None
     if isinstance(bc, str) or len(bc) != d:
         raise ValueError("bc needs one entry per direction (%d)" % d)
     out = []
     for entry in bc:
+        if _bc_periodic(entry):
+            out += [FACES["wall"]] * 2
+            continue
         pair = (entry, entry) if isinstance(entry, str) else tuple(entry) if isinstance(entry, (tuple, list)) else ()
         if len(pair) != 2 or any(not isinstance(e, str) or e.lower() not in FACES for e in pair):
             raise ValueError("a direction's faces are 'wall', 'open' or a pair of them, got %r" % (entry,))
@@ -1785,14 +1853,22 @@ def _face_codes(bc, d):
     return out
 
 
-def project_faces(dims):
+def project_faces(dims, periodic=None):
     """Per compact boundary node (row-major boundary order) 2 k + end of the face whose condition the node takes: the highest
-    direction k in which it is an end node, end 0 = index 0 (cheb_project_faces_host).  An int32 numpy array; needs no device."""
+    direction k in which it is an end node, end 0 = index 0 (cheb_project_faces_host).  An int32 numpy array; needs no device.
+    periodic (one flag per direction, cheb_project_faces_basis_host): a flagged direction has no end nodes; the boundary nodes are
+    the end nodes of the other directions and the highest of those names the face."""
     import numpy as np
     dims = tuple(int(d) for d in dims)
-    nb = int(np.prod(dims)) - int(np.prod([n - 2 for n in dims])) if all(n >= 3 for n in dims) else 0
+    per = _periodic_flags(periodic, len(dims))
+    ok = all(n >= (2 if p else 3) for n, p in zip(dims, per))
+    nb = int(np.prod(dims)) - int(np.prod([n if p else n - 2 for n, p in zip(dims, per)])) if ok else 0
     f = np.empty(max(nb, 0), dtype=np.int32)
-    _chk(lib().cheb_project_faces_host(len(dims), _ints(dims), f.ctypes.data_as(C.POINTER(C.c_int)) if f.size else None))
+    ptr = f.ctypes.data_as(C.POINTER(C.c_int)) if f.size else None
+    if periodic is None:
+        _chk(lib().cheb_project_faces_host(len(dims), _ints(dims), ptr))
+    else:
+        _chk(lib().cheb_project_faces_basis_host(len(dims), _ints(dims), _ints([int(p) for p in per]), ptr))
     return f
 
 
@@ -1805,7 +1881,20 @@ class ChebProject(_Handle):
     With an open face div(out) = 0 at the interior nodes to rounding.  With walls only (`singular`) the solver drops the
     constant-like mode and div(out) is one constant c(u) there: small for resolved fields, O(1) for noise.  An edge or corner node
     meets the wall condition of its highest end direction only.  Asynchronous on torch's current stream; the same input gives the
-    same bits."""
+    same bits.
+
+    A bc entry "periodic" covers a whole direction (cheb_project_create_basis): 2 <= dims[k] <= 256 nodes
+    fourier_nodes(dims[k]), period 2 / scale[k], no faces; `periodic` holds the flags.  The unknowns of phi's problem are then the
+    nodes that are interior in every WALL direction (interior_size) and boundary_size counts the end nodes of the wall directions
+    (project_faces(dims, periodic)).  The divergence of the result, ChebGrad(dims, scale, periodic).div(out):
+      every direction periodic -- zero to rounding at EVERY node, although the handle is `singular`: the range of D_F holds neither
+        the constant nor the Nyquist vector, so div u has no component along any dropped mode.  boundary_size is 0 and flux must
+        be None;
+      an open face -- zero to rounding at the unknown nodes;
+      walls in the wall directions, the rest periodic (a channel) -- `singular`: at the unknown nodes it is free along the dropped
+        modes, which are constant along the wall directions and, per periodic direction, the constant or -- for an EVEN extent --
+        the Nyquist vector (-1)^j: one constant as above when the periodic extents are odd, 2^e coefficients with e even ones
+        (the wall-normal velocity may carry a Nyquist component no potential removes; small for resolved fields)."""
     _destroy = "cheb_project_destroy"
 
     def __init__(self, dims, nvec=1, bc=None, scale=None):
@@ -1814,10 +1903,15 @@ class ChebProject(_Handle):
         self.nvec = int(nvec)
         faces = _face_codes(bc, self.d)
         self.faces = None if faces is None else tuple(faces)
+        self.periodic = (False,) * self.d if faces is None else tuple(_bc_periodic(entry) for entry in bc)
         sc, self.scale = _scale_array(scale, self.d)
         h = C.c_void_p()
-        _chk(lib().cheb_project_create(self.d, _ints(self.dims), None if faces is None else _ints(faces),
-                                       None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
+        if any(self.periodic):
+            _chk(lib().cheb_project_create_basis(self.d, _ints(self.dims), _ints([int(p) for p in self.periodic]), _ints(faces),
+                                                 None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
+        else:
+            _chk(lib().cheb_project_create(self.d, _ints(self.dims), None if faces is None else _ints(faces),
+                                           None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
         self._h = h
         self.size, self.interior_size, self.boundary_size = (lib().cheb_project_size(h, w) for w in range(3))
         self.singular = bool(lib().cheb_project_singular(h))
@@ -1828,6 +1922,8 @@ class ChebProject(_Handle):
         Returns out."""
         import torch
         nu = self.nvec * self.d * self.size
+        if flux is not None and self.boundary_size == 0:
+            raise ChebhipError(4, "flux given, but every direction is periodic: there is no wall to prescribe it on")
         if out is None:
             out = torch.empty((self.nvec * self.d,) + self.dims, dtype=torch.float64, device=u.device)
         if phi is None:

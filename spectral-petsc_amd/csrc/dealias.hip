@@ -5,6 +5,9 @@
 // degree N_k = n_k - 1 per direction of the polynomial product.  Per direction (diffmat.cpp: dealias_matrix_host) R interpolates
 // the n coarse values to m >= n fine nodes, G = R D differentiates and interpolates, P = B_n T_m[0:n, :] takes fine values back to
 // the coarse nodes keeping the modes 0 .. N; with m > 3 (n - 1) / 2 + 1 (the default m = ceil(3n/2)) nothing aliases.
+// A periodic direction (cheb_dealias_create_basis) brings its own R, G = R D_F and P (diffmat.cpp:
+// fourier_dealias_matrix_host: the trigonometric interpolant and the cut at the wavenumbers |k| <= floor(n/2)) and its own default
+// m = 3 floor(n/2) + 1; nothing below knows the difference.
 //
 // Schedule.  No operand ever exists at the fine size.  The direction l with the largest m_l / n_l (the last one on a tie) runs
 // last on the way up: every operand is first taken to the fine grid in all the OTHER directions by plain line products
@@ -199,7 +202,8 @@ struct cheb_dealias {
   int n[MD] = {0}, m[MD] = {0};
   long coarse = 0, fine = 0, img = 0;        // values per field: prod(n), prod(m), prod(m) n_l / m_l
   std::vector<int> up, down;                 // the other directions on the way up; all directions with m != n on the way down
-  std::map<std::pair<int, int>, double *> mats;   // device: R (m n), P (n m), G (m n) of a distinct (n, m), one allocation
+  int basis[MD] = {0};                       // CHEB_BASIS_* per direction (cheb_dealias_create_basis; all CGL otherwise)
+  std::map<std::pair<std::pair<int, int>, int>, double *> mats;   // device: R (m n), P (n m), G (m n) of a distinct ((n, m), basis), one allocation
   double *prod = nullptr;                    // nf * fine: the product on the fine grid
   double *image = nullptr;                   // image_fields * img: the operands before direction l; the way down's intermediates
   double *tmp[2] = {nullptr, nullptr};       // tmp_fields * tmp_len[b]: an operand's intermediates before its image
@@ -208,7 +212,7 @@ struct cheb_dealias {
   size_t mat_bytes = 0;
 
   const double *mat(int k, int which) const {
-    const double *base = mats.at({n[k], m[k]});
+    const double *base = mats.at({{n[k], m[k]}, basis[k]});
     return base + (size_t)which * n[k] * m[k];
   }
   size_t work_bytes() const {
@@ -220,6 +224,28 @@ extern "C" int cheb_dealias_fine_size(int n) {
   return check_extent(n) ? -1 : dealias_fine_size(n);
 }
 
+namespace {
+
+int check_basis_value(int basis) {
+  if (basis != CHEB_BASIS_CGL && basis != CHEB_BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis = %d is neither 0 (CGL) nor 1 (Fourier)", basis);
+  return 0;
+}
+
+// the coarse extent of one direction: check_extent, or the range of a periodic direction
+int check_coarse(int n, int basis) {
+  if (basis != CHEB_BASIS_FOURIER) return check_extent(n);
+  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d: a periodic direction needs at least 2 points", n);
+  if (n > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: a periodic direction supports at most 256 points", n);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cheb_dealias_fine_size_basis(int n, int basis) {
+  if (check_basis_value(basis) || check_coarse(n, basis)) return -1;
+  return basis == CHEB_BASIS_FOURIER ? fourier_dealias_fine_size(n) : dealias_fine_size(n);
+}
+
 extern "C" int cheb_dealias_matrix_host(int n, int m, int which, double *A) {
   int rc;
   if ((rc = check_extent(n)) || (rc = check_extent(m))) return rc;
@@ -227,6 +253,18 @@ extern "C" int cheb_dealias_matrix_host(int n, int m, int which, double *A) {
   if (which < 0 || which > 2) return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d is none of 0 (R), 1 (P), 2 (G)", which);
   if (!A) return chebhip_fail(CHEBHIP_ERR_ARG, "matrix is NULL");
   dealias_matrix_host(n, m, which, A);
+  return 0;
+}
+
+extern "C" int cheb_dealias_matrix_basis_host(int n, int m, int which, int basis, double *A) {
+  int rc;
+  if ((rc = check_basis_value(basis))) return rc;
+  if (basis == CHEB_BASIS_CGL) return cheb_dealias_matrix_host(n, m, which, A);
+  if ((rc = check_coarse(n, basis)) || (rc = check_extent(m))) return rc;
+  if (m < n) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is smaller than n = %d", m, n);
+  if (which < 0 || which > 2) return chebhip_fail(CHEBHIP_ERR_ARG, "which = %d is none of 0 (R), 1 (P), 2 (G)", which);
+  if (!A) return chebhip_fail(CHEBHIP_ERR_ARG, "matrix is NULL");
+  fourier_dealias_matrix_host(n, m, which, A);
   return 0;
 }
 
@@ -267,7 +305,9 @@ int dealias_reserve(cheb_dealias *h, long fields, long job) {
 
 }  // namespace
 
-extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine, int nfields, cheb_dealias **out) {
+// basis null: cheb_dealias_create.  A Fourier direction brings its own three matrices and its own default fine size; the schedule,
+// the buffers and the launches do not know the difference.
+static int dealias_create(int d, const int *dims, const int *dims_fine, const int *basis, int nfields, cheb_dealias **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
@@ -275,8 +315,9 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
   int rc, mk[MD];
   long coarse = 1, fine = 1;
   for (int k = 0; k < d; k++) {
-    if ((rc = check_extent(dims[k]))) return rc;
-    mk[k] = dims_fine ? dims_fine[k] : dealias_fine_size(dims[k]);
+    const int bk = basis ? basis[k] : CHEB_BASIS_CGL;
+    if ((rc = check_basis_value(bk)) || (rc = check_coarse(dims[k], bk))) return rc;
+    mk[k] = dims_fine ? dims_fine[k] : bk == CHEB_BASIS_FOURIER ? fourier_dealias_fine_size(dims[k]) : dealias_fine_size(dims[k]);
     if (mk[k] < dims[k]) return chebhip_fail(CHEBHIP_ERR_ARG, "direction %d: fine size %d is smaller than %d", k, mk[k], dims[k]);
     if (mk[k] > 1024)
       return chebhip_fail(CHEBHIP_ERR_ARG, "direction %d: fine size %d: at most 1024 points per direction%s", k, mk[k],
@@ -290,7 +331,7 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
   h->d = d; h->nf = nfields; h->coarse = coarse; h->fine = fine;
   int l = 0;
   for (int k = 0; k < d; k++) {
-    h->n[k] = dims[k]; h->m[k] = mk[k];
+    h->n[k] = dims[k]; h->m[k] = mk[k]; h->basis[k] = basis ? basis[k] : CHEB_BASIS_CGL;
     if ((long)mk[k] * dims[l] >= (long)mk[l] * dims[k]) l = k;            // the largest m / n, the last one on a tie
   }
   h->l = l;
@@ -315,11 +356,14 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
 
   std::vector<double> buf;
   for (int k = 0; k < d && !rc; k++) {
-    const std::pair<int, int> key{dims[k], mk[k]};
+    const std::pair<std::pair<int, int>, int> key{{dims[k], mk[k]}, h->basis[k]};
     if (h->mats.count(key)) continue;
     const size_t nm = (size_t)dims[k] * mk[k];
     buf.resize(3 * nm);
-    for (int which = 0; which < 3; which++) dealias_matrix_host(dims[k], mk[k], which, buf.data() + which * nm);
+    for (int which = 0; which < 3; which++) {
+      if (h->basis[k] == CHEB_BASIS_FOURIER) fourier_dealias_matrix_host(dims[k], mk[k], which, buf.data() + which * nm);
+      else dealias_matrix_host(dims[k], mk[k], which, buf.data() + which * nm);
+    }
     double *dev = nullptr;
     if ((rc = device_array(&dev, 3 * nm, buf.data(), "dealias matrices"))) break;
     h->mats[key] = dev;
@@ -330,6 +374,16 @@ extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine,
   if (rc) { cheb_dealias_destroy(h); return rc; }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_dealias_create(int d, const int *dims, const int *dims_fine, int nfields, cheb_dealias **out) {
+  return dealias_create(d, dims, dims_fine, nullptr, nfields, out);
+}
+
+extern "C" int cheb_dealias_create_basis(int d, const int *dims, const int *dims_fine, const int *basis, int nfields, cheb_dealias **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return dealias_create(d, dims, dims_fine, basis, nfields, out);
 }
 
 extern "C" int cheb_dealias_reserve_advect(cheb_dealias *h) {

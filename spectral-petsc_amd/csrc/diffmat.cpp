@@ -1211,6 +1211,121 @@ void fourier_line(int n, double s, std::vector<long double> &S, std::vector<long
     if (kind[p] != 2 && k[p] != 0) { const long double a = PI_L * (long double)k[p] * (long double)s; lam[p] = a * a; }
 }
 
+// Dealiased products on a periodic direction (cheb_dealias_create_basis): n coarse nodes x_j = -1 + 2 j / n, m >= n fine
+// nodes y_i = -1 + 2 i / m, K = floor(n / 2).  The interpolant of n periodic values is sum_j u_j r_j(x),
+//   r_j(x) = (1/n) [1 + 2 sum_{k=1}^{K} cos pi k (x - x_j)]                              (n odd)
+//   r_j(x) = (1/n) [1 + 2 sum_{k=1}^{K-1} cos pi k (x - x_j) + cos pi K (x - x_j)]       (n even: the Nyquist vector is cos pi K (x + 1))
+//   which = 0  R (m x n): R[i][j] = r_j(y_i); a fine node that is a coarse node gives the exact unit row
+//   which = 1  P (n x m): P[i][j] = (1/m) [1 + 2 sum_{k=1}^{K} cos pi k (x_i - y_j)], the fine-grid function's Fourier series cut at
+//              |k| <= K, at the coarse nodes (m == n: the exact identity).  For even n the wavenumber K is kept with what the coarse
+//              grid sees of it, cos pi K (x + 1): the square of the Nyquist vector, 1 at every node, comes back as 1/2.
+//   which = 2  G (m x n) = R D_F, the product in long double, rounded once
+// Every cosine takes the integer multiple 2 k a of pi / (n m), a = i n - j m (R) or i m - j n (P), through cos_pi (one table); the sums run in
+// ascending k from the 1.  The Dirichlet kernel of P vanishes where (2K + 1) a is a multiple of n m and a is not: an exact 0.
+// A product of two interpolants reaches wavenumber 2K; on m points it folds onto 2K - m, which P drops iff m - 2K > K: the
+// smallest such m is 3K + 1 (NOT ceil(3n/2): for even n that is 3K, and 2K folds onto -K).
+int fourier_dealias_fine_size(int n) { return 3 * (n / 2) + 1; }
+
+// tab[t] = cos(2 pi t / (n m)), 0 <= t < n m: every cosine of R and P, each evaluated once
+static void fourier_cos_table(long nm, std::vector<long double> &tab) {
+  tab.resize((size_t)nm);
+  for (long t = 0; t < nm; t++) tab[(size_t)t] = cos_pi(2 * t, nm);
+}
+static inline long double tab_cos(const std::vector<long double> &tab, long ka, long nm) {
+  long r = ka % nm;
+  return tab[(size_t)(r < 0 ? r + nm : r)];
+}
+
+static void fourier_interp_ld(int n, int m, std::vector<long double> &R) {
+  const int K = n / 2, Kfull = (n & 1) ? K : K - 1;
+  const long nm = (long)n * m;
+  std::vector<long double> tab;
+  fourier_cos_table(nm, tab);
+  R.assign((size_t)m * n, 0.0L);
+  for (int i = 0; i < m; i++) {
+    long double *row = &R[(size_t)i * n];
+    if (((long)i * n) % m == 0) { row[(long)i * n / m] = 1.0L; continue; }
+    for (int j = 0; j < n; j++) {
+      const long a = (long)i * n - (long)j * m;
+      long double s = 1.0L;
+      for (int k = 1; k <= Kfull; k++) s += 2.0L * tab_cos(tab, k * a, nm);
+      if (!(n & 1)) s += tab_cos(tab, K * a, nm);
+      row[j] = s / (long double)n;
+    }
+  }
+}
+
+void fourier_dealias_matrix_host(int n, int m, int which, double *A) {
+  const size_t sn = n, sm = m;
+  if (which == 1) {
+    const int K = n / 2;
+    const long nm = (long)n * m;
+    std::vector<long double> tab;
+    if (m != n) fourier_cos_table(nm, tab);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < m; j++) {
+        double &out = A[i * sm + j];
+        if (m == n) { out = i == j ? 1.0 : 0.0; continue; }
+        const long a = (long)i * m - (long)j * n;
+        if (a % nm != 0 && ((2L * K + 1) * a) % nm == 0) { out = 0.0; continue; }
+        long double s = 1.0L;
+        for (int k = 1; k <= K; k++) s += 2.0L * tab_cos(tab, k * a, nm);
+        out = (double)(s / (long double)m);
+      }
+    return;
+  }
+  std::vector<long double> R;
+  fourier_interp_ld(n, m, R);
+  if (which == 0) { for (size_t e = 0; e < sm * sn; e++) A[e] = (double)R[e]; return; }
+  std::vector<long double> D;
+  fourier_diff_ld(n, 1, D);
+  for (size_t i = 0; i < sm; i++)
+    for (size_t j = 0; j < sn; j++) {
+      long double s = 0.0L;
+      for (size_t q = 0; q < sn; q++) s += R[i * sn + q] * D[q * sn + j];
+      A[i * sn + j] = (double)s;
+    }
+}
+
+// Evaluation at arbitrary points of a periodic direction (cheb_points_create_basis, k_points_frows of points.hip).  The device table
+// of an extent n, 3 n doubles: the nodes of fourier_nodes_host at [0, n), then sin(pi m / n) at [n, 2n) and cos(pi m / n) at
+// [2n, 3n), m = 0 .. n-1, each rounded once.
+void fourier_points_table_host(int n, double *tab) {
+  fourier_nodes_host(n, tab);
+  for (int j = 0; j < n; j++) { tab[n + j] = (double)sin_pi(j, n); tab[2 * n + j] = (double)cos_pi(j, n); }
+}
+
+// cos / sin (pi k t) for a long double t: k t is reduced modulo 2 before it meets pi
+static void cossin_pik(int k, long double t, long double *c, long double *s) {
+  const long double r = fmodl((long double)k * t, 2.0L);
+  *c = cosl(PI_L * r); *s = sinl(PI_L * r);
+}
+
+// Rows of the trigonometric interpolant (deriv = 0) or of its derivative (deriv = 1) at m arbitrary coordinates, by the cosine sums
+// of fourier_dealias_matrix_host's comment with t = x - x_j: x is first wrapped into [-1, 1] (x - 2 rint(x / 2), exact), the sums run
+// in ascending k.  Long double, rounded once; a NaN or infinite coordinate gives a row of NaN.
+void fourier_points_matrix_host(int n, int m, const double *x, int deriv, double *R) {
+  const int K = n / 2, Kfull = (n & 1) ? K : K - 1;
+  for (int t = 0; t < m; t++) {
+    double *row = R + (size_t)t * n;
+    if (!std::isfinite(x[t])) { for (int j = 0; j < n; j++) row[j] = std::numeric_limits<double>::quiet_NaN(); continue; }
+    const long double xr = (long double)x[t] - 2.0L * rintl(0.5L * (long double)x[t]);
+    for (int j = 0; j < n; j++) {
+      const long double dj = xr - (long double)(2 * j - n) / (long double)n;
+      long double acc = deriv ? 0.0L : 1.0L, c, s;
+      for (int k = 1; k <= Kfull; k++) {
+        cossin_pik(k, dj, &c, &s);
+        acc += deriv ? -2.0L * (PI_L * (long double)k) * s : 2.0L * c;
+      }
+      if (!(n & 1)) {
+        cossin_pik(K, dj, &c, &s);
+        acc += deriv ? -(PI_L * (long double)K) * s : c;
+      }
+      row[j] = (double)(acc / (long double)n);
+    }
+  }
+}
+
 hipError_t diffmat_create_fourier(int n, int order, DiffMat *out) {
   if (n < 2 || n > 256) return hipErrorInvalidValue;
   std::vector<long double> A;

@@ -38,6 +38,9 @@
 // directions' rows exchanged; without a flagged direction they launch k_points_rows and give the plain calls' bits.
 // cheb_points_eval_grad takes every first derivative of a chunk of C / 2 points from ONE direction-0 line product over the stacked
 // value and derivative rows, [field][2 cnt][i_1 .. i_{d-1}], and one launch of k_points_contract_grad over the blocks it writes.
+//
+// A periodic direction (cheb_points_create_basis) takes its rows, value and derivative, from k_points_frows: the
+// trigonometric interpolant in the same nearest-node form, coordinates wrapped into the period.  Everything downstream takes rows.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
@@ -179,6 +182,83 @@ __global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
       if (j != s) { const double dj = x - xn[j]; v = (coef(j) / dj) / sum * (g0 - ds / dj); }
       out[j] = fin ? v : __builtin_nan("");
     }
+  }
+}
+
+// The rows of a PERIODIC direction (cheb_points_create_basis): n nodes x_j = -1 + 2 j / n, period 2, the trigonometric
+// interpolant in its barycentric form r_j ~ (-1)^j cot(pi (x - x_j) / 2) (n even), (-1)^j / sin(pi (x - x_j) / 2) (n odd), in the
+// nearest-node form of k_points_rows: entries relative to node s, one normalising sum over the row's lane group, the same butterflies.
+// A kernel of its own, so that the CGL kernels above keep their code.  g.r.nodes[k] is the table of fourier_points_table_host.
+//   wrapping   any finite x is wrapped, never extrapolated: xr = x - 2 rint(x / 2) in [-1, 1], exact in double;
+//   s          by arithmetic, no search: the candidates rint((xr + 1) n / 2) and its two neighbours, the smallest |distance|, the
+//              lowest index on a tie; the candidate n is node 0 one period on (it serves x ~ +1);
+//   d_s        = xr - x_s with x_s the DOUBLE node of the table (xr - 1 for the candidate n): exact (Sterbenz: |d_s| <= 1 / n <=
+//              |x_s| / 2, or x_s = 0).  The rows are those of the point x_s(exact) + d_s, which is x moved by the rounding of the
+//              node, at most 2^-54: so the doubles fourier_nodes(n), and their images a period away, give the exact unit row;
+//   entries    with a = pi d_s / 2 and b = pi m / n, m = (s - j) mod n, from the table (sinpi / cospi of d_s / 2 for a):
+//              S = sin a cos b + cos a sin b = sin(pi (x - x_j) / 2) up to the sign both parities carry in (-1)^m; the two terms are
+//              within a factor 3 of their sum (|tan a / tan b| <= 1/2), so nothing is lost half a period away, where a rounded
+//              x - x_j would leave the small sine without relative accuracy.  C = cos a cos b - sin a sin b.
+//              n odd: e_j = (-1)^m sin a / S;  n even: e_j = (-1)^m tan a (C / S);  e_s = 1;  r = e / sum e.
+//              Nothing divides by d_s; d_s == 0 is the exact unit row; NaN or +-Inf a row of NaN.
+//   derivative of the same rational function, h = pi / 2, sums over j != s:
+//              n odd:  p_j = h (-1)^m cos a / S,          f_j = -h (-1)^m sin a C / S^2
+//              n even: p_j = h (-1)^m (C / S) / cos^2 a,  f_j = -h (-1)^m tan a / S^2
+//              r'_j = (f_j R + p_j - e_j F) / R^2,  r'_s = -(P + F) / R^2,  R = sum e, F = sum f, P = sum p.
+//              d_s == 0: e = f = 0, R = 1 and r'_j = p_j, r'_s = -P: row s of D_F by the same instructions.
+__global__ __launch_bounds__(256) void k_points_frows(const DRowsJob g) {
+  const int k = blockIdx.y, n = g.r.n[k], lg = g.r.lg[k], what = g.what[k];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
+  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
+  const bool ok = row < g.r.m[k];
+  const double *__restrict__ tab = g.r.nodes[k];
+  const double x = ok ? g.r.x[k][(size_t)row * (size_t)g.r.stride[k]] : 0.0;
+  const bool fin = fabs(x) < INFINITY;                     // (false for a NaN as well)
+  const double xf = fin ? x : 0.0;
+  const double xr = xf - 2.0 * rint(0.5 * xf);
+
+  int s = 0;
+  double ds = 0.0, best = INFINITY;
+  const int c0 = (int)rint((xr + 1.0) * (0.5 * (double)n));
+  for (int c = c0 - 1; c <= c0 + 1; c++) {
+    if (c < 0 || c > n) continue;
+    const int j = c == n ? 0 : c;
+    const double dd = c == n ? xr - 1.0 : xr - tab[j];
+    const double a = fabs(dd);
+    if (a < best || (a == best && j < s)) { best = a; s = j; ds = dd; }
+  }
+  const double sa = sinpi(0.5 * ds), ca = cospi(0.5 * ds), ta = sa / ca, h = 1.5707963267948966;
+  const bool odd = n & 1;
+  // (e, p, f) of node j != s
+  auto parts = [&](int j, double &e, double &p, double &f) {
+    int m = s - j;
+    if (m < 0) m += n;
+    const double sb = tab[n + m], cb = tab[2 * n + m], sg = (m & 1) ? -1.0 : 1.0;
+    const double S = sa * cb + ca * sb, C = ca * cb - sa * sb;
+    if (odd) { e = sg * (sa / S); p = h * sg * (ca / S); f = -h * sg * (sa * C / (S * S)); }
+    else { const double cs = C / S; e = sg * (ta * cs); p = h * sg * (cs / (ca * ca)); f = -h * sg * (ta / (S * S)); }
+  };
+  double R = 0.0, F = 0.0, P = 0.0;
+  for (int j = l; j < n; j += G) {
+    if (j == s) { R += 1.0; continue; }
+    double e, p, f;
+    parts(j, e, p, f);
+    R += e;
+    if (what & 2) { F += f; P += p; }
+  }
+  for (int mm = 1; mm < G; mm <<= 1) R += __shfl_xor(R, mm);
+  if (what & 2)
+    for (int mm = 1; mm < G; mm <<= 1) { F += __shfl_xor(F, mm); P += __shfl_xor(P, mm); }
+  if (!ok) return;
+  double *__restrict__ outv = (what & 1) ? g.r.R[k] + (size_t)row * (size_t)n : nullptr;
+  double *__restrict__ outd = (what & 2) ? g.D[k] + (size_t)row * (size_t)n : nullptr;
+  const double R2 = R * R;
+  for (int j = l; j < n; j += G) {
+    double e = 1.0, p = 0.0, f = 0.0;
+    if (j != s) parts(j, e, p, f);
+    if (outv) outv[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : e / R;
+    if (outd) outd[j] = !fin ? __builtin_nan("") : j == s ? -(P + F) / R2 : (f * R + p - e * F) / R2;
   }
 }
 
@@ -525,16 +605,49 @@ int launch_drows(const DRowsJob &job, hipStream_t st, const char *what) {
   return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s derivative rows launch: %s", what, hipGetErrorString(e));
 }
 
+int launch_frows(const DRowsJob &job, hipStream_t st, const char *what) {
+  unsigned gx = 0;
+  for (int k = 0; k < job.r.nd; k++) {
+    const unsigned rpb = 4u * (64u >> job.r.lg[k]);
+    gx = std::max(gx, (job.r.m[k] + rpb - 1) / rpb);
+  }
+  if (gx == 0) return 0;
+  hipLaunchKernelGGL(k_points_frows, dim3(gx, (unsigned)job.r.nd), dim3(256), 0, st, job);
+  sweep_note_launch();
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s periodic rows launch: %s", what, hipGetErrorString(e));
+}
+
+// A job whose entries may be periodic directions (fb[i] != 0 for entry i; null: none).  The CGL entries run as the launch they
+// have always been (k_points_rows where `plain`: every what is 1; k_points_drows otherwise), the periodic ones as one launch of
+// k_points_frows; an entry is self-contained, so each kernel gets its entries as a compact job.
+int launch_rows_basis(const DRowsJob &job, bool plain, const int *fb, hipStream_t st, const char *what) {
+  bool any = false;
+  for (int i = 0; fb && i < job.r.nd; i++) any = any || fb[i];
+  if (!any) return plain ? launch_rows(job.r, st, what) : launch_drows(job, st, what);
+  DRowsJob part[2] = {};
+  for (int i = 0; i < job.r.nd; i++) {
+    DRowsJob &t = part[fb[i] ? 1 : 0];
+    const int o = t.r.nd++;
+    t.r.n[o] = job.r.n[i]; t.r.lg[o] = job.r.lg[i]; t.r.m[o] = job.r.m[i]; t.r.stride[o] = job.r.stride[i];
+    t.r.x[o] = job.r.x[i]; t.r.nodes[o] = job.r.nodes[i]; t.r.R[o] = job.r.R[i];
+    t.what[o] = job.what[i]; t.D[o] = job.D[i];
+  }
+  int rc = 0;
+  if (part[0].r.nd) rc = plain ? launch_rows(part[0].r, st, what) : launch_drows(part[0], st, what);
+  if (!rc) rc = launch_frows(part[1], st, what);
+  return rc;
+}
+
 // The rows of one chunk, pass or grid.  Without a derivative direction this is today's k_points_rows launch; otherwise
 // k_points_drows writes a flagged direction's derivative rows where its value rows would go.
-int launch_rows_deriv(const RowsJob &job, const int *deriv, hipStream_t st, const char *what) {
+int launch_rows_deriv(const RowsJob &job, const int *deriv, const int *fb, hipStream_t st, const char *what) {
   bool any = false;
   for (int k = 0; deriv && k < job.nd; k++) any = any || deriv[k];
-  if (!any) return launch_rows(job, st, what);
   DRowsJob dj{};
   dj.r = job;
-  for (int k = 0; k < job.nd; k++) { dj.what[k] = deriv[k] ? 2 : 1; dj.D[k] = job.R[k]; }
-  return launch_drows(dj, st, what);
+  for (int k = 0; k < job.nd; k++) { dj.what[k] = any && deriv[k] ? 2 : 1; dj.D[k] = job.R[k]; }
+  return launch_rows_basis(dj, !any, fb, st, what);
 }
 
 // a multi-index of first derivatives: d host ints, each 0 or 1; NULL = all zero
@@ -551,7 +664,10 @@ struct cheb_points {
   long total = 0;                            // nf * prod(dims)
   unsigned C = 0;                            // points per chunk
   PtGeo geo{};
-  std::map<int, double *> nodes;             // device node table per distinct extent
+  int basis[MD] = {0};                       // CHEB_BASIS_* per direction (cheb_points_create_basis; all CGL otherwise)
+  std::map<int, double *> nodes;             // device node table per distinct extent of a CGL direction
+  std::map<int, double *> ftab;              // device table of fourier_points_table_host per distinct extent of a periodic direction
+  const double *table(int k) const { return basis[k] ? ftab.at(geo.n[k]) : nodes.at(geo.n[k]); }
   double *rows = nullptr;                    // C x n_k rows of every direction, direction k at C geo.off[k]
   double *W = nullptr;                       // nf x C x B: direction 0's output
   double *iw = nullptr;                      // spread's CHEB_SPREAD_DELTA: 1 / Clenshaw-Curtis weight, direction k at geo.off[k]; made at first use
@@ -592,6 +708,7 @@ void free_grid(cheb_points *h) {
 extern "C" int cheb_points_destroy(cheb_points *h) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   for (auto &t : h->nodes) if (t.second) (void)hipFree(t.second);
+  for (auto &t : h->ftab) if (t.second) (void)hipFree(t.second);
   if (h->rows) (void)hipFree(h->rows);
   if (h->W) (void)hipFree(h->W);
   if (h->iw) (void)hipFree(h->iw);
@@ -600,7 +717,8 @@ extern "C" int cheb_points_destroy(cheb_points *h) {
   return 0;
 }
 
-extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_points **out) {
+// basis null: cheb_points_create
+static int points_create(int d, const int *dims, int nfields, const int *basis, cheb_points **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
@@ -608,7 +726,11 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   int rc;
   long total = nfields, S = 0;
   for (int k = 0; k < d; k++) {
+    if (basis && basis[k] != CHEB_BASIS_CGL && basis[k] != CHEB_BASIS_FOURIER)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
     if ((rc = check_extent(dims[k]))) return rc;
+    if (basis && basis[k] == CHEB_BASIS_FOURIER && dims[k] > 256)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
     total *= dims[k]; S += dims[k];
     if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
   }
@@ -616,6 +738,7 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   cheb_points *h = new (std::nothrow) cheb_points;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->total = total;
+  for (int k = 0; k < d; k++) h->basis[k] = basis ? basis[k] : CHEB_BASIS_CGL;
   PtGeo &g = h->geo;
   g.d = d;
   for (int k = 0, o = 0; k < d; o += dims[k], k++) { g.n[k] = dims[k]; g.off[k] = (unsigned)o; }
@@ -636,6 +759,14 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   std::vector<double> x;
   for (int k = 0; k < d && !rc; k++) {
     const int nk = dims[k];
+    if (h->basis[k] == CHEB_BASIS_FOURIER) {
+      if (h->ftab.count(nk)) continue;
+      x.resize((size_t)3 * nk);
+      fourier_points_table_host(nk, x.data());
+      double *dev = nullptr;
+      if (!(rc = device_array(&dev, (size_t)3 * nk, x.data(), "periodic node table"))) h->ftab[nk] = dev;
+      continue;
+    }
     if (h->nodes.count(nk)) continue;
     x.resize(nk);
     points_nodes_host(nk, x.data());
@@ -646,6 +777,27 @@ extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_poin
   if (!rc) rc = device_array(&h->W, (size_t)C * nfields * g.B, nullptr, "points work buffer");
   if (rc) { cheb_points_destroy(h); return rc; }
   *out = h;
+  return 0;
+}
+
+extern "C" int cheb_points_create(int d, const int *dims, int nfields, cheb_points **out) {
+  return points_create(d, dims, nfields, nullptr, out);
+}
+
+extern "C" int cheb_points_create_basis(int d, const int *dims, int nfields, const int *basis, cheb_points **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return points_create(d, dims, nfields, basis, out);
+}
+
+extern "C" int cheb_points_fourier_matrix_host(int n, int m, const double *x, int deriv, double *R) {
+  if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d: a periodic direction needs at least 2 points", n);
+  if (n > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: a periodic direction supports at most 256 points", n);
+  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
+  if (deriv != 0 && deriv != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "deriv = %d must be 0 or 1", deriv);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  fourier_points_matrix_host(n, m, x, deriv, R);
   return 0;
 }
 
@@ -660,8 +812,8 @@ extern "C" int cheb_points_rows(cheb_points *h, int k, const double *x, long m, 
   RowsJob job{};
   const int n = h->geo.n[k];
   job.nd = 1; job.n[0] = n; job.lg[0] = rows_lg(n); job.m[0] = (unsigned)m; job.stride[0] = 1;
-  job.x[0] = x; job.nodes[0] = h->nodes[n]; job.R[0] = R;
-  return launch_rows(job, (hipStream_t)stream, "points");
+  job.x[0] = x; job.nodes[0] = h->table(k); job.R[0] = R;
+  return launch_rows_deriv(job, nullptr, &h->basis[k], (hipStream_t)stream, "points");
 }
 
 extern "C" int cheb_points_drows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
@@ -673,8 +825,8 @@ extern "C" int cheb_points_drows(cheb_points *h, int k, const double *x, long m,
   DRowsJob job{};
   const int n = h->geo.n[k];
   job.r.nd = 1; job.r.n[0] = n; job.r.lg[0] = rows_lg(n); job.r.m[0] = (unsigned)m; job.r.stride[0] = 1;
-  job.r.x[0] = x; job.r.nodes[0] = h->nodes[n]; job.what[0] = 2; job.D[0] = R;
-  return launch_drows(job, (hipStream_t)stream, "points");
+  job.r.x[0] = x; job.r.nodes[0] = h->table(k); job.what[0] = 2; job.D[0] = R;
+  return launch_rows_basis(job, false, &h->basis[k], (hipStream_t)stream, "points");
 }
 
 extern "C" int cheb_points_dmatrix_host(int n, int m, const double *x, double *R) {
@@ -705,9 +857,9 @@ int eval_run(cheb_points *h, const double *u, const double *xi, long npts, const
     job.nd = d;
     for (int k = 0; k < d; k++) {
       job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
-      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->rows + (size_t)C * g.off[k];
+      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->table(k); job.R[k] = h->rows + (size_t)C * g.off[k];
     }
-    if ((rc = launch_rows_deriv(job, deriv, st, "eval"))) return rc;
+    if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "eval"))) return rc;
     // d == 1: the line product's [field][point] is the result where it is one chunk or one field
     const bool direct = d == 1 && (h->nf == 1 || cnt == npts);
     ResampleDir p{h->rows, u, direct ? out + p0 : h->W, (unsigned)h->nf, (unsigned)g.n[0], cnt, g.B, (unsigned)h->nf * g.B};
@@ -786,10 +938,10 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
         job.r.nd = d;
         for (int k = 0; k < d; k++) {
           job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = 1; job.r.stride[k] = d;
-          job.r.x[k] = xi + (size_t)p * d + k; job.r.nodes[k] = h->nodes[g.n[k]];
+          job.r.x[k] = xi + (size_t)p * d + k; job.r.nodes[k] = h->table(k);
           job.r.R[k] = job.D[k] = h->rows + g.off[k]; job.what[k] = k == c ? 2 : 1;
         }
-        if ((rc = launch_drows(job, st, "eval_grad"))) return rc;
+        if ((rc = launch_rows_basis(job, false, h->basis, st, "eval_grad"))) return rc;
         ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 1u, g.B, nf * g.B};
         hipError_t e = resample_launch(lp, st);
         if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
@@ -810,11 +962,11 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
     job.r.nd = d;
     for (int k = 0; k < d; k++) {
       job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = cnt; job.r.stride[k] = d;
-      job.r.x[k] = xi + (size_t)p0 * d + k; job.r.nodes[k] = h->nodes[g.n[k]]; job.what[k] = 3;
+      job.r.x[k] = xi + (size_t)p0 * d + k; job.r.nodes[k] = h->table(k); job.what[k] = 3;
       job.r.R[k] = h->rows + (size_t)(2 * H) * g.off[k];
       job.D[k] = job.r.R[k] + (size_t)(k == 0 ? cnt : H) * g.n[k];
     }
-    if ((rc = launch_drows(job, st, "eval_grad"))) return rc;
+    if ((rc = launch_rows_basis(job, false, h->basis, st, "eval_grad"))) return rc;
     ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 2 * cnt, g.B, nf * g.B};
     hipError_t e = resample_launch(lp, st);
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
@@ -850,6 +1002,10 @@ int spread_weights(cheb_points *h) {             // the inverse quadrature weigh
   const PtGeo &g = h->geo;
   std::vector<double> w, iw;
   for (int k = 0; k < h->d; k++) {
+    if (h->basis[k] == CHEB_BASIS_FOURIER) {               // the weight 2 / n of every node of a periodic direction
+      for (int j = 0; j < g.n[k]; j++) iw.push_back(0.5 * (double)g.n[k]);
+      continue;
+    }
     w.resize(g.n[k]);
     modal_weights_host(g.n[k], w.data());
     for (double v : w) iw.push_back((double)(1.0L / (long double)v));
@@ -895,9 +1051,9 @@ int spread_run(cheb_points *h, const double *s, const double *xi, long npts, con
     job.nd = d;
     for (int k = 0; k < d; k++) {
       job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
-      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = sp.buf + (size_t)sp.P * g.off[k];
+      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->table(k); job.R[k] = sp.buf + (size_t)sp.P * g.off[k];
     }
-    if ((rc = launch_rows_deriv(job, deriv, st, "spread"))) return rc;
+    if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "spread"))) return rc;
     const SpreadArgs a{sp.buf, s + p0, (flags & CHEB_SPREAD_DELTA) ? h->iw : nullptr, out, (size_t)npts,
                        (unsigned)sp.P, cnt, (unsigned)h->nf * g.B, g.B, (accumulate || p0 > 0) ? 1 : 0};
     if (g.n[0] > 64) spread_launch<128>(d, g, a, st); else spread_launch<64>(d, g, a, st);
@@ -963,10 +1119,10 @@ int grid_run(cheb_points *h, const double *u, const double *coords, const int *m
   size_t co = 0;
   for (int k = 0; k < d; co += m[k], k++) {
     job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = (unsigned)m[k]; job.stride[k] = 1;
-    job.x[k] = coords + co; job.nodes[k] = h->nodes[g.n[k]]; job.R[k] = h->grows + h->goff[k];
+    job.x[k] = coords + co; job.nodes[k] = h->table(k); job.R[k] = h->grows + h->goff[k];
   }
   int rc;
-  if ((rc = launch_rows_deriv(job, deriv, st, "eval_grid"))) return rc;
+  if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "eval_grid"))) return rc;
   int order[MD];
   long cur[MD];
   for (int k = 0; k < d; k++) { order[k] = k; cur[k] = g.n[k]; }

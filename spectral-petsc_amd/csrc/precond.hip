@@ -1459,18 +1459,23 @@ extern "C" int cheb_opfun_destroy(cheb_opfun *h) {
   return 0;
 }
 
-extern "C" int cheb_opfun_create(int d, const int *dims, const double *bc, const double *scale, double sigma, int nin, int nout, cheb_opfun **out) {
+// basis null: cheb_opfun_create.  Otherwise the solver handle is cheb_helmholtz_create_basis's (a boundary-condition handle whatever
+// bc is: apply_full works, and with every direction periodic it copies, the unknown layout being the full grid)
+static int opfun_create(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nin, int nout,
+                        cheb_opfun **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (nin < 1 || nin > OPFUN_MAX_FIELDS) return chebhip_fail(CHEBHIP_ERR_ARG, "nin = %d must be in 1..16", nin);
   if (nout < 1 || nout > OPFUN_MAX_FIELDS) return chebhip_fail(CHEBHIP_ERR_ARG, "nout = %d must be in 1..16", nout);
-  if (!bc && scale) return chebhip_fail(CHEBHIP_ERR_ARG, "scale needs bc: the box is a boundary-condition handle");
+  if (!basis && !bc && scale) return chebhip_fail(CHEBHIP_ERR_ARG, "scale needs bc: the box is a boundary-condition handle");
   cheb_opfun *h = new (std::nothrow) cheb_opfun;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   const int nf = nin > nout ? nin : nout;
-  int rc = bc ? cheb_helmholtz_create_box(d, dims, bc, scale, sigma, nf, &h->hz) : cheb_helmholtz_create(d, dims, sigma, nf, &h->hz);
+  int rc = basis ? cheb_helmholtz_create_basis(d, dims, basis, bc, scale, sigma, nf, &h->hz)
+           : bc  ? cheb_helmholtz_create_box(d, dims, bc, scale, sigma, nf, &h->hz)
+                 : cheb_helmholtz_create(d, dims, sigma, nf, &h->hz);
   if (rc) { delete h; return rc; }
-  h->nin = nin; h->nout = nout; h->bc = bc != nullptr;
+  h->nin = nin; h->nout = nout; h->bc = h->hz->bc;
   chebhip_fdpc *pc = h->hz->pc;
   h->G = pc->G; h->N = pc->N;
   if (pc->W) { (void)hipFree(pc->W); pc->W = nullptr; }
@@ -1478,6 +1483,17 @@ extern "C" int cheb_opfun_create(int d, const int *dims, const double *bc, const
   (void)opfun_build_table(nin, nout, 0, nullptr, &h->tb);
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_opfun_create(int d, const int *dims, const double *bc, const double *scale, double sigma, int nin, int nout, cheb_opfun **out) {
+  return opfun_create(d, dims, nullptr, bc, scale, sigma, nin, nout, out);
+}
+
+extern "C" int cheb_opfun_create_basis(int d, const int *dims, const int *basis, const double *bc, const double *scale, double sigma, int nin,
+                                       int nout, cheb_opfun **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return opfun_create(d, dims, basis, bc, scale, sigma, nin, nout, out);
 }
 
 extern "C" int cheb_opfun_set_terms(cheb_opfun *h, int nterms, const cheb_opfun_term *terms) {

@@ -9,6 +9,10 @@
 // data g from the divergence, u and the flux), cheb_helmholtz_solve_bc of a box handle (sigma = 0; (0, 1) ends at walls, (1, 0) at
 // open faces), and one accumulating sweep per output component (cheb_grad_axpy_grad: out_k = u_k + (-s_k) D_k phi).
 //
+// A periodic direction (cheb_project_create_basis) has no faces: cheb_grad and the solver are their _basis handles, the
+// unknowns are the nodes interior in every WALL direction (the solver's geometry) and the tables below follow that.  With every
+// direction periodic there is no boundary node, no g and no face table.
+//
 // k_project_rhs: grid-stride over the nodes, one node per lane, the vectors along the grid's second dimension.  The handle's node table (ChebLayout's: m >= 0 the
 // number among the interior nodes, -1 - b on the boundary) sends a node's value to f or g; the face table gives a boundary node's
 // (direction, end) as 2 k + end.  Values are moved and negated, a flux is one subtraction; the field side is read coalesced.  No
@@ -47,31 +51,43 @@ __global__ __launch_bounds__(256) void k_project_rhs(long N, long G, long NB, in
   }
 }
 
-int check_grid(int d, const int *dims, long *N_out, long *G_out) {
+// basis: null (walls everywhere) or one CHEB_BASIS_* per direction.  A wall direction has 3 .. 258 points and dims - 2 unknowns, a
+// periodic one 2 .. 256 points, all of them unknowns (the ranges of cheb_helmholtz_create_basis).  G: the unknown nodes.
+int check_grid(int d, const int *dims, const int *basis, long *N_out, long *G_out) {
   if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
   long N = 1, G = 1;
   for (int k = 0; k < d; k++) {
-    if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d but must be >= 3: a line needs an interior node", k, dims[k]);
-    if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: the direct solve supports at most 258 points per line", k, dims[k]);
-    N *= dims[k]; G *= dims[k] - 2;
+    if (basis && basis[k] != CHEB_BASIS_CGL && basis[k] != CHEB_BASIS_FOURIER)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
+    if (basis && basis[k] == CHEB_BASIS_FOURIER) {
+      if (dims[k] < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d: a periodic direction needs at least 2 points", k, dims[k]);
+      if (dims[k] > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
+      N *= dims[k]; G *= dims[k];
+    } else {
+      if (dims[k] < 3) return chebhip_fail(CHEBHIP_ERR_SIZE, "dims[%d] = %d but must be >= 3: a line needs an interior node", k, dims[k]);
+      if (dims[k] > 258) return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: the direct solve supports at most 258 points per line", k, dims[k]);
+      N *= dims[k]; G *= dims[k] - 2;
+    }
     if (N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 nodes or more");
   }
   *N_out = N; *G_out = G;
   return 0;
 }
 
-// one node walk for both tables (either may be null): map[l] as cheb_layout_map_host, face[b] = 2 k + end of the highest end direction
-void walk(int d, const int *dims, int *map, int *face) {
+// one node walk for both tables (either may be null), in the solver's geometry (cheb_helmholtz_create_basis): a node is an unknown if
+// it is interior in every wall direction -- map[l] = its number among the unknowns, row-major -- and a boundary node otherwise:
+// map[l] = -1 - b, face[b] = 2 k + end of the highest WALL direction in which it is an end node.  A periodic direction has no ends.
+// basis null: map as cheb_layout_map_host.
+void walk(int d, const int *dims, const int *basis, int *map, int *face) {
   BoxGrid box;
   box.set_box(d, dims, 0, dims[0]);
+  auto end = [&](const int *ind, int k) { return !(basis && basis[k] == CHEB_BASIS_FOURIER) && (ind[k] == 0 || ind[k] == dims[k] - 1); };
   int g = 0, b = 0;
-  box.for_each_node([&](long l, const int *ind, bool bdy) {
-    if (!bdy) { if (map) map[l] = g; g++; return; }
-    if (face) {
-      int k = d - 1;
-      while (ind[k] != 0 && ind[k] != dims[k] - 1) k--;
-      face[b] = 2 * k + (ind[k] != 0);
-    }
+  box.for_each_node([&](long l, const int *ind, bool) {
+    int k = d - 1;
+    while (k >= 0 && !end(ind, k)) k--;
+    if (k < 0) { if (map) map[l] = g; g++; return; }
+    if (face) face[b] = 2 * k + (ind[k] != 0);
     if (map) map[l] = -1 - b;
     b++;
   });
@@ -104,25 +120,36 @@ extern "C" int cheb_project_destroy(cheb_project *h) {
 
 extern "C" int cheb_project_faces_host(int d, const int *dims, int *face) {
   int rc; long N, G;
-  if ((rc = check_grid(d, dims, &N, &G))) return rc;
+  if ((rc = check_grid(d, dims, nullptr, &N, &G))) return rc;
   if (!face) return chebhip_fail(CHEBHIP_ERR_ARG, "face is NULL");
-  walk(d, dims, nullptr, face);
+  walk(d, dims, nullptr, nullptr, face);
   return 0;
 }
 
-extern "C" int cheb_project_create(int d, const int *dims, const int *faces, const double *scale, int nvec, cheb_project **out) {
+extern "C" int cheb_project_faces_basis_host(int d, const int *dims, const int *basis, int *face) {
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  int rc; long N, G;
+  if ((rc = check_grid(d, dims, basis, &N, &G))) return rc;
+  if (!face && N != G) return chebhip_fail(CHEBHIP_ERR_ARG, "face is NULL");
+  walk(d, dims, basis, nullptr, face);
+  return 0;
+}
+
+// basis null: cheb_project_create, the handles and the calls it has always made
+static int project_create(int d, const int *dims, const int *basis, const int *faces, const double *scale, int nvec, cheb_project **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
   int rc; long N, G;
-  if ((rc = check_grid(d, dims, &N, &G))) return rc;
+  if ((rc = check_grid(d, dims, basis, &N, &G))) return rc;
   if (nvec < 1 || (long)nvec * d > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nvec = %d: nvec * d must be in 1..16", nvec);
   if ((long)nvec * d * N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
   unsigned open = 0;
   double bc[4 * MD];
   for (int k = 0; k < d; k++) {
     if (scale && (!std::isfinite(scale[k]) || !(scale[k] > 0.0))) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] = %g must be finite and > 0", k, scale[k]);
+    const bool fourier = basis && basis[k] == CHEB_BASIS_FOURIER;          // (no faces: its codes are not read)
     for (int e = 0; e < 2; e++) {
-      const int kind = faces ? faces[2 * k + e] : CHEB_FACE_WALL;
+      const int kind = faces && !fourier ? faces[2 * k + e] : CHEB_FACE_WALL;
       if (kind != CHEB_FACE_WALL && kind != CHEB_FACE_OPEN) return chebhip_fail(CHEBHIP_ERR_ARG, "faces[%d] = %d: CHEB_FACE_WALL or CHEB_FACE_OPEN", 2 * k + e, kind);
       if (kind == CHEB_FACE_OPEN) open |= 1u << (2 * k + e);
       bc[4 * k + 2 * e] = kind == CHEB_FACE_OPEN ? 1.0 : 0.0;         // open: phi = 0; wall: s_k dphi/dnu = g
@@ -133,22 +160,36 @@ extern "C" int cheb_project_create(int d, const int *dims, const int *faces, con
   cheb_project *h = new (std::nothrow) cheb_project;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nvec = nvec; h->N = N; h->G = G; h->open = open;
-  if ((rc = cheb_grad_create(d, dims, scale, &h->grad)) || (rc = cheb_helmholtz_create_box(d, dims, bc, scale, 0.0, nvec, &h->hz))) {
+  rc = basis ? cheb_grad_create_basis(d, dims, scale, basis, &h->grad) : cheb_grad_create(d, dims, scale, &h->grad);
+  if (!rc) rc = basis ? cheb_helmholtz_create_basis(d, dims, basis, bc, scale, 0.0, nvec, &h->hz) : cheb_helmholtz_create_box(d, dims, bc, scale, 0.0, nvec, &h->hz);
+  if (rc) {
     cheb_project_destroy(h);
     return rc;
   }
-  const long NB = N - G;
+  const long NB = N - G;                     // 0 with every direction periodic: no face table, no g
   std::vector<int> map((size_t)N), face((size_t)NB);
-  walk(d, dims, map.data(), face.data());
+  walk(d, dims, basis, map.data(), face.data());
   std::vector<unsigned char> fc(face.begin(), face.end());
   HIP_TRY_MEM_OR(hipMalloc((void **)&h->map, (size_t)N * sizeof(int)), cheb_project_destroy(h));
-  HIP_TRY_MEM_OR(hipMalloc((void **)&h->face, (size_t)NB), cheb_project_destroy(h));
   HIP_TRY_MEM_OR(hipMalloc((void **)&h->f, (size_t)nvec * G * sizeof(double)), cheb_project_destroy(h));
-  HIP_TRY_MEM_OR(hipMalloc((void **)&h->g, (size_t)nvec * NB * sizeof(double)), cheb_project_destroy(h));
   HIP_TRY_OR(hipMemcpy(h->map, map.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice), cheb_project_destroy(h));
-  HIP_TRY_OR(hipMemcpy(h->face, fc.data(), (size_t)NB, hipMemcpyHostToDevice), cheb_project_destroy(h));
+  if (NB) {
+    HIP_TRY_MEM_OR(hipMalloc((void **)&h->face, (size_t)NB), cheb_project_destroy(h));
+    HIP_TRY_MEM_OR(hipMalloc((void **)&h->g, (size_t)nvec * NB * sizeof(double)), cheb_project_destroy(h));
+    HIP_TRY_OR(hipMemcpy(h->face, fc.data(), (size_t)NB, hipMemcpyHostToDevice), cheb_project_destroy(h));
+  }
   *out = h;
   return 0;
+}
+
+extern "C" int cheb_project_create(int d, const int *dims, const int *faces, const double *scale, int nvec, cheb_project **out) {
+  return project_create(d, dims, nullptr, faces, scale, nvec, out);
+}
+
+extern "C" int cheb_project_create_basis(int d, const int *dims, const int *basis, const int *faces, const double *scale, int nvec, cheb_project **out) {
+  if (out) *out = nullptr;
+  if (!basis) return chebhip_fail(CHEBHIP_ERR_ARG, "basis is NULL");
+  return project_create(d, dims, basis, faces, scale, nvec, out);
 }
 
 extern "C" long cheb_project_size(const cheb_project *h, int which) {
@@ -162,6 +203,7 @@ extern "C" int cheb_project_apply(cheb_project *h, const double *u_dev, const do
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "project: NULL handle");
   if (!u_dev || !phi_dev || !out_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "project: NULL array");
   const long N = h->N, G = h->G, NB = N - G, nu = (long)h->nvec * h->d * N, np = (long)h->nvec * N, nb = (long)h->nvec * NB;
+  if (flux_dev && NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "project: flux given, but every direction is periodic: there is no wall to prescribe it on");
   if (out_dev != u_dev && overlap(out_dev, nu, u_dev, nu)) return chebhip_fail(CHEBHIP_ERR_ARG, "project: out is u or does not overlap it");
   if (overlap(phi_dev, np, u_dev, nu) || overlap(phi_dev, np, out_dev, nu)) return chebhip_fail(CHEBHIP_ERR_ARG, "project: phi must not overlap u or out");
   if (flux_dev && (overlap(flux_dev, nb, u_dev, nu) || overlap(flux_dev, nb, out_dev, nu) || overlap(flux_dev, nb, phi_dev, np)))
@@ -173,6 +215,7 @@ extern "C" int cheb_project_apply(cheb_project *h, const double *u_dev, const do
                      flux_dev, h->f, h->g);
   sweep_note_launch();
   HIP_TRY(hipGetLastError());
+  // (every direction periodic: g and the face table are null, no node reads them, and the solve takes no boundary data)
   if ((rc = cheb_helmholtz_solve_bc(h->hz, h->f, h->g, phi_dev, stream))) return rc;
   return cheb_grad_axpy_grad(h->grad, h->nvec, -1.0, phi_dev, u_dev, out_dev, stream);
 }

@@ -279,5 +279,13 @@ void fourier_modes_host(int n, int *k, int *kind);
 void fourier_modal_ld(int n, int which, std::vector<long double> &M);
 void fourier_line(int n, double s, std::vector<long double> &S, std::vector<long double> &Sinv, std::vector<long double> &lam);
 hipError_t diffmat_create_fourier(int n, int order, DiffMat *out);
+// dealiasing on a periodic direction: the default fine size 3 floor(n/2) + 1 and R (0), P (1), G = R D_F (2) for m >= n
+// fine nodes -1 + 2 i / m, the shapes of dealias_matrix_host
+int fourier_dealias_fine_size(int n);
+void fourier_dealias_matrix_host(int n, int m, int which, double *A);
+// evaluation at arbitrary points of a periodic direction: the device table of k_points_frows (3 n doubles: the nodes, sin(pi m / n),
+// cos(pi m / n)) and the host rows of the interpolant (deriv = 0) or its derivative (1) at m coordinates
+void fourier_points_table_host(int n, double *tab);
+void fourier_points_matrix_host(int n, int m, const double *x, int deriv, double *R);
 
 }  // namespace chebhip

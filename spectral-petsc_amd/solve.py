@@ -91,6 +91,19 @@ def channel_poisson(sp, dims, f, periodic, scale=None):
     return helmholtz_bvp(sp, dims, f, None, ["periodic" if p else "dirichlet" for p in flags], 0.0, scale=scale)
 
 
+def channel_project(sp, dims, u, periodic, scale=None, flux=None):
+    """The divergence-free projection of u (nvec * d full-grid fields) on a box whose flagged directions are periodic and whose
+    other faces are walls with the outward normal velocity `flux` (None: 0), for the one-off case: project_velocity with bc
+    "periodic" / "wall", next to channel_poisson.  The nodes are fourier_nodes(dims[k]) along a periodic direction and
+    cgl_nodes(dims[k]) along a wall one.  With every direction periodic there is no wall and flux must be None.  Returns
+    (out, phi) (new tensors)."""
+    dims = tuple(int(d) for d in dims)
+    flags = tuple(bool(p) for p in periodic)
+    if len(flags) != len(dims):
+        raise ValueError("periodic: expected %d flags, got %d" % (len(dims), len(flags)))
+    return project_velocity(sp, dims, u, ["periodic" if p else "wall" for p in flags], scale, flux)
+
+
 def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     """sigma u - Laplace u = f with alpha u + beta du/dnu = g on every face (sp.HelmholtzSolver's `bc`), solved directly.
     f_full: full-grid device tensor (its boundary entries are ignored); g: the compact boundary values in row-major node order
@@ -120,7 +133,8 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
 
 def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
     """(out, phi) of sp.ChebProject(dims, nvec, bc, scale).project(u, flux=flux) with a handle made and destroyed here: u holds
-    nvec * d full-grid fields, out its divergence-free projection (new tensors)."""
+    nvec * d full-grid fields, out its divergence-free projection (new tensors).  A bc entry "periodic" makes that direction periodic
+    (ChebProject's docstring)."""
     dims = tuple(int(d) for d in dims)
     N = 1
     for n in dims:
@@ -143,7 +157,9 @@ def diffuse(sp, dims, u_full, t, bc, g=None, f=None, kappa=1.0, scale=None):
     u_s the steady solution (one HelmholtzSolver.solve_full; 0 without f and g), the exponential one sp.ChebOpFun.apply_full.
     f: full-grid device tensor (boundary entries ignored) or None; g: compact boundary values or None.  u_full is expected to
     meet the conditions; its boundary entries are not read.  Neumann on every face is singular: only f = None, g = None is
-    handled there.  No time stepping: any t >= 0 in one call.  Returns a new (*dims) tensor."""
+    handled there.  No time stepping: any t >= 0 in one call.  Returns a new (*dims) tensor.  A bc entry "periodic" makes that
+    direction periodic (nodes fourier_nodes(dims[k]), no faces, no entries in g); every direction periodic or Neumann / Neumann is
+    singular in the same sense."""
     dims = tuple(int(n) for n in dims)
     t, kappa = float(t), float(kappa)
     if not (t >= 0.0 and kappa > 0.0):
@@ -156,6 +172,11 @@ def diffuse(sp, dims, u_full, t, bc, g=None, f=None, kappa=1.0, scale=None):
         steady = f is not None or g is not None
         if steady and fun.singular:
             raise ValueError("diffuse: Neumann conditions on every face have no steady state for general f and g; pass f = None, g = None")
+        if any(fun.periodic):                           # the unknowns: every node of a periodic direction, the interior of a wall one
+            inner = (slice(None),) + tuple(slice(None) if p else slice(1, -1) for p in fun.periodic)
+            pack = lambda x, xi: xi.copy_(x[inner].reshape(-1))
+        else:
+            pack = lambda x, xi: _layout(sp, dims, u_full.device).pack(1, x, xi=xi)
         v = u_full.reshape((1,) + dims)
         us = None
         if steady:
@@ -164,12 +185,12 @@ def diffuse(sp, dims, u_full, t, bc, g=None, f=None, kappa=1.0, scale=None):
             if f is not None:
                 if f.numel() != fun.full_size:
                     raise ValueError("f has %d elements, expected %d" % (f.numel(), fun.full_size))
-                _layout(sp, dims, u_full.device).pack(1, (f.reshape((1,) + dims) / kappa).contiguous(), xi=rhs)
+                pack((f.reshape((1,) + dims) / kappa).contiguous(), rhs)
             us = torch.empty((1,) + dims, dtype=torch.float64, device=u_full.device)
             solver.solve_full(rhs, g, us.reshape(-1))
             v = v - us
         vi = torch.empty(fun.size, dtype=torch.float64, device=u_full.device)
-        _layout(sp, dims, u_full.device).pack(1, v.contiguous(), xi=vi)
+        pack(v.contiguous(), vi)
         fun.set_terms("exp", tau=t * kappa)
         out = fun.apply_full(vi).reshape((1,) + dims)
         if us is not None:
@@ -457,11 +478,12 @@ def resolution(dims, u_full):
     return out[0] if nf == 1 else out
 
 
-def point_sources(sp, dims, pts, strengths, out=None):
+def point_sources(sp, dims, pts, strengths, out=None, periodic=None):
     """Discrete point sources on the CGL grid dims: the full-grid field g with integral(g phi) = sum_p strengths[p] phi(pts[p]) for
     every polynomial phi of the grid (ChebPoints.spread with delta=True; one handle made and destroyed: for a one-off call).  pts is
     an (npts, d) device tensor, strengths npts values (one field) or (nfields, npts); returns a device tensor of shape
-    (nfields,) + dims: a new one, or `out`, which must be contiguous, hold nfields prod(dims) values and is overwritten."""
+    (nfields,) + dims: a new one, or `out`, which must be contiguous, hold nfields prod(dims) values and is overwritten.
+    periodic: ChebPoints' flags; phi is then trigonometric along a flagged direction and the integral ChebModal(periodic)'s."""
     dims = tuple(int(n) for n in dims)
     if pts.dim() != 2 or pts.shape[1] != len(dims):
         raise ValueError("pts: expected shape (npts, %d), got %r" % (len(dims), tuple(pts.shape)))
@@ -471,7 +493,7 @@ def point_sources(sp, dims, pts, strengths, out=None):
     nf = strengths.shape[0] if strengths.dim() == 2 else 1
     if out is not None and not out.is_contiguous():
         raise ValueError("out must be contiguous")
-    h = sp.ChebPoints(dims, nf)
+    h = sp.ChebPoints(dims, nf, periodic=periodic)
     try:
         g = h.spread(strengths.reshape(nf, npts).contiguous(), pts.contiguous(), out=None if out is None else out.view(-1), delta=True)
         torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
@@ -480,10 +502,11 @@ def point_sources(sp, dims, pts, strengths, out=None):
     return g.view((nf,) + dims)
 
 
-def velocity_gradient(sp, dims, vel_full, pts, scale=None):
+def velocity_gradient(sp, dims, vel_full, pts, scale=None, periodic=None):
     """The velocity-gradient tensor A[p][i][j] = d u_i / d x_j at the points pts (an (npts, d) device tensor of reference
     coordinates) of the d stacked full-grid components vel_full (d prod(dims) values, component-major): one ChebPoints.eval_grad.
-    scale: the d factors 2 / L_k of a box (None: the reference cube).  Returns an (npts, d, d) device tensor."""
+    scale: the d factors 2 / L_k of a box (None: the reference cube).  periodic: ChebPoints' flags.  Returns an (npts, d, d) device
+    tensor."""
     dims = tuple(int(n) for n in dims)
     d = len(dims)
     size = d
@@ -491,7 +514,7 @@ def velocity_gradient(sp, dims, vel_full, pts, scale=None):
         size *= n
     if vel_full.numel() != size:
         raise ValueError("vel_full: expected %d stacked components of prod(dims) values, got %d values" % (d, vel_full.numel()))
-    h = sp.ChebPoints(dims, d)
+    h = sp.ChebPoints(dims, d, periodic=periodic)
     try:
         out = h.eval_grad(vel_full.reshape(-1), pts, scale=scale)
         torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
@@ -500,15 +523,19 @@ def velocity_gradient(sp, dims, vel_full, pts, scale=None):
     return out.permute(2, 0, 1).contiguous()
 
 
-def sample_plane(sp, dims, u_full, axis, coord, m=None, deriv=None):
+def sample_plane(sp, dims, u_full, axis, coord, m=None, deriv=None, periodic=None):
     """The plane x_axis = coord of the full-grid field u_full (all nodes of the CGL grid dims, row-major; nfields stacked fields if it
     holds a multiple of prod(dims) values): one ChebPoints.eval_grid with a single coordinate along `axis`.  The other directions
     keep their CGL nodes (m = None) or take m uniform points from -1 to +1 each.  Returns a device tensor of shape
     (nfields, points of the other directions ...), the direction `axis` dropped.  deriv: one flag (0 or 1) per direction: the
     derivative along the flagged directions with respect to the reference coordinates instead of the value (a vorticity cut is two
-    such planes)."""
+    such planes).  periodic: ChebPoints' flags; a flagged direction keeps its nodes fourier_nodes(n) (m = None), and `coord` along a
+    periodic axis is wrapped into the period."""
     dims = tuple(int(n) for n in dims)
     axis = int(axis)
+    per = (False,) * len(dims) if periodic is None else tuple(bool(p) for p in periodic)
+    if len(per) != len(dims):
+        raise ValueError("periodic: expected %d flags, got %d" % (len(dims), len(per)))
     if not 0 <= axis < len(dims):
         raise ValueError("axis %d out of range 0..%d" % (axis, len(dims) - 1))
     size = 1
@@ -523,10 +550,10 @@ def sample_plane(sp, dims, u_full, axis, coord, m=None, deriv=None):
         if k == axis:
             coords.append(torch.tensor([float(coord)], dtype=torch.float64, device=dev))
         elif m is None:
-            coords.append(torch.from_numpy(sp.cgl_nodes(n)).to(dev))
+            coords.append(torch.from_numpy(sp.fourier_nodes(n) if per[k] else sp.cgl_nodes(n)).to(dev))
         else:
             coords.append(torch.linspace(-1.0, 1.0, int(m), dtype=torch.float64, device=dev))
-    pts = sp.ChebPoints(dims, nf)
+    pts = sp.ChebPoints(dims, nf, periodic=periodic)
     try:
         out = pts.eval_grid(u_full.reshape(-1), coords, deriv=deriv)
         torch.cuda.current_stream().synchronize()       # (the handle's buffers are freed below)
