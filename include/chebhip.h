@@ -1147,6 +1147,60 @@ int  cheb_points_create_basis(int d, const int *dims, int nfields, const int *ba
 int  cheb_points_fourier_matrix_host(int n, int m, const double *x, int deriv, double *R);
 
 /* ------------------------------------------------------------------------- */
+/* The variable-coefficient Helmholtz operator  c(x) u - div(kappa(x) grad u)  */
+/* and its solve (no counterpart in the reference, whose only      */
+/* variable-coefficient operator is MatMult_Elliptic: one field, zero          */
+/* Dirichlet values, the unit cube).  Everything is on the conventions of      */
+/* cheb_helmholtz_create_basis: dims, basis, bc, scale, nfields and their      */
+/* limits, the unknown layout (interior nodes of a wall direction, all nodes   */
+/* of a periodic one, row-major, fields stacked), the compact boundary data g. */
+/* ------------------------------------------------------------------------- */
+/* For unknowns x and boundary data g (NULL = 0):
+ *   1. W = the full-grid extension: on every line of a wall direction k the two end values are Q_k x_line + B_BB^-1 g, the matrices
+ *      of cheb_helmholtz_line_box_host for that direction's ends and scale -- the condition alpha u + beta s_k du/dnu = g, WITHOUT
+ *      kappa: for Neumann data of the flux kappa du/dnu the caller divides g by kappa at the face (conormal Robin data is not built);
+ *   2. y = c x + sum_k (-s_k^2) D_k( kappa D_k W ) at the unknown nodes, D the CGL matrix on a wall direction and D_F on a periodic
+ *      one, directions ascending.  Direction k reads face values of direction k only; edge and corner values influence nothing.
+ * kappa: one full-grid field (prod dims values, read at face nodes too), finite and > 0, shared by the stacked fields; c: a scalar
+ * >= 0 or one full-grid field >= 0.  Results repeat bit for bit; a NaN in one field leaves the others' bits alone. */
+typedef struct cheb_varhelm cheb_varhelm;
+/* basis NULL: walls everywhere.  Errors as cheb_helmholtz_create_basis.  The handle owns its work memory (cheb_varhelm_work_bytes:
+ * its own arrays, the buffers and matrices of the inner direct solve, and the Krylov bases, (2 restart + 1) vectors made by the first
+ * solve and kept; a solve with another restart length waits for the stream, frees them and makes its own, so only one set exists). */
+int  cheb_varhelm_create(int d, const int *dims, const int *basis, const double *bc, const double *scale, int nfields, cheb_varhelm **out);
+int  cheb_varhelm_destroy(cheb_varhelm *h);
+long cheb_varhelm_size(const cheb_varhelm *h);            /* nfields * unknowns         */
+long cheb_varhelm_full_size(const cheb_varhelm *h);       /* nfields * N                */
+long cheb_varhelm_boundary_size(const cheb_varhelm *h);   /* nfields * (N - unknowns)   */
+long cheb_varhelm_work_bytes(const cheb_varhelm *h);
+/* Copies kappa and c (c_dev NULL: the scalar c_scalar) into the handle; device arrays of prod dims values.  Synchronous: it drains
+ * the device first (one checking pass: CHEBHIP_ERR_ARG if kappa is not finite and > 0 or c not finite and >= 0 at some node, and the
+ * handle keeps what it had), sets the preconditioner's shift sigma_p = mean of c / kappa over the unknown nodes, and returns when
+ * the copies are complete, so a later call on any stream sees the new coefficients. */
+int  cheb_varhelm_set_coefficients(cheb_varhelm *h, const double *kappa_dev, const double *c_dev, double c_scalar, void *stream);
+double cheb_varhelm_sigma(const cheb_varhelm *h);         /* sigma_p; -1 before set_coefficients */
+/* 1: c == 0 and every direction periodic or Neumann / Neumann (the inner direct solve is singular): solve refuses; -1: no coefficients yet */
+int  cheb_varhelm_singular(const cheb_varhelm *h);
+/* y = the linear operator (g = 0) of x; out = f - (the operator at g)(x).  Asynchronous on the stream, no allocation; the output
+ * may overlap no input (CHEBHIP_ERR_ARG).  cheb_varhelm_apply: mult with the shape of chebhip_apply_fn (ctx = the handle). */
+int  cheb_varhelm_mult(cheb_varhelm *h, const double *x_dev, double *y_dev, void *stream);
+int  cheb_varhelm_apply(void *h, const double *x_dev, double *y_dev, void *stream);
+int  cheb_varhelm_residual(cheb_varhelm *h, const double *x_dev, const double *f_dev, const double *g_dev, double *out_dev, void *stream);
+/* z = H(sigma_p)^-1 (r / kappa), H the direct solve cheb_helmholtz_create_basis of the same arguments.  Shape of chebhip_apply_fn;
+ * z may be r. */
+int  cheb_varhelm_precond(void *h, const double *r_dev, double *z_dev, void *stream);
+/* b = residual(0, f, g); chebhip_fgmres (restart, rtol, atol, max_it) on A = mult with the right preconditioner precond, from x = 0
+ * (x_nonzero = 0) or from the guess in x_dev; x_dev: the unknowns; u_full_dev (may be NULL): the full grid by the extension of
+ * cheb_helmholtz_solve_bc (every boundary node set once, by the highest direction in which it is an end node).  A singular problem
+ * is refused (CHEBHIP_ERR_ARG).  x may not alias f or g, u_full none of them.  The first solve, and a solve whose restart length
+ * differs from the one before, allocates the Krylov bases (see cheb_varhelm_create). */
+int  cheb_varhelm_solve(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                        double rtol, double atol, int max_it, int restart, void *stream);
+int  cheb_varhelm_iterations(const cheb_varhelm *h);      /* of the last solve, as chebhip_fgmres_* */
+double cheb_varhelm_last_residual(const cheb_varhelm *h);
+int  cheb_varhelm_reason(const cheb_varhelm *h);
+
+/* ------------------------------------------------------------------------- */
 /* Instrumentation (the reference has none: SURVEY 5.1).                      */
 /* ------------------------------------------------------------------------- */
 /* Run-time options: named integer switches, process-wide, read where they apply (the library never reads the

@@ -92,6 +92,10 @@ ABI_SYMBOLS = [
     "cheb_dealias_create_basis", "cheb_dealias_fine_size_basis", "cheb_dealias_matrix_basis_host",
     "cheb_project_create_basis", "cheb_project_faces_basis_host", "cheb_opfun_create_basis",
     "cheb_points_create_basis", "cheb_points_fourier_matrix_host",
+    "cheb_varhelm_create", "cheb_varhelm_destroy", "cheb_varhelm_size", "cheb_varhelm_full_size", "cheb_varhelm_boundary_size",
+    "cheb_varhelm_work_bytes", "cheb_varhelm_set_coefficients", "cheb_varhelm_sigma", "cheb_varhelm_singular", "cheb_varhelm_mult",
+    "cheb_varhelm_apply", "cheb_varhelm_residual", "cheb_varhelm_precond", "cheb_varhelm_solve", "cheb_varhelm_iterations",
+    "cheb_varhelm_last_residual", "cheb_varhelm_reason",
 ]
 
 
@@ -392,6 +396,24 @@ def lib():
         L.cheb_opfun_create_basis.argtypes = [C.c_int, ip, ip, dp, dp, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
         L.cheb_points_create_basis.argtypes = [C.c_int, ip, C.c_int, ip, C.POINTER(vp)]
         L.cheb_points_fourier_matrix_host.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp]
+        L.cheb_varhelm_create.argtypes = [C.c_int, ip, ip, dp, dp, C.c_int, C.POINTER(vp)]
+        L.cheb_varhelm_destroy.argtypes = [vp]
+        for f in (L.cheb_varhelm_size, L.cheb_varhelm_full_size, L.cheb_varhelm_boundary_size, L.cheb_varhelm_work_bytes):
+            f.argtypes = [vp]
+            f.restype = C.c_long
+        L.cheb_varhelm_set_coefficients.argtypes = [vp, vp, vp, C.c_double, vp]
+        L.cheb_varhelm_sigma.argtypes = [vp]
+        L.cheb_varhelm_sigma.restype = C.c_double
+        L.cheb_varhelm_singular.argtypes = [vp]
+        L.cheb_varhelm_mult.argtypes = [vp, vp, vp, vp]
+        L.cheb_varhelm_apply.argtypes = [vp, vp, vp, vp]
+        L.cheb_varhelm_residual.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.cheb_varhelm_precond.argtypes = [vp, vp, vp, vp]
+        L.cheb_varhelm_solve.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp]
+        L.cheb_varhelm_iterations.argtypes = [vp]
+        L.cheb_varhelm_last_residual.argtypes = [vp]
+        L.cheb_varhelm_last_residual.restype = C.c_double
+        L.cheb_varhelm_reason.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -1694,6 +1716,98 @@ class HelmholtzSolver(_FdmSteps, _Handle):
         return u
 
 
+class VarHelmholtz(_Handle):
+    """y = c x - sum_k scale_k^2 d_k( kappa d_k W ) at the unknown nodes, W the full-grid extension of the unknowns x by the faces'
+    conditions (cheb_varhelm_*), and the solve of c u - div(kappa grad u) = f by FGMRES with the direct solve
+    H(sigma_p)^-1 (r / kappa) as its right preconditioner.  dims, nfields (1..16), bc ("periodic" entries included) and scale are
+    HelmholtzSolver's, as are the unknown layout (interior nodes of a wall direction, all nodes of a periodic one, row-major, fields
+    stacked), the compact boundary layout of g and `size`, `full_size`, `boundary_size`.
+
+    The faces carry alpha u + beta scale_k du/dnu = g WITHOUT kappa: for Neumann data of the flux kappa du/dnu divide g by kappa at
+    the face first.  kappa is one full-grid field (finite, > 0, read at face nodes too) shared by the stacked fields; c a scalar >= 0
+    or one full-grid field >= 0.  Usable as the A (entry "mult") and the M (m_entry="precond") of Fgmres.solve."""
+    _destroy = "cheb_varhelm_destroy"
+
+    def __init__(self, dims, nfields=1, bc=None, scale=None):
+        self.dims = tuple(int(d) for d in dims)
+        self.nfields = int(nfields)
+        d = len(self.dims)
+        self.periodic, b, self.bc = bc_split(["dirichlet"] * d if bc is None else bc, d)
+        sc, self.scale = _scale_array(scale, d)
+        h = C.c_void_p()
+        _chk(lib().cheb_varhelm_create(d, _ints(self.dims), _ints([int(p) for p in self.periodic]), (C.c_double * len(b))(*b),
+                                       None if sc is None else _np_dp(sc), self.nfields, C.byref(h)))
+        self._h = h
+        self.size = lib().cheb_varhelm_size(h)
+        self.full_size = lib().cheb_varhelm_full_size(h)
+        self.boundary_size = lib().cheb_varhelm_boundary_size(h)
+        self.nodes = self.full_size // self.nfields
+        self.iterations, self.residual_norm, self.reason = 0, 0.0, 0
+
+    def _vec(self, name, t, n, optional=False):
+        import torch
+        if t is None and optional:
+            return None
+        if name == "g" and n == 0:
+            raise ChebhipError(4, "g given, but every direction is periodic: there is no boundary data to lift")
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 device tensor" % name)
+        if t.numel() != n:
+            raise ValueError("%s has %d elements, expected %d" % (name, t.numel(), n))
+        return t.data_ptr()
+
+    def set_coefficients(self, kappa, c=0.0):
+        """Copies kappa (a full-grid field) and c (a scalar or a full-grid field) into the handle; synchronises.  Raises ChebhipError
+        (code 4) where kappa is not finite and > 0 or c is negative or not finite; the handle then keeps what it had."""
+        import torch
+        cf = isinstance(c, torch.Tensor)
+        _chk(lib().cheb_varhelm_set_coefficients(self._h, self._vec("kappa", kappa, self.nodes), self._vec("c", c, self.nodes) if cf else None,
+                                                 0.0 if cf else float(c), _stream()))
+
+    sigma = property(lambda self: lib().cheb_varhelm_sigma(self._h))
+    singular = property(lambda self: bool(lib().cheb_varhelm_singular(self._h) == 1))
+
+    def work_bytes(self):
+        return lib().cheb_varhelm_work_bytes(self._h)
+
+    def mult(self, x, out):
+        """out = the linear operator (zero boundary data) of x.  Asynchronous on torch's current stream; out may not overlap x."""
+        _chk(lib().cheb_varhelm_mult(self._h, self._vec("x", x, self.size), self._vec("out", out, self.size), _stream()))
+        return out
+
+    def residual(self, x, f, g, out):
+        """out = f - (the operator with boundary data g)(x); g None: zero data.  This is what solve lifts the data with."""
+        _chk(lib().cheb_varhelm_residual(self._h, self._vec("x", x, self.size), self._vec("f", f, self.size),
+                                         self._vec("g", g, self.boundary_size, True), self._vec("out", out, self.size), _stream()))
+        return out
+
+    def precond(self, r, z):
+        """z = H(sigma_p)^-1 (r / kappa): the solve's right preconditioner."""
+        _chk(lib().cheb_varhelm_precond(self._h, self._vec("r", r, self.size), self._vec("z", z, self.size), _stream()))
+        return z
+
+    def solve(self, f, g=None, u_full=None, x0=None, rtol=1e-8, atol=0.0, max_it=200, restart=30):
+        """The unknowns x of (operator at g) x = f, by one library call; u_full (full_size values) receives the full grid.  x0: the
+        initial guess (it is not overwritten).  Afterwards iterations, residual_norm (Fgmres's `residual`; the name is the method's
+        here) and reason as on Fgmres.  A singular problem (c == 0
+        and every direction periodic or Neumann / Neumann) raises ChebhipError (code 4)."""
+        import torch
+        fp = self._vec("f", f, self.size)
+        x = torch.zeros_like(f) if x0 is None else None
+        if x is None:
+            self._vec("x0", x0, self.size)
+            x = x0.clone()
+        try:
+            _chk(lib().cheb_varhelm_solve(self._h, fp, self._vec("g", g, self.boundary_size, True), x.data_ptr(), 0 if x0 is None else 1,
+                                          self._vec("u_full", u_full, self.full_size, True), float(rtol), float(atol), int(max_it), int(restart),
+                                          _stream()))
+        finally:
+            self.iterations = lib().cheb_varhelm_iterations(self._h)
+            self.residual_norm = lib().cheb_varhelm_last_residual(self._h)
+            self.reason = lib().cheb_varhelm_reason(self._h)
+        return x
+
+
 OPFUN_KINDS = {"one": 0, "inv": 1, "res": 2, "exp": 3, "phi1": 4, "phi2": 5, "phi3": 6, "pow": 7}           # CHEB_OPFUN_*
 
 
@@ -2348,6 +2462,8 @@ class Fgmres(_Handle):
             return C.cast(lib().cheb_helmholtz_apply, C.c_void_p), op._h
         if kind == "StokesSaddlePc":
             return C.cast(lib().stokes_saddle_apply, C.c_void_p), op._h
+        if kind == "VarHelmholtz":                       # entry "mult": the operator; "precond": its preconditioner
+            return C.cast(lib().cheb_varhelm_precond if entry == "precond" else lib().cheb_varhelm_apply, C.c_void_p), op._h
         if kind in ("EllipticOp", "StokesOp"):
             name = {"EllipticOp": "ell_op_", "StokesOp": "stokes_op_"}[kind] + entry
             return C.cast(getattr(lib(), name), C.c_void_p), op._h

@@ -31,6 +31,11 @@ int stokes_op_fd_view_any(stokes_op *op, chebhip::FdView *v, int *gP0);
 int stokes_op_fd_view(stokes_op *op, chebhip::FdView *v);    // stokes.hip
 // grad.hip: out[v * d + k] = u[v * d + k] + alpha s_k d_k s[v], one accumulating sweep each; out may be u (project.hip)
 int cheb_grad_axpy_grad(cheb_grad *h, int nvec, double alpha, const double *s_dev, const double *u_dev, double *out_dev, void *stream);
+// precond.hip, for the owner of a boundary-condition Helmholtz handle (varhelm.hip): the full-grid extension u_B = Q u_I + B_BB^-1 g
+// on the caller's arrays (the one solve_bc ends with; g may be null), and a new shift sigma for the same lines (synchronous)
+int helmholtz_extend(const cheb_helmholtz *h, const double *z_dev, const double *g_dev, double *u_dev, void *stream);
+int helmholtz_set_sigma(cheb_helmholtz *h, double sigma);
+size_t helmholtz_work_bytes(const cheb_helmholtz *h);        // device bytes the handle holds: field buffers, line matrices, eigenvalues
 int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip: sets chebhip_last_error(), returns code
 
 // A failed HIP call ends the calling function: `cleanup` runs, the error text is the call as written plus HIP's reason.

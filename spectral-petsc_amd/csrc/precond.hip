@@ -1138,6 +1138,7 @@ struct cheb_helmholtz {
   // boundary-condition handles (helmholtz_create) only: full-grid geometry, per-direction end flags (beta = 0), the singular flag,
   // two nfields * G buffers
   bool bc = false; int singular = 0;
+  bool zero_modes = false;                     // every direction has a zero eigenvalue: singular at sigma = 0 (helmholtz_set_sigma)
   BcGeo geo = {};
   int dir[MAXD][2] = {};
   double *t = nullptr, *z = nullptr;
@@ -1319,6 +1320,7 @@ static int helmholtz_create(int d, const int *dims, const int *basis, const doub
     h->dir[k][0] = bc[4 * k + 1] == 0.0; h->dir[k][1] = bc[4 * k + 3] == 0.0;
     neumann = neumann && bc[4 * k] == 0.0 && bc[4 * k + 2] == 0.0;
   }
+  h->zero_modes = neumann;
   h->singular = sigma == 0.0 && neumann;
   if (hipMalloc((void **)&h->t, (size_t)G * nfields * sizeof(double)) != hipSuccess ||
       hipMalloc((void **)&h->z, (size_t)G * nfields * sizeof(double)) != hipSuccess) {
@@ -1386,6 +1388,49 @@ static int bc_extend(const cheb_helmholtz *h, int nf, const double *z, const dou
   }
   if (first) HIP_TRY(hipMemcpyAsync(u_dev, z, (size_t)nf * geo.N * sizeof(double), hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+// ---- what the variable-coefficient operator (varhelm.hip, through csrc/ops.h) needs of a boundary-condition handle it owns -----------
+// bc_extend on the caller's arrays: u (nfields full grids) from z (nfields unknown fields) and g (may be null)
+int helmholtz_extend(const cheb_helmholtz *h, const double *z_dev, const double *g_dev, double *u_dev, void *stream) {
+  return bc_extend(h, h->pc->nf, z_dev, g_dev, u_dev, (hipStream_t)stream);
+}
+// A new shift for the same lines: sigma rides on the handle's copy of dimension 0's eigenvalues and in the weight array built from
+// them on first use, nowhere else.  Synchronous (the caller has drained the device: no solve of this handle is in flight).
+int helmholtz_set_sigma(cheb_helmholtz *h, double sigma) {
+  int rc = check_sigma(sigma); if (rc) return rc;
+  chebhip_fdpc *pc = h->pc;
+  const int M0 = pc->M[0];
+  std::vector<double> l0(M0);
+  HIP_TRY(hipMemcpy(l0.data(), pc->ln[0]->lam, M0 * sizeof(double), hipMemcpyDeviceToHost));
+  for (int i = 0; i < M0; i++) l0[i] += sigma;
+  HIP_TRY(hipMemcpy(pc->lam0, l0.data(), M0 * sizeof(double), hipMemcpyHostToDevice));
+  pc->W_tried = false;
+  h->singular = sigma == 0.0 && h->zero_modes;
+  return 0;
+}
+
+// The device memory behind the handle, by the allocations of fdpc_create, helmholtz_create and diffmat.cpp: nfields * G values per field
+// buffer (t0, t1, the weight array, t and z of a boundary-condition handle), and per distinct line S^-1 dense, the eigenvalues, the
+// end-value matrices and four fragment matrices (one array of cnt + 1032 doubles and one of 3 cnt, cnt = MTP KS 64 -- or cnt each
+// for a long line)
+size_t helmholtz_work_bytes(const cheb_helmholtz *h) {
+  if (!h || !h->pc) return 0;
+  const chebhip_fdpc *pc = h->pc;
+  const size_t fb = (size_t)(pc->G > 0 ? pc->G : 1) * pc->nf;
+  size_t n = 0;
+  for (const double *p : {pc->t0, pc->t1, pc->t2, pc->t3, pc->t4, pc->t5, pc->W, pc->Einv, h->t, h->z}) if (p) n += fb;
+  if (pc->eta_g) n += fb / pc->nf;
+  if (pc->lam0) n += pc->M[0];
+  for (int k = 0; k < pc->geo.d; k++) n += pc->geo.dims[k];             // xs
+  for (const auto &kv : pc->lines) {
+    const LineMats &lm = kv.second;
+    if (!lm.ok) continue;
+    n += (size_t)lm.M * lm.M + lm.M + (lm.bcm ? 4 * (size_t)lm.M + 4 : 0);
+    for (const DiffMat *m : {&lm.Bcs, &lm.Bca, &lm.Fraw, &lm.Braw})
+      if (m->fragE) { const size_t cnt = (size_t)m->MTP * m->KS * 64; n += cnt + 1032 + 3 * cnt; }
+  }
+  return n * sizeof(double);
 }
 
 extern "C" int cheb_helmholtz_solve_bc(cheb_helmholtz *h, const double *f_dev, const double *g_dev, double *u_dev, void *stream) {

@@ -1,0 +1,368 @@
+// varhelm.hip -- the variable-coefficient Helmholtz operator  c(x) u - div( kappa(x) grad u )  on the conventions of the direct solve
+// (cheb_varhelm_*, include/chebhip.h): the unknown layout, the faces, the scales, the periodic directions and the stacked
+// fields of cheb_helmholtz_create_basis, with a preconditioned FGMRES solve behind one call.
+//
+// Operator.  For unknowns x and boundary data g
+//   1. W = the full-grid extension of x: on every line of a wall direction k the two end values are Q_k x_line + B_BB^-1 g -- the very
+//      launches the direct solve ends with (helmholtz_extend: bc_extend of precond.hip on this handle's arrays);
+//   2. A = sum_k (-s_k^2) D_k( kappa . D_k W ) on the full grid, one direction after the other: one fused launch D(kappa . D W)
+//      where the line's matrix fits the register-resident kernel (every CGL or Fourier line of at most 256 points), otherwise -- the
+//      CGL lines of 257 and 258 points -- the gradient sweep (STORE) and the sweep with the flux multiply on its load side
+//      (IN_FLUX_ETA); the first direction stores, the later ones accumulate (OUT_ACC);
+//   3. y = c x + A at the unknown nodes (k_vh_close), or f - that for the residual.
+// Lines of direction k whose other indices lie on a face run too (the sweeps take whole tensors): what they write lands on face
+// nodes, which step 3 never reads, so edge and corner values of W influence nothing.  Every step is a line product or a pointwise
+// pass over one field: a NaN in field j stays in field j, and nothing depends on timing -- the same call gives the same bits.
+// kappa is kept as nfields stacked copies of the full grid (the flux multiply takes an array of its input's geometry); the
+// preconditioner and the closing pass read copy 0 / the c field by index arithmetic from the unknown layout.
+//
+// Solve.  b = f - (operator at g)(0); FGMRES (krylov.hip) on A = the linear operator with the right preconditioner
+// z = H(sigma_p)^-1 (r / kappa), H the direct solve of the same dims, basis, bc, scale and nfields, sigma_p = mean of c / kappa over
+// the unknown nodes; the full-grid output by the same extension.
+#include "../../include/chebhip.h"
+#include "ops.h"
+#include "sweep.h"
+#include <cmath>
+#include <map>
+#include <new>
+#include <utility>
+#include <vector>
+
+using namespace chebhip;
+
+namespace {
+
+constexpr int VMAXD = 10;
+typedef double vh2 __attribute__((ext_vector_type(2)));
+
+// M[k] unknowns from full-grid index off[k] on (1 between walls, 0 on a periodic direction), row-major strides ls of the full grid;
+// N, G per field.  32-bit: nfields N <= 2^31 - 1.
+struct VhGeo { int d; int M[VMAXD]; int off[VMAXD]; int ls[VMAXD]; unsigned N, G; };
+
+// the full-grid index of the first of the W consecutive unknowns q, q + 1, .. (W divides M[d-1]: they share a line of the last direction)
+__device__ __forceinline__ unsigned vh_node(const VhGeo &g, unsigned q) {
+  unsigned r = q, n = 0;
+  for (int m = VMAXD - 1; m > 0; m--)
+    if (m < g.d) { const unsigned Mm = (unsigned)g.M[m]; const unsigned i = r % Mm; r /= Mm; n += (i + (unsigned)g.off[m]) * (unsigned)g.ls[m]; }
+  return n + (r + (unsigned)g.off[0]) * (unsigned)g.ls[0];
+}
+// W doubles from p: one 16-byte load where the address allows it, else two 8-byte ones
+template <int W> struct VhVec;
+template <> struct VhVec<1> {
+  typedef double T;
+  static __device__ __forceinline__ T load(const double *p) { return *p; }
+  static __device__ __forceinline__ void store(double *p, T v) { *p = v; }
+  static __device__ __forceinline__ T splat(double v) { return v; }
+};
+template <> struct VhVec<2> {
+  typedef vh2 T;
+  static __device__ __forceinline__ T load(const double *p) {
+    if (((size_t)p & 15) == 0) return *reinterpret_cast<const vh2 *>(p);
+    return (vh2){p[0], p[1]};
+  }
+  static __device__ __forceinline__ void store(double *p, T v) { *reinterpret_cast<vh2 *>(p) = v; }      // unknown-layout side: aligned by the launcher
+  static __device__ __forceinline__ T splat(double v) { return (vh2){v, v}; }
+};
+
+// The closing pass: out = c x + A at the unknown nodes (f null), or f - (c x + A) (the residual).  A: nfields full grids; cf: the c
+// field on the full grid, or null and the scalar c0; field = blockIdx.y.  W = 2: M[d-1] even, x / f / out 16-byte aligned.
+template <int W>
+__global__ __launch_bounds__(256) void k_vh_close(VhGeo geo, const double *__restrict__ A, const double *__restrict__ cf, double c0,
+                                                  const double *__restrict__ x, const double *__restrict__ f, double *__restrict__ out) {
+  typedef VhVec<W> V;
+  const unsigned per = geo.G / W;
+  const size_t fu = (size_t)blockIdx.y * geo.G, fn = (size_t)blockIdx.y * geo.N;
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < per; t += gridDim.x * 256u) {
+    const unsigned q = t * W, n = vh_node(geo, q);
+    const typename V::T c = cf ? V::load(cf + n) : V::splat(c0);
+    typename V::T v = c * V::load(x + fu + q) + V::load(A + fn + n);
+    if (f) v = V::load(f + fu + q) - v;
+    V::store(out + fu + q, v);
+  }
+}
+
+// The first step of the preconditioner: t = r / kappa at the unknown nodes, kappa read from the full grid
+template <int W>
+__global__ __launch_bounds__(256) void k_vh_over_kappa(VhGeo geo, const double *__restrict__ r, const double *__restrict__ kappa, double *__restrict__ t) {
+  typedef VhVec<W> V;
+  const unsigned per = geo.G / W;
+  const size_t fu = (size_t)blockIdx.y * geo.G;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < per; i += gridDim.x * 256u) {
+    const unsigned q = i * W;
+    V::store(t + fu + q, V::load(r + fu + q) / V::load(kappa + vh_node(geo, q)));
+  }
+}
+
+// set_coefficients: part[b] = block b's share of sum c / kappa over the unknown nodes (fixed order: the host adds the VH_RB shares in
+// turn), bad[b] = its count of full-grid nodes with kappa not finite or <= 0, or c not finite or < 0
+constexpr int VH_RB = 256;
+__global__ __launch_bounds__(256) void k_vh_coef_check(VhGeo geo, const double *__restrict__ kappa, const double *__restrict__ cf, double c0,
+                                                       double *__restrict__ part, unsigned *__restrict__ bad) {
+  __shared__ double sh[256];
+  __shared__ unsigned shb[256];
+  unsigned nb = 0;
+  for (unsigned n = blockIdx.x * 256u + threadIdx.x; n < geo.N; n += gridDim.x * 256u) {
+    const double k = kappa[n], c = cf ? cf[n] : c0;
+    if (!(k > 0.0) || !(k - k == 0.0) || !(c >= 0.0) || !(c - c == 0.0)) nb++;
+  }
+  double s = 0.0;
+  for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < geo.G; q += gridDim.x * 256u) {
+    const unsigned n = vh_node(geo, q);
+    s += (cf ? cf[n] : c0) / kappa[n];
+  }
+  sh[threadIdx.x] = s; shb[threadIdx.x] = nb;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { sh[threadIdx.x] += sh[threadIdx.x + o]; shb[threadIdx.x] += shb[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { part[blockIdx.x] = sh[0]; bad[blockIdx.x] = shb[0]; }
+}
+
+}  // namespace
+
+struct cheb_varhelm {
+  int d = 0, nf = 1;
+  int P[VMAXD] = {0}, basis[VMAXD] = {0};
+  double s2[VMAXD] = {0};                      // fl(s_k s_k): the factor of direction k is alpha = -s2[k]
+  unsigned inner[VMAXD] = {0};
+  VhGeo geo = {};
+  long N = 0, G = 0, NB = 0;
+  cheb_helmholtz *H = nullptr;                 // the preconditioner's direct solve; also the lines of the extension
+  std::map<std::pair<int, int>, DiffMat> D;    // by (extent, basis)
+  const DiffMat *Dk[VMAXD] = {nullptr};
+  double *Wf = nullptr, *Gk = nullptr, *A = nullptr;   // nf full grids each: the extension, one gradient, the sum
+  double *kap = nullptr;                       // nf stacked copies of kappa
+  double *cfield = nullptr; double c0 = 0.0; bool c_is_field = false;
+  double *tu = nullptr, *bu = nullptr, *zero = nullptr;  // nf G each: r / kappa, the solve's right-hand side, a zero vector
+  double *part = nullptr; unsigned *bad = nullptr;
+  bool have_coef = false, any_two_sweeps = false;
+  double sigma_p = 0.0;
+  chebhip_fgmres *krylov = nullptr; int krylov_restart = 0;   // made by the first solve; a solve with another restart length replaces it
+  int iterations = 0, reason = 0; double residual = 0.0;
+  size_t own_bytes = 0, krylov_bytes = 0;
+};
+
+namespace {
+
+// the fused launch takes every matrix the register-resident kernels hold: diffmat.cpp gives KS <= 32 to every line of at most 256
+// points (H = ceil(P / 2) <= 128); KS = 0 is a long line (257, 258 points here)
+bool vh_fused(const DiffMat &m) { return m.KS == 4 || m.KS == 8 || m.KS == 16 || m.KS == 32; }
+
+int vh_alloc(cheb_varhelm *h, double **p, size_t n) {
+  const size_t bytes = (n ? n : 1) * sizeof(double);
+  if (hipMalloc((void **)p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of device memory (%zu bytes)", bytes); }
+  h->own_bytes += bytes;
+  return 0;
+}
+
+template <class K, class... Args>
+void vh_launch_rows(K kern1, K kern2, bool vec, const cheb_varhelm *h, hipStream_t st, Args... args) {
+  const unsigned per = h->geo.G / (vec ? 2u : 1u);
+  const dim3 grid(grid1d(per, 256, 4096), (unsigned)h->nf);
+  hipLaunchKernelGGL(vec ? kern2 : kern1, grid, dim3(256), 0, st, h->geo, args...);
+  sweep_note_launch();
+}
+bool vh_pairs(const cheb_varhelm *h, const double *a, const double *b, const double *c) {
+  return (h->geo.M[h->d - 1] & 1) == 0 && ((((size_t)a | (size_t)b | (size_t)c) & 15) == 0);
+}
+
+// A = sum_k -s_k^2 D_k( kappa D_k W ) on nf full grids
+int vh_flux_sum(cheb_varhelm *h, const double *W, hipStream_t st) {
+  for (int k = 0; k < h->d; k++) {
+    const DiffMat &m = *h->Dk[k];
+    SweepParams sp = {};
+    sp.ncols = (unsigned)((long)h->nf * h->N / h->P[k]); sp.inner = h->inner[k];
+    sp.alpha = -h->s2[k]; sp.out = h->A;
+    if (k > 0) { sp.out_mode = OUT_ACC; sp.acc = h->A; } else sp.out_mode = OUT_STORE;
+    if (vh_fused(m)) {
+      sp.in0 = W; sp.in_mode = IN_PLAIN; sp.coef_mode = COEF_ETA; sp.in1 = h->kap;
+      HIP_TRY(fused_launch(m, sp, st));
+      continue;
+    }
+    SweepParams sg = {};
+    sg.ncols = sp.ncols; sg.inner = sp.inner; sg.in0 = W; sg.in_mode = IN_PLAIN; sg.alpha = 1.0; sg.out = h->Gk; sg.out_mode = OUT_STORE;
+    HIP_TRY(sweep_launch(m, sg, st));
+    sp.in0 = h->Gk; sp.in1 = h->kap; sp.in_mode = IN_FLUX_ETA;
+    HIP_TRY(sweep_launch(m, sp, st));
+  }
+  return 0;
+}
+
+// out = (operator at g)(x), or f - that
+int vh_operator(cheb_varhelm *h, const double *x, const double *f, const double *g, double *out, hipStream_t st) {
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  const double *W = x;                         // no wall: the unknown layout is the full grid
+  if (h->NB) { int rc = helmholtz_extend(h->H, x, g, h->Wf, st); if (rc) return rc; W = h->Wf; }
+  int rc = vh_flux_sum(h, W, st); if (rc) return rc;
+  const bool vec = vh_pairs(h, x, f, out);
+  vh_launch_rows(k_vh_close<1>, k_vh_close<2>, vec, h, st, (const double *)h->A, (const double *)(h->c_is_field ? h->cfield : nullptr), h->c0, x, f, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int vh_check_vectors(const cheb_varhelm *h, const char *what, const double *x, const double *f, const double *g, const double *out) {
+  const long n = (long)h->nf * h->G, nb = (long)h->nf * h->NB;
+  if (!x || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: NULL vector", what);
+  if (g && h->NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: g given, but every direction is periodic: there is no boundary data", what);
+  if (overlap(out, n, x, n) || (f && overlap(out, n, f, n)) || (g && overlap(out, n, g, nb)))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "%s: out may not alias x, f or g", what);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cheb_varhelm_destroy(cheb_varhelm *h) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (h->krylov) chebhip_fgmres_destroy(h->krylov);
+  if (h->H) cheb_helmholtz_destroy(h->H);
+  for (auto &kv : h->D) diffmat_destroy(&kv.second);
+  double *all[] = {h->Wf, h->Gk, h->A, h->kap, h->cfield, h->tu, h->bu, h->zero, h->part};
+  for (double *p : all) if (p) (void)hipFree(p);
+  if (h->bad) (void)hipFree(h->bad);
+  delete h;
+  return 0;
+}
+
+extern "C" int cheb_varhelm_create(int d, const int *dims, const int *basis, const double *bc, const double *scale, int nfields, cheb_varhelm **out) {
+  if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!dims || d < 1 || d > VMAXD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
+  // the argument checks, limits and lines are the direct solve's: its handle is made first (sigma 0 until set_coefficients)
+  cheb_helmholtz *H = nullptr;
+  std::vector<int> cgl(d, BASIS_CGL);
+  int rc = cheb_helmholtz_create_basis(d, dims, basis ? basis : cgl.data(), bc, scale, 0.0, nfields, &H);
+  if (rc) return rc;
+  cheb_varhelm *h = new (std::nothrow) cheb_varhelm;
+  if (!h) { cheb_helmholtz_destroy(H); return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory"); }
+  h->H = H; h->d = d; h->nf = nfields;
+  VhGeo &geo = h->geo;
+  geo.d = d;
+  long N = 1, G = 1;
+  for (int k = d - 1; k >= 0; k--) {
+    h->P[k] = dims[k]; h->basis[k] = basis ? basis[k] : BASIS_CGL;
+    const double s = scale ? scale[k] : 1.0;
+    h->s2[k] = s * s;
+    h->inner[k] = (unsigned)N;
+    geo.off[k] = h->basis[k] == BASIS_FOURIER ? 0 : 1; geo.M[k] = dims[k] - 2 * geo.off[k]; geo.ls[k] = (int)N;
+    N *= dims[k]; G *= geo.M[k];
+  }
+  h->N = N; h->G = G; h->NB = N - G; geo.N = (unsigned)N; geo.G = (unsigned)G;
+  for (int k = 0; k < d; k++) {
+    const std::pair<int, int> key(dims[k], h->basis[k]);
+    if (!h->D.count(key)) {
+      DiffMat m;
+      HIP_TRY_OR(h->basis[k] == BASIS_FOURIER ? diffmat_create_fourier(dims[k], 1, &m) : diffmat_create(dims[k], &m), cheb_varhelm_destroy(h));
+      h->D[key] = m;
+    }
+    h->Dk[k] = &h->D.at(key);
+    h->any_two_sweeps = h->any_two_sweeps || !vh_fused(*h->Dk[k]);
+  }
+  const size_t nN = (size_t)nfields * N, nG = (size_t)nfields * G;
+  if ((h->NB && (rc = vh_alloc(h, &h->Wf, nN))) || (h->any_two_sweeps && (rc = vh_alloc(h, &h->Gk, nN))) || (rc = vh_alloc(h, &h->A, nN)) ||
+      (rc = vh_alloc(h, &h->kap, nN)) || (rc = vh_alloc(h, &h->cfield, (size_t)N)) || (rc = vh_alloc(h, &h->tu, nG)) || (rc = vh_alloc(h, &h->bu, nG)) ||
+      (rc = vh_alloc(h, &h->zero, nG)) || (rc = vh_alloc(h, &h->part, VH_RB))) { cheb_varhelm_destroy(h); return rc; }
+  HIP_TRY_OR(hipMalloc((void **)&h->bad, VH_RB * sizeof(unsigned)), cheb_varhelm_destroy(h));
+  HIP_TRY_OR(hipMemset(h->zero, 0, (nG ? nG : 1) * sizeof(double)), cheb_varhelm_destroy(h));
+  *out = h;
+  return 0;
+}
+
+extern "C" long cheb_varhelm_size(const cheb_varhelm *h) { return h ? (long)h->nf * h->G : -1; }
+extern "C" long cheb_varhelm_full_size(const cheb_varhelm *h) { return h ? (long)h->nf * h->N : -1; }
+extern "C" long cheb_varhelm_boundary_size(const cheb_varhelm *h) { return h ? (long)h->nf * h->NB : -1; }
+extern "C" long cheb_varhelm_work_bytes(const cheb_varhelm *h) { return h ? (long)(h->own_bytes + h->krylov_bytes + helmholtz_work_bytes(h->H)) : -1; }
+extern "C" int cheb_varhelm_singular(const cheb_varhelm *h) { return h && h->have_coef ? cheb_helmholtz_singular(h->H) : -1; }
+extern "C" double cheb_varhelm_sigma(const cheb_varhelm *h) { return h && h->have_coef ? h->sigma_p : -1.0; }
+
+extern "C" int cheb_varhelm_set_coefficients(cheb_varhelm *h, const double *kappa_dev, const double *c_dev, double c_scalar, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!kappa_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "kappa is NULL");
+  if (!c_dev && (!(c_scalar >= 0.0) || !std::isfinite(c_scalar))) return chebhip_fail(CHEBHIP_ERR_ARG, "c = %g must be finite and >= 0", c_scalar);
+  hipStream_t st = (hipStream_t)stream;
+  // checked on the caller's arrays before anything of the handle changes: a refused call leaves the earlier coefficients in place
+  hipLaunchKernelGGL(k_vh_coef_check, dim3(VH_RB), dim3(256), 0, st, h->geo, kappa_dev, c_dev, c_scalar, h->part, h->bad);
+  HIP_TRY(hipGetLastError());
+  double part[VH_RB]; unsigned bad[VH_RB];
+  HIP_TRY(hipMemcpyAsync(part, h->part, sizeof(part), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(bad, h->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipDeviceSynchronize());               // also: no earlier solve of this handle is still reading what changes below
+  double s = 0.0; unsigned long nbad = 0;
+  for (int b = 0; b < VH_RB; b++) { s += part[b]; nbad += bad[b]; }
+  if (nbad) return chebhip_fail(CHEBHIP_ERR_ARG, "set_coefficients: %lu nodes where kappa is not finite and > 0 or c is not finite and >= 0", nbad);
+  const double sigma = h->G ? s / (double)h->G : 0.0;
+  int rc = helmholtz_set_sigma(h->H, sigma); if (rc) return rc;
+  for (int f = 0; f < h->nf; f++)
+    HIP_TRY(hipMemcpyAsync(h->kap + (size_t)f * h->N, kappa_dev, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (c_dev) HIP_TRY(hipMemcpyAsync(h->cfield, c_dev, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  h->c_is_field = c_dev != nullptr; h->c0 = c_dev ? 0.0 : c_scalar;
+  HIP_TRY(hipStreamSynchronize(st));              // the call is synchronous: the copies are complete for every stream when it returns
+  h->sigma_p = sigma; h->have_coef = true;
+  return 0;
+}
+
+extern "C" int cheb_varhelm_mult(cheb_varhelm *h, const double *x_dev, double *y_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  int rc = vh_check_vectors(h, "mult", x_dev, nullptr, nullptr, y_dev); if (rc) return rc;
+  return vh_operator(h, x_dev, nullptr, nullptr, y_dev, (hipStream_t)stream);
+}
+extern "C" int cheb_varhelm_apply(void *h, const double *x_dev, double *y_dev, void *stream) { return cheb_varhelm_mult((cheb_varhelm *)h, x_dev, y_dev, stream); }
+
+extern "C" int cheb_varhelm_residual(cheb_varhelm *h, const double *x_dev, const double *f_dev, const double *g_dev, double *out_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!f_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "residual: f is NULL");
+  int rc = vh_check_vectors(h, "residual", x_dev, f_dev, g_dev, out_dev); if (rc) return rc;
+  return vh_operator(h, x_dev, f_dev, g_dev, out_dev, (hipStream_t)stream);
+}
+
+extern "C" int cheb_varhelm_precond(void *hv, const double *r_dev, double *z_dev, void *stream) {
+  cheb_varhelm *h = (cheb_varhelm *)hv;
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!r_dev || !z_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "precond: NULL vector");
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  hipStream_t st = (hipStream_t)stream;
+  vh_launch_rows(k_vh_over_kappa<1>, k_vh_over_kappa<2>, vh_pairs(h, r_dev, h->tu, nullptr), h, st, r_dev, (const double *)h->kap, h->tu);
+  HIP_TRY(hipGetLastError());
+  return cheb_helmholtz_solve(h->H, h->tu, z_dev, stream);
+}
+
+extern "C" int cheb_varhelm_solve(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                                  double rtol, double atol, int max_it, int restart, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!f_dev || !x_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: NULL vector");
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  if (restart < 1 || max_it < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: restart = %d, max_it = %d", restart, max_it);
+  const long n = (long)h->nf * h->G, nN = (long)h->nf * h->N, nb = (long)h->nf * h->NB;
+  if (g_dev && h->NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: g given, but every direction is periodic: there is no boundary data");
+  if (overlap(x_dev, n, f_dev, n) || (g_dev && overlap(x_dev, n, g_dev, nb))) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: x may not alias f or g");
+  if (u_full_dev && (overlap(u_full_dev, nN, f_dev, n) || overlap(u_full_dev, nN, x_dev, n) || (g_dev && overlap(u_full_dev, nN, g_dev, nb))))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "solve: u_full may not alias f, g or x");
+  if (cheb_helmholtz_singular(h->H))
+    return chebhip_fail(CHEBHIP_ERR_ARG, "solve: the problem is singular (c == 0 and every direction periodic or Neumann / Neumann); mult and residual still work");
+  if (h->krylov && h->krylov_restart != restart) {          // one pair of bases at a time: at 256^3 and restart 30 they are 8 GB per field
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    chebhip_fgmres_destroy(h->krylov); h->krylov = nullptr; h->krylov_bytes = 0;
+  }
+  if (!h->krylov) {
+    int rc = chebhip_fgmres_create(n, restart, &h->krylov);
+    if (rc) { h->krylov = nullptr; return rc; }
+    h->krylov_restart = restart;
+    h->krylov_bytes = (size_t)(2 * restart + 1) * (size_t)n * sizeof(double);       // the two bases; the rest is O(restart^2)
+  }
+  chebhip_fgmres *ks = h->krylov;
+  int rc = chebhip_fgmres_set_tolerances(ks, rtol, atol, max_it); if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = vh_operator(h, h->zero, f_dev, g_dev, h->bu, st))) return rc;              // b = f - (operator at g)(0): the lift of g
+  rc = chebhip_fgmres_solve(ks, cheb_varhelm_apply, h, cheb_varhelm_precond, h, h->bu, x_dev, x_nonzero ? 1 : 0, stream);
+  h->iterations = chebhip_fgmres_iterations(ks); h->residual = chebhip_fgmres_residual(ks); h->reason = chebhip_fgmres_reason(ks);
+  if (rc) return rc;
+  if (u_full_dev) {
+    if (h->NB) return helmholtz_extend(h->H, x_dev, g_dev, u_full_dev, stream);
+    HIP_TRY(hipMemcpyAsync(u_full_dev, x_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
+extern "C" int cheb_varhelm_iterations(const cheb_varhelm *h) { return h ? h->iterations : -1; }
+extern "C" double cheb_varhelm_last_residual(const cheb_varhelm *h) { return h ? h->residual : -1.0; }
+extern "C" int cheb_varhelm_reason(const cheb_varhelm *h) { return h ? h->reason : 0; }

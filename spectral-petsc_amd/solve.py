@@ -131,6 +131,34 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     return u
 
 
+def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=None, rtol=1e-8, max_it=200, restart=30):
+    """c u - sum_k scale_k^2 d_k(kappa d_k u) = f with alpha u + beta scale_k du/dnu = g on every face (sp.VarHelmholtz's `bc`;
+    None: Dirichlet everywhere), by preconditioned FGMRES in one library call.  kappa: a full-grid device tensor (> 0); c: a scalar
+    or a full-grid device tensor (>= 0); f_full: the full-grid right-hand side (its boundary entries are ignored; a multiple of the
+    grid's size stacks fields); g: the compact boundary values or None.  The faces' conditions do not contain kappa: for Neumann
+    data of the flux kappa du/dnu divide g by kappa first.  Returns (u, iterations): the full-grid u (a new tensor) and the
+    operator applications of the solve; a solve that does not converge raises RuntimeError."""
+    dims = tuple(int(d) for d in dims)
+    N = 1
+    for n in dims:
+        N *= n
+    if f_full.numel() == 0 or f_full.numel() % N:
+        raise ValueError("f_full has %d elements, no multiple of %d" % (f_full.numel(), N))
+    op = sp.VarHelmholtz(dims, f_full.numel() // N, bc=bc, scale=scale)
+    try:
+        op.set_coefficients(kappa.contiguous().reshape(-1), c.contiguous().reshape(-1) if isinstance(c, torch.Tensor) else c)
+        inner = tuple(slice(None) if p else slice(1, -1) for p in op.periodic)
+        f = f_full.reshape((op.nfields,) + dims)[(slice(None),) + inner].contiguous().reshape(-1)
+        u = torch.empty(op.full_size, dtype=torch.float64, device=f_full.device)
+        op.solve(f, g, u_full=u, rtol=rtol, max_it=max_it, restart=restart)
+        if op.reason <= 0:
+            raise RuntimeError("variable_diffusion: FGMRES stopped with reason %d after %d iterations (residual %.3e)"
+                               % (op.reason, op.iterations, op.residual_norm))
+        return u.reshape(f_full.shape), op.iterations
+    finally:
+        op.destroy()
+
+
 def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
     """(out, phi) of sp.ChebProject(dims, nvec, bc, scale).project(u, flux=flux) with a handle made and destroyed here: u holds
     nvec * d full-grid fields, out its divergence-free projection (new tensors).  A bc entry "periodic" makes that direction periodic
