@@ -235,7 +235,7 @@ int  cheb_points_matrix_host(int n, int m, const double *x_host, double *R);
  * the exact derivative of the rational function the value rows evaluate on the rounded nodes.  Nothing divides by d_s: a point on
  * a node gets l'_j = q_j, l'_s = -sum q_k, a row of the differentiation matrix, by the same instructions.  A NaN or infinite
  * coordinate gives a row of NaN, |x| > 1 extrapolates.  cheb_points_drows: R[i][j] = l'_j(x[i]) of direction k, m x dims[k] DEVICE
- * values (k_points_drows: the lane groups, reductions and order of k_points_rows); cheb_points_dmatrix_host is its host twin, long
+ * values (k_points_rows writing derivative rows: the lane groups, reductions and order of its value rows); cheb_points_dmatrix_host is its host twin, long
  * double on the DOUBLE node table, rounded once. */
 int  cheb_points_drows(cheb_points *h, int k, const double *x_dev, long m, double *R_dev, void *stream);
 int  cheb_points_dmatrix_host(int n, int m, const double *x_host, double *R);
@@ -254,9 +254,9 @@ int  cheb_points_eval_grid_deriv(cheb_points *h, const double *u_dev, const doub
 /* The gradient in one call: out[f][c][p] = s_c d u_f / d x_c (xi[p]), c = 0 .. d-1, out nfields x d x npts; with
  * CHEB_POINTS_GRAD_VALUE out is nfields x (d + 1) x npts and component c = d holds the value, so a derivative's index does not
  * depend on the flag.  scale: d finite HOST values s_k = 2 / L_k as in cheb_grad_create, NULL = ones; one multiplication at the
- * store.  Per chunk of cheb_points_chunk / 2 points (the handle's work memory as created): k_points_drows writes both row sets,
+ * store.  Per chunk of cheb_points_chunk / 2 points (the handle's work memory as created): k_points_rows writes both row sets,
  * ONE direction-0 line product over the stacked value and derivative rows gives every point a value block and a derivative
- * block, and k_points_contract_grad walks the value block once for the value and every direction >= 1 and the derivative block
+ * block, and k_points_contract in its gradient form walks the value block once for the value and every direction >= 1 and the derivative block
  * once for direction 0, a workgroup per (field, point) and block.  d = 1: the line product's two outputs are the result.  Where the
  * work memory holds a single point, a point takes one pass of the eval pipeline per component.  No atomics, results repeat bit for
  * bit; the call allocates nothing and does not synchronise the host.  npts = 0 is a no-op; out must not overlap u. */

@@ -875,8 +875,8 @@ class ChebPoints(_Handle):
         """Points per chunk of eval: the rows and direction 0's output of one chunk are the handle's work memory."""
         return lib().cheb_points_chunk(self._h)
 
-    def rows(self, k, x, out=None):
-        """The rows l_j(x_i) of direction k for the device coordinates x: a (len(x), dims[k]) device tensor."""
+    def _rows(self, entry, k, x, out):
+        """rows and drows: the C entry's (len(x), dims[k]) device tensor of direction k's rows for the device coordinates x."""
         import torch
         if not 0 <= int(k) < len(self.dims):
             raise ChebhipError(2, "direction %d out of range 0..%d" % (int(k), len(self.dims) - 1))
@@ -884,8 +884,12 @@ class ChebPoints(_Handle):
         if out is None:
             out = torch.empty((m, n), dtype=torch.float64, device=x.device)
         if m:
-            _chk(lib().cheb_points_rows(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
+            _chk(entry(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
         return out
+
+    def rows(self, k, x, out=None):
+        """The rows l_j(x_i) of direction k for the device coordinates x: a (len(x), dims[k]) device tensor."""
+        return self._rows(lib().cheb_points_rows, k, x, out)
 
     def _deriv(self, deriv):
         """deriv as the C array of d ints (None: NULL, the plain call); values other than 0 and 1 are refused by the library."""
@@ -899,15 +903,7 @@ class ChebPoints(_Handle):
     def drows(self, k, x, out=None):
         """The rows l'_j(x_i) of the interpolant's derivative in direction k for the device coordinates x (cheb_points_drows): a
         (len(x), dims[k]) device tensor."""
-        import torch
-        if not 0 <= int(k) < len(self.dims):
-            raise ChebhipError(2, "direction %d out of range 0..%d" % (int(k), len(self.dims) - 1))
-        m, n = x.numel(), self.dims[int(k)]
-        if out is None:
-            out = torch.empty((m, n), dtype=torch.float64, device=x.device)
-        if m:
-            _chk(lib().cheb_points_drows(self._h, int(k), _dev_ptr(x, m), m, _dev_ptr(out, m * n), _stream()))
-        return out
+        return self._rows(lib().cheb_points_drows, k, x, out)
 
     def eval_grad(self, u, pts, out=None, value=False, scale=None):
         """out[f][c][p] = scale[c] d u_f / d x_c at pts[p], c < d, in one call (cheb_points_eval_grad): an (nfields, d, npts) device
@@ -941,12 +937,9 @@ class ChebPoints(_Handle):
         if out is None:
             out = torch.empty((self.nfields, npts), dtype=torch.float64, device=u.device)
         dv = self._deriv(deriv)
-        if dv is not None:
+        if npts or dv is not None:                         # (no points and no flags to refuse: nothing to call)
             _chk(lib().cheb_points_eval_deriv(self._h, _dev_ptr(u, self.size()) if npts else None, _dev_ptr(pts, npts * d) if npts else None,
                                               npts, dv, _dev_ptr(out, self.nfields * npts) if npts else None, _stream()))
-        elif npts:
-            _chk(lib().cheb_points_eval(self._h, _dev_ptr(u, self.size()), _dev_ptr(pts, npts * d), npts,
-                                        _dev_ptr(out, self.nfields * npts), _stream()))
         return out
 
     def spread(self, s, pts, out=None, accumulate=False, delta=False, deriv=None):
@@ -970,10 +963,7 @@ class ChebPoints(_Handle):
         flags = (1 if accumulate else 0) | (2 if delta else 0)                     # CHEB_SPREAD_ACCUMULATE, CHEB_SPREAD_DELTA
         dv = self._deriv(deriv)
         sp_, xp_ = (_dev_ptr(s, self.nfields * npts), _dev_ptr(pts, npts * d)) if npts else (None, None)
-        if dv is not None:
-            _chk(lib().cheb_points_spread_deriv(self._h, sp_, xp_, npts, dv, _dev_ptr(out, self.size()), flags, _stream()))
-        else:
-            _chk(lib().cheb_points_spread(self._h, sp_, xp_, npts, _dev_ptr(out, self.size()), flags, _stream()))
+        _chk(lib().cheb_points_spread_deriv(self._h, sp_, xp_, npts, dv, _dev_ptr(out, self.size()), flags, _stream()))
         return out
 
     def spread_pass(self):
@@ -1007,10 +997,7 @@ class ChebPoints(_Handle):
         xs = torch.cat([c.reshape(-1) for c in coords]) if len(coords) > 1 else coords[0].reshape(-1).contiguous()
         dv = self._deriv(deriv)
         args = (self._h, _dev_ptr(u, self.size()), _dev_ptr(xs, sum(m)) if sum(m) else None, _ints(m))
-        if dv is not None:
-            _chk(lib().cheb_points_eval_grid_deriv(*args, dv, _dev_ptr(out, nout) if nout else None, _stream()))
-        else:
-            _chk(lib().cheb_points_eval_grid(*args, _dev_ptr(out, nout) if nout else None, _stream()))
+        _chk(lib().cheb_points_eval_grid_deriv(*args, dv, _dev_ptr(out, nout) if nout else None, _stream()))
         return out
 
 

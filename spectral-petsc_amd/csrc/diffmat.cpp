@@ -1044,7 +1044,7 @@ void points_matrix_host(int n, int m, const double *x, double *R) {
   }
 }
 
-// Rows of the interpolant's derivative, l'_j(x) = d l_j / dx (cheb_points_dmatrix_host; the device twin is k_points_drows).  With
+// Rows of the interpolant's derivative, l'_j(x) = d l_j / dx (cheb_points_dmatrix_host; the device twin is k_points_rows where it writes derivative rows).  With
 // c_j = w_j / w_s, q_j = c_j / d_j, r_j = q_j d_s (j != s), R = 1 + sum r_j, Q2 = sum q_k / d_k, T = sum q_k (x_s - x_k) / d_k, the
 // sums over k != s in ascending k:
 //   l'_j = (q_j / R) ((1 + d_s^2 Q2) / R - d_s / d_j)   (j != s),     l'_s = -T / R^2

@@ -33,14 +33,16 @@
 // (v iw_0[i_0]) (iw_1[i_1] (.. iw_{d-1}[i_{d-1}])) under CHEB_SPREAD_DELTA.  No atomics: every element of `out` belongs to one lane,
 // and the order of its additions depends on (dims, nfields, npts, pass size) alone.
 //
-// First derivatives are another row per direction (k_points_drows: the derivative of the same rational function, by a formula that
-// never divides by d_s).  cheb_points_eval_deriv / _spread_deriv / _eval_grid_deriv run the pipelines above with the flagged
-// directions' rows exchanged; without a flagged direction they launch k_points_rows and give the plain calls' bits.
-// cheb_points_eval_grad takes every first derivative of a chunk of C / 2 points from ONE direction-0 line product over the stacked
-// value and derivative rows, [field][2 cnt][i_1 .. i_{d-1}], and one launch of k_points_contract_grad over the blocks it writes.
+// First derivatives are another row per direction (k_points_rows writes value rows, derivative rows or both, as its job says: the
+// derivative of the same rational function, by a formula that never divides by d_s).  cheb_points_eval_deriv / _spread_deriv /
+// _eval_grid_deriv run the pipelines above with the flagged directions' rows exchanged; the plain calls are these with no direction
+// flagged.  cheb_points_eval_grad takes every first derivative of a chunk of C / 2 points from ONE direction-0 line product over the
+// stacked value and derivative rows, [field][2 cnt][i_1 .. i_{d-1}], and one launch of k_points_contract<DC, true>, the same
+// contraction with an accumulator per component, over the blocks it writes.
 //
 // A periodic direction (cheb_points_create_basis) takes its rows, value and derivative, from k_points_frows: the
 // trigonometric interpolant in the same nearest-node form, coordinates wrapped into the period.  Everything downstream takes rows.
+// One rows job holds the entries of both bases; launch_rows runs the CGL ones, then the periodic ones.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
@@ -49,6 +51,7 @@
 #include <cmath>
 #include <map>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 using namespace chebhip;
@@ -60,14 +63,21 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int MD = 10;               // directions
 constexpr long WORK_MIN = 32L << 20; // bytes of work memory a handle may always take
 
-// one launch of k_points_rows: direction k (blockIdx.y) has m[k] coordinates x[k][i stride[k]] and writes m[k] rows of n[k]
+// one entry of a rows job: m coordinates x[i stride] of a direction of n points, m rows of n values each
+struct RowsEntry {
+  int n, lg;                         // extent; log2 of the lanes that share a row
+  int what;                          // 1 the value rows into R, 2 the derivative rows into D, 3 both
+  int periodic;                      // the rows of k_points_frows (nodes: its table), not of k_points_rows
+  unsigned m;
+  long stride;
+  const double *x, *nodes;
+  double *R, *D;
+};
+
+// the rows of a chunk, pass or grid: entry blockIdx.y of a launch.  A launch holds entries of one basis (launch_rows)
 struct RowsJob {
   int nd;
-  int n[MD], lg[MD];                 // extent; log2 of the lanes that share a row
-  unsigned m[MD];
-  long stride[MD];
-  const double *x[MD], *nodes[MD];
-  double *R[MD];
+  RowsEntry e[MD];
 };
 
 struct PtGeo {
@@ -77,63 +87,46 @@ struct PtGeo {
   unsigned rpb, B;                   // rows of n_{d-1} values per block; values per block, n_1 .. n_{d-1}
 };
 
-__global__ __launch_bounds__(256) void k_points_rows(const RowsJob g) {
-  const int k = blockIdx.y, n = g.n[k], N = n - 1, lg = g.lg[k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
-  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
-  const bool ok = row < g.m[k];
-  const double *__restrict__ xn = g.nodes[k];
-  const double x = ok ? g.x[k][(size_t)row * (size_t)g.stride[k]] : 0.0;
-
-  // the nearest node, the lowest index on a tie
-  double best = INFINITY;
-  int s = 0x7fffffff;
-  for (int j = l; j < n; j += G) { const double a = fabs(x - xn[j]); if (a < best) { best = a; s = j; } }
-  for (int mm = 1; mm < G; mm <<= 1) {
-    const double ob = __shfl_xor(best, mm);
-    const int os = __shfl_xor(s, mm);
-    if (ob < best || (ob == best && os < s)) { best = ob; s = os; }
-  }
-  const bool fin = fabs(x) < INFINITY;                     // (false for a NaN as well)
-  if (!fin) s = 0;
-  const double ds = x - xn[s], ihs = (s == 0 || s == N) ? 2.0 : 1.0;
-  auto entry = [&](int j) -> double {
-    if (j == s) return 1.0;
-    const double hj = (j == 0 || j == N) ? 0.5 : 1.0;
-    return (((j - s) & 1) ? -hj : hj) * ihs * (ds / (x - xn[j]));
-  };
-  double sum = 0.0;
-  for (int j = l; j < n; j += G) sum += entry(j);
-  for (int mm = 1; mm < G; mm <<= 1) sum += __shfl_xor(sum, mm);
-  if (!ok) return;
-  double *__restrict__ out = g.R[k] + (size_t)row * (size_t)n;
-  for (int j = l; j < n; j += G)
-    out[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : entry(j) / sum;
-}
-
-// one launch of k_points_drows: the job of k_points_rows, and per direction what to write: 1 the value rows into r.R, 2 the
-// derivative rows into D, 3 both
-struct DRowsJob {
-  RowsJob r;
-  int what[MD];
-  double *D[MD];
+// A row is built by the G = 2^lg lanes of a group, lane l of it taking the nodes l, l + G, ..: 64 / G rows a wave, four waves.
+// ok: the row exists (the lanes of a missing one take x = 0 through the shuffles and store nothing)
+struct RowLanes {
+  int n, G, l;
+  unsigned row;
+  bool ok;
+  double x;
 };
 
-// k_points_rows and the rows of the interpolant's derivative, l'_j(x) = d l_j / dx.  With c_j = w_j / w_s, q_j = c_j / d_j (j != s),
+__device__ __forceinline__ RowLanes row_lanes(const RowsEntry &e) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int G = 1 << e.lg, rpw = 64 >> e.lg, grp = lane >> e.lg;
+  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
+  const bool ok = row < e.m;
+  return RowLanes{e.n, G, lane & (G - 1), row, ok, ok ? e.x[(size_t)row * (size_t)e.stride] : 0.0};
+}
+
+// the sums over a row's lane group, by a butterfly: every lane gets them, in an order that depends on G alone (sums that are
+// ready together go through one call: their shuffles overlap)
+template <class... T>
+__device__ __forceinline__ void group_sum(int G, T &...v) {
+  for (int mm = 1; mm < G; mm <<= 1) ((v += __shfl_xor(v, mm)), ...);
+}
+
+// entry j of a value row from its unnormalised entry e: a row of NaN for a coordinate that is not finite, the exact unit row on node s
+__device__ __forceinline__ double row_value(bool fin, double ds, bool self, double e, double sum) {
+  return !fin ? __builtin_nan("") : ds == 0.0 ? (self ? 1.0 : 0.0) : e / sum;
+}
+
+// The rows of a CGL direction, values and derivatives l'_j(x) = d l_j / dx.  With c_j = w_j / w_s, q_j = c_j / d_j (j != s),
 // R = 1 + sum r_j (the value rows' normalising sum), Q2 = sum q_k / d_k and T = sum q_k ((x_s - x_k) / d_k), all sums over k != s:
 //   l'_j = (q_j / R) ((1 + d_s^2 Q2) / R - d_s / d_j)   (j != s),     l'_s = -T / R^2
 // Nothing divides by d_s; d_s == 0 gives R = 1, (x_s - x_k) / d_k = 1 exactly and the row l'_j = q_j, l'_s = -sum q_k of the
-// differentiation matrix by the same instructions.  The same lane groups, nearest-node reduction and butterflies as k_points_rows;
-// the value rows are formed by the same expressions in the same order.
-__global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
-  const int k = blockIdx.y, n = g.r.n[k], N = n - 1, lg = g.r.lg[k], what = g.what[k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
-  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
-  const bool ok = row < g.r.m[k];
-  const double *__restrict__ xn = g.r.nodes[k];
-  const double x = ok ? g.r.x[k][(size_t)row * (size_t)g.r.stride[k]] : 0.0;
+// differentiation matrix by the same instructions.  The value rows do not depend on whether the derivative rows are asked for.
+__global__ __launch_bounds__(256) void k_points_rows(const RowsJob g) {
+  const RowsEntry &e = g.e[blockIdx.y];
+  const RowLanes r = row_lanes(e);
+  const int n = r.n, N = n - 1, G = r.G, l = r.l, what = e.what;
+  const double *__restrict__ xn = e.nodes;
+  const double x = r.x;
 
   // the nearest node, the lowest index on a tie
   double best = INFINITY;
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
   };
   double sum = 0.0;
   for (int j = l; j < n; j += G) sum += entry(j);
-  for (int mm = 1; mm < G; mm <<= 1) sum += __shfl_xor(sum, mm);
+  group_sum(G, sum);
   double q2 = 0.0, t = 0.0;
   if (what & 2) {
     for (int j = l; j < n; j += G)
@@ -166,16 +159,15 @@ __global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
         q2 += q / dj;
         t += q * ((xs - xn[j]) / dj);
       }
-    for (int mm = 1; mm < G; mm <<= 1) { q2 += __shfl_xor(q2, mm); t += __shfl_xor(t, mm); }
+    group_sum(G, q2, t);
   }
-  if (!ok) return;
+  if (!r.ok) return;
   if (what & 1) {
-    double *__restrict__ out = g.r.R[k] + (size_t)row * (size_t)n;
-    for (int j = l; j < n; j += G)
-      out[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : entry(j) / sum;
+    double *__restrict__ out = e.R + (size_t)r.row * (size_t)n;
+    for (int j = l; j < n; j += G) out[j] = row_value(fin, ds, j == s, entry(j), sum);
   }
   if (what & 2) {
-    double *__restrict__ out = g.D[k] + (size_t)row * (size_t)n;
+    double *__restrict__ out = e.D + (size_t)r.row * (size_t)n;
     const double g0 = (1.0 + ds * ds * q2) / sum, ls = -t / (sum * sum);
     for (int j = l; j < n; j += G) {
       double v = ls;
@@ -188,7 +180,8 @@ __global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
 // The rows of a PERIODIC direction (cheb_points_create_basis): n nodes x_j = -1 + 2 j / n, period 2, the trigonometric
 // interpolant in its barycentric form r_j ~ (-1)^j cot(pi (x - x_j) / 2) (n even), (-1)^j / sin(pi (x - x_j) / 2) (n odd), in the
 // nearest-node form of k_points_rows: entries relative to node s, one normalising sum over the row's lane group, the same butterflies.
-// A kernel of its own, so that the CGL kernels above keep their code.  g.r.nodes[k] is the table of fourier_points_table_host.
+// The arithmetic is this kernel's own; the lane groups, the group sums and the value-row store are k_points_rows' helpers.  An
+// entry's `nodes` is the table of fourier_points_table_host.
 //   wrapping   any finite x is wrapped, never extrapolated: xr = x - 2 rint(x / 2) in [-1, 1], exact in double;
 //   s          by arithmetic, no search: the candidates rint((xr + 1) n / 2) and its two neighbours, the smallest |distance|, the
 //              lowest index on a tie; the candidate n is node 0 one period on (it serves x ~ +1);
@@ -206,14 +199,12 @@ __global__ __launch_bounds__(256) void k_points_drows(const DRowsJob g) {
 //              n even: p_j = h (-1)^m (C / S) / cos^2 a,  f_j = -h (-1)^m tan a / S^2
 //              r'_j = (f_j R + p_j - e_j F) / R^2,  r'_s = -(P + F) / R^2,  R = sum e, F = sum f, P = sum p.
 //              d_s == 0: e = f = 0, R = 1 and r'_j = p_j, r'_s = -P: row s of D_F by the same instructions.
-__global__ __launch_bounds__(256) void k_points_frows(const DRowsJob g) {
-  const int k = blockIdx.y, n = g.r.n[k], lg = g.r.lg[k], what = g.what[k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int G = 1 << lg, rpw = 64 >> lg, grp = lane >> lg, l = lane & (G - 1);
-  const unsigned row = (blockIdx.x * 4u + (unsigned)wv) * (unsigned)rpw + (unsigned)grp;
-  const bool ok = row < g.r.m[k];
-  const double *__restrict__ tab = g.r.nodes[k];
-  const double x = ok ? g.r.x[k][(size_t)row * (size_t)g.r.stride[k]] : 0.0;
+__global__ __launch_bounds__(256) void k_points_frows(const RowsJob g) {
+  const RowsEntry &en = g.e[blockIdx.y];
+  const RowLanes r = row_lanes(en);
+  const int n = r.n, G = r.G, l = r.l, what = en.what;
+  const double *__restrict__ tab = en.nodes;
+  const double x = r.x;
   const bool fin = fabs(x) < INFINITY;                     // (false for a NaN as well)
   const double xf = fin ? x : 0.0;
   const double xr = xf - 2.0 * rint(0.5 * xf);
@@ -247,17 +238,16 @@ __global__ __launch_bounds__(256) void k_points_frows(const DRowsJob g) {
     R += e;
     if (what & 2) { F += f; P += p; }
   }
-  for (int mm = 1; mm < G; mm <<= 1) R += __shfl_xor(R, mm);
-  if (what & 2)
-    for (int mm = 1; mm < G; mm <<= 1) { F += __shfl_xor(F, mm); P += __shfl_xor(P, mm); }
-  if (!ok) return;
-  double *__restrict__ outv = (what & 1) ? g.r.R[k] + (size_t)row * (size_t)n : nullptr;
-  double *__restrict__ outd = (what & 2) ? g.D[k] + (size_t)row * (size_t)n : nullptr;
+  group_sum(G, R);
+  if (what & 2) group_sum(G, F, P);
+  if (!r.ok) return;
+  double *__restrict__ outv = (what & 1) ? en.R + (size_t)r.row * (size_t)n : nullptr;
+  double *__restrict__ outd = (what & 2) ? en.D + (size_t)r.row * (size_t)n : nullptr;
   const double R2 = R * R;
   for (int j = l; j < n; j += G) {
     double e = 1.0, p = 0.0, f = 0.0;
     if (j != s) parts(j, e, p, f);
-    if (outv) outv[j] = !fin ? __builtin_nan("") : ds == 0.0 ? (j == s ? 1.0 : 0.0) : e / R;
+    if (outv) outv[j] = row_value(fin, ds, j == s, e, R);
     if (outd) outd[j] = !fin ? __builtin_nan("") : j == s ? -(P + F) / R2 : (f * R + p - e * F) / R2;
   }
 }
@@ -275,56 +265,27 @@ __device__ __forceinline__ double wave_sum(double s) {
   return s;
 }
 
-// out[f][p0 + p] = sum over the block W[f][p][i_1 .. i_{d-1}] of l_1[i_1] .. l_{d-1}[i_{d-1}] W: workgroup (p, f), 1 or 4 waves
-// (blockDim.x).  The block is rpb rows of n = n_{d-1} values; LPR lanes walk a row by pairs, a wave takes 64 / LPR rows at a
-// time, a row's weight is the product of the middle directions' entries (DC: d known at compile time, 0: any d up to MD).
-template <int DC>
-__global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const double *__restrict__ rows, unsigned C,
-                                                         const double *__restrict__ W, unsigned cnt, double *__restrict__ out,
-                                                         size_t npts) {
-  __shared__ double swl[1024];
-  __shared__ double red[4];
-  const int d = DC ? DC : g.d;
-  const unsigned n = (unsigned)g.n[d - 1];
-  const unsigned p = blockIdx.x, f = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-  const double *rl = rows + (size_t)C * g.off[d - 1] + (size_t)p * n;
-  for (unsigned j = tid; j < n; j += blockDim.x) swl[j] = rl[j];
-  __syncthreads();
-  const unsigned lpr = 1u << g.lg, rpw = 64u >> g.lg, grp = (unsigned)lane >> g.lg, l = (unsigned)lane & (lpr - 1);
-  const double *blk = W + ((size_t)f * cnt + p) * g.B;
-  double acc = 0.0;
-  for (unsigned r = (unsigned)wv * rpw + grp; r < g.rpb; r += (unsigned)nw * rpw) {
-    double wr = 1.0;
-    if (DC == 3) wr = rows[(size_t)C * g.off[1] + (size_t)p * g.n[1] + r];
-    if (DC == 0) {
-      unsigned q = r;
-      for (int m = d - 2; m >= 1; m--) {
-        const unsigned nm = (unsigned)g.n[m], i = m > 1 ? q % nm : q;
-        q /= nm;
-        wr *= rows[(size_t)C * g.off[m] + (size_t)p * nm + i];
-      }
-    }
-    const double *pr = blk + (size_t)r * n;
-    const bool al = ((size_t)pr & 15) == 0;
-    double s = 0.0;
-    for (unsigned j = 2 * l; j < n; j += 2 * lpr) {
-      const d2 a = load_pair(pr, al, j, n);
-      s += swl[j] * a.x + (j + 1 < n ? swl[j + 1] : 0.0) * a.y;
-    }
-    acc += wr * s;
-  }
-  acc = wave_sum(acc);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = red[0];
-    for (int q = 1; q < nw; q++) s += red[q];
-    out[(size_t)f * npts + p] = s;
+// The indices (i_1 .. i_{end-1}) of the flat index q over the directions 1 .. end - 1, the last one fastest: f(k, i_k) from
+// k = end - 1 down to 1.  DC: an upper bound of `end` known at compile time (the loop is unrolled, so f may keep per-direction
+// state in registers), 0: none.  k_points_spread keeps its two walks written out: through this helper the compiler schedules
+// them otherwise, and that kernel's listing is held to the instruction (profiles/points/unify_isa.txt).
+template <int DC, class F>
+__device__ __forceinline__ void unflatten(unsigned q, const int *n, int end, F f) {
+  auto step = [&](int k) {
+    const unsigned nk = (unsigned)n[k], i = k > 1 ? q % nk : q;
+    q /= nk;
+    f(k, i);
+  };
+  if (DC) {
+#pragma unroll
+    for (int k = DC - 1; k >= 1; k--)
+      if (k < end) step(k);
+  } else {
+    for (int k = end - 1; k >= 1; k--) step(k);
   }
 }
 
-struct GradArgs {
+struct ConArgs {
   const double *rows;                // direction k's value rows at rows + P off[k], its derivative rows H n_k values further
   unsigned P, H;
   const double *V, *D;               // direction 0's value and derivative blocks, (f, p) at ((f bs) + p) B; D null: none
@@ -332,33 +293,43 @@ struct GradArgs {
   double *out;                       // component c of (f, p) at out[(f nc + c) npts + p]
   size_t npts;
   int nc;                            // components per field
-  unsigned mask;                     // sums to store: bit k < d the derivative along k, bit d the value sum of V
+  unsigned mask;                     // sums to store: bit k < d the derivative along k (GRAD), bit d the value sum of V
   int vdst;                          // the component the value sum of V goes to
   double scale[MD + 1];              // per component, multiplied at the store
 };
 
-// The gradient of k_points_contract's sum: workgroup (p, f, 0) walks the value block V once, forming per block row
-// s = sum_j l_{d-1}[j] v and s' = sum_j l'_{d-1}[j] v; the value takes w s, the last direction's derivative w s', a middle direction's
-// w_k s with w the product of the middle directions' value entries and w_k the same product with direction k's derivative entry.
-// Workgroup (p, f, 1) walks the derivative block D once for direction 0's derivative, w sum_j l_{d-1}[j] v: the value sum of that
-// block (two workgroups a point: at 256^3 a chunk of 64 points is 64 MiB of blocks, which 64 workgroups read at half the rate
-// 128 do).  The pair loads, the lanes' and the waves' order are k_points_contract's.  With bit d alone in the mask and D null this
-// is k_points_contract with a scale and a component stride.
-template <int DC>
-__global__ __launch_bounds__(256) void k_points_contract_grad(const PtGeo g, const GradArgs a) {
-  constexpr int NA = (DC ? DC : MD) + 1;
-  __shared__ double swl[1024], swd[1024];
+// Workgroup (p, f), 1 or 4 waves (blockDim.x), contracts the point's block W[f][p][i_1 .. i_{d-1}] with the rows of directions
+// 1 .. d - 1.  The block is rpb rows of n = n_{d-1} values, the last direction's row is in LDS; LPR lanes walk a block row by pairs,
+// a wave takes 64 / LPR rows at a time, a row's weight w is the product of the middle directions' entries (DC: d known at compile
+// time, 0: any d up to MD).  No atomics, a fixed order of additions.
+//   GRAD false  one sum, sum_rows w sum_j l_{d-1}[j] v over V, stored as component vdst (bit d of the mask, D null): the scattered
+//               evaluation, out[f][p], and eval_grad's chunk of one point, a component a launch.  No derivative row in LDS, no
+//               derivative weights, one accumulator.
+//   GRAD true   the gradient of that sum: workgroup (p, f, 0) walks V once, forming per block row s = sum_j l_{d-1}[j] v and
+//               s' = sum_j l'_{d-1}[j] v; the value takes w s, the last direction's derivative w s', a middle direction's w_k s with
+//               w_k the product w with direction k's derivative entry.  Workgroup (p, f, 1) walks the derivative block D once for
+//               direction 0's derivative, w sum_j l_{d-1}[j] v: the value sum of that block (two workgroups a point: at 256^3 a
+//               chunk of 64 points is 64 MiB of blocks, which 64 workgroups read at half the rate 128 do).
+// The value sum is formed by the same instructions in the same order in both.
+template <int DC, bool GRAD>
+__global__ __launch_bounds__(256) void k_points_contract(const PtGeo g, const ConArgs a) {
+  constexpr int DM = DC ? DC : MD;
+  constexpr int NA = GRAD ? DM + 1 : 1;                    // accumulators: the value sum in the last, the derivative along c in acc[c]
+  __shared__ double swl[1024], swd[GRAD ? 1024 : 1];
   __shared__ double red[4][NA];
   const int d = DC ? DC : g.d;
   const unsigned n = (unsigned)g.n[d - 1];
   const unsigned p = blockIdx.x, f = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-  const bool second = blockIdx.z != 0;
-  const unsigned mask = second ? (a.mask & 1u) << d : a.D ? a.mask & ~1u : a.mask;
+  const bool second = GRAD && blockIdx.z != 0;
+  const unsigned mask = second ? (a.mask & 1u) << d : (GRAD && a.D) ? a.mask & ~1u : a.mask;
   const int vdst = second ? 0 : a.vdst;
-  const bool derivs = (mask & ((1u << d) - 2u)) != 0;      // any of directions 1 .. d - 1
+  const bool derivs = GRAD && (mask & ((1u << d) - 2u)) != 0;  // any of directions 1 .. d - 1
   const double *rl = a.rows + (size_t)a.P * g.off[d - 1] + (size_t)p * n;
-  for (unsigned j = tid; j < n; j += blockDim.x) { swl[j] = rl[j]; swd[j] = derivs ? rl[(size_t)a.H * n + j] : 0.0; }
+  for (unsigned j = tid; j < n; j += blockDim.x) {
+    swl[j] = rl[j];
+    if (GRAD) swd[j] = derivs ? rl[(size_t)a.H * n + j] : 0.0;
+  }
   __syncthreads();
   const unsigned lpr = 1u << g.lg, rpw = 64u >> g.lg, grp = (unsigned)lane >> g.lg, l = (unsigned)lane & (lpr - 1);
   const double *bv = (second ? a.D : a.V) + ((size_t)f * a.bs + p) * g.B;
@@ -367,34 +338,29 @@ __global__ __launch_bounds__(256) void k_points_contract_grad(const PtGeo g, con
   for (int c = 0; c < NA; c++) acc[c] = 0.0;
   for (unsigned r = (unsigned)wv * rpw + grp; r < g.rpb; r += (unsigned)nw * rpw) {
     double wr = 1.0, wk[NA];                               // wk[m]: the weight with direction m's derivative entry, 1 <= m <= d - 2
-    if (DC == 3) {
-      wr = a.rows[(size_t)a.P * g.off[1] + (size_t)p * g.n[1] + r];
-      wk[1] = derivs ? a.rows[(size_t)a.P * g.off[1] + (size_t)(a.H + p) * g.n[1] + r] : 0.0;
-    }
-    if (DC == 0) {
-      unsigned q = r;
 #pragma unroll
-      for (int m = 1; m < MD; m++) wk[m] = 1.0;
-      for (int m = d - 2; m >= 1; m--) {
-        const unsigned nm = (unsigned)g.n[m], i = m > 1 ? q % nm : q;
-        q /= nm;
-        const size_t e = (size_t)a.P * g.off[m] + (size_t)p * nm + i;
-        const double lv = a.rows[e], ld = derivs ? a.rows[e + (size_t)a.H * nm] : 0.0;
-        wr *= lv;
+    for (int c = 0; c < NA; c++) wk[c] = 1.0;
+    unflatten<DC>(r, g.n, d - 1, [&](int m, unsigned i) {
+      const unsigned nm = (unsigned)g.n[m];
+      const size_t e = (size_t)a.P * g.off[m] + (size_t)p * nm + i;
+      const double lv = a.rows[e];
+      wr *= lv;
+      if (GRAD) {
+        const double ld = derivs ? a.rows[e + (size_t)a.H * nm] : 0.0;
 #pragma unroll
-        for (int c = 1; c < MD - 1; c++)
+        for (int c = 1; c < NA - 2; c++)
           if (c < d - 1) wk[c] *= c == m ? ld : lv;
       }
-    }
+    });
     const double *pr = bv + (size_t)r * n;
     const bool al = ((size_t)pr & 15) == 0;
     double s = 0.0, sd = 0.0;
     for (unsigned j = 2 * l; j < n; j += 2 * lpr) {
       const d2 v = load_pair(pr, al, j, n);
       s += swl[j] * v.x + (j + 1 < n ? swl[j + 1] : 0.0) * v.y;
-      sd += swd[j] * v.x + (j + 1 < n ? swd[j + 1] : 0.0) * v.y;
+      if (GRAD) sd += swd[j] * v.x + (j + 1 < n ? swd[j + 1] : 0.0) * v.y;
     }
-    acc[NA - 1] += wr * s;                                 // the block's value sum; acc[c], 1 <= c < d: the derivative along c
+    acc[NA - 1] += wr * s;
 #pragma unroll
     for (int c = 1; c < NA - 1; c++)
       if (c < d) acc[c] += c == d - 1 ? wr * sd : wk[c] * s;
@@ -579,81 +545,67 @@ int rows_lg(int n) {                 // log2 of the power of two >= n, at most 6
   return lg;
 }
 
+// The rows of a job: its CGL entries as one launch of k_points_rows, then its periodic ones as one launch of k_points_frows.  An
+// entry is self-contained, so a launch takes the entries of its basis, in their order, as a job of their own; a basis with no
+// entry, or with no coordinate, launches nothing.
 int launch_rows(const RowsJob &job, hipStream_t st, const char *what) {
-  unsigned gx = 0;
-  for (int k = 0; k < job.nd; k++) {
-    const unsigned rpb = 4u * (64u >> job.lg[k]);
-    gx = std::max(gx, (job.m[k] + rpb - 1) / rpb);
+  for (int periodic = 0; periodic < 2; periodic++) {
+    RowsJob part{};
+    unsigned gx = 0;
+    for (int i = 0; i < job.nd; i++) {
+      const RowsEntry &e = job.e[i];
+      if ((e.periodic != 0) != (periodic != 0)) continue;
+      part.e[part.nd++] = e;
+      const unsigned rpb = 4u * (64u >> e.lg);
+      gx = std::max(gx, (e.m + rpb - 1) / rpb);
+    }
+    if (gx == 0) continue;
+    void (*const kernel)(const RowsJob) = periodic ? k_points_frows : k_points_rows;
+    hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)part.nd), dim3(256), 0, st, part);
+    sweep_note_launch();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+      return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s %srows launch: %s", what, periodic ? "periodic " : "", hipGetErrorString(e));
   }
-  if (gx == 0) return 0;
-  hipLaunchKernelGGL(k_points_rows, dim3(gx, (unsigned)job.nd), dim3(256), 0, st, job);
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s rows launch: %s", what, hipGetErrorString(e));
-}
-
-int launch_drows(const DRowsJob &job, hipStream_t st, const char *what) {
-  unsigned gx = 0;
-  for (int k = 0; k < job.r.nd; k++) {
-    const unsigned rpb = 4u * (64u >> job.r.lg[k]);
-    gx = std::max(gx, (job.r.m[k] + rpb - 1) / rpb);
-  }
-  if (gx == 0) return 0;
-  hipLaunchKernelGGL(k_points_drows, dim3(gx, (unsigned)job.r.nd), dim3(256), 0, st, job);
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s derivative rows launch: %s", what, hipGetErrorString(e));
-}
-
-int launch_frows(const DRowsJob &job, hipStream_t st, const char *what) {
-  unsigned gx = 0;
-  for (int k = 0; k < job.r.nd; k++) {
-    const unsigned rpb = 4u * (64u >> job.r.lg[k]);
-    gx = std::max(gx, (job.r.m[k] + rpb - 1) / rpb);
-  }
-  if (gx == 0) return 0;
-  hipLaunchKernelGGL(k_points_frows, dim3(gx, (unsigned)job.r.nd), dim3(256), 0, st, job);
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s periodic rows launch: %s", what, hipGetErrorString(e));
-}
-
-// A job whose entries may be periodic directions (fb[i] != 0 for entry i; null: none).  The CGL entries run as the launch they
-// have always been (k_points_rows where `plain`: every what is 1; k_points_drows otherwise), the periodic ones as one launch of
-// k_points_frows; an entry is self-contained, so each kernel gets its entries as a compact job.
-int launch_rows_basis(const DRowsJob &job, bool plain, const int *fb, hipStream_t st, const char *what) {
-  bool any = false;
-  for (int i = 0; fb && i < job.r.nd; i++) any = any || fb[i];
-  if (!any) return plain ? launch_rows(job.r, st, what) : launch_drows(job, st, what);
-  DRowsJob part[2] = {};
-  for (int i = 0; i < job.r.nd; i++) {
-    DRowsJob &t = part[fb[i] ? 1 : 0];
-    const int o = t.r.nd++;
-    t.r.n[o] = job.r.n[i]; t.r.lg[o] = job.r.lg[i]; t.r.m[o] = job.r.m[i]; t.r.stride[o] = job.r.stride[i];
-    t.r.x[o] = job.r.x[i]; t.r.nodes[o] = job.r.nodes[i]; t.r.R[o] = job.r.R[i];
-    t.what[o] = job.what[i]; t.D[o] = job.D[i];
-  }
-  int rc = 0;
-  if (part[0].r.nd) rc = plain ? launch_rows(part[0].r, st, what) : launch_drows(part[0], st, what);
-  if (!rc) rc = launch_frows(part[1], st, what);
-  return rc;
-}
-
-// The rows of one chunk, pass or grid.  Without a derivative direction this is today's k_points_rows launch; otherwise
-// k_points_drows writes a flagged direction's derivative rows where its value rows would go.
-int launch_rows_deriv(const RowsJob &job, const int *deriv, const int *fb, hipStream_t st, const char *what) {
-  bool any = false;
-  for (int k = 0; deriv && k < job.nd; k++) any = any || deriv[k];
-  DRowsJob dj{};
-  dj.r = job;
-  for (int k = 0; k < job.nd; k++) { dj.what[k] = any && deriv[k] ? 2 : 1; dj.D[k] = job.R[k]; }
-  return launch_rows_basis(dj, !any, fb, st, what);
+  return 0;
 }
 
 // a multi-index of first derivatives: d host ints, each 0 or 1; NULL = all zero
 int check_deriv(int d, const int *deriv, const char *what) {
   for (int k = 0; deriv && k < d; k++)
     if (deriv[k] != 0 && deriv[k] != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "%s: deriv[%d] = %d must be 0 or 1", what, k, deriv[k]);
+  return 0;
+}
+
+// fn(std::integral_constant<int, DC>) for the kernels' template argument DC: d where a kernel is built for it (1 .. 3), 0 above
+template <class F>
+void dispatch_dc(int d, F fn) {
+  switch (d) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    default: fn(std::integral_constant<int, 0>{});
+  }
+}
+
+// one launch of the contraction (d >= 2: at d = 1 the line product's output is the result)
+template <bool GRAD>
+void contract_launch(int d, dim3 grid, dim3 block, hipStream_t st, const PtGeo &g, const ConArgs &a) {
+  dispatch_dc(d, [&](auto dc) {
+    constexpr int DC = decltype(dc)::value > 1 ? decltype(dc)::value : 0;
+    hipLaunchKernelGGL((k_points_contract<DC, GRAD>), grid, block, 0, st, g, a);
+  });
+  sweep_note_launch();
+}
+
+// what the three *_matrix_host entries check after n, and their work: fill() writes the m rows
+template <class F>
+int matrix_host(int m, int deriv, const double *x, const double *R, F fill) {
+  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
+  if (deriv != 0 && deriv != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "deriv = %d must be 0 or 1", deriv);
+  if (m == 0) return 0;
+  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
+  fill();
   return 0;
 }
 
@@ -678,6 +630,28 @@ struct cheb_points {
   double *gwork[2] = {nullptr, nullptr};     // ping-pong intermediates
 };
 
+namespace {
+// direction k's entry of a rows job: the value rows of the m coordinates x[i stride] into R
+RowsEntry rows_entry(const cheb_points *h, int k, const double *x, long stride, unsigned m, double *R) {
+  const int n = h->geo.n[k];
+  return RowsEntry{n, rows_lg(n), 1, h->basis[k] != CHEB_BASIS_CGL, m, stride, x, h->table(k), R, R};
+}
+
+// the rows job of a chunk of cnt scattered points xi[p][k]: direction k's rows at base + cap off[k]
+RowsJob chunk_job(const cheb_points *h, const double *xi, unsigned cnt, double *base, size_t cap) {
+  RowsJob job{};
+  job.nd = h->d;
+  for (int k = 0; k < h->d; k++) job.e[k] = rows_entry(h, k, xi + k, h->d, cnt, base + cap * h->geo.off[k]);
+  return job;
+}
+
+// a flagged direction's derivative rows where its value rows would go (deriv null: none flagged)
+void job_deriv(RowsJob &job, const int *deriv) {
+  for (int k = 0; deriv && k < job.nd; k++)
+    if (deriv[k]) { job.e[k].what = 2; job.e[k].D = job.e[k].R; }
+}
+}  // namespace
+
 extern "C" int cheb_nodes_host(int n, double *x) {
   int rc;
   if ((rc = check_extent(n))) return rc;
@@ -689,11 +663,7 @@ extern "C" int cheb_nodes_host(int n, double *x) {
 extern "C" int cheb_points_matrix_host(int n, int m, const double *x, double *R) {
   int rc;
   if ((rc = check_extent(n))) return rc;
-  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
-  if (m == 0) return 0;
-  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  points_matrix_host(n, m, x, R);
-  return 0;
+  return matrix_host(m, 0, x, R, [&] { points_matrix_host(n, m, x, R); });
 }
 
 namespace {
@@ -793,50 +763,37 @@ extern "C" int cheb_points_create_basis(int d, const int *dims, int nfields, con
 extern "C" int cheb_points_fourier_matrix_host(int n, int m, const double *x, int deriv, double *R) {
   if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d: a periodic direction needs at least 2 points", n);
   if (n > 256) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: a periodic direction supports at most 256 points", n);
-  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
-  if (deriv != 0 && deriv != 1) return chebhip_fail(CHEBHIP_ERR_ARG, "deriv = %d must be 0 or 1", deriv);
-  if (m == 0) return 0;
-  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  fourier_points_matrix_host(n, m, x, deriv, R);
-  return 0;
+  return matrix_host(m, deriv, x, R, [&] { fourier_points_matrix_host(n, m, x, deriv, R); });
 }
 
 extern "C" long cheb_points_chunk(const cheb_points *h) { return h ? (long)h->C : -1; }
 
-extern "C" int cheb_points_rows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
+// cheb_points_rows (deriv 0) and cheb_points_drows (deriv 1): the m rows of direction k into R
+static int rows_run(cheb_points *h, int k, const double *x, long m, int deriv, double *R, void *stream) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
   if (m < 0 || m >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %ld must be in 0..2^31-1", m);
   if (m == 0) return 0;
   if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
   RowsJob job{};
-  const int n = h->geo.n[k];
-  job.nd = 1; job.n[0] = n; job.lg[0] = rows_lg(n); job.m[0] = (unsigned)m; job.stride[0] = 1;
-  job.x[0] = x; job.nodes[0] = h->table(k); job.R[0] = R;
-  return launch_rows_deriv(job, nullptr, &h->basis[k], (hipStream_t)stream, "points");
+  job.nd = 1;
+  job.e[0] = rows_entry(h, k, x, 1, (unsigned)m, R);
+  job_deriv(job, &deriv);
+  return launch_rows(job, (hipStream_t)stream, "points");
+}
+
+extern "C" int cheb_points_rows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
+  return rows_run(h, k, x, m, 0, R, stream);
 }
 
 extern "C" int cheb_points_drows(cheb_points *h, int k, const double *x, long m, double *R, void *stream) {
-  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
-  if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
-  if (m < 0 || m >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %ld must be in 0..2^31-1", m);
-  if (m == 0) return 0;
-  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  DRowsJob job{};
-  const int n = h->geo.n[k];
-  job.r.nd = 1; job.r.n[0] = n; job.r.lg[0] = rows_lg(n); job.r.m[0] = (unsigned)m; job.r.stride[0] = 1;
-  job.r.x[0] = x; job.r.nodes[0] = h->table(k); job.what[0] = 2; job.D[0] = R;
-  return launch_rows_basis(job, false, &h->basis[k], (hipStream_t)stream, "points");
+  return rows_run(h, k, x, m, 1, R, stream);
 }
 
 extern "C" int cheb_points_dmatrix_host(int n, int m, const double *x, double *R) {
   int rc;
   if ((rc = check_extent(n))) return rc;
-  if (m < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "m = %d is negative", m);
-  if (m == 0) return 0;
-  if (!x || !R) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
-  points_dmatrix_host(n, m, x, R);
-  return 0;
+  return matrix_host(m, 0, x, R, [&] { points_dmatrix_host(n, m, x, R); });
 }
 
 namespace {
@@ -851,15 +808,14 @@ int eval_run(cheb_points *h, const double *u, const double *xi, long npts, const
   const int d = h->d;
   const long C = h->C;
   int rc;
+  ConArgs a{};                                             // the contraction's one sum, out[f][p]
+  a.rows = h->rows; a.P = (unsigned)C; a.V = h->W; a.npts = (size_t)npts; a.nc = 1; a.mask = 1u << d;
+  for (double &s : a.scale) s = 1.0;
   for (long p0 = 0; p0 < npts; p0 += C) {
     const unsigned cnt = (unsigned)std::min(C, npts - p0);
-    RowsJob job{};
-    job.nd = d;
-    for (int k = 0; k < d; k++) {
-      job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
-      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->table(k); job.R[k] = h->rows + (size_t)C * g.off[k];
-    }
-    if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "eval"))) return rc;
+    RowsJob job = chunk_job(h, xi + (size_t)p0 * d, cnt, h->rows, (size_t)C);
+    job_deriv(job, deriv);
+    if ((rc = launch_rows(job, st, "eval"))) return rc;
     // d == 1: the line product's [field][point] is the result where it is one chunk or one field
     const bool direct = d == 1 && (h->nf == 1 || cnt == npts);
     ResampleDir p{h->rows, u, direct ? out + p0 : h->W, (unsigned)h->nf, (unsigned)g.n[0], cnt, g.B, (unsigned)h->nf * g.B};
@@ -873,11 +829,8 @@ int eval_run(cheb_points *h, const double *u, const double *xi, long npts, const
       }
       continue;
     }
-    const dim3 grid(cnt, (unsigned)h->nf), block(g.B <= 1024 ? 64 : 256);
-#define POINTS_CON(DC) hipLaunchKernelGGL(k_points_contract<DC>, grid, block, 0, st, g, h->rows, (unsigned)C, h->W, cnt, out + p0, (size_t)npts)
-    switch (d) { case 2: POINTS_CON(2); break; case 3: POINTS_CON(3); break; default: POINTS_CON(0); }
-#undef POINTS_CON
-    sweep_note_launch();
+    a.bs = cnt; a.out = out + p0;
+    contract_launch<false>(d, dim3(cnt, (unsigned)h->nf), dim3(g.B <= 1024 ? 64 : 256), st, g, a);
     e = hipGetLastError();
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval contraction launch: %s", hipGetErrorString(e));
   }
@@ -897,15 +850,6 @@ extern "C" int cheb_points_eval_deriv(cheb_points *h, const double *u, const dou
   return eval_run(h, u, xi, npts, deriv, out, stream);
 }
 
-namespace {
-void grad_contract_launch(int d, dim3 grid, dim3 block, hipStream_t st, const PtGeo &g, const GradArgs &a) {
-#define POINTS_GRAD(DC) hipLaunchKernelGGL(k_points_contract_grad<DC>, grid, block, 0, st, g, a)
-  switch (d) { case 2: POINTS_GRAD(2); break; case 3: POINTS_GRAD(3); break; default: POINTS_GRAD(0); }
-#undef POINTS_GRAD
-  sweep_note_launch();
-}
-}  // namespace
-
 extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const double *xi, long npts, const double *scale, int flags,
                                      double *out, void *stream) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
@@ -922,7 +866,7 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
   const long C = h->C, H = C / 2;                          // a gradient chunk: half an eval chunk, two row sets and two blocks a point
   const unsigned nf = (unsigned)h->nf;
   int rc;
-  GradArgs a{};
+  ConArgs a{};
   a.rows = h->rows; a.out = out; a.npts = (size_t)npts; a.nc = nc;
   for (int k = 0; k <= MD; k++) a.scale[k] = (scale && k < d) ? scale[k] : 1.0;
   const dim3 block(g.B <= 1024 ? 64 : 256);
@@ -934,19 +878,14 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
     a.P = 1; a.H = 0; a.V = h->W; a.D = nullptr; a.bs = 1; a.mask = 1u << d;
     for (long p = 0; p < npts; p++)
       for (int c = 0; c < nc; c++) {
-        DRowsJob job{};
-        job.r.nd = d;
-        for (int k = 0; k < d; k++) {
-          job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = 1; job.r.stride[k] = d;
-          job.r.x[k] = xi + (size_t)p * d + k; job.r.nodes[k] = h->table(k);
-          job.r.R[k] = job.D[k] = h->rows + g.off[k]; job.what[k] = k == c ? 2 : 1;
-        }
-        if ((rc = launch_rows_basis(job, false, h->basis, st, "eval_grad"))) return rc;
+        RowsJob job = chunk_job(h, xi + (size_t)p * d, 1u, h->rows, 1);
+        if (c < d) job.e[c].what = 2;
+        if ((rc = launch_rows(job, st, "eval_grad"))) return rc;
         ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 1u, g.B, nf * g.B};
         hipError_t e = resample_launch(lp, st);
         if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
         a.out = out + p; a.vdst = c;
-        grad_contract_launch(d, dim3(1, nf), block, st, g, a);
+        contract_launch<false>(d, dim3(1, nf), block, st, g, a);
         e = hipGetLastError();
         if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
       }
@@ -958,15 +897,9 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
     const unsigned cnt = (unsigned)std::min(H, npts - p0);
     // direction 0: cnt value rows, then cnt derivative rows, one matrix of 2 cnt rows; direction k >= 1: its value rows at
     // rows + 2 H off[k], its derivative rows H n_k values further
-    DRowsJob job{};
-    job.r.nd = d;
-    for (int k = 0; k < d; k++) {
-      job.r.n[k] = g.n[k]; job.r.lg[k] = rows_lg(g.n[k]); job.r.m[k] = cnt; job.r.stride[k] = d;
-      job.r.x[k] = xi + (size_t)p0 * d + k; job.r.nodes[k] = h->table(k); job.what[k] = 3;
-      job.r.R[k] = h->rows + (size_t)(2 * H) * g.off[k];
-      job.D[k] = job.r.R[k] + (size_t)(k == 0 ? cnt : H) * g.n[k];
-    }
-    if ((rc = launch_rows_basis(job, false, h->basis, st, "eval_grad"))) return rc;
+    RowsJob job = chunk_job(h, xi + (size_t)p0 * d, cnt, h->rows, (size_t)(2 * H));
+    for (int k = 0; k < d; k++) { job.e[k].what = 3; job.e[k].D = job.e[k].R + (size_t)(k == 0 ? cnt : H) * g.n[k]; }
+    if ((rc = launch_rows(job, st, "eval_grad"))) return rc;
     ResampleDir lp{h->rows, u, h->W, nf, (unsigned)g.n[0], 2 * cnt, g.B, nf * g.B};
     hipError_t e = resample_launch(lp, st);
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
@@ -976,7 +909,7 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
       sweep_note_launch();
     } else {
       a.V = h->W; a.D = h->W + (size_t)cnt * g.B; a.bs = 2 * cnt; a.out = out + p0;
-      grad_contract_launch(d, dim3(cnt, nf, 2), block, st, g, a);
+      contract_launch<true>(d, dim3(cnt, nf, 2), block, st, g, a);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
@@ -1016,9 +949,7 @@ int spread_weights(cheb_points *h) {             // the inverse quadrature weigh
 template <int BM>
 void spread_launch(int d, const PtGeo &g, const SpreadArgs &a, hipStream_t st) {
   const dim3 grid((a.L + RS_BN - 1) / RS_BN, ((unsigned)g.n[0] + BM - 1) / BM);
-#define POINTS_SPREAD(DC) hipLaunchKernelGGL((k_points_spread<DC, BM>), grid, dim3(256), 0, st, g, a)
-  switch (d) { case 1: POINTS_SPREAD(1); break; case 2: POINTS_SPREAD(2); break; case 3: POINTS_SPREAD(3); break; default: POINTS_SPREAD(0); }
-#undef POINTS_SPREAD
+  dispatch_dc(d, [&](auto dc) { hipLaunchKernelGGL((k_points_spread<decltype(dc)::value, BM>), grid, dim3(256), 0, st, g, a); });
 }
 }  // namespace
 
@@ -1047,13 +978,9 @@ int spread_run(cheb_points *h, const double *s, const double *xi, long npts, con
   const SpreadPass sp = spread_pass(h);
   for (long p0 = 0; p0 < npts; p0 += sp.P) {
     const unsigned cnt = (unsigned)std::min(sp.P, npts - p0);
-    RowsJob job{};
-    job.nd = d;
-    for (int k = 0; k < d; k++) {
-      job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = cnt; job.stride[k] = d;
-      job.x[k] = xi + (size_t)p0 * d + k; job.nodes[k] = h->table(k); job.R[k] = sp.buf + (size_t)sp.P * g.off[k];
-    }
-    if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "spread"))) return rc;
+    RowsJob job = chunk_job(h, xi + (size_t)p0 * d, cnt, sp.buf, (size_t)sp.P);
+    job_deriv(job, deriv);
+    if ((rc = launch_rows(job, st, "spread"))) return rc;
     const SpreadArgs a{sp.buf, s + p0, (flags & CHEB_SPREAD_DELTA) ? h->iw : nullptr, out, (size_t)npts,
                        (unsigned)sp.P, cnt, (unsigned)h->nf * g.B, g.B, (accumulate || p0 > 0) ? 1 : 0};
     if (g.n[0] > 64) spread_launch<128>(d, g, a, st); else spread_launch<64>(d, g, a, st);
@@ -1117,12 +1044,10 @@ int grid_run(cheb_points *h, const double *u, const double *coords, const int *m
   RowsJob job{};
   job.nd = d;
   size_t co = 0;
-  for (int k = 0; k < d; co += m[k], k++) {
-    job.n[k] = g.n[k]; job.lg[k] = rows_lg(g.n[k]); job.m[k] = (unsigned)m[k]; job.stride[k] = 1;
-    job.x[k] = coords + co; job.nodes[k] = h->table(k); job.R[k] = h->grows + h->goff[k];
-  }
+  for (int k = 0; k < d; co += m[k], k++) job.e[k] = rows_entry(h, k, coords + co, 1, (unsigned)m[k], h->grows + h->goff[k]);
+  job_deriv(job, deriv);
   int rc;
-  if ((rc = launch_rows_deriv(job, deriv, h->basis, st, "eval_grid"))) return rc;
+  if ((rc = launch_rows(job, st, "eval_grid"))) return rc;
   int order[MD];
   long cur[MD];
   for (int k = 0; k < d; k++) { order[k] = k; cur[k] = g.n[k]; }

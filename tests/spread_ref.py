@@ -73,7 +73,7 @@ def worst_ratio(g, t, B, c):
 
 # ---- the float64 model of the device algorithm ----------------------------------------------------------------------------------
 def rows_f64(n, x):
-    """k_points_rows in numpy double (the sum in ascending j)."""
+    """The value rows of k_points_rows in numpy double (the sum in ascending j)."""
     xn = sp.cgl_nodes(n)
     x = np.asarray(x, dtype=np.float64).ravel()
     N, m = n - 1, x.size

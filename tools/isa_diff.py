@@ -44,7 +44,8 @@ def demangle(names):
     for tool in ('llvm-cxxfilt', 'c++filt'):
         try:
             r = subprocess.run([tool], input='\n'.join(names), capture_output=True, text=True, check=True)
-            return dict(zip(names, r.stdout.split('\n')))
+            # (the parentheses of an unnamed namespace would end the name where the parameter list is cut off)
+            return dict(zip(names, r.stdout.replace('(anonymous namespace)::', '').split('\n')))
         except Exception:
             pass
     return {n: n for n in names}
