@@ -200,7 +200,8 @@ def fgmres(A, M, b, x0, restart, max_it, rtol=1e-300, atol=1e-50, exact=False, d
     """chebhip_fgmres_solve in `dt` arithmetic: the one-reduction classical Gram-Schmidt with carried rn (exact: the three-launch
     step), the clamp of e2 at 1e-12 w.w, the estimated h_{j+1,j} on a cycle's last column, the Givens solve, x += Z y.
     A(x) and M(v) work in dt; x0 None is the zero guess that is never stored.  fault: a key of FAULTS (trip: elements of fault b's
-    first trip).  Returns dict(x, its, reason, rnorm, last_est, trace)."""
+    first trip).  Returns dict(x, its, reason, rnorm, last_est, trace, tol, hist): hist holds every residual norm the solve compared
+    with tol, in order (a cycle's start residual, then one per column)."""
     b = np.asarray(b, dtype=dt)
     n, m = b.size, restart
     one, zero, D = dt(1), dt(0), dt(dup)
@@ -220,6 +221,7 @@ def fgmres(A, M, b, x0, restart, max_it, rtol=1e-300, atol=1e-50, exact=False, d
     x = None if x0 is None else np.array(x0, dtype=dt)
     its, reason, first, rnorm, last_est = 0, 0, True, zero, False
     tr = dict(bnsq=bnsq, cycles=[])
+    hist = []
     while True:
         ax = rnsq = None
         if first and x is None:
@@ -231,6 +233,7 @@ def fgmres(A, M, b, x0, restart, max_it, rtol=1e-300, atol=1e-50, exact=False, d
             beta = np.sqrt(D * rnsq)
         first = False
         rnorm = beta
+        hist.append(beta)
         cyc = dict(ax=ax, rnsq=rnsq, steps=[])
         tr["cycles"].append(cyc)
         if not beta == beta:
@@ -318,6 +321,7 @@ def fgmres(A, M, b, x0, restart, max_it, rtol=1e-300, atol=1e-50, exact=False, d
                 reason, kk, stop = -9, j, True
             else:
                 kk, rnorm = j + 1, res
+                hist.append(res)
                 if res <= tol or its + kk >= max_it:
                     stop = True
         last_est = (not exact) and kk > 0 and not (kk < m and its + kk < max_it)
@@ -344,7 +348,7 @@ def fgmres(A, M, b, x0, restart, max_it, rtol=1e-300, atol=1e-50, exact=False, d
             break
     if x is None:
         x = np.zeros(n, dtype=dt)
-    return dict(x=x, its=its, reason=reason, rnorm=rnorm, last_est=last_est, trace=tr if trace else None)
+    return dict(x=x, its=its, reason=reason, rnorm=rnorm, last_est=last_est, trace=tr if trace else None, tol=tol, hist=hist)
 
 
 def solve_ratios(x, x_ld, x_rest):

@@ -188,5 +188,7 @@ def test_saddle_inner_layouts_agree(dims, kind):
         ys.append(pc.apply(x, torch.empty(st.global_size, dtype=torch.float64, device="cuda")).cpu().numpy())
         its = pc.inner_iterations
         pc.destroy()
+        # velocity iterations summed over the applies of KSPVelocity (two for type 0, one otherwise), Schur iterations (README:43)
+        assert 0 < its[0] <= (2 if kind == 0 else 1) * 4 and 0 < its[1] <= 3, its
     assert relerr(ys[0], ys[1]) < 1e-9, relerr(ys[0], ys[1])
     st.destroy()
