@@ -1200,6 +1200,62 @@ int  cheb_varhelm_iterations(const cheb_varhelm *h);      /* of the last solve, 
 double cheb_varhelm_last_residual(const cheb_varhelm *h);
 int  cheb_varhelm_reason(const cheb_varhelm *h);
 
+/* The deflated solve of a singular handle.  With c == 0 and every direction periodic or Neumann / Neumann the null
+ * space of mult is known for any kappa: the products over the directions of the constant and, on a periodic direction of even
+ * extent, the Nyquist vector (-1)^j -- q = 2^(even periodic directions) mutually orthogonal vectors z_1 .. z_q of +-1 in the
+ * unknown layout, N = [z_1 .. z_q], N^T N = G I (G unknowns per field).  Pi = I - N N^T / G, per stacked field.
+ * cheb_varhelm_solve_deflated returns x with N^T x = 0 and Pi (b - A x) = 0, b = residual(0, f, g): FGMRES on v -> Pi A v from
+ * Pi b and the guess Pi x, right preconditioner r -> Pi H(0)^-1 (r / kappa), one last Pi on x, u_full the extension of that x.
+ * What is left of b - A x is N lambda, the source the discrete problem cannot balance (collocation has no exact compatibility
+ * condition).  iterations, last_residual and reason are those of the projected system: |Pi (b - A x)| against rtol |Pi b|.
+ * On a nonsingular handle the call is cheb_varhelm_solve: the same launches, the same bits.  More than three even periodic
+ * directions (q > 8): CHEBHIP_ERR_ARG.  Arguments, aliasing rules and the Krylov bases as cheb_varhelm_solve. */
+int  cheb_varhelm_solve_deflated(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                                 double rtol, double atol, int max_it, int restart, void *stream);
+/* q of the handle as its coefficients stand: 0 where it is not singular; -1: NULL, no coefficients yet, or q > 8 */
+int  cheb_varhelm_null_count(const cheb_varhelm *h);
+/* lambda = N^T (b - A x) / G of the last deflated solve of a singular problem, nfields x q values to the HOST; from one residual
+ * at the end of that solve.  Synchronises the device.  CHEBHIP_ERR_ARG where no such solve has run. */
+int  cheb_varhelm_defect(cheb_varhelm *h, double *out);
+/* The null vectors of a geometry (HOST, no device): flags[j], j < q, has bit k set where vector j alternates, (-1)^index, in
+ * direction k; flags[0] = 0 is the constant, and vector j's directions are the bits of j over the even periodic directions in
+ * ascending order.  flags: 8 ints.  Returns q, or -CHEBHIP_ERR_ARG with the error set (q > 8 among the reasons). */
+int  cheb_varhelm_null_signs_host(int d, const int *dims, const int *basis, int *flags);
+/* out = Pi in, three launches and no allocation: the q signed sums and sum |in| per field as block shares in a fixed order, their
+ * totals, the subtraction.  A field whose every |z_j^T in| is at most (q + 4) 2^-53 sum |in| is left bit for bit as it is: Pi
+ * could bring it no closer to its range.  out may be in.  The identity on a nonsingular handle.  Results repeat bit for bit. */
+int  cheb_varhelm_remove_null(cheb_varhelm *h, const double *in_dev, double *out_dev, void *stream);
+/* Pi mult and Pi precond with the shape of chebhip_apply_fn (ctx = the handle): a caller's chebhip_fgmres_solve on the two from
+ * b = remove_null(residual(0, f, g)), followed by remove_null of its x, gives cheb_varhelm_solve_deflated's bits. */
+int  cheb_varhelm_apply_deflated(void *h, const double *x_dev, double *y_dev, void *stream);
+int  cheb_varhelm_precond_deflated(void *h, const double *r_dev, double *z_dev, void *stream);
+
+/* The variable-density projection: out_k = u_k - kappa s_k d_k phi at every node, kappa = 1 / rho > 0 one full-grid
+ * field shared by the vectors, phi from
+ *   unknown nodes:   sum_k s_k^2 d_k( kappa d_k phi ) = sum_k s_k d_k u_k
+ *   boundary node b (k the highest direction in which b is an end node):
+ *     wall:  kappa s_k dphi/dnu = +- u_k - flux_b      open:  phi = 0
+ * so that the normal velocity of the result at a wall node is flux, as for cheb_project_apply.  The handle of
+ * cheb_project_create_variable (arguments of cheb_project_create_basis; basis NULL: no periodic direction) owns a cheb_varhelm
+ * (nvec fields, c = 0, (0, 1) ends at walls and (1, 0) at open faces) in place of the direct solve, the unknowns of its last solve
+ * and d work grids per vector.  cheb_project_set_inverse_density is cheb_varhelm_set_coefficients(kappa, c = 0): synchronous, and a
+ * refused kappa leaves the handle as it was.  cheb_project_apply_variable: the divergence into phi; one launch for f = -div u and
+ * g = (+- u_k - flux) / kappa (the operator's faces carry no kappa); cheb_varhelm_solve_deflated with rtol, atol, max_it, restart,
+ * from 0 or -- warm != 0 and an earlier call has solved -- from that call's unknowns, the full grid into phi; the gradient of phi
+ * (d sweeps per vector), at the nodes of a wall the normal derivative +-g from the condition that defines phi there, and one
+ * pointwise pass.  Arrays and aliasing as cheb_project_apply; nothing is allocated per call after the
+ * first solve's Krylov bases; the same input gives the same bits.
+ * At the unknown nodes div(out) = -cheb_varhelm_residual(phi, -div u, g) exactly as computed: with an open face it is at the
+ * solve's tolerance (not at rounding, as the direct solve's is); with walls and periodic directions only it lies in the span of
+ * the null vectors up to that tolerance, with the coefficients -cheb_varhelm_defect.  cheb_project_varhelm: the inner handle, for
+ * cheb_varhelm_iterations, _last_residual, _reason, _null_count and _defect (NULL for a handle of the other constructors, which
+ * cheb_project_apply_variable refuses, as cheb_project_apply refuses a variable one). */
+int  cheb_project_create_variable(int d, const int *dims, const int *basis, const int *faces, const double *scale, int nvec, cheb_project **out);
+int  cheb_project_set_inverse_density(cheb_project *h, const double *kappa_dev, void *stream);
+int  cheb_project_apply_variable(cheb_project *h, const double *u_dev, const double *flux_dev, double *phi_dev, double *out_dev, int warm,
+                                 double rtol, double atol, int max_it, int restart, void *stream);
+cheb_varhelm *cheb_project_varhelm(const cheb_project *h);
+
 /* ------------------------------------------------------------------------- */
 /* Instrumentation (the reference has none: SURVEY 5.1).                      */
 /* ------------------------------------------------------------------------- */

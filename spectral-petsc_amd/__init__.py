@@ -96,6 +96,9 @@ ABI_SYMBOLS = [
     "cheb_varhelm_work_bytes", "cheb_varhelm_set_coefficients", "cheb_varhelm_sigma", "cheb_varhelm_singular", "cheb_varhelm_mult",
     "cheb_varhelm_apply", "cheb_varhelm_residual", "cheb_varhelm_precond", "cheb_varhelm_solve", "cheb_varhelm_iterations",
     "cheb_varhelm_last_residual", "cheb_varhelm_reason",
+    "cheb_varhelm_solve_deflated", "cheb_varhelm_null_count", "cheb_varhelm_defect", "cheb_varhelm_null_signs_host",
+    "cheb_varhelm_remove_null", "cheb_varhelm_apply_deflated", "cheb_varhelm_precond_deflated",
+    "cheb_project_create_variable", "cheb_project_set_inverse_density", "cheb_project_apply_variable", "cheb_project_varhelm",
 ]
 
 
@@ -414,6 +417,18 @@ def lib():
         L.cheb_varhelm_last_residual.argtypes = [vp]
         L.cheb_varhelm_last_residual.restype = C.c_double
         L.cheb_varhelm_reason.argtypes = [vp]
+        L.cheb_varhelm_solve_deflated.argtypes = L.cheb_varhelm_solve.argtypes
+        L.cheb_varhelm_null_count.argtypes = [vp]
+        L.cheb_varhelm_defect.argtypes = [vp, dp]
+        L.cheb_varhelm_null_signs_host.argtypes = [C.c_int, ip, ip, ip]
+        L.cheb_varhelm_remove_null.argtypes = [vp, vp, vp, vp]
+        L.cheb_varhelm_apply_deflated.argtypes = [vp, vp, vp, vp]
+        L.cheb_varhelm_precond_deflated.argtypes = [vp, vp, vp, vp]
+        L.cheb_project_create_variable.argtypes = [C.c_int, ip, ip, ip, dp, C.c_int, C.POINTER(vp)]
+        L.cheb_project_set_inverse_density.argtypes = [vp, vp, vp]
+        L.cheb_project_apply_variable.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp]
+        L.cheb_project_varhelm.argtypes = [vp]
+        L.cheb_project_varhelm.restype = vp
         _lib = L
     return _lib
 
@@ -1778,6 +1793,9 @@ class VarHelmholtz(_Handle):
         initial guess (it is not overwritten).  Afterwards iterations, residual_norm (Fgmres's `residual`; the name is the method's
         here) and reason as on Fgmres.  A singular problem (c == 0
         and every direction periodic or Neumann / Neumann) raises ChebhipError (code 4)."""
+        return self._solve(lib().cheb_varhelm_solve, f, g, u_full, x0, rtol, atol, max_it, restart)
+
+    def _solve(self, entry, f, g, u_full, x0, rtol, atol, max_it, restart):
         import torch
         fp = self._vec("f", f, self.size)
         x = torch.zeros_like(f) if x0 is None else None
@@ -1785,14 +1803,76 @@ class VarHelmholtz(_Handle):
             self._vec("x0", x0, self.size)
             x = x0.clone()
         try:
-            _chk(lib().cheb_varhelm_solve(self._h, fp, self._vec("g", g, self.boundary_size, True), x.data_ptr(), 0 if x0 is None else 1,
-                                          self._vec("u_full", u_full, self.full_size, True), float(rtol), float(atol), int(max_it), int(restart),
-                                          _stream()))
+            _chk(entry(self._h, fp, self._vec("g", g, self.boundary_size, True), x.data_ptr(), 0 if x0 is None else 1,
+                       self._vec("u_full", u_full, self.full_size, True), float(rtol), float(atol), int(max_it), int(restart), _stream()))
         finally:
             self.iterations = lib().cheb_varhelm_iterations(self._h)
             self.residual_norm = lib().cheb_varhelm_last_residual(self._h)
             self.reason = lib().cheb_varhelm_reason(self._h)
         return x
+
+    def solve_deflated(self, f, g=None, u_full=None, x0=None, rtol=1e-8, atol=0.0, max_it=200, restart=30):
+        """solve for a singular problem: the x with N^T x = 0 and Pi (b - A x) = 0, N the `null_count` null vectors of
+        +-1 (`null_space()`), Pi = I - N N^T / G per field, b = residual(0, f, g).  What is left of b - A x is N lambda: `defect`.
+        iterations, residual_norm and reason are those of the projected system, |Pi (b - A x)| against rtol |Pi b|.  On a
+        nonsingular handle this is solve, bit for bit.  More than three even periodic directions raise ChebhipError (code 4)."""
+        return self._solve(lib().cheb_varhelm_solve_deflated, f, g, u_full, x0, rtol, atol, max_it, restart)
+
+    null_count = property(lambda self: lib().cheb_varhelm_null_count(self._h))
+
+    @property
+    def defect(self):
+        """lambda = N^T (b - A x) / G of the last solve_deflated of a singular problem: a (nfields, q) NumPy array.  Synchronises."""
+        import numpy as np
+        q = self.null_count
+        out = np.zeros((self.nfields, max(q, 0)))
+        if q > 0:
+            _chk(lib().cheb_varhelm_defect(self._h, _np_dp(out)))
+        return out
+
+    def null_space(self):
+        """The null vectors of the geometry with every wall Neumann / Neumann and c == 0: a host array (q, *unknown dims) of +-1."""
+        return null_space(self.dims, self.periodic)
+
+    def remove_null(self, x, out=None):
+        """out = Pi x (out None: in place); the identity on a nonsingular handle."""
+        out = x if out is None else out
+        _chk(lib().cheb_varhelm_remove_null(self._h, self._vec("x", x, self.size), self._vec("out", out, self.size), _stream()))
+        return out
+
+    def mult_deflated(self, x, out):
+        """out = Pi mult(x): the operator of solve_deflated (a_entry="mult_deflated" of Fgmres.solve)."""
+        _chk(lib().cheb_varhelm_apply_deflated(self._h, self._vec("x", x, self.size), self._vec("out", out, self.size), _stream()))
+        return out
+
+    def precond_deflated(self, r, z):
+        """z = Pi precond(r): the right preconditioner of solve_deflated (m_entry="precond_deflated")."""
+        _chk(lib().cheb_varhelm_precond_deflated(self._h, self._vec("r", r, self.size), self._vec("z", z, self.size), _stream()))
+        return z
+
+
+def null_signs(dims, periodic):
+    """cheb_varhelm_null_signs_host: per null vector the bit mask of the directions in which it alternates (host only)."""
+    d = len(dims)
+    flags = (C.c_int * 8)()
+    q = lib().cheb_varhelm_null_signs_host(d, _ints([int(p) for p in dims]), _ints([int(bool(p)) for p in periodic]), flags)
+    if q < 0:
+        _chk(-q)
+    return [int(flags[j]) for j in range(q)]
+
+
+def null_space(dims, periodic):
+    """The null vectors of c == 0, every direction periodic or Neumann / Neumann: (q, *unknown dims) of +-1, from null_signs."""
+    import numpy as np
+    M = [int(p) if per else int(p) - 2 for p, per in zip(dims, periodic)]
+    out = []
+    for mask in null_signs(dims, periodic):
+        z = np.ones(M)
+        for k, m in enumerate(M):
+            if mask >> k & 1:
+                z = z * ((-1.0) ** np.arange(m)).reshape([-1 if a == k else 1 for a in range(len(M))])
+        out.append(z)
+    return np.stack(out)
 
 
 OPFUN_KINDS = {"one": 0, "inv": 1, "res": 2, "exp": 3, "phi1": 4, "phi2": 5, "phi3": 6, "pow": 7}           # CHEB_OPFUN_*
@@ -1995,10 +2075,18 @@ class ChebProject(_Handle):
       walls in the wall directions, the rest periodic (a channel) -- `singular`: at the unknown nodes it is free along the dropped
         modes, which are constant along the wall directions and, per periodic direction, the constant or -- for an EVEN extent --
         the Nyquist vector (-1)^j: one constant as above when the periodic extents are odd, 2^e coefficients with e even ones
-        (the wall-normal velocity may carry a Nyquist component no potential removes; small for resolved fields)."""
+        (the wall-normal velocity may carry a Nyquist component no potential removes; small for resolved fields).
+
+    variable=True (cheb_project_create_variable): out_k = u_k - kappa scale_k d_k phi with kappa = 1 / rho > 0 one
+    full-grid field shared by the vectors (set_inverse_density, before the first project), phi from
+    sum_k scale_k^2 d_k(kappa d_k phi) = div u by VarHelmholtz.solve_deflated (FGMRES: project's warm, rtol, atol, max_it and
+    restart; afterwards iterations, residual_norm, reason and defect).  The normal velocity of the result at a wall node is
+    `flux` as above.  At the unknown nodes div(out) is the negative of the solve's residual: with an open face it is at the
+    solve's TOLERANCE, not at rounding; with walls and periodic directions only it lies, up to that tolerance, in the span of the
+    null vectors (null_count of them, coefficients -defect)."""
     _destroy = "cheb_project_destroy"
 
-    def __init__(self, dims, nvec=1, bc=None, scale=None):
+    def __init__(self, dims, nvec=1, bc=None, scale=None, variable=False):
         self.dims = tuple(int(d) for d in dims)
         self.d = len(self.dims)
         self.nvec = int(nvec)
@@ -2007,7 +2095,12 @@ class ChebProject(_Handle):
         self.periodic = (False,) * self.d if faces is None else tuple(_bc_periodic(entry) for entry in bc)
         sc, self.scale = _scale_array(scale, self.d)
         h = C.c_void_p()
-        if any(self.periodic):
+        self.variable = bool(variable)
+        self.iterations, self.residual_norm, self.reason = 0, 0.0, 0
+        if self.variable:
+            _chk(lib().cheb_project_create_variable(self.d, _ints(self.dims), _ints([int(p) for p in self.periodic]) if any(self.periodic) else None,
+                                                    None if faces is None else _ints(faces), None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
+        elif any(self.periodic):
             _chk(lib().cheb_project_create_basis(self.d, _ints(self.dims), _ints([int(p) for p in self.periodic]), _ints(faces),
                                                  None if sc is None else _np_dp(sc), self.nvec, C.byref(h)))
         else:
@@ -2017,10 +2110,30 @@ class ChebProject(_Handle):
         self.size, self.interior_size, self.boundary_size = (lib().cheb_project_size(h, w) for w in range(3))
         self.singular = bool(lib().cheb_project_singular(h))
 
-    def project(self, u, out=None, phi=None, flux=None):
+    def set_inverse_density(self, kappa):
+        """kappa = 1 / rho at every node (a device tensor of `size` values, finite and > 0), for a variable=True handle; synchronises.
+        Refusals as VarHelmholtz.set_coefficients: the handle then keeps what it had."""
+        _chk(lib().cheb_project_set_inverse_density(self._h, _dev_ptr(kappa, self.size), _stream()))
+
+    def _varhelm(self):
+        return lib().cheb_project_varhelm(self._h)
+
+    null_count = property(lambda self: lib().cheb_varhelm_null_count(self._varhelm()) if self.variable else 0)
+
+    @property
+    def defect(self):
+        """VarHelmholtz.defect of the last project of a variable=True handle without an open face: (nvec, null_count)."""
+        import numpy as np
+        q = self.null_count
+        out = np.zeros((self.nvec, max(q, 0)))
+        if q > 0:
+            _chk(lib().cheb_varhelm_defect(self._varhelm(), _np_dp(out)))
+        return out
+
+    def project(self, u, out=None, phi=None, flux=None, warm=False, rtol=1e-8, atol=0.0, max_it=200, restart=30):
         """u: (nvec * d, *dims); flux: nvec * boundary_size prescribed outward normal velocities at the boundary nodes (compact,
         row-major) or None; phi: nvec * size values, receives the potential (allocated if None); out (allocated if None) may be u.
-        Returns out."""
+        Returns out.  warm .. restart: a variable=True handle's solve (warm: from the unknowns of the call before)."""
         import torch
         nu = self.nvec * self.d * self.size
         if flux is not None and self.boundary_size == 0:
@@ -2029,6 +2142,16 @@ class ChebProject(_Handle):
             out = torch.empty((self.nvec * self.d,) + self.dims, dtype=torch.float64, device=u.device)
         if phi is None:
             phi = torch.empty((self.nvec,) + self.dims, dtype=torch.float64, device=u.device)
+        if self.variable:
+            try:
+                _chk(lib().cheb_project_apply_variable(self._h, _dev_ptr(u, nu), None if flux is None else _dev_ptr(flux, self.nvec * self.boundary_size),
+                                                       _dev_ptr(phi, self.nvec * self.size), _dev_ptr(out, nu), int(bool(warm)), float(rtol), float(atol),
+                                                       int(max_it), int(restart), _stream()))
+            finally:
+                vh = self._varhelm()
+                self.iterations, self.reason = lib().cheb_varhelm_iterations(vh), lib().cheb_varhelm_reason(vh)
+                self.residual_norm = lib().cheb_varhelm_last_residual(vh)
+            return out
         _chk(lib().cheb_project_apply(self._h, _dev_ptr(u, nu), None if flux is None else _dev_ptr(flux, self.nvec * self.boundary_size),
                                       _dev_ptr(phi, self.nvec * self.size), _dev_ptr(out, nu), _stream()))
         return out
@@ -2449,8 +2572,10 @@ class Fgmres(_Handle):
             return C.cast(lib().cheb_helmholtz_apply, C.c_void_p), op._h
         if kind == "StokesSaddlePc":
             return C.cast(lib().stokes_saddle_apply, C.c_void_p), op._h
-        if kind == "VarHelmholtz":                       # entry "mult": the operator; "precond": its preconditioner
-            return C.cast(lib().cheb_varhelm_precond if entry == "precond" else lib().cheb_varhelm_apply, C.c_void_p), op._h
+        if kind == "VarHelmholtz":                       # entry "mult": the operator; "precond": its preconditioner; "*_deflated": Pi of them
+            name = {"precond": "cheb_varhelm_precond", "mult_deflated": "cheb_varhelm_apply_deflated",
+                    "precond_deflated": "cheb_varhelm_precond_deflated"}.get(entry, "cheb_varhelm_apply")
+            return C.cast(getattr(lib(), name), C.c_void_p), op._h
         if kind in ("EllipticOp", "StokesOp"):
             name = {"EllipticOp": "ell_op_", "StokesOp": "stokes_op_"}[kind] + entry
             return C.cast(getattr(lib(), name), C.c_void_p), op._h

@@ -35,6 +35,7 @@ int cheb_grad_axpy_grad(cheb_grad *h, int nvec, double alpha, const double *s_de
 // on the caller's arrays (the one solve_bc ends with; g may be null), and a new shift sigma for the same lines (synchronous)
 int helmholtz_extend(const cheb_helmholtz *h, const double *z_dev, const double *g_dev, double *u_dev, void *stream);
 int helmholtz_set_sigma(cheb_helmholtz *h, double sigma);
+const double *varhelm_kappa(const cheb_varhelm *h);          // varhelm.hip: the handle's copy of kappa (the first of its stacked copies), device [N]
 size_t helmholtz_work_bytes(const cheb_helmholtz *h);        // device bytes the handle holds: field buffers, line matrices, eigenvalues
 int chebhip_fail(int code, const char *fmt, ...);            // chebhip.hip: sets chebhip_last_error(), returns code
 

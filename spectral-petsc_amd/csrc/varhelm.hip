@@ -19,6 +19,11 @@
 // Solve.  b = f - (operator at g)(0); FGMRES (krylov.hip) on A = the linear operator with the right preconditioner
 // z = H(sigma_p)^-1 (r / kappa), H the direct solve of the same dims, basis, bc, scale and nfields, sigma_p = mean of c / kappa over
 // the unknown nodes; the full-grid output by the same extension.
+//
+// Deflated solve.  With c == 0 and no Dirichlet or Robin face A is singular, its null space N known for any kappa (the
+// constant and, per periodic direction of even extent, the Nyquist vector).  solve_deflated is the same FGMRES on Pi A with the
+// preconditioner Pi H(0)^-1 (r / kappa), Pi = I - N N^T / G per field, between projections of b, of the guess and of the result;
+// Pi is the three launches k_vh_null_partial, k_vh_null_total, k_vh_null_subtract below (fixed addition order, no atomics).
 #include "../../include/chebhip.h"
 #include "ops.h"
 #include "sweep.h"
@@ -53,6 +58,8 @@ template <> struct VhVec<1> {
   static __device__ __forceinline__ T load(const double *p) { return *p; }
   static __device__ __forceinline__ void store(double *p, T v) { *p = v; }
   static __device__ __forceinline__ T splat(double v) { return v; }
+  static __device__ __forceinline__ double get(T v, int) { return v; }
+  static __device__ __forceinline__ void sub(T &v, int, double c) { v -= c; }
 };
 template <> struct VhVec<2> {
   typedef vh2 T;
@@ -62,6 +69,8 @@ template <> struct VhVec<2> {
   }
   static __device__ __forceinline__ void store(double *p, T v) { *reinterpret_cast<vh2 *>(p) = v; }      // unknown-layout side: aligned by the launcher
   static __device__ __forceinline__ T splat(double v) { return (vh2){v, v}; }
+  static __device__ __forceinline__ double get(T v, int w) { return w ? v.y : v.x; }
+  static __device__ __forceinline__ void sub(T &v, int w, double c) { if (w) v.y -= c; else v.x -= c; }
 };
 
 // The closing pass: out = c x + A at the unknown nodes (f null), or f - (c x + A) (the residual).  A: nfields full grids; cf: the c
@@ -119,6 +128,124 @@ __global__ __launch_bounds__(256) void k_vh_coef_check(VhGeo geo, const double *
   if (threadIdx.x == 0) { part[blockIdx.x] = sh[0]; bad[blockIdx.x] = shb[0]; }
 }
 
+// ---- the projection Pi = I - N N^T / G of the deflated solve ------------------------------------------------------------
+// The null space of a singular handle: the m even periodic directions dir[0] < dir[1] < .. (m <= 3); null vector j of the q = 2^m
+// alternates, (-1)^index, in dir[b] for every bit b of j.  Vector 0 is the constant.
+struct VhNull { int m; int dir[3]; };
+constexpr int VH_PB = 512;                     // blocks of the partial pass per field
+constexpr int VH_TS = 24;                      // doubles per field of a totals array: [0, 8) the sums, [8, 16) the sums / G, [16] 1 = subtract
+constexpr double VH_U = 1.1102230246251565e-16;
+
+// bit b: the parity of unknown q's index in direction dir[b]
+__device__ __forceinline__ unsigned vh_parity(const VhGeo &g, const VhNull &z, unsigned q) {
+  unsigned r = q, p = 0;
+  int b = z.m - 1;
+  for (int m = VMAXD - 1; m > 0; m--)
+    if (m < g.d) {
+      const unsigned Mm = (unsigned)g.M[m]; const unsigned i = r % Mm; r /= Mm;
+      if (b >= 0 && z.dir[b] == m) { p |= (i & 1u) << b; b--; }
+    }
+  if (b >= 0) p |= (r & 1u) << b;              // (dir[0] == 0)
+  return p;
+}
+__device__ __forceinline__ double vh_signed(unsigned j, unsigned p, double v) { return (__popc(j & p) & 1) ? -v : v; }
+
+// the sums of a block of 256 in a fixed order: sh[j][0] = the tree 128, 64, .. 1 over the threads' values
+template <int R>
+__device__ __forceinline__ void vh_block_tree(double (&sh)[R][256]) {
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o)
+#pragma unroll
+      for (int j = 0; j < R; j++) sh[j][threadIdx.x] += sh[j][threadIdx.x + o];
+    __syncthreads();
+  }
+}
+
+// First pass: part[(field (Q + 1) + j) VH_PB + block] = the block's share of z_j^T x (j < Q) and of sum |x| (j = Q); a thread adds
+// its elements in ascending order.  W = 2: pairs along the last direction (M[d-1] even, so the first of a pair has an even index).
+template <int W, int Q>
+__global__ __launch_bounds__(256) void k_vh_null_partial(VhGeo geo, VhNull z, const double *__restrict__ in, double *__restrict__ part) {
+  typedef VhVec<W> V;
+  __shared__ double sh[Q + 1][256];
+  const unsigned per = geo.G / W;
+  const size_t fu = (size_t)blockIdx.y * geo.G;
+  const unsigned pairbit = (Q > 1 && W == 2 && z.dir[z.m - 1] == geo.d - 1) ? 1u << (z.m - 1) : 0u;
+  double s[Q + 1];
+#pragma unroll
+  for (int j = 0; j <= Q; j++) s[j] = 0.0;
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < per; t += (unsigned)VH_PB * 256u) {
+    const unsigned q = t * W, p = Q > 1 ? vh_parity(geo, z, q) : 0u;
+    const typename V::T v = V::load(in + fu + q);
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+      const double x = V::get(v, w);
+      const unsigned pw = w ? p ^ pairbit : p;
+#pragma unroll
+      for (int j = 0; j < Q; j++) s[j] += vh_signed((unsigned)j, pw, x);
+      s[Q] += fabs(x);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j <= Q; j++) sh[j][threadIdx.x] = s[j];
+  vh_block_tree(sh);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int j = 0; j <= Q; j++) part[((size_t)blockIdx.y * (Q + 1) + j) * VH_PB + blockIdx.x] = sh[j][0];
+}
+
+// Second pass, one block per field: the VH_PB shares in a fixed order (share t + share t + 256, then the tree), the coefficients
+// s_j / G, and whether the third pass subtracts: not where every |s_j| <= tau sum |x| -- x is in the range of Pi already as far as
+// Pi can bring it there, and stays bit for bit
+template <int Q>
+__global__ __launch_bounds__(256) void k_vh_null_total(const double *__restrict__ part, double G, double tau, double *__restrict__ tot) {
+  __shared__ double sh[Q + 1][256];
+  const double *pf = part + (size_t)blockIdx.x * (Q + 1) * VH_PB;
+#pragma unroll
+  for (int j = 0; j <= Q; j++) sh[j][threadIdx.x] = pf[j * VH_PB + threadIdx.x] + pf[j * VH_PB + threadIdx.x + 256];
+  vh_block_tree(sh);
+  if (threadIdx.x == 0) {
+    double *tf = tot + (size_t)blockIdx.x * VH_TS;
+    bool keep = true;
+    for (int j = 0; j < Q; j++) {
+      tf[j] = sh[j][0]; tf[8 + j] = sh[j][0] / G;
+      keep = keep && fabs(sh[j][0]) <= tau * sh[Q][0];
+    }
+    tf[16] = keep ? 0.0 : 1.0;
+  }
+}
+
+// Third pass: out = in - sum_j z_j (s_j / G), the correction added up over j ascending and subtracted once; in == out allowed
+template <int W, int Q>
+__global__ __launch_bounds__(256) void k_vh_null_subtract(VhGeo geo, VhNull z, const double *__restrict__ tot, const double *in, double *out) {
+  typedef VhVec<W> V;
+  const unsigned per = geo.G / W;
+  const size_t fu = (size_t)blockIdx.y * geo.G;
+  const double *tf = tot + (size_t)blockIdx.y * VH_TS;
+  const bool sub = tf[16] != 0.0;
+  if (!sub && in == out) return;
+  const unsigned pairbit = (Q > 1 && W == 2 && z.dir[z.m - 1] == geo.d - 1) ? 1u << (z.m - 1) : 0u;
+  double c[Q];
+#pragma unroll
+  for (int j = 0; j < Q; j++) c[j] = tf[8 + j];
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < per; t += gridDim.x * 256u) {
+    const unsigned q = t * W;
+    typename V::T v = V::load(in + fu + q);
+    if (sub) {
+      const unsigned p = Q > 1 ? vh_parity(geo, z, q) : 0u;
+#pragma unroll
+      for (int w = 0; w < W; w++) {
+        const unsigned pw = w ? p ^ pairbit : p;
+        double corr = c[0];
+#pragma unroll
+        for (int j = 1; j < Q; j++) corr += vh_signed((unsigned)j, pw, c[j]);
+        V::sub(v, w, corr);
+      }
+    }
+    V::store(out + fu + q, v);
+  }
+}
+
 }  // namespace
 
 struct cheb_varhelm {
@@ -136,6 +263,9 @@ struct cheb_varhelm {
   double *cfield = nullptr; double c0 = 0.0; bool c_is_field = false;
   double *tu = nullptr, *bu = nullptr, *zero = nullptr;  // nf G each: r / kappa, the solve's right-hand side, a zero vector
   double *part = nullptr; unsigned *bad = nullptr;
+  VhNull null = {};                            // the even periodic directions; null.m > 3: the deflated calls refuse
+  double *npart = nullptr, *ntot = nullptr, *dtot = nullptr;   // the projection's block shares and totals; the totals of the last defect
+  int defect_q = 0;                            // null vectors of the last deflated solve (0: none yet, or a nonsingular one)
   bool have_coef = false, any_two_sweeps = false;
   double sigma_p = 0.0;
   chebhip_fgmres *krylov = nullptr; int krylov_restart = 0;   // made by the first solve; a solve with another restart length replaces it
@@ -210,6 +340,54 @@ int vh_check_vectors(const cheb_varhelm *h, const char *what, const double *x, c
   return 0;
 }
 
+// the even periodic directions of a geometry, ascending; returns their number (any number: the callers check the limit of 3)
+int vh_even_periodic(int d, const int *dims, const int *basis, int *dir3) {
+  int m = 0;
+  for (int k = 0; k < d; k++)
+    if (basis && basis[k] == BASIS_FOURIER && (dims[k] & 1) == 0) { if (m < 3) dir3[m] = k; m++; }
+  return m;
+}
+
+// q of the handle as its coefficients stand: 0 nonsingular, 2^m singular; -1 with the error set: more than three even periodic directions
+int vh_null_count(const cheb_varhelm *h, const char *what) {
+  if (!cheb_helmholtz_singular(h->H)) return 0;
+  if (h->null.m > 3) {
+    chebhip_fail(CHEBHIP_ERR_ARG, "%s: %d even periodic directions give %ld null vectors: more than three such directions (8 vectors) are not supported", what, h->null.m, 1L << h->null.m);
+    return -1;
+  }
+  return 1 << h->null.m;
+}
+
+// (Depth of the fixed addition order of one of these sums, the T of DESIGN 10q: a thread's elements in turn, at most
+// 2 ceil(G / (2 VH_PB 256)); the block's tree, 8; the pair of shares, 1; the tree over them, 8.)
+template <int Q>
+void vh_null_launch(const cheb_varhelm *h, bool vec, const double *in, double *out, double *tot, double tau, hipStream_t st) {
+  const dim3 pgrid(VH_PB, (unsigned)h->nf);
+  if (vec) hipLaunchKernelGGL((k_vh_null_partial<2, Q>), pgrid, dim3(256), 0, st, h->geo, h->null, in, h->npart);
+  else hipLaunchKernelGGL((k_vh_null_partial<1, Q>), pgrid, dim3(256), 0, st, h->geo, h->null, in, h->npart);
+  sweep_note_launch();
+  hipLaunchKernelGGL((k_vh_null_total<Q>), dim3((unsigned)h->nf), dim3(256), 0, st, (const double *)h->npart, (double)h->G, tau, tot);
+  sweep_note_launch();
+  if (out) vh_launch_rows(k_vh_null_subtract<1, Q>, k_vh_null_subtract<2, Q>, vec, h, st, h->null, (const double *)tot, in, out);
+}
+
+// out = Pi in (in == out allowed), or with out null the sums alone, into the totals array tot; q = 1, 2, 4 or 8
+int vh_remove_null(cheb_varhelm *h, int q, const double *in, double *out, double *tot, hipStream_t st) {
+  if (h->G == 0) return 0;
+  const bool vec = vh_pairs(h, in, out, nullptr);
+  // every computed |s_j| <= (q + 4) U sum |x|: with the sums' own error T U sum |x| the true ones are within the (T + q + 4) U sum |x|
+  // that a subtraction guarantees, and x is left as it is
+  const double tau = (double)(q + 4) * VH_U;
+  switch (q) {
+    case 1: vh_null_launch<1>(h, vec, in, out, tot, tau, st); break;
+    case 2: vh_null_launch<2>(h, vec, in, out, tot, tau, st); break;
+    case 4: vh_null_launch<4>(h, vec, in, out, tot, tau, st); break;
+    default: vh_null_launch<8>(h, vec, in, out, tot, tau, st); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int cheb_varhelm_destroy(cheb_varhelm *h) {
@@ -217,7 +395,7 @@ extern "C" int cheb_varhelm_destroy(cheb_varhelm *h) {
   if (h->krylov) chebhip_fgmres_destroy(h->krylov);
   if (h->H) cheb_helmholtz_destroy(h->H);
   for (auto &kv : h->D) diffmat_destroy(&kv.second);
-  double *all[] = {h->Wf, h->Gk, h->A, h->kap, h->cfield, h->tu, h->bu, h->zero, h->part};
+  double *all[] = {h->Wf, h->Gk, h->A, h->kap, h->cfield, h->tu, h->bu, h->zero, h->part, h->npart, h->ntot, h->dtot};
   for (double *p : all) if (p) (void)hipFree(p);
   if (h->bad) (void)hipFree(h->bad);
   delete h;
@@ -262,6 +440,14 @@ extern "C" int cheb_varhelm_create(int d, const int *dims, const int *basis, con
   if ((h->NB && (rc = vh_alloc(h, &h->Wf, nN))) || (h->any_two_sweeps && (rc = vh_alloc(h, &h->Gk, nN))) || (rc = vh_alloc(h, &h->A, nN)) ||
       (rc = vh_alloc(h, &h->kap, nN)) || (rc = vh_alloc(h, &h->cfield, (size_t)N)) || (rc = vh_alloc(h, &h->tu, nG)) || (rc = vh_alloc(h, &h->bu, nG)) ||
       (rc = vh_alloc(h, &h->zero, nG)) || (rc = vh_alloc(h, &h->part, VH_RB))) { cheb_varhelm_destroy(h); return rc; }
+  // the projection of the deflated solve, where the geometry can be singular at all (no Dirichlet or Robin face: cheb_helmholtz_singular
+  // at sigma = 0) and has at most 8 null vectors
+  h->null.m = vh_even_periodic(d, dims, basis, h->null.dir);
+  if (cheb_helmholtz_singular(H) && h->null.m <= 3) {
+    const size_t q1 = (size_t)(1 << h->null.m) + 1;
+    if ((rc = vh_alloc(h, &h->npart, (size_t)nfields * q1 * VH_PB)) || (rc = vh_alloc(h, &h->ntot, (size_t)nfields * VH_TS)) ||
+        (rc = vh_alloc(h, &h->dtot, (size_t)nfields * VH_TS))) { cheb_varhelm_destroy(h); return rc; }
+  }
   HIP_TRY_OR(hipMalloc((void **)&h->bad, VH_RB * sizeof(unsigned)), cheb_varhelm_destroy(h));
   HIP_TRY_OR(hipMemset(h->zero, 0, (nG ? nG : 1) * sizeof(double)), cheb_varhelm_destroy(h));
   *out = h;
@@ -272,6 +458,7 @@ extern "C" long cheb_varhelm_size(const cheb_varhelm *h) { return h ? (long)h->n
 extern "C" long cheb_varhelm_full_size(const cheb_varhelm *h) { return h ? (long)h->nf * h->N : -1; }
 extern "C" long cheb_varhelm_boundary_size(const cheb_varhelm *h) { return h ? (long)h->nf * h->NB : -1; }
 extern "C" long cheb_varhelm_work_bytes(const cheb_varhelm *h) { return h ? (long)(h->own_bytes + h->krylov_bytes + helmholtz_work_bytes(h->H)) : -1; }
+const double *varhelm_kappa(const cheb_varhelm *h) { return h->kap; }
 extern "C" int cheb_varhelm_singular(const cheb_varhelm *h) { return h && h->have_coef ? cheb_helmholtz_singular(h->H) : -1; }
 extern "C" double cheb_varhelm_sigma(const cheb_varhelm *h) { return h && h->have_coef ? h->sigma_p : -1.0; }
 
@@ -326,18 +513,18 @@ extern "C" int cheb_varhelm_precond(void *hv, const double *r_dev, double *z_dev
   return cheb_helmholtz_solve(h->H, h->tu, z_dev, stream);
 }
 
-extern "C" int cheb_varhelm_solve(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
-                                  double rtol, double atol, int max_it, int restart, void *stream) {
-  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
-  if (!f_dev || !x_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: NULL vector");
-  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+// solve (q = 0) and solve_deflated on a singular handle (q = its null vectors): b = f - (operator at g)(0), FGMRES, the full grid.
+// With q > 0 the system is Pi A x = Pi b in the range of Pi: b, the guess and the result are projected, the operator and the
+// preconditioner are the _deflated entries, and the coefficients of the residual b - A x in the null vectors are left in dtot.
+static int vh_solve(cheb_varhelm *h, int q, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                    double rtol, double atol, int max_it, int restart, void *stream) {
   if (restart < 1 || max_it < 0) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: restart = %d, max_it = %d", restart, max_it);
   const long n = (long)h->nf * h->G, nN = (long)h->nf * h->N, nb = (long)h->nf * h->NB;
   if (g_dev && h->NB == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: g given, but every direction is periodic: there is no boundary data");
   if (overlap(x_dev, n, f_dev, n) || (g_dev && overlap(x_dev, n, g_dev, nb))) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: x may not alias f or g");
   if (u_full_dev && (overlap(u_full_dev, nN, f_dev, n) || overlap(u_full_dev, nN, x_dev, n) || (g_dev && overlap(u_full_dev, nN, g_dev, nb))))
     return chebhip_fail(CHEBHIP_ERR_ARG, "solve: u_full may not alias f, g or x");
-  if (cheb_helmholtz_singular(h->H))
+  if (!q && cheb_helmholtz_singular(h->H))
     return chebhip_fail(CHEBHIP_ERR_ARG, "solve: the problem is singular (c == 0 and every direction periodic or Neumann / Neumann); mult and residual still work");
   if (h->krylov && h->krylov_restart != restart) {          // one pair of bases at a time: at 256^3 and restart 30 they are 8 GB per field
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -352,15 +539,103 @@ extern "C" int cheb_varhelm_solve(cheb_varhelm *h, const double *f_dev, const do
   chebhip_fgmres *ks = h->krylov;
   int rc = chebhip_fgmres_set_tolerances(ks, rtol, atol, max_it); if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
+  h->defect_q = 0;
   if ((rc = vh_operator(h, h->zero, f_dev, g_dev, h->bu, st))) return rc;              // b = f - (operator at g)(0): the lift of g
-  rc = chebhip_fgmres_solve(ks, cheb_varhelm_apply, h, cheb_varhelm_precond, h, h->bu, x_dev, x_nonzero ? 1 : 0, stream);
+  if (q) {
+    if ((rc = vh_remove_null(h, q, h->bu, h->bu, h->ntot, st))) return rc;
+    if (x_nonzero && (rc = vh_remove_null(h, q, x_dev, x_dev, h->ntot, st))) return rc;
+  }
+  rc = chebhip_fgmres_solve(ks, q ? cheb_varhelm_apply_deflated : cheb_varhelm_apply, h, q ? cheb_varhelm_precond_deflated : cheb_varhelm_precond, h,
+                            h->bu, x_dev, x_nonzero ? 1 : 0, stream);
   h->iterations = chebhip_fgmres_iterations(ks); h->residual = chebhip_fgmres_residual(ks); h->reason = chebhip_fgmres_reason(ks);
   if (rc) return rc;
+  if (q) {
+    // the last Pi: the Krylov vectors are in the range of Pi only as far as their roundings allow
+    if ((rc = vh_remove_null(h, q, x_dev, x_dev, h->ntot, st))) return rc;
+    // what is left of b - A x lies in the null space: its coefficients, from one residual (into the preconditioner's work vector)
+    if ((rc = vh_operator(h, x_dev, f_dev, g_dev, h->tu, st)) || (rc = vh_remove_null(h, q, h->tu, nullptr, h->dtot, st))) return rc;
+    h->defect_q = q;
+  }
   if (u_full_dev) {
     if (h->NB) return helmholtz_extend(h->H, x_dev, g_dev, u_full_dev, stream);
     HIP_TRY(hipMemcpyAsync(u_full_dev, x_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
   return 0;
+}
+
+extern "C" int cheb_varhelm_solve(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                                  double rtol, double atol, int max_it, int restart, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!f_dev || !x_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: NULL vector");
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  return vh_solve(h, 0, f_dev, g_dev, x_dev, x_nonzero, u_full_dev, rtol, atol, max_it, restart, stream);
+}
+
+extern "C" int cheb_varhelm_solve_deflated(cheb_varhelm *h, const double *f_dev, const double *g_dev, double *x_dev, int x_nonzero, double *u_full_dev,
+                                           double rtol, double atol, int max_it, int restart, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!f_dev || !x_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "solve: NULL vector");
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  const int q = vh_null_count(h, "solve_deflated");
+  if (q < 0) return CHEBHIP_ERR_ARG;
+  return vh_solve(h, q, f_dev, g_dev, x_dev, x_nonzero, u_full_dev, rtol, atol, max_it, restart, stream);
+}
+
+// Pi of in (in == out allowed); the identity on a nonsingular handle
+extern "C" int cheb_varhelm_remove_null(cheb_varhelm *h, const double *in_dev, double *out_dev, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (!in_dev || !out_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "remove_null: NULL vector");
+  if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
+  const long n = (long)h->nf * h->G;
+  if (in_dev != out_dev && overlap(in_dev, n, out_dev, n)) return chebhip_fail(CHEBHIP_ERR_ARG, "remove_null: out may be in itself, but may not overlap it otherwise");
+  const int q = vh_null_count(h, "remove_null");
+  if (q < 0) return CHEBHIP_ERR_ARG;
+  if (q) return vh_remove_null(h, q, in_dev, out_dev, h->ntot, (hipStream_t)stream);
+  if (in_dev != out_dev) HIP_TRY(hipMemcpyAsync(out_dev, in_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int cheb_varhelm_apply_deflated(void *hv, const double *x_dev, double *y_dev, void *stream) {
+  int rc = cheb_varhelm_apply(hv, x_dev, y_dev, stream); if (rc) return rc;
+  return cheb_varhelm_remove_null((cheb_varhelm *)hv, y_dev, y_dev, stream);
+}
+extern "C" int cheb_varhelm_precond_deflated(void *hv, const double *r_dev, double *z_dev, void *stream) {
+  int rc = cheb_varhelm_precond(hv, r_dev, z_dev, stream); if (rc) return rc;
+  return cheb_varhelm_remove_null((cheb_varhelm *)hv, z_dev, z_dev, stream);
+}
+
+extern "C" int cheb_varhelm_null_count(const cheb_varhelm *h) {
+  if (!h || !h->have_coef) return -1;
+  if (!cheb_helmholtz_singular(h->H)) return 0;
+  return h->null.m > 3 ? -1 : 1 << h->null.m;
+}
+
+// lambda = N^T (b - A x) / G of the last deflated solve: nfields x q values, field by field
+extern "C" int cheb_varhelm_defect(cheb_varhelm *h, double *out) {
+  if (!h || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "defect: NULL argument");
+  if (!h->defect_q) return chebhip_fail(CHEBHIP_ERR_ARG, "defect: no deflated solve of a singular problem has run on this handle");
+  std::vector<double> tot((size_t)h->nf * VH_TS);
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(tot.data(), h->dtot, tot.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int f = 0; f < h->nf; f++)
+    for (int j = 0; j < h->defect_q; j++) out[(size_t)f * h->defect_q + j] = tot[(size_t)f * VH_TS + 8 + j];
+  return 0;
+}
+
+// The null vectors of a geometry whose every direction is periodic or Neumann / Neumann: flags[j], j < q, has bit k set where
+// vector j alternates ((-1)^index) in direction k; flags[0] = 0 is the constant.  Returns q = 2^(even periodic directions), or
+// -CHEBHIP_ERR_* with the error set (more than three such directions among them).  Host only.
+extern "C" int cheb_varhelm_null_signs_host(int d, const int *dims, const int *basis, int *flags) {
+  if (!dims || !flags || d < 1 || d > VMAXD) return -chebhip_fail(CHEBHIP_ERR_ARG, "null_signs: d = %d must be in 1..10 and dims, flags given", d);
+  for (int k = 0; k < d; k++) if (dims[k] < 1) return -chebhip_fail(CHEBHIP_ERR_ARG, "null_signs: dims[%d] = %d", k, dims[k]);
+  int dir[3];
+  const int m = vh_even_periodic(d, dims, basis, dir);
+  if (m > 3) return -chebhip_fail(CHEBHIP_ERR_ARG, "null_signs: %d even periodic directions give %ld null vectors: more than three such directions (8 vectors) are not supported", m, 1L << m);
+  for (int j = 0; j < (1 << m); j++) {
+    flags[j] = 0;
+    for (int b = 0; b < m; b++) if (j >> b & 1) flags[j] |= 1 << dir[b];
+  }
+  return 1 << m;
 }
 
 extern "C" int cheb_varhelm_iterations(const cheb_varhelm *h) { return h ? h->iterations : -1; }

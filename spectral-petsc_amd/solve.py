@@ -131,13 +131,17 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     return u
 
 
-def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=None, rtol=1e-8, max_it=200, restart=30):
+def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=None, rtol=1e-8, max_it=200, restart=30, singular="refuse"):
     """c u - sum_k scale_k^2 d_k(kappa d_k u) = f with alpha u + beta scale_k du/dnu = g on every face (sp.VarHelmholtz's `bc`;
     None: Dirichlet everywhere), by preconditioned FGMRES in one library call.  kappa: a full-grid device tensor (> 0); c: a scalar
     or a full-grid device tensor (>= 0); f_full: the full-grid right-hand side (its boundary entries are ignored; a multiple of the
     grid's size stacks fields); g: the compact boundary values or None.  The faces' conditions do not contain kappa: for Neumann
     data of the flux kappa du/dnu divide g by kappa first.  Returns (u, iterations): the full-grid u (a new tensor) and the
-    operator applications of the solve; a solve that does not converge raises RuntimeError."""
+    operator applications of the solve; a solve that does not converge raises RuntimeError.  singular: "refuse" -- a singular
+    problem (c == 0, every direction periodic or Neumann / Neumann) raises ChebhipError -- or "deflate": VarHelmholtz.solve_deflated,
+    the solution without null-space part of the problem whose source has lost its null-space part."""
+    if singular not in ("refuse", "deflate"):
+        raise ValueError("singular = %r: 'refuse' or 'deflate'" % (singular,))
     dims = tuple(int(d) for d in dims)
     N = 1
     for n in dims:
@@ -150,7 +154,7 @@ def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=No
         inner = tuple(slice(None) if p else slice(1, -1) for p in op.periodic)
         f = f_full.reshape((op.nfields,) + dims)[(slice(None),) + inner].contiguous().reshape(-1)
         u = torch.empty(op.full_size, dtype=torch.float64, device=f_full.device)
-        op.solve(f, g, u_full=u, rtol=rtol, max_it=max_it, restart=restart)
+        (op.solve_deflated if singular == "deflate" else op.solve)(f, g, u_full=u, rtol=rtol, max_it=max_it, restart=restart)
         if op.reason <= 0:
             raise RuntimeError("variable_diffusion: FGMRES stopped with reason %d after %d iterations (residual %.3e)"
                                % (op.reason, op.iterations, op.residual_norm))
@@ -159,10 +163,12 @@ def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=No
         op.destroy()
 
 
-def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
+def project_velocity(sp, dims, u, bc=None, scale=None, flux=None, inverse_density=None, **solve_options):
     """(out, phi) of sp.ChebProject(dims, nvec, bc, scale).project(u, flux=flux) with a handle made and destroyed here: u holds
     nvec * d full-grid fields, out its divergence-free projection (new tensors).  A bc entry "periodic" makes that direction periodic
-    (ChebProject's docstring)."""
+    (ChebProject's docstring).  inverse_density: kappa = 1 / rho at every node -- the variable-density projection
+    out_k = u_k - kappa scale_k d_k phi (ChebProject(variable=True); solve_options: its rtol, atol, max_it, restart); a solve that
+    does not converge raises RuntimeError."""
     dims = tuple(int(d) for d in dims)
     N = 1
     for n in dims:
@@ -170,10 +176,19 @@ def project_velocity(sp, dims, u, bc=None, scale=None, flux=None):
     per = N * len(dims)
     if u.numel() == 0 or u.numel() % per:
         raise ValueError("u has %d elements, no multiple of %d" % (u.numel(), per))
-    h = sp.ChebProject(dims, u.numel() // per, bc, scale)
+    if inverse_density is None and solve_options:
+        raise ValueError("%s: options of the variable-density solve, but no inverse_density" % ", ".join(sorted(solve_options)))
+    h = sp.ChebProject(dims, u.numel() // per, bc, scale) if inverse_density is None else sp.ChebProject(dims, u.numel() // per, bc, scale, variable=True)
     try:
         phi = torch.empty((h.nvec,) + dims, dtype=torch.float64, device=u.device)
-        out = h.project(u, phi=phi, flux=flux)
+        if inverse_density is None:
+            out = h.project(u, phi=phi, flux=flux)
+        else:
+            h.set_inverse_density(inverse_density.contiguous().reshape(-1))
+            out = h.project(u, phi=phi, flux=flux, **solve_options)
+            if h.reason <= 0:
+                raise RuntimeError("project_velocity: FGMRES stopped with reason %d after %d iterations (residual %.3e)"
+                                   % (h.reason, h.iterations, h.residual_norm))
     finally:
         h.destroy()
     return out, phi
