@@ -1111,6 +1111,24 @@ class ChebDealias(_Handle):
         return out
 
 
+def _set_direction_weights(h, setter, k, w, named=None):
+    """set_weights of ChebReduce and ChebStats: dims[k] host values into direction k through `setter`, None for the default;
+    `named(n, w)` turns what is no array (a kind of reduce_weights) into one, or returns w."""
+    import numpy as np
+    k = int(k)
+    if not 0 <= k < len(h.dims):
+        raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(h.dims) - 1))
+    if w is None:
+        _chk(setter(h._h, k, None))
+        return
+    if named is not None:
+        w = named(h.dims[k], w)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (h.dims[k],):
+        raise ValueError("weights of direction %d: expected %d values, got shape %r" % (k, h.dims[k], w.shape))
+    _chk(setter(h._h, k, _np_dp(w)))
+
+
 REDUCE_W = {"integral": 0, "mean": 1, "node": 2, "dnode": 3, "point": 4, "dpoint": 5}
 
 
@@ -1171,19 +1189,10 @@ class ChebReduce(_Handle):
     def set_weights(self, k, w):
         """The weights of the contracted direction k: dims[k] host values, or what reduce_weights takes as `kind` ("mean",
         ("dnode", 0), ..); None restores the default.  Synchronous."""
-        import numpy as np
-        k = int(k)
-        if not 0 <= k < len(self.dims):
-            raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(self.dims) - 1))
-        if w is None:
-            _chk(lib().cheb_reduce_set_weights(self._h, k, None))
-            return
-        if isinstance(w, str) or (isinstance(w, (tuple, list)) and len(w) == 2 and isinstance(w[0], str)):
-            w = reduce_weights(self.dims[k], w)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.shape != (self.dims[k],):
-            raise ValueError("weights of direction %d: expected %d values, got shape %r" % (k, self.dims[k], w.shape))
-        _chk(lib().cheb_reduce_set_weights(self._h, k, _np_dp(w)))
+        def named(n, w):
+            kind = isinstance(w, str) or (isinstance(w, (tuple, list)) and len(w) == 2 and isinstance(w[0], str))
+            return reduce_weights(n, w) if kind else w
+        _set_direction_weights(self, lib().cheb_reduce_set_weights, k, w, named)
 
     def apply(self, u, v=None, out=None):
         """The contraction of u (of u v; `v is u` gives squares) as a device tensor of shape (nfields,) + out_dims; does not
@@ -1258,17 +1267,7 @@ class ChebStats(_Handle):
 
     def set_weights(self, k, w):
         """The weights of direction k: dims[k] host values; None restores the Clenshaw-Curtis weights.  Synchronous."""
-        import numpy as np
-        k = int(k)
-        if not 0 <= k < len(self.dims):
-            raise ChebhipError(2, "direction %d out of range 0..%d" % (k, len(self.dims) - 1))
-        if w is None:
-            _chk(lib().cheb_stats_set_weights(self._h, k, None))
-            return
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.shape != (self.dims[k],):
-            raise ValueError("weights of direction %d: expected %d values, got shape %r" % (k, self.dims[k], w.shape))
-        _chk(lib().cheb_stats_set_weights(self._h, k, _np_dp(w)))
+        _set_direction_weights(self, lib().cheb_stats_set_weights, k, w)
 
     def summary(self, u, center=None, out=None):
         """A device tensor (nfields, 9): the columns of ChebStats.SUMMARY.  `center`: a device tensor of nfields values the

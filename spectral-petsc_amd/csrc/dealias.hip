@@ -310,9 +310,9 @@ int dealias_reserve(cheb_dealias *h, long fields, long job) {
 static int dealias_create(int d, const int *dims, const int *dims_fine, const int *basis, int nfields, cheb_dealias **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   int rc, mk[MD];
+  if ((rc = check_field_count(d, dims, nfields))) return rc;
+  // (not check_field_extents: a direction's faults have this module's texts, shared with *_basis_host, and the bound is the fine grid's)
   long coarse = 1, fine = 1;
   for (int k = 0; k < d; k++) {
     const int bk = basis ? basis[k] : CHEB_BASIS_CGL;

@@ -17,6 +17,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "rowpass.h"
 #include <map>
 #include <new>
 #include <utility>
@@ -25,8 +26,6 @@
 using namespace chebhip;
 
 namespace {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr int MD = 10;          // directions
 constexpr int MAXF = 16;        // input fields of a call
@@ -187,18 +186,11 @@ extern "C" int cheb_grad_destroy(cheb_grad *h) {
 static int grad_create(int d, const int *dims, const double *scale, const int *basis, cheb_grad **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
   int rc;
-  long N = 1;
-  for (int k = 0; k < d; k++) {
-    if ((rc = check_extent(dims[k]))) return rc;
-    N *= dims[k];
-    if (N >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
+  long N = 0;
+  if ((rc = check_field_grid(d, dims, basis, 1, &N, nullptr))) return rc;      // (the handle has no field count: calls bring theirs)
+  for (int k = 0; k < d; k++)
     if (scale && !(scale[k] == scale[k] && scale[k] - scale[k] == 0.0)) return chebhip_fail(CHEBHIP_ERR_ARG, "scale[%d] is not finite", k);
-    if (basis && basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
-    if (basis && basis[k] == BASIS_FOURIER && dims[k] > 256)
-      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
-  }
   if ((rc = require_device())) return rc;
   cheb_grad *h = new (std::nothrow) cheb_grad;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");

@@ -14,6 +14,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "rowpass.h"
 #include <algorithm>
 #include <map>
 #include <new>
@@ -24,11 +25,8 @@ using namespace chebhip;
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 constexpr int MD = 10;               // directions
 constexpr unsigned SPEC_CR = 8;      // k_modal_spectrum: rows per wave and step (at least; 64 / LPR if that is more)
-constexpr int FOLD_PARTS = 64, FOLD_OUT = 4;   // k_modal_fold: a workgroup adds 4 results from 64 slices of the partials each
 
 struct ModalGeo {
   int d, lg;                         // directions; log2 LPR
@@ -44,19 +42,6 @@ __device__ __forceinline__ void row_index(const ModalGeo &g, unsigned r, int *i)
   if (DC == 3) { const unsigned n1 = (unsigned)g.n[1]; i[0] = (int)(r / n1); i[1] = (int)(r - (r / n1) * n1); return; }
   for (int m = g.d - 2; m > 0; m--) { const unsigned nm = (unsigned)g.n[m]; i[m] = (int)(r % nm); r /= nm; }
   if (g.d > 1) i[0] = (int)r;
-}
-
-// the pair (j, j + 1) of a row; the second value is 0 past the end of the row
-__device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
-  if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
-  d2 v; v.x = row[j]; v.y = j + 1 < n ? row[j + 1] : 0.0;
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
-  return s;
 }
 
 // partial[field][workgroup] = sum over the workgroup's rows of W u (v): field = blockIdx.y; workgroup b takes the rows
@@ -290,33 +275,24 @@ void fourier_filter_matrix(int n, const double *sigma, double *F) {
 static int modal_create(int d, const int *dims, int nfields, const int *basis, cheb_modal **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   int rc;
-  long total = nfields, S = 0;
-  for (int k = 0; k < d; k++) {
-    if ((rc = check_extent(dims[k]))) return rc;
-    if (basis && basis[k] != BASIS_CGL && basis[k] != BASIS_FOURIER) return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
-    if (basis && basis[k] == BASIS_FOURIER && dims[k] > 256)
-      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
-    total *= dims[k]; S += dims[k];
-    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
-  }
+  long N = 0, S = 0;
+  if ((rc = check_field_grid(d, dims, basis, nfields, &N, &S))) return rc;
   if ((rc = require_device())) return rc;
+  const long total = nfields * N;
   cheb_modal *h = new (std::nothrow) cheb_modal;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->total = total;
   ModalGeo &g = h->geo;
-  g.d = d; g.S = (unsigned)S; g.N = (unsigned)(total / nfields);
+  g.d = d; g.S = (unsigned)S; g.N = (unsigned)N;
   const int n = dims[d - 1];
   g.rpf = g.N / (unsigned)n;
-  g.lg = 0;
-  while (g.lg < 6 && (1 << g.lg) < (n + 1) / 2) g.lg++;
-  std::vector<double> w(S);
-  for (int k = 0, o = 0; k < d; o += dims[k], k++) {
-    g.n[k] = dims[k]; g.off[k] = o; h->basis[k] = basis ? basis[k] : BASIS_CGL;
-    if (h->basis[k] == BASIS_FOURIER) for (int j = 0; j < dims[k]; j++) w[o + j] = (double)(2.0L / (long double)dims[k]);
-    else modal_weights_host(dims[k], w.data() + o);
+  g.lg = row_lanes_lg(n);
+  table_offsets(d, dims, g.off);
+  std::vector<double> w = weight_table(d, dims, g.off, S);
+  for (int k = 0; k < d; k++) {
+    g.n[k] = dims[k]; h->basis[k] = basis ? basis[k] : BASIS_CGL;
+    if (h->basis[k] == BASIS_FOURIER) for (int j = 0; j < dims[k]; j++) w[g.off[k] + j] = (double)(2.0L / (long double)dims[k]);
   }
 
   // launch geometry of the two reductions, fixed per handle: results do not depend on anything but the shape
@@ -416,17 +392,11 @@ extern "C" int cheb_modal_filter(cheb_modal *h, const double *u, double *v, void
   return modal_product(h, h->F, u, v, stream, "filter");
 }
 
-namespace {
-
-int modal_fold(cheb_modal *h, unsigned gx, unsigned S, double *out, hipStream_t st, const char *what) {
+static int modal_fold(cheb_modal *h, unsigned gx, unsigned S, double *out, hipStream_t st, const char *what) {
   const unsigned total = (unsigned)h->nf * S;
   hipLaunchKernelGGL(k_modal_fold, dim3((total + FOLD_OUT - 1) / FOLD_OUT), dim3(256), 0, st, h->partial, gx, S, total, out);
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
+  return check_launch(what);
 }
-
-}  // namespace
 
 extern "C" int cheb_modal_integrate(cheb_modal *h, const double *u, const double *v, double *out, void *stream) {
   if (!h || !u || !out) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL argument");
@@ -435,9 +405,8 @@ extern "C" int cheb_modal_integrate(cheb_modal *h, const double *u, const double
 #define MODAL_INT(DC) hipLaunchKernelGGL(k_modal_integrate<DC>, grid, dim3(256), 0, st, h->geo, h->w, u, v, h->partial)
   switch (h->d) { case 1: MODAL_INT(1); break; case 2: MODAL_INT(2); break; case 3: MODAL_INT(3); break; default: MODAL_INT(0); }
 #undef MODAL_INT
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "integrate launch: %s", hipGetErrorString(e));
+  int rc;
+  if ((rc = check_launch("integrate"))) return rc;
   return modal_fold(h, h->gx_int, 1, out, st, "integrate");
 }
 
@@ -449,8 +418,7 @@ extern "C" int cheb_modal_spectrum(cheb_modal *h, const double *a, double *E, vo
   const int n = h->geo.n[h->d - 1];                            // pairs of a row per lane: ceil(n / 2 LPR), LPR = 64 from n = 65 on
   if (n <= 128) MODAL_SPEC(1); else if (n <= 256) MODAL_SPEC(2); else if (n <= 512) MODAL_SPEC(4); else MODAL_SPEC(8);
 #undef MODAL_SPEC
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "spectrum launch: %s", hipGetErrorString(e));
+  int rc;
+  if ((rc = check_launch("spectrum"))) return rc;
   return modal_fold(h, h->gx_spec, h->geo.S, E, st, "spectrum");
 }

@@ -1,9 +1,10 @@
-// ops.h -- the plumbing every module of the library shares: the error-return macros around HIP calls, the grid-stride loop and the
-// launch size of the pointwise kernels, the argument checks of the handle constructors, BoxGrid (the local box of an operator handle
-// and which of its nodes lie on the boundary of the global grid), and what the preconditioner module (precond.hip) needs to see of
-// the operator handles.
+// ops.h -- the plumbing every module of the library shares: the error-return macros around HIP calls, the launch check, the grid-stride
+// loop and the launch size of the pointwise kernels, the argument checks of the handle constructors (check_field_grid: the toolbox
+// modules' stacked full-grid fields) and their concatenated per-direction weight table, BoxGrid (the local box of an operator handle and
+// which of its nodes lie on the boundary of the global grid), and what the preconditioner module (precond.hip) needs to see of the operator handles.
 #pragma once
 #include "../../include/chebhip.h"
+#include "sweep.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
@@ -113,6 +114,65 @@ inline int check_extent(int n) {
   if (n < 2) return chebhip_fail(CHEBHIP_ERR_SIZE, "n = %d but must be >= 2", n);
   if (n > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "n = %d: at most 1024 points per direction", n);
   return 0;
+}
+
+// d and nfields of a toolbox handle over `nfields` stacked full-grid fields of d directions (d_code: what a bad d is answered with)
+inline int check_field_count(int d, const int *dims, int nfields, int d_code = CHEBHIP_ERR_DIMS) {
+  if (!dims || d < 1 || d > 10) return chebhip_fail(d_code, "d = %d must be in 1..10", d);
+  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  return 0;
+}
+
+// The directions of such a handle, d and nfields checked: per direction its basis code (basis null: CGL everywhere), its extent, the cap
+// of a periodic direction and the running product nfields * prod n_k < 2^31.  *values_per_field = prod n_k, *S = sum n_k (or null).
+inline int check_field_extents(int d, const int *dims, const int *basis, int nfields, long *values_per_field, long *S) {
+  int rc;
+  long total = nfields, sum = 0;
+  for (int k = 0; k < d; k++) {
+    if (basis && basis[k] != CHEB_BASIS_CGL && basis[k] != CHEB_BASIS_FOURIER)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
+    if ((rc = check_extent(dims[k]))) return rc;
+    if (basis && basis[k] == CHEB_BASIS_FOURIER && dims[k] > 256)
+      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
+    total *= dims[k]; sum += dims[k];
+    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
+  }
+  if (values_per_field) *values_per_field = total / nfields;
+  if (S) *S = sum;
+  return 0;
+}
+
+// d, nfields, then the directions (cheb_reduce_create and cheb_stats_check call the halves, with a check of their own between them)
+inline int check_field_grid(int d, const int *dims, const int *basis, int nfields, long *values_per_field, long *S) {
+  int rc;
+  if ((rc = check_field_count(d, dims, nfields))) return rc;
+  return check_field_extents(d, dims, basis, nfields, values_per_field, S);
+}
+
+// The concatenated per-direction table of such a grid (weights, rates, spectrum bins): direction k's n_k entries start at off[k]
+template <class Off> void table_offsets(int d, const int *dims, Off *off) {
+  for (int k = 0, o = 0; k < d; o += dims[k], k++) off[k] = (Off)o;
+}
+template <class Off>      // ... filled with every direction's Clenshaw-Curtis weights
+std::vector<double> weight_table(int d, const int *dims, const Off *off, long S) {
+  std::vector<double> w(S);
+  for (int k = 0; k < d; k++) modal_weights_host(dims[k], w.data() + off[k]);
+  return w;
+}
+
+// direction k's n entries of a device table, from the host; null: back to the Clenshaw-Curtis weights.  Synchronous.
+inline int set_direction_weights(double *table, long off, int n, const double *w_host, const char *what) {
+  std::vector<double> def;
+  if (!w_host) { def.resize(n); modal_weights_host(n, def.data()); w_host = def.data(); }
+  hipError_t e = hipMemcpy(table + off, w_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_MEMORY, "%s: %s", what, hipGetErrorString(e));
+}
+
+// after a kernel launch: counts it, and fails with "<what> launch: <hip reason>" if it was refused
+inline int check_launch(const char *what) {
+  sweep_note_launch();
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
 }
 
 inline bool overlap(const double *a, long na, const double *b, long nb) { return a < b + nb && b < a + na; }

@@ -46,6 +46,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "rowpass.h"
 #include "linetile.h"
 #include <algorithm>
 #include <cmath>
@@ -57,8 +58,6 @@
 using namespace chebhip;
 
 namespace {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr int MD = 10;               // directions
 constexpr long WORK_MIN = 32L << 20; // bytes of work memory a handle may always take
@@ -250,19 +249,6 @@ __global__ __launch_bounds__(256) void k_points_frows(const RowsJob g) {
     if (outv) outv[j] = row_value(fin, ds, j == s, e, R);
     if (outd) outd[j] = !fin ? __builtin_nan("") : j == s ? -(P + F) / R2 : (f * R + p - e * F) / R2;
   }
-}
-
-// the pair (j, j + 1) of a row; the second value is 0 past the end of the row
-__device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
-  if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
-  d2 v; v.x = row[j]; v.y = j + 1 < n ? row[j + 1] : 0.0;
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
-  return s;
 }
 
 // The indices (i_1 .. i_{end-1}) of the flat index q over the directions 1 .. end - 1, the last one fastest: f(k, i_k) from
@@ -564,7 +550,7 @@ int launch_rows(const RowsJob &job, hipStream_t st, const char *what) {
     hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)part.nd), dim3(256), 0, st, part);
     sweep_note_launch();
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
+    if (e != hipSuccess)      // (two-part name: not check_launch)
       return chebhip_fail(CHEBHIP_ERR_DEVICE, "%s %srows launch: %s", what, periodic ? "periodic " : "", hipGetErrorString(e));
   }
   return 0;
@@ -588,14 +574,13 @@ void dispatch_dc(int d, F fn) {
   }
 }
 
-// one launch of the contraction (d >= 2: at d = 1 the line product's output is the result)
+// one launch of the contraction (d >= 2: at d = 1 the line product's output is the result); the caller checks it (check_launch)
 template <bool GRAD>
 void contract_launch(int d, dim3 grid, dim3 block, hipStream_t st, const PtGeo &g, const ConArgs &a) {
   dispatch_dc(d, [&](auto dc) {
     constexpr int DC = decltype(dc)::value > 1 ? decltype(dc)::value : 0;
     hipLaunchKernelGGL((k_points_contract<DC, GRAD>), grid, block, 0, st, g, a);
   });
-  sweep_note_launch();
 }
 
 // what the three *_matrix_host entries check after n, and their work: fill() writes the m rows
@@ -691,31 +676,22 @@ extern "C" int cheb_points_destroy(cheb_points *h) {
 static int points_create(int d, const int *dims, int nfields, const int *basis, cheb_points **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
   int rc;
-  long total = nfields, S = 0;
-  for (int k = 0; k < d; k++) {
-    if (basis && basis[k] != CHEB_BASIS_CGL && basis[k] != CHEB_BASIS_FOURIER)
-      return chebhip_fail(CHEBHIP_ERR_ARG, "basis[%d] = %d is neither 0 (CGL) nor 1 (Fourier)", k, basis[k]);
-    if ((rc = check_extent(dims[k]))) return rc;
-    if (basis && basis[k] == CHEB_BASIS_FOURIER && dims[k] > 256)
-      return chebhip_fail(CHEBHIP_ERR_ARG, "dims[%d] = %d: a periodic direction supports at most 256 points", k, dims[k]);
-    total *= dims[k]; S += dims[k];
-    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
-  }
+  long N = 0, S = 0;
+  if ((rc = check_field_grid(d, dims, basis, nfields, &N, &S))) return rc;
   if ((rc = require_device())) return rc;
+  const long total = nfields * N;
   cheb_points *h = new (std::nothrow) cheb_points;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
   h->d = d; h->nf = nfields; h->total = total;
   for (int k = 0; k < d; k++) h->basis[k] = basis ? basis[k] : CHEB_BASIS_CGL;
   PtGeo &g = h->geo;
   g.d = d;
-  for (int k = 0, o = 0; k < d; o += dims[k], k++) { g.n[k] = dims[k]; g.off[k] = (unsigned)o; }
-  g.B = (unsigned)(total / nfields / dims[0]);
+  for (int k = 0; k < d; k++) g.n[k] = dims[k];
+  table_offsets(d, dims, g.off);
+  g.B = (unsigned)(N / dims[0]);
   g.rpb = g.B / (unsigned)dims[d - 1];
-  g.lg = 0;
-  while (g.lg < 6 && (1 << g.lg) < (dims[d - 1] + 1) / 2) g.lg++;
+  g.lg = row_lanes_lg(dims[d - 1]);
 
   // the chunk: rows and direction 0's output within max(bytes of the fields, 32 MiB); a multiple of 128 (the line product's
   // tile of output points), of 64 below that, whatever fits below 64
@@ -831,8 +807,7 @@ int eval_run(cheb_points *h, const double *u, const double *xi, long npts, const
     }
     a.bs = cnt; a.out = out + p0;
     contract_launch<false>(d, dim3(cnt, (unsigned)h->nf), dim3(g.B <= 1024 ? 64 : 256), st, g, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval contraction launch: %s", hipGetErrorString(e));
+    if ((rc = check_launch("eval contraction"))) return rc;
   }
   return 0;
 }
@@ -886,8 +861,7 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
         if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad line product launch: %s", hipGetErrorString(e));
         a.out = out + p; a.vdst = c;
         contract_launch<false>(d, dim3(1, nf), block, st, g, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
+        if ((rc = check_launch("eval_grad contraction"))) return rc;
       }
     return 0;
   }
@@ -906,13 +880,11 @@ extern "C" int cheb_points_eval_grad(cheb_points *h, const double *u, const doub
     if (d == 1) {
       hipLaunchKernelGGL(k_points_grad1, dim3((cnt * nf + 255) / 256), dim3(256), 0, st, h->W, cnt, nf, value, a.scale[0], out + p0,
                          (size_t)npts);
-      sweep_note_launch();
     } else {
       a.V = h->W; a.D = h->W + (size_t)cnt * g.B; a.bs = 2 * cnt; a.out = out + p0;
       contract_launch<true>(d, dim3(cnt, nf, 2), block, st, g, a);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "eval_grad contraction launch: %s", hipGetErrorString(e));
+    if ((rc = check_launch("eval_grad contraction"))) return rc;
   }
   return 0;
 }
@@ -984,9 +956,7 @@ int spread_run(cheb_points *h, const double *s, const double *xi, long npts, con
     const SpreadArgs a{sp.buf, s + p0, (flags & CHEB_SPREAD_DELTA) ? h->iw : nullptr, out, (size_t)npts,
                        (unsigned)sp.P, cnt, (unsigned)h->nf * g.B, g.B, (accumulate || p0 > 0) ? 1 : 0};
     if (g.n[0] > 64) spread_launch<128>(d, g, a, st); else spread_launch<64>(d, g, a, st);
-    sweep_note_launch();
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "spread launch: %s", hipGetErrorString(e));
+    if ((rc = check_launch("spread"))) return rc;
   }
   return 0;
 }

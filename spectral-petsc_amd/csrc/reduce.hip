@@ -22,12 +22,13 @@
 //                   (j, j + 1) of one run of the output and adds W_c u over the contracted indices c of its slice, RB loads in
 //                   flight; the lanes of a wave read and store neighbouring pairs.
 // An output whose terms are many, or a contraction with too few outputs to fill the device, is cut into `slices` equal ranges of
-// c: slice s stores its partial sums at partial[s][output] and k_reduce_fold adds the slices in a fixed order (the scheme of
-// k_modal_fold; a copy, so that modal.hip keeps its code and its bits).  With one slice the kernels store into `out` directly.
+// c: slice s stores its partial sums at partial[s][output] and k_reduce_fold adds the slices in a fixed order.  With one slice
+// the kernels store into `out` directly.
 // No atomics; slices and the launch geometry depend on (dims, nfields, mask) alone; an output reads only the values it owns.
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "rowpass.h"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -39,14 +40,11 @@ static_assert(CHEB_W_INTEGRAL == REDUCE_W_INTEGRAL && CHEB_W_MEAN == REDUCE_W_ME
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 constexpr int MD = 10;                          // directions
 constexpr unsigned TARGET_LANES = 1u << 18;     // lanes a launch should have before an output's terms stop being sliced
 constexpr unsigned MAX_SLICES = 4096;
 constexpr unsigned MAX_WGS = 4096;             // k_reduce_rows: workgroups of a launch, all fields together
 constexpr unsigned MIN_ROWS = 4, MIN_TERMS = 8; // a slice has at least this many rows per lane group (rows) / terms (cols)
-constexpr int FOLD_PARTS = 64, FOLD_OUT = 4;    // k_reduce_fold: a workgroup adds 4 outputs from 64 parts of the slices each
 
 struct ReduceGeo {
   int nkg, ncd;                      // kept groups decoded from the output index (cols: without the trailing run); directions walked by c
@@ -59,13 +57,6 @@ struct ReduceGeo {
   unsigned nteams;                   // nunits * slices
   unsigned N, NT;                    // values of a field; nfields * nout
 };
-
-// the pair (j, j + 1) of a row; the second value is 0 past the end of the row
-__device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
-  if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
-  d2 v; v.x = row[j]; v.y = j + 1 < n ? row[j + 1] : 0.0;
-  return v;
-}
 
 // offset of the kept indices of output (or run) r
 __device__ __forceinline__ unsigned kept_offset(const ReduceGeo &g, unsigned r) {
@@ -189,7 +180,9 @@ __global__ __launch_bounds__(256) void k_reduce_cols(const ReduceGeo g, const do
 }
 
 // out[t] = sum over the slices of partial[slice][t], t < NT: thread (part, t) adds the slices part, part + 64, ... in ascending
-// order, then the 64 parts are added in ascending order.
+// order, then the 64 parts are added in ascending order.  (The scheme of k_modal_fold; each file keeps its
+// own kernel so that its code object stays what it was: with one shared kernel .text starts 256 bytes later and the rows route
+// ran 0.6 .. 1.5 % slower with identical kernels, profiles/fieldpass/ab.txt.)
 __global__ __launch_bounds__(256) void k_reduce_fold(const double *__restrict__ partial, unsigned slices, unsigned NT, double *__restrict__ out) {
   __shared__ double sp[FOLD_PARTS][FOLD_OUT];
   const unsigned bl = threadIdx.x % FOLD_OUT, part = threadIdx.x / FOLD_OUT, t = blockIdx.x * FOLD_OUT + bl;
@@ -263,32 +256,28 @@ extern "C" int cheb_reduce_destroy(cheb_reduce *h) {
 extern "C" int cheb_reduce_create(int d, const int *dims, int nfields, const int *contract, cheb_reduce **out) {
   if (!out) return chebhip_fail(CHEBHIP_ERR_ARG, "out is NULL");
   *out = nullptr;
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_DIMS, "d = %d must be in 1..10", d);
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
-  if (!contract) return chebhip_fail(CHEBHIP_ERR_ARG, "contract is NULL");
   int rc, nc = 0;
-  long total = nfields, S = 0;
-  for (int k = 0; k < d; k++) {
-    if ((rc = check_extent(dims[k]))) return rc;
-    total *= dims[k]; S += dims[k];
-    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
-    nc += contract[k] != 0;
-  }
+  long N = 0, S = 0;
+  if ((rc = check_field_count(d, dims, nfields))) return rc;
+  if (!contract) return chebhip_fail(CHEBHIP_ERR_ARG, "contract is NULL");
+  if ((rc = check_field_extents(d, dims, nullptr, nfields, &N, &S))) return rc;
+  for (int k = 0; k < d; k++) nc += contract[k] != 0;
   if (nc == 0) return chebhip_fail(CHEBHIP_ERR_ARG, "no direction is contracted");
   if ((rc = require_device())) return rc;
   cheb_reduce *h = new (std::nothrow) cheb_reduce;
   if (!h) return chebhip_fail(CHEBHIP_ERR_MEMORY, "out of host memory");
-  h->d = d; h->nf = nfields; h->total = total;
+  h->d = d; h->nf = nfields; h->total = nfields * N;
   h->rows = contract[d - 1] != 0;
   ReduceGeo &g = h->geo;
-  g.N = (unsigned)(total / nfields);
+  g.N = (unsigned)N;
   unsigned stride[MD];
   stride[d - 1] = 1;
   for (int k = d - 2; k >= 0; k--) stride[k] = stride[k + 1] * (unsigned)dims[k + 1];
-  std::vector<double> w(S, 0.0);
-  for (int k = 0, o = 0; k < d; o += dims[k], k++) {
-    h->n[k] = dims[k]; h->off[k] = o; h->contract[k] = contract[k] != 0;
-    if (contract[k]) modal_weights_host(dims[k], w.data() + o);
+  table_offsets(d, dims, h->off);
+  std::vector<double> w = weight_table(d, dims, h->off, S);
+  for (int k = 0; k < d; k++) {
+    h->n[k] = dims[k]; h->contract[k] = contract[k] != 0;
+    if (!contract[k]) std::fill_n(w.begin() + h->off[k], dims[k], 0.0);      // a kept direction takes no weights
   }
 
   // the directions c walks (rows: all contracted ones but the last), and the kept groups (cols: all but the trailing run)
@@ -317,8 +306,7 @@ extern "C" int cheb_reduce_create(int d, const int *dims, int nfields, const int
   if (h->rows) {
     const int n = dims[d - 1];
     g.n = (unsigned)n; g.wl = (unsigned)h->off[d - 1];
-    g.lg = 0;
-    while (g.lg < 6 && (1 << g.lg) < (n + 1) / 2) g.lg++;
+    g.lg = row_lanes_lg(n);
     g.lt = (d >= 2 && contract[d - 2]) ? 6 : g.lg;
     g.P = 0; g.nunits = g.nout;
     lanes_per_unit = 1u << g.lt;
@@ -359,10 +347,7 @@ extern "C" int cheb_reduce_set_weights(cheb_reduce *h, int k, const double *w_ho
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
   if (!h->contract[k]) return chebhip_fail(CHEBHIP_ERR_ARG, "direction %d is kept: it takes no weights", k);
-  std::vector<double> def;
-  if (!w_host) { def.resize(h->n[k]); modal_weights_host(h->n[k], def.data()); w_host = def.data(); }      // NULL: back to the default
-  hipError_t e = hipMemcpy(h->w + h->off[k], w_host, (size_t)h->n[k] * sizeof(double), hipMemcpyHostToDevice);
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_MEMORY, "reduction weights: %s", hipGetErrorString(e));
+  return set_direction_weights(h->w, h->off[k], h->n[k], w_host, "reduction weights");
 }
 
 extern "C" int cheb_reduce_apply(cheb_reduce *h, const double *u, const double *v, double *out, void *stream) {
@@ -384,14 +369,11 @@ extern "C" int cheb_reduce_apply(cheb_reduce *h, const double *u, const double *
       default: launch_cols<3>(g, h->grid, st, h->w, u, v, dst);
     }
   }
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "reduce launch: %s", hipGetErrorString(e));
+  int rc;
+  if ((rc = check_launch("reduce"))) return rc;
   if (g.slices > 1) {
     hipLaunchKernelGGL(k_reduce_fold, dim3((g.NT + FOLD_OUT - 1) / FOLD_OUT), dim3(256), 0, st, h->partial, g.slices, g.NT, out);
-    sweep_note_launch();
-    e = hipGetLastError();
-    if (e != hipSuccess) return chebhip_fail(CHEBHIP_ERR_DEVICE, "reduce fold launch: %s", hipGetErrorString(e));
+    return check_launch("reduce fold");
   }
   return 0;
 }

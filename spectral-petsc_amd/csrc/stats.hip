@@ -23,6 +23,7 @@
 #include "../../include/chebhip.h"
 #include "sweep.h"
 #include "ops.h"
+#include "rowpass.h"
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -32,8 +33,6 @@ using namespace chebhip;
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 constexpr int MD = 10;                          // directions
 constexpr unsigned NONE = 0xffffffffu;          // no element yet
 constexpr unsigned ROW_WGS = 2048;              // summary, cfl: workgroups of a launch, all fields together
@@ -42,7 +41,6 @@ constexpr unsigned HIST_WGS = 2048;             // histogram: workgroups of a la
 constexpr unsigned HIST_MIN = 8192;             // ... each of at least this many values
 constexpr int SUMMARY_OUT = 9, SUMMARY_PART = 9;
 constexpr unsigned SERIAL_MIN = 8;              // k_stats_hist: lanes of a batch in one slot from which they are added in registers
-constexpr int FOLD_PARTS = 64, FOLD_OUT = 4;    // k_stats_fold_hist: a workgroup adds 4 outputs from 64 parts of the workgroups each
 
 struct StatsGeo {
   int d;
@@ -51,13 +49,6 @@ struct StatsGeo {
   int lg;                           // log2 of the lanes per row
   unsigned G;                       // workgroups per field (summary, cfl)
 };
-
-// the pair (j, j + 1) of a row; the second value is 0 past the end of the row
-__device__ __forceinline__ d2 load_pair(const double *row, bool aligned, unsigned j, unsigned n) {
-  if (aligned && j + 1 < n) return *reinterpret_cast<const d2 *>(row + j);
-  d2 v; v.x = row[j]; v.y = j + 1 < n ? row[j + 1] : 0.0;
-  return v;
-}
 
 // is the element (a, ia) ahead of (b, ib) as a minimum (SGN = +1) or as a maximum (SGN = -1)?  NONE loses against every element.
 template <int SGN>
@@ -403,7 +394,9 @@ __global__ __launch_bounds__(256) void k_stats_hist(const StatsGeo g, const doub
 }
 
 // out[f][0][s] = the sum over the workgroups of their masses, out[f][1][s] of their counts: thread (part, t) adds the workgroups
-// part, part + 64, .. in ascending order, then the 64 parts are added in ascending order (the scheme of k_reduce_fold; a copy)
+// part, part + 64, .. in ascending order, then the parts are added in ascending order: the tiling of k_modal_fold and k_reduce_fold, but not
+// their sum: a part starts from its first term, not from 0.0, and a part without a term is left out, so that a sum of -0.0 terms
+// keeps its sign, and the integer counts ride along.  Those are other bits, on purpose.
 __global__ __launch_bounds__(256) void k_stats_fold_hist(const double *__restrict__ pm, const unsigned *__restrict__ pc, unsigned G,
                                                          unsigned slots, unsigned nf, double *__restrict__ out) {
   __shared__ double spm[FOLD_PARTS][FOLD_OUT];
@@ -426,12 +419,6 @@ __global__ __launch_bounds__(256) void k_stats_fold_hist(const double *__restric
     out[(size_t)f * 2 * slots + s] = m;
     out[(size_t)f * 2 * slots + slots + s] = (double)c;
   }
-}
-
-int check_launch(const char *what) {
-  sweep_note_launch();
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
 }
 
 }  // namespace
@@ -469,18 +456,12 @@ extern "C" int cheb_stats_rate_host(int n, double s, double *r) {
 }
 
 extern "C" int cheb_stats_check(int d, const int *dims, int nfields, int max_bins, int nbins) {
-  if (!dims || d < 1 || d > MD) return chebhip_fail(CHEBHIP_ERR_ARG, "d = %d must be in 1..10", d);
-  if (nfields < 1 || nfields > 16) return chebhip_fail(CHEBHIP_ERR_ARG, "nfields = %d must be in 1..16", nfields);
+  int rc;
+  // (this module answers a bad d with CHEBHIP_ERR_ARG where every other module says CHEBHIP_ERR_DIMS: kept)
+  if ((rc = check_field_count(d, dims, nfields, CHEBHIP_ERR_ARG))) return rc;
   if (max_bins < 1 || max_bins > 1024) return chebhip_fail(CHEBHIP_ERR_ARG, "max_bins = %d must be in 1..1024", max_bins);
   if (nbins < 1 || nbins > max_bins) return chebhip_fail(CHEBHIP_ERR_ARG, "nbins = %d must be in 1..max_bins = %d", nbins, max_bins);
-  long total = nfields;
-  for (int k = 0; k < d; k++) {
-    int rc;
-    if ((rc = check_extent(dims[k]))) return rc;
-    total *= dims[k];
-    if (total >= 0x80000000L) return chebhip_fail(CHEBHIP_ERR_DIMS, "2^31 values or more");
-  }
-  return 0;
+  return check_field_extents(d, dims, nullptr, nfields, nullptr, nullptr);
 }
 
 extern "C" int cheb_stats_destroy(cheb_stats *h) {
@@ -507,11 +488,11 @@ extern "C" int cheb_stats_create(int d, const int *dims, int nfields, int max_bi
   g.d = d;
   long T = 1;
   int S = 0;
-  for (int k = 0; k < d; k++) { g.n[k] = (unsigned)dims[k]; g.off[k] = (unsigned)S; S += dims[k]; T *= dims[k]; }
+  for (int k = 0; k < d; k++) { g.n[k] = (unsigned)dims[k]; S += dims[k]; T *= dims[k]; }
+  table_offsets(d, dims, g.off);
   h->S = S; h->total = T * nfields;
   g.T = (unsigned)T; g.nlast = (unsigned)dims[d - 1]; g.R = g.T / g.nlast;
-  g.lg = 0;
-  while (g.lg < 6 && (1 << g.lg) < (dims[d - 1] + 1) / 2) g.lg++;
+  g.lg = row_lanes_lg(dims[d - 1]);
   // launch geometry, fixed per handle: a function of the shape alone
   const unsigned per_wg = 256u >> g.lg, passes = (g.R + per_wg - 1) / per_wg;
   g.G = std::max(1u, std::min(std::min((g.T + ROW_MIN - 1) / ROW_MIN, passes), ROW_WGS / (unsigned)nfields));
@@ -519,8 +500,7 @@ extern "C" int cheb_stats_create(int d, const int *dims, int nfields, int max_bi
   h->chunk = ((g.T + h->Gh - 1) / h->Gh + 255u) / 256u * 256u;
   h->Gh = (g.T + h->chunk - 1) / h->chunk;
 
-  std::vector<double> w(S);
-  for (int k = 0; k < d; k++) modal_weights_host(dims[k], w.data() + g.off[k]);
+  const std::vector<double> w = weight_table(d, dims, g.off, S);
   const size_t slots = (size_t)max_bins + 3;
   rc = device_array(&h->w, S, w.data(), "stats weights");
   if (!rc) rc = device_array(&h->rate, S, nullptr, "stats rates");
@@ -550,11 +530,7 @@ extern "C" long cheb_stats_size(const cheb_stats *h, int which) {
 extern "C" int cheb_stats_set_weights(cheb_stats *h, int k, const double *w_host) {
   if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
   if (k < 0 || k >= h->d) return chebhip_fail(CHEBHIP_ERR_TDIM, "direction %d out of range 0..%d", k, h->d - 1);
-  const int n = (int)h->geo.n[k];
-  std::vector<double> def;
-  if (!w_host) { def.resize(n); modal_weights_host(n, def.data()); w_host = def.data(); }      // NULL: back to the default
-  hipError_t e = hipMemcpy(h->w + h->geo.off[k], w_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-  return e == hipSuccess ? 0 : chebhip_fail(CHEBHIP_ERR_MEMORY, "stats weights: %s", hipGetErrorString(e));
+  return set_direction_weights(h->w, h->geo.off[k], (int)h->geo.n[k], w_host, "stats weights");
 }
 
 extern "C" int cheb_stats_summary(cheb_stats *h, const double *u, const double *center, double *out, void *stream) {
