@@ -1181,6 +1181,27 @@ int  cheb_varhelm_set_coefficients(cheb_varhelm *h, const double *kappa_dev, con
 double cheb_varhelm_sigma(const cheb_varhelm *h);         /* sigma_p; -1 before set_coefficients */
 /* 1: c == 0 and every direction periodic or Neumann / Neumann (the inner direct solve is singular): solve refuses; -1: no coefficients yet */
 int  cheb_varhelm_singular(const cheb_varhelm *h);
+/* Tensor diffusivity and advection, d = 2 or 3 (any other d: CHEBHIP_ERR_ARG).  With W the extension above and
+ * directions ascending in every sum:
+ *     G_k = s_k D_k W  (k < d, the whole grid),   F_j = sum_k K_jk G_k,   a = sum_k v_k G_k,   y = c x + a - sum_j s_j D_j F_j
+ * at the unknown nodes: c u + v . grad u - div(K grad u).  K_dev: d (d + 1) / 2 full-grid fields one after the other, the
+ * diagonal first, then the upper triangle row-major -- d = 3: 00 11 22 01 02 12; d = 2: 00 11 01 -- finite and positive definite
+ * at EVERY node (it is read at face nodes too; the test is the leading principal minors in double: K00 > 0, K00 K11 - K01^2 > 0,
+ * det K > 0).  vel_dev: d full-grid fields, finite, or NULL (no advection).  c as in set_coefficients.  One K, v and c for all
+ * stacked fields.  The faces carry alpha u + beta s_k du/dnu = g with NEITHER K NOR v (conormal data n . K grad u is not built).
+ * Unlike the scalar operator this one reads the tangential derivatives of W on the faces, hence the edge values of the extension
+ * (every boundary node set once, by the highest direction in which it is an end node); corner values influence nothing.
+ * Synchronous like set_coefficients, with the same refusals (the handle keeps what it had); the first call allocates the copies
+ * of K and v and d gradient grids per field (cheb_varhelm_work_bytes grows by them).  The preconditioner becomes
+ * H(sigma_p)^-1 (r / kbar), kbar = trace(K) / d, sigma_p = mean of c / kbar over the unknown nodes: it ignores v and the
+ * anisotropy.  Every other entry point works as in the scalar mode (the null space of a singular handle is the same);
+ * cheb_varhelm_set_coefficients puts the handle back into the scalar mode, and after either call it gives the bits of a fresh
+ * handle that received that call alone. */
+int  cheb_varhelm_set_tensor(cheb_varhelm *h, const double *K_dev, const double *vel_dev, const double *c_dev, double c_scalar, void *stream);
+#define CHEB_VARHELM_MODE_NONE   0
+#define CHEB_VARHELM_MODE_SCALAR 1
+#define CHEB_VARHELM_MODE_TENSOR 2
+int  cheb_varhelm_mode(const cheb_varhelm *h);            /* which setter came last; -1: NULL */
 /* y = the linear operator (g = 0) of x; out = f - (the operator at g)(x).  Asynchronous on the stream, no allocation; the output
  * may overlap no input (CHEBHIP_ERR_ARG).  cheb_varhelm_apply: mult with the shape of chebhip_apply_fn (ctx = the handle). */
 int  cheb_varhelm_mult(cheb_varhelm *h, const double *x_dev, double *y_dev, void *stream);

@@ -98,6 +98,7 @@ ABI_SYMBOLS = [
     "cheb_varhelm_last_residual", "cheb_varhelm_reason",
     "cheb_varhelm_solve_deflated", "cheb_varhelm_null_count", "cheb_varhelm_defect", "cheb_varhelm_null_signs_host",
     "cheb_varhelm_remove_null", "cheb_varhelm_apply_deflated", "cheb_varhelm_precond_deflated",
+    "cheb_varhelm_set_tensor", "cheb_varhelm_mode",
     "cheb_project_create_variable", "cheb_project_set_inverse_density", "cheb_project_apply_variable", "cheb_project_varhelm",
 ]
 
@@ -405,6 +406,8 @@ def lib():
             f.argtypes = [vp]
             f.restype = C.c_long
         L.cheb_varhelm_set_coefficients.argtypes = [vp, vp, vp, C.c_double, vp]
+        L.cheb_varhelm_set_tensor.argtypes = [vp, vp, vp, vp, C.c_double, vp]
+        L.cheb_varhelm_mode.argtypes = [vp]
         L.cheb_varhelm_sigma.argtypes = [vp]
         L.cheb_varhelm_sigma.restype = C.c_double
         L.cheb_varhelm_singular.argtypes = [vp]
@@ -1765,6 +1768,21 @@ class VarHelmholtz(_Handle):
         _chk(lib().cheb_varhelm_set_coefficients(self._h, self._vec("kappa", kappa, self.nodes), self._vec("c", c, self.nodes) if cf else None,
                                                  0.0 if cf else float(c), _stream()))
 
+    def set_tensor(self, K, c=0.0, vel=None):
+        """The tensor mode (cheb_varhelm_set_tensor; 2-D and 3-D): the operator becomes
+        c u + vel . grad u - div(K grad u).  K: the d (d + 1) / 2 full-grid fields of a symmetric positive definite tensor, stacked
+        in the order tensor_order(d) (diagonal first, then the upper triangle row-major); vel: d stacked full-grid fields or None;
+        c as in set_coefficients.  Synchronises.  Raises ChebhipError (code 4) for another d, where K is not finite and positive
+        definite at some node, vel is not finite or c is negative or not finite; the handle then keeps what it had.  precond
+        becomes H(sigma_p)^-1 (r / kbar) with kbar = trace(K) / d; set_coefficients returns the handle to the scalar mode."""
+        import torch
+        d = len(self.dims)
+        cf = isinstance(c, torch.Tensor)
+        _chk(lib().cheb_varhelm_set_tensor(self._h, self._vec("K", K, len(tensor_order(d)) * self.nodes),
+                                           self._vec("vel", vel, d * self.nodes, True), self._vec("c", c, self.nodes) if cf else None,
+                                           0.0 if cf else float(c), _stream()))
+
+    mode = property(lambda self: lib().cheb_varhelm_mode(self._h), doc="0: no coefficients yet, 1: scalar (set_coefficients), 2: tensor (set_tensor)")
     sigma = property(lambda self: lib().cheb_varhelm_sigma(self._h))
     singular = property(lambda self: bool(lib().cheb_varhelm_singular(self._h) == 1))
 
@@ -1848,6 +1866,13 @@ class VarHelmholtz(_Handle):
         """z = Pi precond(r): the right preconditioner of solve_deflated (m_entry="precond_deflated")."""
         _chk(lib().cheb_varhelm_precond_deflated(self._h, self._vec("r", r, self.size), self._vec("z", z, self.size), _stream()))
         return z
+
+
+def tensor_order(d):
+    """The index pairs (j, k) of the fields VarHelmholtz.set_tensor takes, in its order: the diagonal, then the upper triangle
+    row-major -- d = 3: 00 11 22 01 02 12."""
+    d = int(d)
+    return [(j, j) for j in range(d)] + [(j, k) for j in range(d) for k in range(j + 1, d)]
 
 
 def null_signs(dims, periodic):

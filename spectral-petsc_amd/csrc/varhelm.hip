@@ -24,6 +24,13 @@
 // constant and, per periodic direction of even extent, the Nyquist vector).  solve_deflated is the same FGMRES on Pi A with the
 // preconditioner Pi H(0)^-1 (r / kappa), Pi = I - N N^T / G per field, between projections of b, of the guess and of the result;
 // Pi is the three launches k_vh_null_partial, k_vh_null_total, k_vh_null_subtract below (fixed addition order, no atomics).
+//
+// Tensor mode (set_tensor).  c u + v . grad u - div( K grad u ), K a symmetric positive definite d x d tensor field
+// (d = 2, 3), v a velocity field or none: the same extension, then G_k = s_k D_k W on the whole grid (d sweeps), the node pass
+// k_vh_flux (F_j = sum_k K_jk G_k over G_j, a = sum_k v_k G_k into A), then A (+)= -s_j D_j F_j (d sweeps) and the same closing pass.
+// Here the lines that lie on a face matter: F_j at a face node of direction j holds the tangential derivatives G_k of W on that
+// face, whose end values are edge values of W -- those of the extension, every boundary node set once by the highest direction in
+// which it is an end node.  The preconditioner and the solves are the scalar mode's on kappa = trace(K) / d.
 #include "../../include/chebhip.h"
 #include "ops.h"
 #include "sweep.h"
@@ -126,6 +133,125 @@ __global__ __launch_bounds__(256) void k_vh_coef_check(VhGeo geo, const double *
     __syncthreads();
   }
   if (threadIdx.x == 0) { part[blockIdx.x] = sh[0]; bad[blockIdx.x] = shb[0]; }
+}
+
+// ---- tensor mode -------------------------------------------------------------------------------------------------------
+// K: d (d + 1) / 2 full grids, the diagonal first, then the upper triangle row-major (3-D: 00 11 22 01 02 12; 2-D: 00 11 01).
+// The mean diagonal entry: what the preconditioner divides by
+template <int D>
+__device__ __forceinline__ double vh_kbar(const double *__restrict__ K, unsigned N, unsigned n) {
+  double t = K[n] + K[(size_t)N + n];
+  if (D == 3) t += K[2 * (size_t)N + n];
+  return t / (double)D;
+}
+__device__ __forceinline__ bool vh_finite(double a) { return a - a == 0.0; }
+// finite and positive definite by its leading principal minors
+template <int D>
+__device__ __forceinline__ bool vh_spd(const double *__restrict__ K, unsigned N, unsigned n) {
+  const size_t s = N;
+  if (D == 2) {
+    const double k00 = K[n], k11 = K[s + n], k01 = K[2 * s + n];
+    if (!vh_finite(k00) || !vh_finite(k11) || !vh_finite(k01)) return false;
+    return k00 > 0.0 && k00 * k11 - k01 * k01 > 0.0;
+  }
+  const double k00 = K[n], k11 = K[s + n], k22 = K[2 * s + n], k01 = K[3 * s + n], k02 = K[4 * s + n], k12 = K[5 * s + n];
+  if (!vh_finite(k00) || !vh_finite(k11) || !vh_finite(k22) || !vh_finite(k01) || !vh_finite(k02) || !vh_finite(k12)) return false;
+  const double det = k00 * (k11 * k22 - k12 * k12) - k01 * (k01 * k22 - k12 * k02) + k02 * (k01 * k12 - k11 * k02);
+  return k00 > 0.0 && k00 * k11 - k01 * k01 > 0.0 && det > 0.0;
+}
+
+// set_tensor: k_vh_coef_check for a tensor.  bad[b] = block b's count of full-grid nodes where K is not finite and positive
+// definite, v (if given) or c not finite, or c < 0; kbar[n] = trace(K) / d at every node; part[b] = the block's share of
+// sum c / kbar over the unknown nodes (a thread's nodes in turn, the block's tree, the host adds the VH_RB shares in turn)
+template <int D>
+__global__ __launch_bounds__(256) void k_vh_tensor_check(VhGeo geo, const double *__restrict__ K, const double *__restrict__ vel, const double *__restrict__ cf,
+                                                         double c0, double *__restrict__ kbar, double *__restrict__ part, unsigned *__restrict__ bad) {
+  __shared__ double sh[256];
+  __shared__ unsigned shb[256];
+  unsigned nb = 0;
+  for (unsigned n = blockIdx.x * 256u + threadIdx.x; n < geo.N; n += gridDim.x * 256u) {
+    bool ok = vh_spd<D>(K, geo.N, n);
+    if (vel)
+#pragma unroll
+      for (int k = 0; k < D; k++) ok = ok && vh_finite(vel[(size_t)k * geo.N + n]);
+    const double c = cf ? cf[n] : c0;
+    if (!ok || !(c >= 0.0) || !vh_finite(c)) nb++;
+    kbar[n] = vh_kbar<D>(K, geo.N, n);
+  }
+  double s = 0.0;
+  for (unsigned q = blockIdx.x * 256u + threadIdx.x; q < geo.G; q += gridDim.x * 256u) {
+    const unsigned n = vh_node(geo, q);
+    s += (cf ? cf[n] : c0) / vh_kbar<D>(K, geo.N, n);
+  }
+  sh[threadIdx.x] = s; shb[threadIdx.x] = nb;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { sh[threadIdx.x] += sh[threadIdx.x + o]; shb[threadIdx.x] += shb[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { part[blockIdx.x] = sh[0]; bad[blockIdx.x] = shb[0]; }
+}
+
+// two consecutive doubles (two = false: the first alone, the last node of an odd grid): one 16-byte access where the address
+// allows it -- the stacked grids of an odd N put every other field on an 8-byte boundary -- else 8-byte ones
+__device__ __forceinline__ vh2 vh_ld2(const double *p, bool two) {
+  if (two && ((size_t)p & 15) == 0) return *reinterpret_cast<const vh2 *>(p);
+  return (vh2){p[0], two ? p[1] : 0.0};
+}
+__device__ __forceinline__ void vh_st2(double *p, vh2 v, bool two) {
+  if (two && ((size_t)p & 15) == 0) { *reinterpret_cast<vh2 *>(p) = v; return; }
+  p[0] = v.x;
+  if (two) p[1] = v.y;
+}
+// sum_k a_k g_k, k ascending: one product, then fused multiply-adds, written out -- D roundings whatever the compiler's
+// contraction setting and whatever the width of the accesses around it
+__device__ __forceinline__ double vh_dot2(double a0, double a1, double g0, double g1) { return __builtin_fma(a1, g1, a0 * g0); }
+__device__ __forceinline__ double vh_dot3(double a0, double a1, double a2, double g0, double g1, double g2) {
+  return __builtin_fma(a2, g2, __builtin_fma(a1, g1, a0 * g0));
+}
+
+// The node pass of the tensor mode, field = blockIdx.y, a lane per pair of neighbouring nodes of the full grid: G_k = Gt + k gs
+// (k < D) are the scaled gradients of the nf stacked fields; on return G_j holds F_j = sum_k K_jk G_k and, with a velocity, A
+// holds a = sum_k v_k G_k.  K and vel are indexed by node (one copy for all fields).  A lane reads all it needs before its first
+// store and no lane reads another's nodes: in place.  No LDS, no atomics; the sums are vh_dot2 / vh_dot3 (explicit fused
+// multiply-adds), so their rounding does not depend on the access width.
+template <int D, bool VEL>
+__global__ __launch_bounds__(256) void k_vh_flux(unsigned N, size_t gs, const double *__restrict__ K, const double *__restrict__ vel,
+                                                 double *Gt, double *__restrict__ A) {
+  const unsigned per = (N + 1u) / 2u;
+  const size_t fo = (size_t)blockIdx.y * N, s = N;
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < per; t += gridDim.x * 256u) {
+    const unsigned n = 2u * t;
+    const bool two = n + 1u < N;
+    double *g = Gt + fo + n;
+    const vh2 g0 = vh_ld2(g, two), g1 = vh_ld2(g + gs, two);
+    const vh2 k00 = vh_ld2(K + n, two), k11 = vh_ld2(K + s + n, two);
+    if (D == 2) {
+      const vh2 k01 = vh_ld2(K + 2 * s + n, two);
+      vh2 a = {0.0, 0.0};
+      if (VEL) {
+        const vh2 v0 = vh_ld2(vel + n, two), v1 = vh_ld2(vel + s + n, two);
+        a = (vh2){vh_dot2(v0.x, v1.x, g0.x, g1.x), vh_dot2(v0.y, v1.y, g0.y, g1.y)};
+      }
+      const vh2 f0 = {vh_dot2(k00.x, k01.x, g0.x, g1.x), vh_dot2(k00.y, k01.y, g0.y, g1.y)};
+      const vh2 f1 = {vh_dot2(k01.x, k11.x, g0.x, g1.x), vh_dot2(k01.y, k11.y, g0.y, g1.y)};
+      vh_st2(g, f0, two); vh_st2(g + gs, f1, two);
+      if (VEL) vh_st2(A + fo + n, a, two);
+    } else {
+      const vh2 g2 = vh_ld2(g + 2 * gs, two);
+      const vh2 k22 = vh_ld2(K + 2 * s + n, two), k01 = vh_ld2(K + 3 * s + n, two), k02 = vh_ld2(K + 4 * s + n, two), k12 = vh_ld2(K + 5 * s + n, two);
+      vh2 a = {0.0, 0.0};
+      if (VEL) {
+        const vh2 v0 = vh_ld2(vel + n, two), v1 = vh_ld2(vel + s + n, two), v2 = vh_ld2(vel + 2 * s + n, two);
+        a = (vh2){vh_dot3(v0.x, v1.x, v2.x, g0.x, g1.x, g2.x), vh_dot3(v0.y, v1.y, v2.y, g0.y, g1.y, g2.y)};
+      }
+      const vh2 f0 = {vh_dot3(k00.x, k01.x, k02.x, g0.x, g1.x, g2.x), vh_dot3(k00.y, k01.y, k02.y, g0.y, g1.y, g2.y)};
+      const vh2 f1 = {vh_dot3(k01.x, k11.x, k12.x, g0.x, g1.x, g2.x), vh_dot3(k01.y, k11.y, k12.y, g0.y, g1.y, g2.y)};
+      const vh2 f2 = {vh_dot3(k02.x, k12.x, k22.x, g0.x, g1.x, g2.x), vh_dot3(k02.y, k12.y, k22.y, g0.y, g1.y, g2.y)};
+      vh_st2(g, f0, two); vh_st2(g + gs, f1, two); vh_st2(g + 2 * gs, f2, two);
+      if (VEL) vh_st2(A + fo + n, a, two);
+    }
+  }
 }
 
 // ---- the projection Pi = I - N N^T / G of the deflated solve ------------------------------------------------------------
@@ -252,6 +378,7 @@ struct cheb_varhelm {
   int d = 0, nf = 1;
   int P[VMAXD] = {0}, basis[VMAXD] = {0};
   double s2[VMAXD] = {0};                      // fl(s_k s_k): the factor of direction k is alpha = -s2[k]
+  double s1[VMAXD] = {0};                      // s_k: the factor of both sweeps of the tensor mode
   unsigned inner[VMAXD] = {0};
   VhGeo geo = {};
   long N = 0, G = 0, NB = 0;
@@ -261,6 +388,10 @@ struct cheb_varhelm {
   double *Wf = nullptr, *Gk = nullptr, *A = nullptr;   // nf full grids each: the extension, one gradient, the sum
   double *kap = nullptr;                       // nf stacked copies of kappa
   double *cfield = nullptr; double c0 = 0.0; bool c_is_field = false;
+  int mode = 0;                                // CHEB_VARHELM_MODE_*: none, scalar (set_coefficients), tensor (set_tensor)
+  double *Kt = nullptr, *vel = nullptr;        // tensor mode, made by the first set_tensor: d (d + 1) / 2 and d full grids, one copy for all fields
+  double *Gt = nullptr;                        // ... and d gradient grids of nf fields each
+  bool has_vel = false;
   double *tu = nullptr, *bu = nullptr, *zero = nullptr;  // nf G each: r / kappa, the solve's right-hand side, a zero vector
   double *part = nullptr; unsigned *bad = nullptr;
   VhNull null = {};                            // the even periodic directions; null.m > 3: the deflated calls refuse
@@ -319,12 +450,41 @@ int vh_flux_sum(cheb_varhelm *h, const double *W, hipStream_t st) {
   return 0;
 }
 
+// tensor mode: A = sum_k v_k G_k - sum_j s_j D_j( sum_k K_jk G_k ), G_k = s_k D_k W, on nf full grids
+int vh_tensor_sum(cheb_varhelm *h, const double *W, hipStream_t st) {
+  const size_t gs = (size_t)h->nf * h->N;
+  SweepParams sp = {};
+  for (int k = 0; k < h->d; k++) {
+    sp.ncols = (unsigned)((long)h->nf * h->N / h->P[k]); sp.inner = h->inner[k];
+    sp.in0 = W; sp.in_mode = IN_PLAIN; sp.alpha = h->s1[k]; sp.out = h->Gt + k * gs; sp.out_mode = OUT_STORE; sp.acc = nullptr;
+    HIP_TRY(sweep_launch(*h->Dk[k], sp, st));
+  }
+  const dim3 grid(grid1d(((long)h->N + 1) / 2, 256, 4096), (unsigned)h->nf);
+  const unsigned N = (unsigned)h->N;
+  if (h->d == 2) {
+    if (h->has_vel) hipLaunchKernelGGL((k_vh_flux<2, true>), grid, dim3(256), 0, st, N, gs, (const double *)h->Kt, (const double *)h->vel, h->Gt, h->A);
+    else hipLaunchKernelGGL((k_vh_flux<2, false>), grid, dim3(256), 0, st, N, gs, (const double *)h->Kt, (const double *)nullptr, h->Gt, h->A);
+  } else {
+    if (h->has_vel) hipLaunchKernelGGL((k_vh_flux<3, true>), grid, dim3(256), 0, st, N, gs, (const double *)h->Kt, (const double *)h->vel, h->Gt, h->A);
+    else hipLaunchKernelGGL((k_vh_flux<3, false>), grid, dim3(256), 0, st, N, gs, (const double *)h->Kt, (const double *)nullptr, h->Gt, h->A);
+  }
+  sweep_note_launch();
+  HIP_TRY(hipGetLastError());
+  for (int j = 0; j < h->d; j++) {
+    sp.ncols = (unsigned)((long)h->nf * h->N / h->P[j]); sp.inner = h->inner[j];
+    sp.in0 = h->Gt + j * gs; sp.alpha = -h->s1[j]; sp.out = h->A;
+    if (j > 0 || h->has_vel) { sp.out_mode = OUT_ACC; sp.acc = h->A; } else { sp.out_mode = OUT_STORE; sp.acc = nullptr; }
+    HIP_TRY(sweep_launch(*h->Dk[j], sp, st));
+  }
+  return 0;
+}
+
 // out = (operator at g)(x), or f - that
 int vh_operator(cheb_varhelm *h, const double *x, const double *f, const double *g, double *out, hipStream_t st) {
   if (!h->have_coef) return chebhip_fail(CHEBHIP_ERR_ARG, "cheb_varhelm: set_coefficients has not been called");
   const double *W = x;                         // no wall: the unknown layout is the full grid
   if (h->NB) { int rc = helmholtz_extend(h->H, x, g, h->Wf, st); if (rc) return rc; W = h->Wf; }
-  int rc = vh_flux_sum(h, W, st); if (rc) return rc;
+  int rc = h->mode == CHEB_VARHELM_MODE_TENSOR ? vh_tensor_sum(h, W, st) : vh_flux_sum(h, W, st); if (rc) return rc;
   const bool vec = vh_pairs(h, x, f, out);
   vh_launch_rows(k_vh_close<1>, k_vh_close<2>, vec, h, st, (const double *)h->A, (const double *)(h->c_is_field ? h->cfield : nullptr), h->c0, x, f, out);
   HIP_TRY(hipGetLastError());
@@ -395,7 +555,7 @@ extern "C" int cheb_varhelm_destroy(cheb_varhelm *h) {
   if (h->krylov) chebhip_fgmres_destroy(h->krylov);
   if (h->H) cheb_helmholtz_destroy(h->H);
   for (auto &kv : h->D) diffmat_destroy(&kv.second);
-  double *all[] = {h->Wf, h->Gk, h->A, h->kap, h->cfield, h->tu, h->bu, h->zero, h->part, h->npart, h->ntot, h->dtot};
+  double *all[] = {h->Wf, h->Gk, h->A, h->kap, h->cfield, h->tu, h->bu, h->zero, h->part, h->npart, h->ntot, h->dtot, h->Kt, h->vel, h->Gt};
   for (double *p : all) if (p) (void)hipFree(p);
   if (h->bad) (void)hipFree(h->bad);
   delete h;
@@ -420,7 +580,7 @@ extern "C" int cheb_varhelm_create(int d, const int *dims, const int *basis, con
   for (int k = d - 1; k >= 0; k--) {
     h->P[k] = dims[k]; h->basis[k] = basis ? basis[k] : BASIS_CGL;
     const double s = scale ? scale[k] : 1.0;
-    h->s2[k] = s * s;
+    h->s2[k] = s * s; h->s1[k] = s;
     h->inner[k] = (unsigned)N;
     geo.off[k] = h->basis[k] == BASIS_FOURIER ? 0 : 1; geo.M[k] = dims[k] - 2 * geo.off[k]; geo.ls[k] = (int)N;
     N *= dims[k]; G *= geo.M[k];
@@ -484,7 +644,45 @@ extern "C" int cheb_varhelm_set_coefficients(cheb_varhelm *h, const double *kapp
   if (c_dev) HIP_TRY(hipMemcpyAsync(h->cfield, c_dev, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice, st));
   h->c_is_field = c_dev != nullptr; h->c0 = c_dev ? 0.0 : c_scalar;
   HIP_TRY(hipStreamSynchronize(st));              // the call is synchronous: the copies are complete for every stream when it returns
-  h->sigma_p = sigma; h->have_coef = true;
+  h->sigma_p = sigma; h->have_coef = true; h->mode = CHEB_VARHELM_MODE_SCALAR;
+  return 0;
+}
+
+extern "C" int cheb_varhelm_mode(const cheb_varhelm *h) { return h ? h->mode : -1; }
+
+extern "C" int cheb_varhelm_set_tensor(cheb_varhelm *h, const double *K_dev, const double *vel_dev, const double *c_dev, double c_scalar, void *stream) {
+  if (!h) return chebhip_fail(CHEBHIP_ERR_ARG, "NULL handle");
+  if (h->d != 2 && h->d != 3) return chebhip_fail(CHEBHIP_ERR_ARG, "set_tensor: d = %d; the tensor mode exists for d = 2 and d = 3", h->d);
+  if (!K_dev) return chebhip_fail(CHEBHIP_ERR_ARG, "K is NULL");
+  if (!c_dev && (!(c_scalar >= 0.0) || !std::isfinite(c_scalar))) return chebhip_fail(CHEBHIP_ERR_ARG, "c = %g must be finite and >= 0", c_scalar);
+  hipStream_t st = (hipStream_t)stream;
+  const int d = h->d, nk = d * (d + 1) / 2;
+  const size_t N = (size_t)h->N;
+  int rc;
+  if ((!h->Kt && (rc = vh_alloc(h, &h->Kt, nk * N))) || (!h->vel && (rc = vh_alloc(h, &h->vel, d * N))) ||
+      (!h->Gt && (rc = vh_alloc(h, &h->Gt, d * (size_t)h->nf * N)))) return rc;
+  // no earlier call of this handle is still using the gradient grids: the check leaves trace(K) / d in the first of them, and
+  // nothing of the handle's coefficients changes before it has passed
+  HIP_TRY(hipDeviceSynchronize());
+  if (d == 2) hipLaunchKernelGGL(k_vh_tensor_check<2>, dim3(VH_RB), dim3(256), 0, st, h->geo, K_dev, vel_dev, c_dev, c_scalar, h->Gt, h->part, h->bad);
+  else hipLaunchKernelGGL(k_vh_tensor_check<3>, dim3(VH_RB), dim3(256), 0, st, h->geo, K_dev, vel_dev, c_dev, c_scalar, h->Gt, h->part, h->bad);
+  HIP_TRY(hipGetLastError());
+  double part[VH_RB]; unsigned bad[VH_RB];
+  HIP_TRY(hipMemcpyAsync(part, h->part, sizeof(part), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(bad, h->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipDeviceSynchronize());
+  double s = 0.0; unsigned long nbad = 0;
+  for (int b = 0; b < VH_RB; b++) { s += part[b]; nbad += bad[b]; }
+  if (nbad) return chebhip_fail(CHEBHIP_ERR_ARG, "set_tensor: %lu nodes where K is not finite and positive definite, v is not finite or c is not finite and >= 0", nbad);
+  const double sigma = h->G ? s / (double)h->G : 0.0;
+  rc = helmholtz_set_sigma(h->H, sigma); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h->kap, h->Gt, N * sizeof(double), hipMemcpyDeviceToDevice, st));     // copy 0: all the preconditioner reads
+  HIP_TRY(hipMemcpyAsync(h->Kt, K_dev, nk * N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (vel_dev) HIP_TRY(hipMemcpyAsync(h->vel, vel_dev, d * N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (c_dev) HIP_TRY(hipMemcpyAsync(h->cfield, c_dev, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+  h->c_is_field = c_dev != nullptr; h->c0 = c_dev ? 0.0 : c_scalar; h->has_vel = vel_dev != nullptr;
+  HIP_TRY(hipStreamSynchronize(st));
+  h->sigma_p = sigma; h->have_coef = true; h->mode = CHEB_VARHELM_MODE_TENSOR;
   return 0;
 }
 

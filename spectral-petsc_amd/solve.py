@@ -131,7 +131,8 @@ def helmholtz_bvp(sp, dims, f_full, g, bc, sigma=0.0, solver=None, scale=None):
     return u
 
 
-def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=None, rtol=1e-8, max_it=200, restart=30, singular="refuse"):
+def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=None, rtol=1e-8, max_it=200, restart=30, singular="refuse",
+                       tensor=None, velocity=None):
     """c u - sum_k scale_k^2 d_k(kappa d_k u) = f with alpha u + beta scale_k du/dnu = g on every face (sp.VarHelmholtz's `bc`;
     None: Dirichlet everywhere), by preconditioned FGMRES in one library call.  kappa: a full-grid device tensor (> 0); c: a scalar
     or a full-grid device tensor (>= 0); f_full: the full-grid right-hand side (its boundary entries are ignored; a multiple of the
@@ -139,7 +140,11 @@ def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=No
     data of the flux kappa du/dnu divide g by kappa first.  Returns (u, iterations): the full-grid u (a new tensor) and the
     operator applications of the solve; a solve that does not converge raises RuntimeError.  singular: "refuse" -- a singular
     problem (c == 0, every direction periodic or Neumann / Neumann) raises ChebhipError -- or "deflate": VarHelmholtz.solve_deflated,
-    the solution without null-space part of the problem whose source has lost its null-space part."""
+    the solution without null-space part of the problem whose source has lost its null-space part.
+    tensor, velocity (2-D and 3-D): c u + velocity . grad u - div(K grad u) = f by VarHelmholtz.set_tensor -- tensor: the
+    d (d + 1) / 2 full-grid fields of K stacked in the order sp.tensor_order(d), kappa is then not read (None will do); tensor None
+    with a velocity: K = kappa I; velocity: d stacked full-grid fields or None.  Scales enter as in the operator: every derivative
+    is scale_k d_k."""
     if singular not in ("refuse", "deflate"):
         raise ValueError("singular = %r: 'refuse' or 'deflate'" % (singular,))
     dims = tuple(int(d) for d in dims)
@@ -150,7 +155,14 @@ def variable_diffusion(sp, dims, kappa, f_full, c=0.0, bc=None, g=None, scale=No
         raise ValueError("f_full has %d elements, no multiple of %d" % (f_full.numel(), N))
     op = sp.VarHelmholtz(dims, f_full.numel() // N, bc=bc, scale=scale)
     try:
-        op.set_coefficients(kappa.contiguous().reshape(-1), c.contiguous().reshape(-1) if isinstance(c, torch.Tensor) else c)
+        cc = c.contiguous().reshape(-1) if isinstance(c, torch.Tensor) else c
+        if tensor is None and velocity is None:
+            op.set_coefficients(kappa.contiguous().reshape(-1), cc)
+        else:
+            if tensor is None:
+                k = kappa.contiguous().reshape(-1)
+                tensor = torch.cat([k] * len(dims) + [torch.zeros_like(k)] * (len(dims) * (len(dims) - 1) // 2))
+            op.set_tensor(tensor.contiguous().reshape(-1), cc, None if velocity is None else velocity.contiguous().reshape(-1))
         inner = tuple(slice(None) if p else slice(1, -1) for p in op.periodic)
         f = f_full.reshape((op.nfields,) + dims)[(slice(None),) + inner].contiguous().reshape(-1)
         u = torch.empty(op.full_size, dtype=torch.float64, device=f_full.device)
