@@ -1,7 +1,18 @@
 """cheb_modal_* on the device (ChebModal): coefficient transforms, filters, spectra and Clenshaw-Curtis integrals against the host
-matrices (element by element in one direction, normwise as tensor products), against numpy's own Chebyshev recurrence, on single
-modes and single nodes; round trips, projections, run-to-run bits; the interface."""
+matrices (element by element in one direction and as tensor products, there also normwise), against numpy's own Chebyshev
+recurrence, on single modes and single nodes; round trips, projections, run-to-run bits; the interface.
+
+The tensor products are held to the bar of resample_ref.py: |y - truth| <= cap 2^-53 B per element, truth the long-double
+application of the double host matrices, B = (x |M_k|) |x|, cap = sum of n_k + 8 over the directions that are not dropped.
+Worst ratios measured on an MI355X (printed with pytest -s; profiles/modal/ratios.txt holds one line per test id and input kind,
+written where MODAL_RATIOS_OUT names a file):
+  test_tensor_product_parity      72 figures, worst 23.9 (cap 1032) at [1024-f16] noise filter (12, 20);
+                                  nearest to its cap: 4.6 of 40 at [12x12x12x12x12-f1] noise filter
+  test_dropped_directions          1 figure,  2.5 (cap  15) at [5x7x9-f16] (11, 1, 0, 3)
+  test_odd_element_offsets         1 figure,  0.3 (cap  68) at [20x15x9-f3] (2, 9, 2, 1)
+  test_non_default_stream_ordering 1 figure,  0.1 (cap 312) at [96x96x96-f1] (0, 75, 68, 4)"""
 import functools
+import os
 from importlib import import_module
 
 import numpy as np
@@ -10,6 +21,8 @@ import torch
 from numpy.polynomial import chebyshev as npcheb
 
 import __graft_entry__ as ge
+import linewise as lw
+import resample_ref as rr
 
 pytestmark = pytest.mark.gpu
 sp = ge.load()
@@ -17,6 +30,26 @@ solve = import_module(sp.__name__ + ".solve")
 SEED = 20240229
 LD = np.longdouble
 U = 2.0 ** -53
+RATIOS = []                       # (test, case, kind, worst ratio, cap, element)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _ratios_file():
+    yield
+    path = os.environ.get("MODAL_RATIOS_OUT")
+    if path and RATIOS:
+        with open(path, "w") as f:
+            f.write("# worst |y - truth| / (2^-53 B) per test id and input kind (tests/test_gpu_modal.py); cap = sum of n_k + 8 over the directions not dropped\n")
+            for test, case, kind, r, cap, idx in RATIOS:
+                f.write("%-28s %-20s %-18s %8.3f of cap %4d at %s\n" % (test, case, kind, r, cap, idx))
+
+
+def held(test, case, kind, mats, x, y, dims, nf):
+    """The per-element bar of resample_ref.py on nf stacked fields: printed, recorded, asserted."""
+    t, B, cap = rr.chain_truth_bound(mats, np.asarray(x).reshape((nf,) + tuple(dims)), first_axis=1, skip_identities=False)
+    ratio, idx = lw.check(np.asarray(y).reshape(t.shape), t, B, cap, "%s %s %s" % (test, case, kind))
+    print("%-28s %-20s %-18s %8.3f of cap %4d at %s" % (test, case, kind, ratio, cap, idx))
+    RATIOS.append((test, case, kind, ratio, cap, idx))
 
 # every boundary of the GEMM tiles and of the reductions' vector paths: 64 lines, 64 / 128 output points, 16-point chunks, Q <= 4
 # against Q > 4, odd rows and odd field sizes (8-byte aligned rows and fields), one to five directions
@@ -112,6 +145,21 @@ def case(dims, nf):
     return r
 
 
+@functools.lru_cache(maxsize=None)
+def case_scaled(dims, nf):
+    """The transforms and the filter of case() on fields scaled by 10^+100 and 10^-100 in turn."""
+    m = sp.ChebModal(dims, nf)
+    u = np.random.default_rng(SEED + sum(dims) + nf + 1).standard_normal((nf,) + tuple(dims))
+    u *= (10.0 ** (100 * (-1) ** np.arange(nf))).reshape((nf,) + (1,) * len(dims))
+    ud = dev(u)
+    r = dict(u=u.ravel(), a=host(m.forward(ud, new(m.size()))), back=host(m.backward(ud, new(m.size()))))
+    for k, s in enumerate(sigmas(dims)):
+        m.set_filter(k, s)
+    r.update(f1=host(m.filter(ud, new(m.size()))))
+    m.destroy()
+    return r
+
+
 # ---- 1. one direction, element by element ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [2, 17, 64, 65, 257, 1024])
 def test_one_direction_elementwise(n):
@@ -143,6 +191,10 @@ def test_tensor_product_parity(dims, nf):
         err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
         print("%s %s: %.2e" % (case_ids(dims), name, err))
         assert np.isfinite(got).all() and err <= 1e-13, name
+    cid = "%s-f%d" % (case_ids(dims), nf)
+    for kind, rc in (("noise", r), ("scaled", case_scaled(dims, nf))):
+        for name, key, mats in (("forward", "a", T), ("backward", "back", B), ("filter", "f1", F)):
+            held("tensor_product_parity", cid, kind + "-" + name, mats, rc["u"], rc[key], dims, nf)
 
 
 # ---- 3. numpy's Chebyshev recurrence as an independent oracle -------------------------------------------------------------------
@@ -254,8 +306,10 @@ def test_dropped_directions():
     c0 = sp.lib().chebhip_launch_count()
     v = m.filter(u, new(m.size()))
     assert sp.lib().chebhip_launch_count() - c0 == 1
-    ref = along([None, sp.filter_matrix(7, sp.exp_filter(7, order=4)), None], host(u), dims, 16)
+    F = [None, sp.filter_matrix(7, sp.exp_filter(7, order=4)), None]
+    ref = along(F, host(u), dims, 16)
     assert np.linalg.norm(host(v) - ref) <= 1e-13 * np.linalg.norm(ref)
+    held("dropped_directions", "5x7x9-f16", "noise-filter", F, host(u), host(v), dims, 16)            # cap 7 + 8: one direction
     m.destroy()
 
 
@@ -271,8 +325,10 @@ def test_odd_element_offsets():
     bx[1:1 + n] = dev(x)
     m.forward(bx[1:1 + n], by[3:3 + n])
     out = host(by)
-    ref = along([sp.modal_matrix(k, "forward") for k in dims], x, dims, nf)
+    T = [sp.modal_matrix(k, "forward") for k in dims]
+    ref = along(T, x, dims, nf)
     assert np.linalg.norm(out[3:3 + n] - ref) <= 1e-13 * np.linalg.norm(ref)
+    held("odd_element_offsets", "20x15x9-f3", "noise-forward", T, x, out[3:3 + n], dims, nf)
     assert (out[:3] == -7.0).all() and out[-1] == -7.0                    # nothing written outside the slice
     aligned = dev(x)
     be = torch.full((m.spectrum_size() + 2,), -7.0, dtype=torch.float64, device="cuda")
@@ -305,8 +361,10 @@ def test_non_default_stream_ordering():
             z, q, e = y.clone(), m.integrate(xin).clone(), m.spectrum(y).clone()
     s.synchronize()
     x3 = x.cpu().numpy() * 3.0
-    ref = along([sp.modal_matrix(n, "forward") for n in dims], x3, dims, 1)
+    T = [sp.modal_matrix(n, "forward") for n in dims]
+    ref = along(T, x3, dims, 1)
     assert np.linalg.norm(z.cpu().numpy() - ref) <= 1e-13 * np.linalg.norm(ref)
+    held("non_default_stream", "96x96x96-f1", "noise-forward", T, x3, z.cpu().numpy(), dims, 1)
     W = weights(dims).astype(np.float64).ravel()
     assert abs(float(q[0]) - W @ x3) <= 2 * (x3.size + 8) * U * (W @ np.abs(x3))          # (device sum and numpy's dot)
     assert abs(float(e[:96].sum()) - ref @ ref) <= 1e-10 * (ref @ ref)
